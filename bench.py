@@ -145,6 +145,35 @@ def cpu_baseline(batch, length, steps, threads):
     return batch * cut / 16000 / dt, dt, times
 
 
+DUMP_MAX_ELEMS = 1 << 21       # --dump-outputs: an array larger than this is stored as a fixed, seeded sample of this many elements
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, out, mod):
+    """--dump-outputs: what the last timed step computed, as DIR/<name>.npy (float32; float64 where the tensor is), for comparing two
+    builds output for output: the tensors training_step returned, the losses it logged, and the parameters after its two Adam
+    updates.  Arrays over DUMP_MAX_ELEMS elements (the discriminator's 23 M parameters) keep the flattened elements at a fixed
+    index sample (torch.Generator seed 0, sorted), named <name>_sample.npy."""
+    import numpy as np
+
+    arrays = dict(out)
+    arrays.update({"logged." + k.replace("/", "."): v for k, v in mod.logged.items()})
+    for net in ("generator", "discriminator"):
+        arrays[f"{net}_params"] = torch.cat([p.detach().reshape(-1) for p in getattr(mod, net).parameters()])
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ELEMS].sort().values
+            t, name = t.reshape(-1)[idx.to(t.device)], name + "_sample"
+        a = t.cpu().numpy().astype(np.float64 if t.dtype == torch.float64 else np.float32)
+        total += a.nbytes
+        assert total <= DUMP_MAX_BYTES, f"--dump-outputs: more than {DUMP_MAX_BYTES >> 20} MB"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return len(arrays), total
+
+
 def percentile(sorted_vals, q):
     if not sorted_vals:
         return None
@@ -200,7 +229,11 @@ def main():
     ap.add_argument("--stft-math", default=None, choices=["bf16x3", "folded", "dense", "folded_x3", "folded_x6"],
                     help="MRSTFT windowed-DFT contractions (default: 'folded', exact fp32 on the even / odd parts of the frames)")
     ap.add_argument("--no-f32-leg", action="store_true", help="skip the extra fp32 timing reported beside a bf16 run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (returned tensors, logged losses, parameters after its "
+                         "Adam updates) as DIR/<name>.npy, at most 64 MB; rank 0 only (e.g. bench_outputs/)")
     args = ap.parse_args()
+    assert args.steps >= 1, "--steps: at least one timed step"
 
     import torch.distributed as dist
 
@@ -326,6 +359,7 @@ def main():
         torch.cuda.synchronize()
 
     host_s = [0.0]
+    last_out = [None]   # what the last step of the latest timed_steps() returned (--dump-outputs)
 
     def timed_steps(n):
         """EXACTLY n steps between two barrier + synchronize brackets (wall clock), with a HIP event at every step boundary on the main
@@ -335,7 +369,9 @@ def main():
         t0 = time.perf_counter()
         evs[0].record()
         for i in range(n):
-            mod.training_step(next_batch())
+            out = mod.training_step(next_batch())
+            if i == n - 1:
+                last_out[0] = out
             evs[i + 1].record()
         host_s[0] = (time.perf_counter() - t0) / n   # what the host needed to enqueue a step (the GPU runs behind it)
         barrier()
@@ -379,6 +415,10 @@ def main():
     host_ms = host_s[0] * 1e3
     n_graphs = ops.graphs_captured()   # launch sequences replayed as HIP graphs during the timed steps
     exposed = {name: sy.exposed_comm_ms() for name, sy in syncs}
+    # the legs below run further steps (and other plans) on the same module: the timed path's last step is written out now
+    if args.dump_outputs and rank == 0:
+        n_files, n_bytes = dump_outputs(args.dump_outputs, last_out[0], mod)
+        print(f"[bench] last timed step's outputs: {n_files} arrays, {n_bytes / 2**20:.1f} MB in {args.dump_outputs}", file=sys.stderr, flush=True)
     # The two roofline launches are bracketed by HIP events on the stream they are launched on.  Events cannot sit between the nodes of
     # a replayed HIP graph, and the timed steps above replay the discriminator chains as graphs (ops.ReplayedChain): the brackets are
     # taken over a second run of the same steps with the chains launched kernel by kernel (same kernels, same streams, same batch)

@@ -14,7 +14,7 @@ obj="$here/../lib/obj"
 mkdir -p "$obj"
 stamp="$(printf '%s\n' "${flags[@]}" | cat - "$here"/*.h "$root"/include/*.h | md5sum | cut -d' ' -f1)"
 srcs=("$here"/*.hip "$here"/exact_fp32/*.hip)   # exact_fp32/: the kernel families only the exact-fp32 reference plan reaches
-jobs="${EBEN_BUILD_JOBS:-$(nproc)}"
+jobs="${EBEN_BUILD_JOBS:-${MAX_JOBS:-$(nproc)}}"   # MAX_JOBS: the usual cap on parallel compiles
 pids=()
 fail=0
 for s in "${srcs[@]}"; do
