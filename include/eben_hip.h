@@ -78,9 +78,9 @@ typedef struct EbenConv1dDesc {
 } EbenConv1dDesc;
 
 EBEN_API const char* eben_last_error(void);
-/* Bumped whenever a POD structure, an entry point's signature or a table stride changes (2: EbenWnBwdItem.col_perm_k; 3: eben_rubl_*).
+/* Bumped whenever a POD structure, an entry point's signature or a table stride changes (2: EbenWnBwdItem.col_perm_k; 3: eben_rubl_*; 4: eben_si_sdr / eben_stoi).
  * eben_version() returns the value the library was built with; bindings compare it with the header they were written against. */
-#define EBEN_ABI_VERSION 3
+#define EBEN_ABI_VERSION 4
 EBEN_API int eben_version(void);
 /* fills name with the device's gcnArchName; returns compute-unit count (or negative) */
 EBEN_API int eben_device_info(char* name, size_t name_bytes);
@@ -516,6 +516,19 @@ EBEN_API int eben_resample(const float* x, const float* kernels, float* out, int
 /* ---- misc ------------------------------------------------------------------------------- */
 /* out[0] = sqrt(sum x^2) (torch.norm at eben.py:226); `out` must hold 257 floats (scratch) */
 EBEN_API int eben_l2norm(const float* x, size_t n, float* out, void* stream);
+
+/* ---- validation metrics (base_se.py common_eval_logging: torchmetrics SI-SDR and STOI) ------------------------------
+ * eben_si_sdr: out[r] = scale_invariant_signal_distortion_ratio(preds[r, :], target[r, :], zero_mean=False), fp64 sums.
+ * eben_stoi: out[r] = pystoi stoi(x = clean[r, :], y = processed[r, :], fs), extended=False (torchmetrics' call order).
+ *   fs != 10000: both signals are first resampled to 10 kHz as scipy resample_poly(x, p, q, window=h), p/q = 10000/fs reduced;
+ *   resample_table holds `up * h` (taps = 2*half+1 floats, on the device), built by the caller once per fs.  At fs == 10000
+ *   the table is ignored.  `workspace` (device, eben_stoi_workspace(rows, t, fs) bytes) holds the resampled signals, frame
+ *   energies, the kept-frame tables and band envelopes; no host synchronisation.  Rows left with fewer than 30 STFT frames
+ *   after silence removal get 1e-5. */
+EBEN_API int eben_si_sdr(const float* preds, const float* target, int rows, int t, float* out, void* stream);
+EBEN_API size_t eben_stoi_workspace(int rows, int t, int fs);
+EBEN_API int eben_stoi(const float* clean, const float* processed, int rows, int t, int fs, const float* resample_table, int taps,
+              void* workspace, size_t ws_bytes, float* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -194,13 +194,16 @@ SIGNATURES = {
     "eben_adam_step": (c_int, [POINTER(EbenAdamTensor), c_int, c_int64, c_float, c_float, c_float, c_float, c_float, c_int, c_float, _P]),
     "eben_noisy_collate": (c_int, [POINTER(EbenCollateItem), c_int, c_int, _P, _P, _P]),
     "eben_l2norm": (c_int, [_P, c_size_t, _P, _P]),
+    "eben_si_sdr": (c_int, [_P, _P, c_int, c_int, _P, _P]),
+    "eben_stoi_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "eben_stoi": (c_int, [_P, _P, c_int, c_int, c_int, _P, c_int, _P, c_size_t, _P, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None
 
 
 #: include/eben_hip.h EBEN_ABI_VERSION this module's structures and signatures were written against
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 
 def load(path: Optional[str] = None) -> ctypes.CDLL:

@@ -1,0 +1,370 @@
+// Validation metrics of base_se.py's common_eval_logging (torchmetrics SI-SDR, classic STOI) on the device.
+//
+// SI-SDR (torchmetrics scale_invariant_signal_distortion_ratio, zero_mean=False): one workgroup per row, two passes over the
+// row with fp64 accumulators -- pass 1 gives sum(p*t), sum(t*t), pass 2 sum((alpha*t - p)^2) exactly as written, so there is
+// no closed-form cancellation at high SI-SDR.
+//
+// STOI (pystoi 0.4.x stoi(x=clean, y=processed, fs), extended=False), batched over rows, no host synchronisation:
+//   1. stoi_resample_kernel   polyphase resample_poly(x, p, q, window=h) of both signals to 10 kHz (skipped at fs = 10 kHz)
+//   2. stoi_frames_kernel     one workgroup per row: frame energies of the clean signal, max, the -40 dB mask and a
+//                             ballot/prefix compaction into the kept-frame index table and its count (kept on the device)
+//   3. stoi_bands_kernel      one workgroup per (STFT frame, row): the frame of the overlap-added silence-removed signal is
+//                             gathered straight from the kept frames (never materialised), then a direct 512-point DFT of the
+//                             bins the third-octave bands cover, folded into the 15 band envelopes
+//   4. stoi_corr_kernel       one workgroup per row: the 30-frame segment correlations and d
+// Buffers are sized for the all-frames-kept case; rows whose kept count is smaller leave the tail workgroups idle.
+#include <cmath>
+
+#include "common.h"
+
+namespace eben {
+namespace {
+
+constexpr int kFs = 10000;
+constexpr int kFrame = 256;
+constexpr int kHop = 128;
+constexpr int kNfft = 512;
+constexpr int kBands = 15;
+constexpr int kSeg = 30;
+constexpr double kDynRange = 40.0;
+constexpr double kEps64 = 2.220446049250313e-16;    // float64 machine epsilon (pystoi EPS)
+constexpr double kSdrEps = 1.1920928955078125e-07;  // float32 machine epsilon (torchmetrics, fp32 inputs)
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// sum over a 256-thread workgroup; every thread gets the result
+__device__ __forceinline__ double block_sum(double v, double* red) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return red[0] + red[1] + red[2] + red[3];
+}
+
+// ---- SI-SDR -------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void si_sdr_kernel(const float* __restrict__ preds, const float* __restrict__ target, int t,
+                                                     float* __restrict__ out) {
+  __shared__ double red[4];
+  const long long r = blockIdx.x;
+  const float* p = preds + r * t;
+  const float* g = target + r * t;
+  double pt = 0.0, tt = 0.0;
+  for (int i = threadIdx.x; i < t; i += 256) {
+    const double a = p[i], b = g[i];
+    pt = fma(a, b, pt);
+    tt = fma(b, b, tt);
+  }
+  pt = block_sum(pt, red);
+  tt = block_sum(tt, red);
+  const double alpha = (pt + kSdrEps) / (tt + kSdrEps);
+  double nn = 0.0;
+  for (int i = threadIdx.x; i < t; i += 256) {
+    const double e = alpha * (double)g[i] - (double)p[i];
+    nn = fma(e, e, nn);
+  }
+  nn = block_sum(nn, red);
+  if (threadIdx.x == 0) out[r] = (float)(10.0 * log10((alpha * alpha * tt + kSdrEps) / (nn + kSdrEps)));
+}
+
+// ---- STOI ---------------------------------------------------------------------------------------------------------------
+struct StoiBands {
+  int lo[kBands];  // [lo, hi) FFT bins of each third-octave band (thirdoct(10000, 512, 15, 150))
+  int hi[kBands];
+  int bin0, nbins;  // the bins any band covers: [bin0, bin0 + nbins)
+};
+
+// out[n] = sum_m x[m] * table[half + n*q - m*p], m in [0, t_in): scipy resample_poly's zero-padded, centred polyphase sum
+// (table = up * h, 2*half+1 taps).  blockIdx.z selects the signal (0 clean, 1 processed).
+__global__ __launch_bounds__(256) void stoi_resample_kernel(const float* __restrict__ clean, const float* __restrict__ processed,
+                                                            const float* __restrict__ table, int half, int p, int q, int t_in,
+                                                            int t_out, int rows, float* __restrict__ out) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= t_out) return;
+  const long long r = blockIdx.y;
+  const float* x = (blockIdx.z ? processed : clean) + r * t_in;
+  const long long c = (long long)n * q;
+  const long long lo_num = c - half;
+  int m0 = lo_num <= 0 ? 0 : (int)((lo_num + p - 1) / p);
+  int m1 = (int)((c + half) / p);
+  if (m1 > t_in - 1) m1 = t_in - 1;
+  float acc = 0.f;
+  for (int m = m0; m <= m1; ++m) acc = fmaf(x[m], table[c + half - (long long)m * p], acc);
+  out[((long long)blockIdx.z * rows + r) * t_out + n] = acc;
+}
+
+__device__ __forceinline__ double hann258(int j) {  // np.hanning(258)[1:-1][j]
+  return 0.5 - 0.5 * cos(2.0 * M_PI * (double)(j + 1) / (double)(kFrame + 1));
+}
+
+// one workgroup per row: energies 20*log10(||w*frame|| + EPS) of the clean frames at range(0, t - 256, 128), the mask
+// max - 40 - e < 0 and the kept-frame table kept[row, 0:count[row]] in frame order
+__global__ __launch_bounds__(256) void stoi_frames_kernel(const float* __restrict__ clean, int t, int nf, double* __restrict__ energy,
+                                                          int* __restrict__ kept, int* __restrict__ count) {
+  __shared__ double win[kFrame];
+  __shared__ double red[4];
+  __shared__ int wave_cnt[4];
+  const long long r = blockIdx.x;
+  const float* x = clean + r * t;
+  double* e = energy + r * nf;
+  int* k = kept + r * nf;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  win[threadIdx.x] = hann258(threadIdx.x);
+  __syncthreads();
+  double emax = -INFINITY;
+  for (int f = wave; f < nf; f += 4) {
+    const float* fr = x + (long long)f * kHop;
+    double s = 0.0;
+#pragma unroll
+    for (int j = lane; j < kFrame; j += 64) {
+      const double v = win[j] * (double)fr[j];
+      s = fma(v, v, s);
+    }
+    s = wave_sum(s);
+    const double en = 20.0 * log10(sqrt(s) + kEps64);
+    if (lane == 0) e[f] = en;
+    emax = fmax(emax, en);
+  }
+  // block max (every lane of a wave holds the same value)
+  if (lane == 0) red[wave] = emax;
+  __syncthreads();
+  emax = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+  int base = 0;
+  for (int c0 = 0; c0 < nf; c0 += 256) {
+    const int f = c0 + threadIdx.x;
+    const bool keep = f < nf && (emax - kDynRange - e[f]) < 0.0;
+    const unsigned long long m = __ballot(keep);
+    if (lane == 0) wave_cnt[wave] = __popcll(m);
+    __syncthreads();
+    int off = base;
+    for (int w = 0; w < wave; ++w) off += wave_cnt[w];
+    if (keep) k[off + __popcll(m & ((1ull << lane) - 1ull))] = f;
+    base += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) count[r] = base;
+}
+
+// one workgroup per (STFT frame i, row).  With kept frames k_0..k_{K-1} (k_m[u] = w[u] * sig[128*kept[m] + u]) the
+// overlap-added signal has K+1 hops and K-1 STFT frames; frame i is w * [k_i[0:128] + k_{i-1}[128:256], k_i[128:256] + k_{i+1}[0:128]]
+// (k_{-1} = 0).  tob[row, s, band, i] = sqrt(sum over the band's bins of |rfft(frame, 512)|^2).
+__global__ __launch_bounds__(256) void stoi_bands_kernel(const float* __restrict__ sx, const float* __restrict__ sy, int t, int nf, const int* __restrict__ kept,
+                                                         const int* __restrict__ count, StoiBands bands, int fmax, double* __restrict__ tob) {
+  __shared__ float win[kFrame];
+  __shared__ float cs[kNfft];
+  __shared__ float fr[2][kFrame];
+  __shared__ float pw[2][kNfft / 2 + 1];
+  const int i = blockIdx.x;
+  const long long r = blockIdx.y;
+  const int nk = count[r];
+  if (i >= nk - 1) return;  // uniform over the workgroup
+  const int j = threadIdx.x;
+  win[j] = (float)hann258(j);
+  cs[j] = (float)cos(2.0 * M_PI * (double)j / kNfft);
+  cs[j + 256] = -cs[j];
+  __syncthreads();
+  const int* k = kept + r * nf;
+  const long long cur = (long long)k[i] * kHop;
+  const long long nb = j < kHop ? (i > 0 ? (long long)k[i - 1] * kHop + kHop + j : -1) : (long long)k[i + 1] * kHop + (j - kHop);
+  const int nu = j < kHop ? j + kHop : j - kHop;  // the neighbour frame's own sample index
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    const float* x = (s ? sy : sx) + r * t;
+    float v = win[j] * x[cur + j];
+    if (nb >= 0) v += win[nu] * x[nb];
+    fr[s][j] = win[j] * v;
+  }
+  __syncthreads();
+  for (int pidx = j; pidx < 2 * bands.nbins; pidx += 256) {
+    const int s = pidx >= bands.nbins;
+    const int bin = bands.bin0 + pidx - s * bands.nbins;
+    const float* f = fr[s];
+    float re = 0.f, im = 0.f;
+    int ph = 0;  // bin * n mod 512
+    for (int n = 0; n < kFrame; ++n) {
+      re = fmaf(f[n], cs[ph], re);
+      im = fmaf(f[n], cs[(ph - 128) & (kNfft - 1)], im);  // sin(2 pi ph / 512)
+      ph = (ph + bin) & (kNfft - 1);
+    }
+    pw[s][bin] = re * re + im * im;
+  }
+  __syncthreads();
+  if (j < 2 * kBands) {
+    const int s = j / kBands, b = j - s * kBands;
+    double acc = 0.0;
+    for (int q = bands.lo[b]; q < bands.hi[b]; ++q) acc += (double)pw[s][q];
+    tob[((r * 2 + s) * kBands + b) * (long long)fmax + i] = sqrt(acc);
+  }
+}
+
+// one workgroup per row: d = sum over segments m and bands of corr(x_seg, y'_seg) / (J * 15), J = frames - 29
+__global__ __launch_bounds__(256) void stoi_corr_kernel(const double* __restrict__ tob, const int* __restrict__ count, int fmax,
+                                                        float* __restrict__ out) {
+  __shared__ double red[4];
+  const long long r = blockIdx.x;
+  const int frames = count[r] - 1;
+  if (frames < kSeg) {  // uniform over the workgroup
+    if (threadIdx.x == 0) out[r] = 1e-5f;
+    return;
+  }
+  const int J = frames - kSeg + 1;
+  const double clip = 1.0 + pow(10.0, 15.0 / 20.0);  // 1 + 10^(-BETA/20)
+  double acc = 0.0;
+  for (int pidx = threadIdx.x; pidx < J * kBands; pidx += 256) {
+    const int m = pidx / kBands, b = pidx - m * kBands;
+    const double* x = tob + ((r * 2 + 0) * kBands + b) * (long long)fmax + m;
+    const double* y = tob + ((r * 2 + 1) * kBands + b) * (long long)fmax + m;
+    double xx = 0.0, yy = 0.0;
+    for (int n = 0; n < kSeg; ++n) {
+      xx = fma(x[n], x[n], xx);
+      yy = fma(y[n], y[n], yy);
+    }
+    const double c = sqrt(xx) / (sqrt(yy) + kEps64);
+    double mx = 0.0, my = 0.0;
+    for (int n = 0; n < kSeg; ++n) {
+      mx += x[n];
+      my += fmin(y[n] * c, x[n] * clip);
+    }
+    mx /= kSeg;
+    my /= kSeg;
+    double sxy = 0.0, sxx = 0.0, syy = 0.0;
+    for (int n = 0; n < kSeg; ++n) {
+      const double a = x[n] - mx, bb = fmin(y[n] * c, x[n] * clip) - my;
+      sxy = fma(a, bb, sxy);
+      sxx = fma(a, a, sxx);
+      syy = fma(bb, bb, syy);
+    }
+    acc += sxy / ((sqrt(sxx) + kEps64) * (sqrt(syy) + kEps64));
+  }
+  acc = block_sum(acc, red);
+  if (threadIdx.x == 0) out[r] = (float)(acc / ((double)J * kBands));
+}
+
+struct StoiShape {
+  int p, q, t10, nf, fmax;
+};
+
+int gcd_int(int a, int b) {
+  while (b) {
+    const int c = a % b;
+    a = b;
+    b = c;
+  }
+  return a;
+}
+
+StoiShape stoi_shape(int t, int fs) {
+  StoiShape s{1, 1, t, 0, 1};
+  if (fs != kFs) {
+    const int g = gcd_int(kFs, fs);
+    s.p = kFs / g;
+    s.q = fs / g;
+    s.t10 = (int)(((long long)t * s.p + s.q - 1) / s.q);
+  }
+  s.nf = s.t10 > kFrame ? (s.t10 - kFrame + kHop - 1) / kHop : 0;
+  s.fmax = s.nf > 1 ? s.nf - 1 : 1;
+  return s;
+}
+
+size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+struct StoiWs {
+  size_t sig, energy, kept, count, tob, total;
+};
+
+StoiWs stoi_ws(int rows, const StoiShape& s, int fs) {
+  StoiWs w{};
+  size_t off = 0;
+  w.sig = off;
+  off += fs != kFs ? align256(sizeof(float) * 2 * (size_t)rows * s.t10) : 0;
+  w.energy = off;
+  off += align256(sizeof(double) * (size_t)rows * (s.nf > 0 ? s.nf : 1));
+  w.kept = off;
+  off += align256(sizeof(int) * (size_t)rows * (s.nf > 0 ? s.nf : 1));
+  w.count = off;
+  off += align256(sizeof(int) * (size_t)rows);
+  w.tob = off;
+  off += align256(sizeof(double) * (size_t)rows * 2 * kBands * s.fmax);
+  w.total = off;
+  return w;
+}
+
+// thirdoct(10000, 512, 15, 150): band edges 150 * 2^((2k -+ 1)/6) Hz, each snapped to the nearest bin of linspace(0, fs, 513)[:257]
+// (first bin on a tie, as np.argmin)
+StoiBands stoi_bands() {
+  StoiBands b{};
+  auto nearest = [](double hz) {
+    int best = 0;
+    double bd = INFINITY;
+    for (int k = 0; k <= kNfft / 2; ++k) {
+      const double d = (k * (double)kFs / kNfft - hz) * (k * (double)kFs / kNfft - hz);
+      if (d < bd) {
+        bd = d;
+        best = k;
+      }
+    }
+    return best;
+  };
+  for (int k = 0; k < kBands; ++k) {
+    b.lo[k] = nearest(150.0 * pow(2.0, (2.0 * k - 1.0) / 6.0));
+    b.hi[k] = nearest(150.0 * pow(2.0, (2.0 * k + 1.0) / 6.0));
+  }
+  b.bin0 = b.lo[0];
+  b.nbins = b.hi[kBands - 1] - b.bin0;
+  return b;
+}
+
+}  // namespace
+}  // namespace eben
+
+using namespace eben;
+
+extern "C" int eben_si_sdr(const float* preds, const float* target, int rows, int t, float* out, void* stream) {
+  EBEN_REQUIRE(preds && target && out && rows > 0 && t > 0, "bad si_sdr arguments");
+  hipLaunchKernelGGL(si_sdr_kernel, dim3(rows), dim3(256), 0, as_stream(stream), preds, target, t, out);
+  EBEN_CHECK_LAUNCH("si_sdr_kernel");
+  return EBEN_OK;
+}
+
+extern "C" size_t eben_stoi_workspace(int rows, int t, int fs) {
+  if (rows <= 0 || t <= 0 || fs <= 0) return 0;
+  return stoi_ws(rows, stoi_shape(t, fs), fs).total;
+}
+
+extern "C" int eben_stoi(const float* clean, const float* processed, int rows, int t, int fs, const float* resample_table, int taps,
+                         void* workspace, size_t ws_bytes, float* out, void* stream) {
+  EBEN_REQUIRE(clean && processed && out && workspace && rows > 0 && rows <= 65535 && t > 0 && fs > 0, "bad stoi arguments");
+  const StoiShape s = stoi_shape(t, fs);
+  const StoiWs w = stoi_ws(rows, s, fs);
+  if (ws_bytes < w.total) return fail(EBEN_EWORKSPACE, "stoi needs %zu workspace bytes", w.total);
+  char* ws = static_cast<char*>(workspace);
+  const hipStream_t st = as_stream(stream);
+  const float* sx = clean;  // both signals at 10 kHz, (rows, t10) each
+  const float* sy = processed;
+  if (fs != kFs) {
+    EBEN_REQUIRE(resample_table && taps > 0 && (taps & 1), "stoi at fs != 10000 needs the odd-length resampling table");
+    float* rs = reinterpret_cast<float*>(ws + w.sig);
+    hipLaunchKernelGGL(stoi_resample_kernel, dim3(ceil_div(s.t10, 256), rows, 2), dim3(256), 0, st, clean, processed, resample_table,
+                       (taps - 1) / 2, s.p, s.q, t, s.t10, rows, rs);
+    EBEN_CHECK_LAUNCH("stoi_resample_kernel");
+    sx = rs;
+    sy = rs + (size_t)rows * s.t10;
+  }
+  double* energy = reinterpret_cast<double*>(ws + w.energy);
+  int* kept = reinterpret_cast<int*>(ws + w.kept);
+  int* count = reinterpret_cast<int*>(ws + w.count);
+  double* tob = reinterpret_cast<double*>(ws + w.tob);
+  hipLaunchKernelGGL(stoi_frames_kernel, dim3(rows), dim3(256), 0, st, sx, s.t10, s.nf, energy, kept, count);
+  EBEN_CHECK_LAUNCH("stoi_frames_kernel");
+  if (s.nf > 1) {
+    hipLaunchKernelGGL(stoi_bands_kernel, dim3(s.fmax, rows), dim3(256), 0, st, sx, sy, s.t10, s.nf, kept, count, stoi_bands(), s.fmax,
+                       tob);
+    EBEN_CHECK_LAUNCH("stoi_bands_kernel");
+  }
+  hipLaunchKernelGGL(stoi_corr_kernel, dim3(rows), dim3(256), 0, st, tob, count, s.fmax, out);
+  EBEN_CHECK_LAUNCH("stoi_corr_kernel");
+  return EBEN_OK;
+}

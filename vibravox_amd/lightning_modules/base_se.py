@@ -1,7 +1,10 @@
 """Constructor / logging contract of ``vibravox/lightning_modules/base_se.py:16-196`` that the EBEN
-train step relies on.  The evaluation hooks of the reference (torchmetrics / torchaudio SQUIM
-pipelines, audio logging) are out of scope: only ``sample_rate``,
-``description`` and the Lightning plumbing used by ``training_step`` are provided.
+train step relies on, plus the speech-quality half of the reference's evaluation hooks:
+``on_validation_batch_end`` / ``on_test_batch_end`` -> ``common_eval_logging`` log
+``{stage}/torchmetrics_si_sdr[/dataloader]`` and ``{stage}/torchmetrics_stoi[/dataloader]`` for every batch with a
+reference, computed at 16 kHz on the device (``vibravox_amd.metrics``: HIP kernels, no host round trip).  Still out of
+scope: the model-based scores ``noresqa_mos`` and ``torchsquim_stoi`` (they need downloaded
+weights, so batches without a reference log nothing here) and the audio logging.
 
 Lightning is optional: when ``lightning`` is importable the class is a real ``LightningModule``
 (so ``run.py lightning_module=eben`` drives it through ``Trainer.fit``); otherwise a small
@@ -13,6 +16,8 @@ from __future__ import annotations
 from typing import Dict, List
 
 import torch
+
+from ..metrics import ScaleInvariantSignalDistortionRatio, ShortTimeObjectiveIntelligibility
 
 try:  # pragma: no cover - not installed in the build image
     from lightning import LightningModule as _Base
@@ -81,3 +86,33 @@ class BaseSELightningModule(_Base):
         self.sample_rate = sample_rate
         self.description = description
         self.dataloader_names = None
+        # base_se.py:38-45 (the two metrics that need no pretrained network); no parameters or buffers, so no state_dict keys
+        self.metrics = torch.nn.ModuleDict(dict(torchmetrics_si_sdr=ScaleInvariantSignalDistortionRatio(),
+                                                torchmetrics_stoi=ShortTimeObjectiveIntelligibility(fs=16000)))
+
+    def _to_16k(self, x: torch.Tensor) -> torch.Tensor:
+        """torchaudio ``Resample(sample_rate, 16000)`` of the reference (identity at 16 kHz)."""
+        if int(self.sample_rate) == 16000:
+            return x
+        from ..augment import resample
+
+        return resample(x.contiguous(), int(self.sample_rate), 16000)
+
+    def common_eval_logging(self, stage: str, outputs, batch_idx: int, dataloader_idx: int = 0) -> None:
+        """base_se.py:67-130: with a reference, SI-SDR and STOI of the enhanced speech at 16 kHz, batch means logged as
+        ``{stage}/torchmetrics_si_sdr{suffix}`` and ``{stage}/torchmetrics_stoi{suffix}`` (the metric objects also accumulate,
+        as torchmetrics' forward does).  Without a reference the reference logs only model-based scores, which are out of
+        scope: nothing is logged."""
+        if "reference" not in outputs:
+            return
+        names = getattr(self, "dataloader_names", None)
+        suffix = f"/{names[dataloader_idx]}" if names is not None else ""
+        enhanced, reference = self._to_16k(outputs["enhanced"]), self._to_16k(outputs["reference"])
+        for key, metric in self.metrics.items():
+            self.log(f"{stage}/{key}{suffix}", metric(enhanced, reference), sync_dist=True, prog_bar=True, add_dataloader_idx=False)
+
+    def on_validation_batch_end(self, outputs, batch, batch_idx: int, dataloader_idx: int = 0) -> None:
+        self.common_eval_logging("validation", outputs, batch_idx, dataloader_idx)
+
+    def on_test_batch_end(self, outputs, batch, batch_idx: int, dataloader_idx: int = 0) -> None:
+        self.common_eval_logging("test", outputs, batch_idx, dataloader_idx)

@@ -1,0 +1,149 @@
+"""Speech-quality validation metrics on the device (the SI-SDR and STOI of ``base_se.py``'s ``common_eval_logging``).
+
+* ``si_sdr(preds, target)``: ``torchmetrics.functional.scale_invariant_signal_distortion_ratio(preds, target, zero_mean=False)``,
+  one HIP launch (``eben_si_sdr``) with fp64 sums and a second pass for the noise energy.
+* ``stoi(preds, target, fs)``: ``torchmetrics.functional.short_time_objective_intelligibility(preds, target, fs)``, i.e. pystoi
+  0.4.x ``stoi(target, preds, fs, extended=False)`` per clip, restated as four HIP launches (``eben_stoi``) over the whole batch:
+  resampling to 10 kHz, silence removal, third-octave band envelopes, segment correlations.  pystoi is not installed here,
+  so its conventions are restated from its published source (parity unpinned, like the auraloss / torchaudio restatements).
+
+Both take ``(..., T)`` float tensors on a HIP device and return ``(...)`` float32 on that device, with torchmetrics' argument
+order (preds first).  There is no CPU path: a CPU tensor raises ``EbenError`` (the float64 restatement used to check these
+kernels is test code under ``tests/``).
+
+``ScaleInvariantSignalDistortionRatio`` and ``ShortTimeObjectiveIntelligibility`` mirror the torchmetrics classes
+(``update`` / ``compute`` / ``reset``; ``forward`` returns the batch mean and accumulates).  Their running sum and count
+live on the device as plain attributes, not buffers, so a module that holds them keeps its ``state_dict`` keys.
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+import torch
+
+from ._lib import EbenError, check, load, ptr, stream
+
+STOI_FS = 10000
+
+
+def _rows(preds: torch.Tensor, target: torch.Tensor, what: str) -> Tuple[torch.Tensor, torch.Tensor, Tuple[int, ...]]:
+    if preds.shape != target.shape:
+        raise ValueError(f"{what}: preds and target must have the same shape, got {tuple(preds.shape)} and {tuple(target.shape)}")
+    if preds.dim() < 1 or preds.shape[-1] < 1:
+        raise ValueError(f"{what}: expected (..., time) signals, got shape {tuple(preds.shape)}")
+    for t in (preds, target):
+        if not t.is_cuda:
+            raise EbenError(f"{what} runs only on an MI355X HIP device (got a tensor on '{t.device}'); there is no CPU path")
+    lead = tuple(preds.shape[:-1])
+    t = preds.shape[-1]
+    p2 = preds.detach().to(torch.float32).contiguous().reshape(-1, t)
+    g2 = target.detach().to(torch.float32).contiguous().reshape(-1, t)
+    return p2, g2, lead
+
+
+def si_sdr(preds: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """Scale-invariant SDR in dB per signal: (..., T) -> (...)."""
+    p2, g2, lead = _rows(preds, target, "si_sdr")
+    out = torch.empty(p2.shape[0], dtype=torch.float32, device=p2.device)
+    check(load().eben_si_sdr(ptr(p2), ptr(g2), p2.shape[0], p2.shape[1], ptr(out), stream()), "si_sdr")
+    return out.reshape(lead)
+
+
+def stoi_resample_table(fs: int) -> Tuple[np.ndarray, int, int]:
+    """(up * h as float64, up, down) of pystoi's ``resample_oct(x, 10000, fs)``: a Kaiser-windowed sinc (60 dB rejection,
+    roll-off a tenth of the cut-off) normalised to unit sum; resample_poly scales an array window by ``up``."""
+    g = math.gcd(STOI_FS, int(fs))
+    up, down = STOI_FS // g, int(fs) // g
+    cutoff = 1.0 / (2 * max(up, down))
+    rejection_db = 60.0
+    half = math.ceil((rejection_db - 8) / (28.714 * cutoff / 10))
+    n = np.arange(-half, half + 1)
+    h = np.kaiser(2 * half + 1, 0.1102 * (rejection_db - 8.7)) * (2 * up * cutoff * np.sinc(2 * cutoff * n))
+    return up * h / h.sum(), up, down
+
+
+_tables: Dict[Tuple[int, torch.device], torch.Tensor] = {}
+
+
+def stoi(preds: torch.Tensor, target: torch.Tensor, fs: int) -> torch.Tensor:
+    """Classic STOI per signal (target = clean reference): (..., T) -> (...)."""
+    p2, g2, lead = _rows(preds, target, "stoi")
+    fs = int(fs)
+    if fs <= 0:
+        raise ValueError(f"stoi: fs must be positive, got {fs}")
+    rows, t = p2.shape
+    dev = p2.device
+    lib = load()
+    table, taps = None, 0
+    if fs != STOI_FS:
+        key = (fs, dev)
+        if key not in _tables:
+            _tables[key] = torch.from_numpy(stoi_resample_table(fs)[0]).to(torch.float32).to(dev)
+        table = _tables[key]
+        taps = table.numel()
+    ws_bytes = lib.eben_stoi_workspace(rows, t, fs)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(rows, dtype=torch.float32, device=dev)
+    check(lib.eben_stoi(ptr(g2), ptr(p2), rows, t, fs, ptr(table), taps, ws.data_ptr(), ws_bytes, ptr(out), stream()), "stoi")
+    return out.reshape(lead)
+
+
+class _MeanMetric(torch.nn.Module):
+    """torchmetrics-style mean of a per-signal metric: state is a device-side sum and count (not buffers)."""
+
+    def __init__(self):
+        super().__init__()
+        self._sum: Optional[torch.Tensor] = None
+        self._count: Optional[torch.Tensor] = None
+
+    def _values(self, preds: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        raise NotImplementedError
+
+    def _accumulate(self, values: torch.Tensor) -> None:
+        if self._sum is None or self._sum.device != values.device:
+            self._sum = torch.zeros((), dtype=torch.float64, device=values.device)
+            self._count = torch.zeros((), dtype=torch.int64, device=values.device)
+        self._sum += values.sum(dtype=torch.float64)
+        self._count += values.numel()
+
+    def update(self, preds: torch.Tensor, target: torch.Tensor) -> None:
+        self._accumulate(self._values(preds, target))
+
+    def compute(self) -> torch.Tensor:
+        if self._sum is None:
+            raise RuntimeError(f"{type(self).__name__}.compute() called before any update()")
+        return (self._sum / self._count).to(torch.float32)
+
+    def reset(self) -> None:
+        self._sum = self._count = None
+
+    def forward(self, preds: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        """Batch mean of this call; also accumulated into the running state."""
+        values = self._values(preds, target)
+        self._accumulate(values)
+        return values.mean()
+
+
+class ScaleInvariantSignalDistortionRatio(_MeanMetric):
+    def __init__(self, zero_mean: bool = False):
+        super().__init__()
+        if zero_mean:
+            raise NotImplementedError("only zero_mean=False (torchmetrics' default, the one base_se.py uses) is implemented")
+        self.zero_mean = zero_mean
+
+    def _values(self, preds, target):
+        return si_sdr(preds, target)
+
+
+class ShortTimeObjectiveIntelligibility(_MeanMetric):
+    def __init__(self, fs: int, extended: bool = False):
+        super().__init__()
+        if extended:
+            raise NotImplementedError("only classic STOI (extended=False, the one base_se.py uses) is implemented")
+        self.fs = int(fs)
+        self.extended = extended
+
+    def _values(self, preds, target):
+        return stoi(preds, target, self.fs)

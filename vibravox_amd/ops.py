@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import gc
 import os
 import weakref
 from dataclasses import dataclass
@@ -555,6 +556,20 @@ def graphs_captured() -> int:
     return sum(1 for r in list(_replayed) if r.graph is not None)
 
 
+@contextlib.contextmanager
+def _no_gc():
+    """Keeps Python's cyclic garbage collector off while a HIP graph is being captured.  torch.cuda.graph collects once on entry,
+    but a collection that triggers mid-capture destroys whatever unreachable objects it finds there -- graphs, streams, events and
+    tensors of earlier modules -- and releasing those inside a capture aborts the process."""
+    was = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was:
+            gc.enable()
+
+
 class ReplayedPrepack:
     """Graph replay of a prepack sequence.  Rebuilding the packed weight images after an optimiser step is ~150 tiny launches per
     step (one or two per layer and direction) whose cost is entirely host-side: ~3 ms of Python / launch time per step during which
@@ -584,7 +599,7 @@ class ReplayedPrepack:
     def _capture(body, stream_):
         """``body()`` recorded into a HIP graph on ``stream_`` (tests substitute a recorder)."""
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, stream=stream_, capture_error_mode="thread_local"):
+        with _no_gc(), torch.cuda.graph(graph, stream=stream_, capture_error_mode="thread_local"):
             body()
         return graph
 
@@ -655,7 +670,7 @@ class ReplayedChain:
         stream (a sequence that normally runs on the default stream, which cannot capture); the replays are launched on whatever stream
         is current then."""
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, stream=stream_, capture_error_mode="thread_local"):
+        with _no_gc(), torch.cuda.graph(graph, stream=stream_, capture_error_mode="thread_local"):
             out = fn()
         return graph, out
 
