@@ -61,5 +61,7 @@ struct Tap3Plan {
 
 // bigtap.hip
 int tap4_launch(const Tap3Plan& p, const Tap3Args& a, hipStream_t st);
+// thin_bl.hip: the thin bundle-layout launches of a tap3 plan, one kernel per direction; 1 (result in *rc) when it took the launch
+int thin_bl_launch(const Tap3Plan& p, const Tap3Args& a, int reflect, int nblocks, hipStream_t st, int* rc);
 
 }  // namespace eben

@@ -1569,6 +1569,10 @@ int tap3_launch(const Canon& c, int dir, const TapIO& io, int reflect, hipStream
     if (p.nph > 8) return fail(EBEN_EUNSUPPORTED, "tap4: more than 8 output phases");
     return tap4_launch(p, a, st);
   }
+  {
+    int rc = EBEN_OK;
+    if (thin_bl_launch(p, a, reflect, (int)nb, st, &rc)) return rc;
+  }
 #define EBEN_T3_CASE(FMV)                                                          \
   switch (p.XRB) {                                                                 \
     case 2: return launch3_cfg<FMV, 2>(a, (int)nb, p.lds_bytes, p.npw, p.npx, st);               \
