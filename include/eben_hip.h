@@ -78,9 +78,10 @@ typedef struct EbenConv1dDesc {
 } EbenConv1dDesc;
 
 EBEN_API const char* eben_last_error(void);
-/* Bumped whenever a POD structure, an entry point's signature or a table stride changes (2: EbenWnBwdItem.col_perm_k; 3: eben_rubl_*; 4: eben_si_sdr / eben_stoi).
+/* Bumped whenever a POD structure, an entry point's signature or a table stride changes (2: EbenWnBwdItem.col_perm_k; 3: eben_rubl_*; 4: eben_si_sdr / eben_stoi;
+ * 5: eben_multirate_down* / eben_resample_adjoint).
  * eben_version() returns the value the library was built with; bindings compare it with the header they were written against. */
-#define EBEN_ABI_VERSION 4
+#define EBEN_ABI_VERSION 5
 EBEN_API int eben_version(void);
 /* fills name with the device's gcnArchName; returns compute-unit count (or negative) */
 EBEN_API int eben_device_info(char* name, size_t name_bytes);
@@ -512,6 +513,20 @@ EBEN_API int eben_phase_vocoder(const float* spec, float* out, int rows, int bin
                        void* stream);
 EBEN_API int eben_resample(const float* x, const float* kernels, float* out, int rows, int t_in, int t_out, int orig, int nw,
                   int width, void* stream);
+
+/* ---- multi-rate downsampling (MelganMultiScalesDiscriminator: torchaudio Resample, "sinc_interp_kaiser") -----------------
+ * Same arithmetic as eben_resample: y[r, q*nw + p] = sum_{j < taps} kernels[p, j] * x[r, q*orig + j - width] (zero outside the row).
+ * eben_multirate_down: every scale s = 1 .. scales-1 reduces to orig = 2^s, new = 1; tables holds their (1, taps_s =
+ *   2*widths[s-1] + 2^s) kernels back to back on the device; widths (host, scales-1 ints); outs (host array of scales-1 device
+ *   pointers) receive (rows, ceil(t_in / 2^s)).  One launch for all scales.  2 <= scales <= 6.
+ * eben_multirate_down_adjoint: dx = g0 + sum_s A_s^T gs[s-1], one launch, no atomics (g0 nullable = 0).
+ * eben_resample_adjoint: dx = A^T g for eben_resample's arguments (accumulate != 0: dx += A^T g); no atomics. */
+EBEN_API int eben_multirate_down(const float* x, const float* tables, const int* widths, float* const* outs, int rows, int t_in,
+                                 int scales, void* stream);
+EBEN_API int eben_multirate_down_adjoint(const float* g0, const float* const* gs, const float* tables, const int* widths, float* dx,
+                                         int rows, int t_in, int scales, void* stream);
+EBEN_API int eben_resample_adjoint(const float* g, const float* kernels, float* dx, int rows, int t_in, int t_out, int orig, int nw,
+                                   int width, int accumulate, void* stream);
 
 /* ---- misc ------------------------------------------------------------------------------- */
 /* out[0] = sqrt(sum x^2) (torch.norm at eben.py:226); `out` must hold 257 floats (scratch) */

@@ -86,6 +86,10 @@ def compose(overrides: List[str]) -> Dict[str, Any]:
     for ov in overrides:
         key, _, val = ov.partition("=")
         bare = key.lstrip("+")
+        group_path, at, package = bare.partition("@")   # Hydra's group/option@package=choice, e.g. a dnn_module as the discriminator
+        if at and os.path.exists(os.path.join(CONFIG_DIR, *group_path.split("/"), val + ".yaml")):
+            group_choice[package] = val
+            continue
         is_group = os.path.isdir(os.path.join(CONFIG_DIR, *bare.split("."))) or bare in ("lightning_module", "lightning_datamodule", "trainer")
         if is_group and os.path.exists(os.path.join(CONFIG_DIR, *bare.split("."), val + ".yaml")):
             group_choice[bare] = val

@@ -197,13 +197,16 @@ SIGNATURES = {
     "eben_si_sdr": (c_int, [_P, _P, c_int, c_int, _P, _P]),
     "eben_stoi_workspace": (c_size_t, [c_int, c_int, c_int]),
     "eben_stoi": (c_int, [_P, _P, c_int, c_int, c_int, _P, c_int, _P, c_size_t, _P, _P]),
+    "eben_multirate_down": (c_int, [_P, _P, POINTER(c_int), POINTER(c_void_p), c_int, c_int, c_int, _P]),
+    "eben_multirate_down_adjoint": (c_int, [_P, POINTER(c_void_p), _P, POINTER(c_int), _P, c_int, c_int, c_int, _P]),
+    "eben_resample_adjoint": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None
 
 
 #: include/eben_hip.h EBEN_ABI_VERSION this module's structures and signatures were written against
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 
 def load(path: Optional[str] = None) -> ctypes.CDLL:

@@ -25,8 +25,28 @@ from . import ops
 from ._lib import check, load, ptr, stream
 
 
-def sinc_resample_kernel(orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99, device=None):
-    """(kernels (new, 2*width+orig) float32, width, orig, new) -- torchaudio.functional._get_sinc_resample_kernel, hann."""
+KAISER_BETA = 14.769656459379492   # torchaudio's default beta of "sinc_interp_kaiser"
+
+
+def sinc_resample_kernel(orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99, device=None,
+                         resampling_method: str = "sinc_interp_hann", beta: Optional[float] = None):
+    """(kernels (new, 2*width+orig) float32, width, orig, new) -- torchaudio.functional._get_sinc_resample_kernel.
+
+    The phase/tap grid t is built in float64 and clamped to +-lowpass_filter_width; the sinc, the window and the
+    ``base / orig`` scale are float64 and the product is cast to float32 once.  Windows:
+
+      * ``"sinc_interp_hann"`` (default): cos(pi t / (2 width))^2.
+      * ``"sinc_interp_kaiser"``: i0(beta sqrt(1 - (t/width)^2)) / i0(beta), beta defaulting to 14.769656459379492.  As
+        torchaudio does, beta becomes a 0-dim tensor built from a Python float at the default dtype (float32, so beta is
+        rounded to float32 first); its product with the float64 grid is float64, so the numerator i0 runs in float64, while
+        the denominator i0(beta) is evaluated on the float32 scalar in float32 and promoted to float64 by the division.
+
+    torchaudio is not installed here: both windows are restatements, not pinned against it.  One known difference:
+    torchaudio forms the phase offsets ``arange(0, -new, -1) / new`` at the default dtype (float32) before adding the
+    float64 tap grid; here they are float64 (exact for new = 1, within ~1e-7 of torchaudio's table otherwise).
+    """
+    if resampling_method not in ("sinc_interp_hann", "sinc_interp_kaiser"):
+        raise ValueError(f"Invalid resampling method: {resampling_method}")
     g = math.gcd(int(orig_freq), int(new_freq))
     orig, new = int(orig_freq) // g, int(new_freq) // g
     base = min(orig, new) * rolloff
@@ -34,7 +54,11 @@ def sinc_resample_kernel(orig_freq: int, new_freq: int, lowpass_filter_width: in
     idx = torch.arange(-width, width + orig, dtype=torch.float64)[None, :] / orig
     t = torch.arange(0, -new, -1, dtype=torch.float64)[:, None] / new + idx
     t = (t * base).clamp_(-lowpass_filter_width, lowpass_filter_width)
-    window = torch.cos(t * math.pi / lowpass_filter_width / 2) ** 2
+    if resampling_method == "sinc_interp_hann":
+        window = torch.cos(t * math.pi / lowpass_filter_width / 2) ** 2
+    else:
+        beta_t = torch.tensor(float(KAISER_BETA if beta is None else beta), dtype=torch.float32)
+        window = torch.i0(beta_t * torch.sqrt(1 - (t / lowpass_filter_width) ** 2)) / torch.i0(beta_t)
     t = t * math.pi
     k = torch.where(t == 0, torch.ones_like(t), torch.sin(t) / t) * window * (base / orig)
     return k.to(torch.float32).contiguous().to(device), width, orig, new

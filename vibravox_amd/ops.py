@@ -1189,6 +1189,128 @@ def fir_interp_sum(y, w, lx, stride, off0):
 
 
 # --------------------------------------------------------------------------------------------
+# multi-rate downsampling (MelganMultiScalesDiscriminator: torchaudio Resample, "sinc_interp_kaiser")
+# --------------------------------------------------------------------------------------------
+_multirate_cache: Dict[tuple, object] = {}
+
+
+def _kaiser_table(orig_freq: int, new_freq: int, device):
+    """(kernels, width, orig, new) of Resample(orig_freq, new_freq, "sinc_interp_kaiser"), cached per (rates, device)."""
+    key = ("kaiser", int(orig_freq), int(new_freq), device)
+    if key not in _multirate_cache:
+        from .augment import sinc_resample_kernel
+
+        _multirate_cache[key] = sinc_resample_kernel(orig_freq, new_freq, device=device, resampling_method="sinc_interp_kaiser")
+    return _multirate_cache[key]
+
+
+def _fused_plan(sample_rate: int, scales: int, device):
+    """Packed tables and widths of the fused path, or None when some scale does not reduce to new = 1 (orig = 2^s)."""
+    key = ("fused", int(sample_rate), int(scales), device)
+    if key not in _multirate_cache:
+        plan = None
+        if 2 <= scales <= 6 and all(_kaiser_table(sample_rate, sample_rate // 2 ** s, "cpu")[2:] == (2 ** s, 1) for s in range(1, scales)):
+            tabs = [_kaiser_table(sample_rate, sample_rate // 2 ** s, "cpu") for s in range(1, scales)]
+            packed = torch.cat([k.reshape(-1) for k, *_ in tabs]).to(device)
+            plan = (packed, (ctypes.c_int * (scales - 1))(*[w for _, w, _, _ in tabs]))
+        _multirate_cache[key] = plan
+    return _multirate_cache[key]
+
+
+class _MultirateFusedFn(torch.autograd.Function):
+    """(x, A_1 x, ..., A_{S-1} x) for scales that all reduce to orig = 2^s, new = 1: one forward, one adjoint launch.
+    The identity scale is returned as-is (autograd hands it back as a view of x) so that its gradient joins the adjoint."""
+
+    @staticmethod
+    def forward(ctx, x, plan, scales: int):
+        packed, widths = plan
+        lead, t = x.shape[:-1], x.shape[-1]
+        rows = max(1, x.numel() // max(t, 1))
+        x2 = x.contiguous()
+        outs = [torch.empty((*lead, -(-t // 2 ** s)), dtype=torch.float32, device=x.device) for s in range(1, scales)]
+        check(load().eben_multirate_down(ptr(x2), ptr(packed), widths, _ptr_array(outs), rows, t, scales, stream()), "multirate_down")
+        ctx.geom = (plan, scales, rows, t, x.shape)
+        return (x, *outs)
+
+    @staticmethod
+    def backward(ctx, g0, *gs):
+        plan, scales, rows, t, shape = ctx.geom
+        packed, widths = plan
+        g0 = g0.contiguous()
+        gs = [g.contiguous() for g in gs]
+        dx = torch.empty(shape, dtype=torch.float32, device=g0.device)
+        check(load().eben_multirate_down_adjoint(ptr(g0), _ptr_array(gs), ptr(packed), widths, ptr(dx), rows, t, scales, stream()),
+              "multirate_down_adjoint")
+        return dx, None, None
+
+
+def _resample_fwd(x2, k, rows, t, t_out, orig, new, width):
+    out = torch.empty((rows, t_out), dtype=torch.float32, device=x2.device)
+    check(load().eben_resample(ptr(x2), ptr(k), ptr(out), rows, t, t_out, orig, new, width, stream()), "resample")
+    return out
+
+
+class _ResampleFn(torch.autograd.Function):
+    """torchaudio _apply_sinc_resample_kernel for any reduced ratio orig : new: forward eben_resample, backward its adjoint."""
+
+    @staticmethod
+    def forward(ctx, x, table):
+        k, width, orig, new = table
+        lead, t = x.shape[:-1], x.shape[-1]
+        rows = max(1, x.numel() // max(t, 1))
+        t_out = -(-new * t // orig)
+        ctx.geom = (table, rows, t, t_out, x.shape)
+        return _resample_fwd(x.contiguous().reshape(rows, t), k, rows, t, t_out, orig, new, width).reshape(*lead, t_out)
+
+    @staticmethod
+    def backward(ctx, g):
+        (k, width, orig, new), rows, t, t_out, shape = ctx.geom
+        g = g.contiguous()
+        dx = torch.empty(shape, dtype=torch.float32, device=g.device)
+        check(load().eben_resample_adjoint(ptr(g), ptr(k), ptr(dx), rows, t, t_out, orig, new, width, 0, stream()), "resample_adjoint")
+        return dx, None
+
+
+def resample_adjoint(g: torch.Tensor, orig_freq: int, new_freq: int, t_in: int, accumulate_into: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A^T g of kaiser_resample(., orig_freq, new_freq) for inputs of length t_in (dx += A^T g if accumulate_into is given)."""
+    k, width, orig, new = _kaiser_table(orig_freq, new_freq, g.device)
+    g = g.contiguous()
+    rows, t_out = max(1, g.numel() // g.shape[-1]), g.shape[-1]
+    dx = accumulate_into if accumulate_into is not None else torch.empty((*g.shape[:-1], t_in), dtype=torch.float32, device=g.device)
+    check(load().eben_resample_adjoint(ptr(g), ptr(k), ptr(dx), rows, t_in, t_out, orig, new, width, int(accumulate_into is not None),
+                                       stream()), "resample_adjoint")
+    return dx
+
+
+def kaiser_resample(x: torch.Tensor, orig_freq: int, new_freq: int) -> torch.Tensor:
+    """torchaudio Resample(orig_freq, new_freq, resampling_method="sinc_interp_kaiser")(x), differentiable; x (..., time).
+    orig == new returns x itself, as Resample.forward does."""
+    if not x.is_cuda:
+        ptr(x)   # raises: there is no CPU path
+    if int(orig_freq) == int(new_freq):
+        return x
+    return _ResampleFn.apply(x, _kaiser_table(orig_freq, new_freq, x.device))
+
+
+def multirate_downsample(x: torch.Tensor, sample_rate: int, scales: int) -> List[torch.Tensor]:
+    """[Resample(sample_rate, sample_rate // 2**s, "sinc_interp_kaiser")(x) for s < scales] on the device, differentiable.
+
+    When every ratio reduces to new = 1 (sample_rate divisible by 2^(scales-1)) all scales come from one fused forward launch and
+    their gradients, the identity scale's included, go back through one fused adjoint launch; otherwise each scale runs the
+    general rational path (eben_resample / eben_resample_adjoint).  Scale 0 is x itself (a view of it on the fused path)."""
+    if not x.is_cuda:
+        ptr(x)   # raises: there is no CPU path
+    if scales < 1:
+        raise ValueError(f"scales must be >= 1, got {scales}")
+    if scales == 1:
+        return [x]
+    plan = _fused_plan(sample_rate, scales, x.device) if x.dtype is torch.float32 else None
+    if plan is not None:
+        return list(_MultirateFusedFn.apply(x, plan, scales))
+    return [kaiser_resample(x, sample_rate, sample_rate // 2 ** s) for s in range(scales)]
+
+
+# --------------------------------------------------------------------------------------------
 # losses
 # --------------------------------------------------------------------------------------------
 def _ptr_array(tensors: Sequence[torch.Tensor]):
