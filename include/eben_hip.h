@@ -462,6 +462,8 @@ EBEN_API int eben_stft_frames(const float* sig, float* out, int rows, int t, int
 EBEN_API int eben_stft_frames_folded(const float* sig, float* out, int rows, int t, int win, int hop, int pad, int frames, int split,
                             void* stream);
 EBEN_API int eben_split3(const float* in, float* out, int groups, int rows_per_group, long long cols, void* stream);
+/* 1 if eben_overlap_add_folded takes its LDS-tile launch at this geometry (EBEN_OLA_TILED=0 at process start: never), else 0. */
+EBEN_API int eben_overlap_add_folded_tiled(int lx, int win, int hop, int pad);
 EBEN_API int eben_overlap_add_folded(const float* frames_buf, float* x, int batch, int lx, int win, int frames, int hop, int pad,
                             int accumulate, long long row_stride, long long j_stride, void* stream);
 EBEN_API int eben_stft_loss_sums_ex(const float* spec_x, const float* spec_y, int rows, int bins, int frames, long long row_stride,

@@ -1,0 +1,115 @@
+"""CPU (no GPU): the geometry of MultiResolutionSTFTLoss's per-resolution plans against torch.stft(center=True) in float64.
+
+The device computes |STFT| as (windowed-DFT basis) x (frames of `win` samples taken at reflect padding `plan.pad`, `plan.frames(t)` of
+them per row).  Here that plan -- the module's own basis, pad and frame count -- is restated in float64 (index arithmetic of the framing
+kernels, one matrix product) and compared with torch.stft at every parity of (n_fft, win), win == n_fft, hop > win, lengths at
+t % hop in {0, 1, hop - 1} and the shortest length torch accepts.  Where a plan takes a folded form (the even / odd parts of the frame
+about the window centre, StftPlan.folded_parts), that contraction is restated too."""
+import pytest
+import torch
+
+from vibravox_amd.torch_modules.losses.mrstft_loss import MultiResolutionSTFTLoss
+
+GEOMETRIES = [
+    # (n_fft, hop, win): the three defaults, every parity of (n_fft, win), win == n_fft, hop > win, a short window at hop 1-3
+    (512, 50, 240), (1024, 120, 600), (2048, 240, 1200),
+    (512, 50, 241), (511, 50, 240), (511, 50, 241), (1024, 120, 601),
+    (256, 64, 256), (255, 64, 255), (256, 64, 255), (255, 64, 254),
+    (128, 300, 64), (129, 200, 101), (64, 100, 63),
+    (16, 1, 16), (32, 2, 32), (127, 3, 126),
+]
+
+
+def _lengths(n_fft, hop):
+    base = max(4000 - 4000 % hop, n_fft)   # a multiple of hop past n_fft
+    return sorted({base, base + 1, base + hop - 1, n_fft // 2 + 1})
+
+
+CASES = [(n, h, w, t) for n, h, w in GEOMETRIES for t in _lengths(n, h)]
+
+
+def _plan(n_fft, hop, win):
+    loss = MultiResolutionSTFTLoss(fft_sizes=(n_fft,), hop_sizes=(hop,), win_lengths=(win,))
+    (plan,) = loss._build_plans()
+    return plan
+
+
+def _frames(x, win, hop, pad, frames):
+    """(rows, t) -> (rows, win, frames): sample j of frame f is x[reflect(f*hop + j - pad)], as eben_stft_frames indexes it."""
+    t = x.shape[-1]
+    q = torch.arange(frames).unsqueeze(0) * hop + torch.arange(win).unsqueeze(1) - pad
+    q = torch.where(q < 0, -q, q)
+    q = torch.where(q >= t, 2 * (t - 1) - q, q)
+    assert int(q.min()) >= 0 and int(q.max()) < t, "frames reach past the once-reflected signal"
+    return x[:, q]
+
+
+def _signal(t, seed):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(3, t, generator=g, dtype=torch.float64)
+
+
+def _torch_mag(x, n_fft, hop, win):
+    spec = torch.stft(x, n_fft, hop, win, torch.hann_window(win, dtype=torch.float64), center=True, pad_mode="reflect",
+                      return_complex=True)
+    return spec.abs()
+
+
+@pytest.mark.parametrize("n_fft,hop,win,t", CASES)
+def test_plan_restated_in_float64_matches_torch_stft(n_fft, hop, win, t):
+    plan = _plan(n_fft, hop, win)
+    x = _signal(t, n_fft * 7919 + hop * 31 + win + t)
+    ref = _torch_mag(x, n_fft, hop, win)
+    frames = plan.frames(t)
+    fr = _frames(x, win, hop, plan.pad, frames)
+    basis = plan.basis_f[:, :, 0].double()                    # (2*bins, win)
+    spec = torch.einsum("kj,rjf->rkf", basis, fr)
+    mag = torch.sqrt(spec[:, :plan.bins] ** 2 + spec[:, plan.bins:] ** 2)
+    assert mag.shape == ref.shape, (mag.shape, ref.shape)
+    err = float((mag - ref).abs().max())
+    assert err <= 1e-6 * float(ref.abs().max()), err
+
+
+@pytest.mark.parametrize("n_fft,hop,win,t", CASES)
+def test_folded_plan_restated_in_float64_matches_torch_stft(n_fft, hop, win, t):
+    """The folded contraction (two groups: the real rows over E[m] = s[h+m] + s[h-m], the imaginary rows over O[m] = s[h+m] - s[h-m])
+    rests on the window's centre h = win/2 sitting on the DFT's symmetry point n_fft/2.  Every geometry the plan sends down a folded
+    path must reproduce torch.stft through it; the others must take "dense"."""
+    plan = _plan(n_fft, hop, win)
+    math = plan.math_for("folded")
+    if math != "folded":
+        assert n_fft % 2 or win % 2, (n_fft, win)
+        return
+    h, bins = win // 2, plan.bins
+    x = _signal(t, n_fft * 7919 + hop * 31 + win + t + 1)
+    ref = _torch_mag(x, n_fft, hop, win)
+    fr = _frames(x, win, hop, plan.pad, plan.frames(t))
+    m = torch.arange(1, h)
+    e = torch.cat((fr[:, h:h + 1], fr[:, h + m] + fr[:, h - m]), dim=1)
+    o = torch.cat((torch.zeros_like(fr[:, :1]), fr[:, h + m] - fr[:, h - m]), dim=1)
+    _, w, *_ = plan.folded_parts("folded")                    # (2*bins, h, 1): group 0 rows over E, group 1 rows over O
+    w = w[:, :, 0].double()
+    re, im = torch.einsum("km,rmf->rkf", w[:bins], e), torch.einsum("km,rmf->rkf", w[bins:], o)
+    mag = torch.sqrt(re ** 2 + im ** 2)
+    assert mag.shape == ref.shape
+    err = float((mag - ref).abs().max())
+    assert err <= 1e-6 * float(ref.abs().max()), err
+
+
+@pytest.mark.parametrize("n_fft,hop,win", [g for g in GEOMETRIES if g[0] % 2 == 0 and g[2] % 2 == 0])
+def test_even_geometry_pad_and_frames_unchanged(n_fft, hop, win):
+    """For even n_fft and win the plan is what it was before any parity was accepted: pad win/2, (t + 2 pad - win) // hop + 1 frames,
+    and the folded arithmetic."""
+    plan = _plan(n_fft, hop, win)
+    assert plan.pad == win // 2
+    assert plan.math_for("folded_x6") == "folded_x6"
+    for t in _lengths(n_fft, hop) + [31968, 4321]:
+        assert plan.frames(t) == (t + 2 * (win // 2) - win) // hop + 1
+
+
+@pytest.mark.parametrize("n_fft,win", [(256, 257), (511, 512), (512, 1024)])
+def test_window_longer_than_fft_is_rejected(n_fft, win):
+    with pytest.raises(ValueError):
+        MultiResolutionSTFTLoss(fft_sizes=(n_fft,), hop_sizes=(64,), win_lengths=(win,))
+    with pytest.raises(RuntimeError):   # torch.stft refuses it too
+        torch.stft(torch.zeros(2 * n_fft), n_fft, 64, win, torch.hann_window(win), return_complex=True)

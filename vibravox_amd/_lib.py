@@ -186,6 +186,7 @@ SIGNATURES = {
     "eben_stft_frames": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "eben_stft_frames_folded": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "eben_split3": (c_int, [_P, _P, c_int, c_int, c_int64, _P]),
+    "eben_overlap_add_folded_tiled": (c_int, [c_int, c_int, c_int, c_int]),
     "eben_overlap_add_folded": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64, _P]),
     "eben_stft_loss_sums_ex": (c_int, [_P, _P, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_float, _P, c_size_t, _P, _P]),
     "eben_stft_loss_bwd_ex": (c_int, [_P, _P, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_float, _P, _P, c_float, _P, c_int64, c_int64,

@@ -4,6 +4,7 @@
 // time) float32 rows with coalesced accesses; reductions are two-level and order-deterministic.
 #include "common.h"
 
+#include <cfloat>
 #include <cstdlib>
 
 namespace eben {
@@ -451,7 +452,9 @@ __global__ __launch_bounds__(256) void stft_bwd_kernel(const float* __restrict__
   const long long im_off = L.im_off;
   const int n = bins * frames;
   const float g = gout[0] * scale;
-  const float c_sc = g / ((float)rows * sqrtf(sums[3 * r]) * sqrtf(sums[3 * r + 1]));
+  // d ||Y - X|| is taken as 0 where ||Y - X|| = 0 (a row whose spectra agree exactly), as torch.linalg.vector_norm's backward does:
+  // the floor keeps c_sc finite there, so c_sc * (xm - ym = 0) is 0 rather than inf * 0 = NaN; it leaves every sum >= FLT_MIN as it is
+  const float c_sc = g / ((float)rows * sqrtf(fmaxf(sums[3 * r], FLT_MIN)) * sqrtf(sums[3 * r + 1]));
   const float c_lg = g / ((float)rows * (float)bins * (float)frames);
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
     const int k = i / frames;
@@ -1363,14 +1366,21 @@ extern "C" int eben_overlap_add(const float* frames_buf, float* x, int batch, in
   return eben_overlap_add_ex(frames_buf, x, batch, lx, win, frames, hop, pad, reflect, accumulate, (long long)win * frames, frames, stream);
 }
 
+extern "C" int eben_overlap_add_folded_tiled(int lx, int win, int hop, int pad) {
+  static const bool tiled = !(getenv("EBEN_OLA_TILED") && atoi(getenv("EBEN_OLA_TILED")) == 0);
+  if (lx <= 0 || win <= 0 || hop <= 0 || pad < 0) return 0;
+  const int fcap = OLA_U / hop + win / hop + pad / hop + 4;
+  const size_t lds = sizeof(float) * (size_t)fcap * win;
+  // fcap <= 256: the tile's unfold spreads its <= fcap frames over the 256 lanes (mstep = 256 / nfp would be 0 past that, at hop 1-2)
+  return tiled && fcap <= 256 && lds <= 64 * 1024 && pad < win && lx > 2 * pad;
+}
 extern "C" int eben_overlap_add_folded(const float* frames_buf, float* x, int batch, int lx, int win, int frames, int hop, int pad,
                                        int accumulate, long long row_stride, long long j_stride, void* stream) {
   EBEN_REQUIRE(frames_buf && x && batch > 0 && lx > 0 && win > 0 && (win & 1) == 0 && frames > 0 && hop > 0 && pad >= 0 && pad < lx,
                "bad overlap_add_folded arguments");
-  static const bool tiled = !(getenv("EBEN_OLA_TILED") && atoi(getenv("EBEN_OLA_TILED")) == 0);
   const int fcap = OLA_U / hop + win / hop + pad / hop + 4;
   const size_t lds = sizeof(float) * (size_t)fcap * win;
-  if (tiled && lds <= 64 * 1024 && pad < win && lx > 2 * pad) {
+  if (eben_overlap_add_folded_tiled(lx, win, hop, pad)) {
     hipLaunchKernelGGL(overlap_add_folded_t_kernel, dim3(ceil_div(lx, OLA_U), batch), dim3(256), lds, as_stream(stream), frames_buf, x, lx, win,
                        frames, hop, pad, accumulate, row_stride, j_stride, fcap);
     EBEN_CHECK_LAUNCH("overlap_add_folded_t_kernel");

@@ -1438,6 +1438,15 @@ class StftPlan:
     folded: Optional[dict] = None   # math -> (spec_f, basis_f, spec_t, basis_t, cache_fwd, cache_bwd), built on first use
     gemm: Optional[dict] = None     # (math, which) -> (basis address, packed image, basis) for the grouped GEMM kernel
 
+    def frames(self, t: int) -> int:
+        """Frames of a length-t signal: torch.stft(center=True) pads n_fft // 2 on each side and steps an n_fft window by hop."""
+        return (t + 2 * (self.n_fft // 2) - self.n_fft) // self.hop + 1
+
+    def math_for(self, math: str) -> str:
+        """The arithmetic a plan runs: the folded forms need the window's centre h = win / 2 on the DFT's symmetry point n_fft / 2
+        (win and n_fft even, frames at reflect padding win / 2); every other geometry takes "dense"."""
+        return math if self.win % 2 == 0 and self.n_fft % 2 == 0 and self.pad == self.win // 2 else "dense"
+
     def gemm_image(self, math: str, which: int, basis: torch.Tensor) -> torch.Tensor:
         """Packed basis of the folded contraction for ``eben_gemm_fwd``: which = 0 the forward's (2 groups x bins x win/2), 1 its
         transpose's (2 groups x win/2 x bins); built once per (math, basis storage) -- the bases are constants."""
@@ -1453,6 +1462,49 @@ class StftPlan:
             check(lib.eben_gemm_pack(cmath, 2, m, k, ptr(basis), ptr(wp), stream()), "gemm_pack")
             hit = self.gemm[key] = (basis.data_ptr(), wp, basis)
         return hit[1]
+
+    def dft(self, math: str, fr: torch.Tensor, cols: int) -> torch.Tensor:
+        """(1, 2*bins, cols) windowed DFT of a frame matrix: fr is (1, win, cols) from eben_stft_frames for "dense", else the
+        (1, c_in, cols) parts from eben_stft_frames_folded (split for "bf16x3")."""
+        lib, st = load(), stream()
+        if math == "dense":
+            spec_f, basis_f, cache, cmath = self.spec_f, self.basis_f, self.cache_fwd, MATH_F32
+        else:
+            spec_f, basis_f, _, _, cache, _ = self.folded_parts(math)
+            cmath = _STFT_CONV_MATH.get(math, MATH_F32)
+        spec = torch.empty((1, 2 * self.bins, cols), dtype=torch.float32, device=fr.device)
+        if STFT_GEMM and math in ("folded_x3", "folded_x6"):
+            # the folded contraction as what it is, a 2-group GEMM (pw_gemm.hip): no input tile, no staging pass per row tile
+            check(lib.eben_gemm_fwd(cmath, 2, self.bins, self.win // 2, cols, ptr(fr), ptr(self.gemm_image(math, 0, basis_f)), ptr(spec), st),
+                  "stft_fwd")
+        else:
+            d2 = conv_desc(spec_f, 1, cols, cmath)
+            pw = pack_weights(spec_f, d2, basis_f, None, cache, False)
+            check(lib.eben_conv1d_fwd(ctypes.byref(d2), ptr(fr), ptr(pw.wp_fwd), None, None, ptr(spec), st), "stft_fwd")
+        return spec
+
+    def dft_t(self, math: str, dspec: torch.Tensor, cols: int) -> torch.Tensor:
+        """The adjoint of ``dft``: (1, 2*bins, cols) -> (1, win, cols) frame gradients ("dense") or the (1, 2*(win/2), cols) [dE ; dO]
+        parts eben_overlap_add_folded takes."""
+        lib, st = load(), stream()
+        if math == "dense":
+            spec_t, basis_t, cache, cmath = self.spec_t, self.basis_t, self.cache_bwd, MATH_F32
+        else:
+            _, _, spec_t, basis_t, _, cache = self.folded_parts(math)
+            cmath = _STFT_CONV_MATH.get(math, MATH_F32)
+            if math == "bf16x3":
+                dsplit = torch.empty((1, spec_t.c_in, cols), dtype=torch.float32, device=dspec.device)
+                check(lib.eben_split3(ptr(dspec), ptr(dsplit), 2, self.bins, cols, st), "split3")
+                dspec = dsplit
+        dfr = torch.empty((1, spec_t.c_out, cols), dtype=torch.float32, device=dspec.device)
+        if STFT_GEMM and math in ("folded_x3", "folded_x6"):
+            check(lib.eben_gemm_fwd(cmath, 2, self.win // 2, self.bins, cols, ptr(dspec), ptr(self.gemm_image(math, 1, basis_t)), ptr(dfr), st),
+                  "stft_bwd_gemm")
+        else:
+            d1 = conv_desc(spec_t, 1, cols, cmath)
+            pw = pack_weights(spec_t, d1, basis_t, None, cache, False)
+            check(lib.eben_conv1d_fwd(ctypes.byref(d1), ptr(dspec), ptr(pw.wp_fwd), None, None, ptr(dfr), st), "stft_bwd_gemm")
+        return dfr
 
     def folded_parts(self, math: str):
         """Weights of the folded pointwise convs (eben_stft_frames_folded): forward, 2 groups x (nsub*h -> bins) with
@@ -1515,27 +1567,17 @@ class _MRSTFTFn(torch.autograd.Function):
         total = None
         saved = []
         for p in plans:
-            frames = (t + 2 * p.pad - p.win) // p.hop + 1
+            frames = p.frames(t)
             cols = 2 * rows * frames
-            math = p.math if p.win % 2 == 0 and p.pad == p.win // 2 else "dense"
+            math = p.math_for(p.math)
             if math == "dense":
                 fr = torch.empty((1, p.win, cols), dtype=torch.float32, device=x.device)
                 check(lib.eben_stft_frames(ptr(sig), ptr(fr), 2 * rows, t, p.win, p.hop, p.pad, frames, st), "stft_frames")
-                spec_f, basis_f, cache, cmath = p.spec_f, p.basis_f, p.cache_fwd, MATH_F32
             else:
-                spec_f, basis_f, _, _, cache, _ = p.folded_parts(math)
-                cmath = _STFT_CONV_MATH.get(math, MATH_F32)
-                fr = torch.empty((1, spec_f.c_in, cols), dtype=torch.float32, device=x.device)
+                fr = torch.empty((1, p.folded_parts(math)[0].c_in, cols), dtype=torch.float32, device=x.device)
                 check(lib.eben_stft_frames_folded(ptr(sig), ptr(fr), 2 * rows, t, p.win, p.hop, p.pad, frames, 1 if math == "bf16x3" else 0, st),
                       "stft_frames_folded")
-            spec = torch.empty((1, 2 * p.bins, cols), dtype=torch.float32, device=x.device)
-            if STFT_GEMM and math in ("folded_x3", "folded_x6"):
-                # the folded contraction as what it is, a 2-group GEMM (pw_gemm.hip): no input tile, no staging pass per row tile
-                check(lib.eben_gemm_fwd(cmath, 2, p.bins, p.win // 2, cols, ptr(fr), ptr(p.gemm_image(math, 0, basis_f)), ptr(spec), st), "stft_fwd")
-            else:
-                d2 = conv_desc(spec_f, 1, cols, cmath)
-                pw = pack_weights(spec_f, d2, basis_f, None, cache, False)
-                check(lib.eben_conv1d_fwd(ctypes.byref(d2), ptr(fr), ptr(pw.wp_fwd), None, None, ptr(spec), st), "stft_fwd")
+            spec = p.dft(math, fr, cols)
             sums = torch.empty((rows, 3), dtype=torch.float32, device=x.device)
             # y rows: same strides, column offset rows*frames
             ws_bytes = lib.eben_stft_loss_sums_workspace(rows)
@@ -1569,22 +1611,7 @@ class _MRSTFTFn(torch.autograd.Function):
                                             ptr(sums), ptr(gout), 1.0 / len(ctx.plans), ptr(dspec), frames, xcols, p.bins * xcols, st),
                   "stft_loss_bwd")
             # d(frames)[j, (r, f)] = sum_m basis[m, j] dspec[m, (r, f)]: one dense GEMM, then overlap-add
-            if math == "dense":
-                spec_t, basis_t, cache, cmath = p.spec_t, p.basis_t, p.cache_bwd, MATH_F32
-            else:
-                _, _, spec_t, basis_t, _, cache = p.folded_parts(math)
-                cmath = _STFT_CONV_MATH.get(math, MATH_F32)
-                if math == "bf16x3":
-                    dsplit = torch.empty((1, spec_t.c_in, xcols), dtype=torch.float32, device=gout.device)
-                    check(lib.eben_split3(ptr(dspec), ptr(dsplit), 2, p.bins, xcols, st), "split3")
-                    dspec = dsplit
-            dfr = torch.empty((1, spec_t.c_out, xcols), dtype=torch.float32, device=gout.device)
-            if STFT_GEMM and math in ("folded_x3", "folded_x6"):
-                check(lib.eben_gemm_fwd(cmath, 2, p.win // 2, p.bins, xcols, ptr(dspec), ptr(p.gemm_image(math, 1, basis_t)), ptr(dfr), st), "stft_bwd_gemm")
-            else:
-                d1 = conv_desc(spec_t, 1, xcols, cmath)
-                pw = pack_weights(spec_t, d1, basis_t, None, cache, False)
-                check(lib.eben_conv1d_fwd(ctypes.byref(d1), ptr(dspec), ptr(pw.wp_fwd), None, None, ptr(dfr), st), "stft_bwd_gemm")
+            dfr = p.dft_t(math, dspec, xcols)
             if math == "dense":
                 check(lib.eben_overlap_add_ex(ptr(dfr), ptr(dsig), rows, t, p.win, frames, p.hop, p.pad, 1, 1 if i else 0, frames, xcols, st),
                       "overlap_add")

@@ -9,7 +9,8 @@ mean over resolutions) -- parity for this term is therefore *unpinned* (see DESI
 
 Per resolution the STFT is a framing pass + one dense GEMM: hann(win) centred in n_fft and center=True
 reflect padding reduce to frames of ``win`` samples at hop ``hop`` over the signal reflect-padded by
-``win/2``, multiplied by the 2*(n_fft/2+1) rows [w cos ; -w sin] of the windowed DFT basis.
+``n_fft//2 - (n_fft - win)//2`` (``win/2`` when both are even), multiplied by the 2*(n_fft/2+1) rows
+[w cos ; -w sin] of the windowed DFT basis.  Any ``win <= n_fft`` is accepted, as by torch.stft.
 """
 from __future__ import annotations
 
@@ -69,6 +70,9 @@ class MultiResolutionSTFTLoss(torch.nn.Module):
                  scale_invariance: bool = False, eps: float = 1e-8, **kwargs):
         super().__init__()
         assert len(fft_sizes) == len(hop_sizes) == len(win_lengths)
+        for n_fft, win in zip(fft_sizes, win_lengths):
+            if not 0 < win <= n_fft:
+                raise ValueError(f"win_length must satisfy 0 < win_length <= n_fft, got win_length={win}, n_fft={n_fft}")
         if window != "hann_window" or w_sc != 1.0 or w_log_mag != 1.0 or w_lin_mag or w_phs or scale or scale_invariance:
             raise NotImplementedError("only the configuration of configs/lightning_module/loss_module/multi_stft.yaml is built")
         if perceptual_weighting and sample_rate is None:
@@ -86,9 +90,10 @@ class MultiResolutionSTFTLoss(torch.nn.Module):
         plans = []
         for i, (n_fft, hop, win) in enumerate(zip(self.fft_sizes, self.hop_sizes, self.win_lengths)):
             bins = n_fft // 2 + 1
-            # hann(win) centred in n_fft + center=True reflect padding of n_fft/2 == frames of length `win` taken at
-            # reflect padding win/2 (the window is zero outside its centred `win` samples)
-            plans.append(ops.StftPlan(n_fft=n_fft, hop=hop, win=win, bins=bins, pad=win // 2,
+            # hann(win) centred in n_fft (torch.stft puts it (n_fft - win)//2 samples into the frame) + center=True reflect
+            # padding of n_fft//2 == frames of length `win` taken at reflect padding n_fft//2 - (n_fft - win)//2 (the window is
+            # zero outside its `win` samples); win/2 when n_fft and win are both even
+            plans.append(ops.StftPlan(n_fft=n_fft, hop=hop, win=win, bins=bins, pad=n_fft // 2 - (n_fft - win) // 2,
                                       spec_f=ops.ConvSpec(c_in=win, c_out=2 * bins, ksize=1), basis_f=getattr(self, f"basis_{i}"),
                                       spec_t=ops.ConvSpec(c_in=2 * bins, c_out=win, ksize=1), basis_t=getattr(self, f"basis_t_{i}"),
                                       cache_fwd=ops.PackedWeights(), cache_bwd=ops.PackedWeights()))
