@@ -475,6 +475,29 @@ EBEN_API int eben_stft_loss_bwd_ex(const float* spec_x, const float* spec_y, int
 EBEN_API int eben_overlap_add_ex(const float* frames_buf, float* x, int batch, int lx, int win, int frames, int hop, int pad,
                         int reflect, int accumulate, long long row_stride, long long j_stride, void* stream);
 
+/* The magnitude terms of auraloss STFTLoss outside multi_stft.yaml's configuration (stft_terms.hip): an optional mel projection
+ * (scale="mel") and the weighted SC / log-magnitude / linear-magnitude terms under an L1 or L2 distance.  spec is the flat
+ * (2*bins, 2*rows*frames) windowed-DFT output (bin k of column c at k*cols + c, imaginary at + bins*cols; x rows in columns
+ * [0, rows*frames), y rows after them); M = sqrt(clamp(re^2 + im^2, eps)).  terms: mask of 1 (SC), 2 (log), 4 (lin); l2 = 0: |.|,
+ * 1: (.)^2.  Mel projection M'[m] = sum_j fb_w[j] M[fb_lo[m] + j - fb_off[m]], j in [fb_off[m], fb_off[m+1]), for m < n_out;
+ * fb_lo = NULL: no projection, n_out = bins.
+ *   eben_stft_terms_fwd: sums[4r .. 4r+3] = sum (M'y - M'x)^2, sum M'y^2, sum dist(log M'x, log M'y), sum dist(M'x, M'y) per row
+ *     (terms not in the mask left 0); with the projection, mags receives M'x then M'y as (2, rows, n_out, frames).
+ *   eben_stft_terms_bwd: dspec (2*bins, rows*frames) = d loss / d spec_x, loss = sum of the weighted terms (SC: mean over rows;
+ *     log / lin: over rows * n_out * frames), times gout[0] * scale; the adjoint projection through each bin's <= 2 (filter, weight)
+ *     pairs bin_m[2k + q] (-1: none), bin_w[2k + q]; zero where re^2 + im^2 < eps.
+ *   eben_stft_terms_total: out = mean over the n <= 16 resolutions of w_sc mean_r sqrt(s0 / s1) + w_log sum_r s2 * inv_counts[i]
+ *     + w_lin sum_r s3 * inv_counts[i]  (inv_counts[i] = 1 / (rows n_out_i frames_i); terms outside the mask are not read). */
+EBEN_API size_t eben_stft_terms_workspace(int rows);
+EBEN_API int eben_stft_terms_fwd(const float* spec, int rows, int bins, int frames, float eps, int n_out, const int* fb_lo, const int* fb_off,
+                                 const float* fb_w, int terms, int l2, float* mags, float* partial_ws, size_t ws_bytes, float* sums,
+                                 void* stream);
+EBEN_API int eben_stft_terms_bwd(const float* spec, int rows, int bins, int frames, float eps, int n_out, const int* bin_m, const float* bin_w,
+                                 const float* mags, int terms, int l2, float w_sc, float w_log, float w_lin, const float* sums,
+                                 const float* gout, float scale, float* dspec, void* stream);
+EBEN_API int eben_stft_terms_total(const void* const* sums, const float* inv_counts, int n, int rows, int terms, float w_sc, float w_log,
+                                   float w_lin, float* out, void* stream);
+
 /* ---- optimiser (torch.optim.Adam as configured by configs/lightning_module/optimizer/adam.yaml) --- */
 typedef struct EbenAdamTensor {
   float* param;

@@ -192,6 +192,11 @@ SIGNATURES = {
     "eben_stft_loss_bwd_ex": (c_int, [_P, _P, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_float, _P, _P, c_float, _P, c_int64, c_int64,
                                       c_int64, _P]),
     "eben_overlap_add_ex": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64, _P]),
+    "eben_stft_terms_workspace": (c_size_t, [c_int]),
+    "eben_stft_terms_fwd": (c_int, [_P, c_int, c_int, c_int, c_float, c_int, _P, _P, _P, c_int, c_int, _P, _P, c_size_t, _P, _P]),
+    "eben_stft_terms_bwd": (c_int, [_P, c_int, c_int, c_int, c_float, c_int, _P, _P, _P, c_int, c_int, c_float, c_float, c_float, _P, _P,
+                                    c_float, _P, _P]),
+    "eben_stft_terms_total": (c_int, [POINTER(c_void_p), POINTER(c_float), c_int, c_int, c_int, c_float, c_float, c_float, _P, _P]),
     "eben_adam_step": (c_int, [POINTER(EbenAdamTensor), c_int, c_int64, c_float, c_float, c_float, c_float, c_float, c_int, c_float, _P]),
     "eben_noisy_collate": (c_int, [POINTER(EbenCollateItem), c_int, c_int, _P, _P, _P]),
     "eben_l2norm": (c_int, [_P, c_size_t, _P, _P]),

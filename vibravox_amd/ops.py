@@ -275,6 +275,13 @@ def _empty(n_bytes: int, like: torch.Tensor) -> torch.Tensor:
     return torch.empty(max(1, (n_bytes + 3) // 4), dtype=torch.float32, device=like.device)
 
 
+def _iptr(t: torch.Tensor) -> int:
+    """Device pointer of a contiguous int32 table (``ptr`` takes float32 only)."""
+    if not t.is_cuda or t.dtype is not torch.int32 or not t.is_contiguous():
+        raise _lib.EbenError(f"expected a contiguous int32 tensor on a HIP device, got {t.dtype} on '{t.device}'")
+    return t.data_ptr()
+
+
 # --------------------------------------------------------------------------------------------
 # conv layers
 # --------------------------------------------------------------------------------------------
@@ -1437,6 +1444,11 @@ class StftPlan:
     math: str = "folded"
     folded: Optional[dict] = None   # math -> (spec_f, basis_f, spec_t, basis_t, cache_fwd, cache_bwd), built on first use
     gemm: Optional[dict] = None     # (math, which) -> (basis address, packed image, basis) for the grouped GEMM kernel
+    #: the window's float32 sample 0 is exactly 0 and w[h + m] == w[h - m] (hann, blackman, bartlett): the folded forms drop sample 0
+    #: and read only the right half of the basis, so hamming or kaiser (w[0] != 0) take "dense"
+    foldable: bool = True
+    #: mel projection of the magnitudes (eben_stft_terms_fwd / _bwd): (n_mels, fb_lo, fb_off, fb_w, bin_m, bin_w), or None
+    mel: Optional[tuple] = None
 
     def frames(self, t: int) -> int:
         """Frames of a length-t signal: torch.stft(center=True) pads n_fft // 2 on each side and steps an n_fft window by hop."""
@@ -1444,8 +1456,9 @@ class StftPlan:
 
     def math_for(self, math: str) -> str:
         """The arithmetic a plan runs: the folded forms need the window's centre h = win / 2 on the DFT's symmetry point n_fft / 2
-        (win and n_fft even, frames at reflect padding win / 2); every other geometry takes "dense"."""
-        return math if self.win % 2 == 0 and self.n_fft % 2 == 0 and self.pad == self.win // 2 else "dense"
+        (win and n_fft even, frames at reflect padding win / 2) and a window they can fold (``foldable``); every other plan takes
+        "dense"."""
+        return math if self.foldable and self.win % 2 == 0 and self.n_fft % 2 == 0 and self.pad == self.win // 2 else "dense"
 
     def gemm_image(self, math: str, which: int, basis: torch.Tensor) -> torch.Tensor:
         """Packed basis of the folded contraction for ``eben_gemm_fwd``: which = 0 the forward's (2 groups x bins x win/2), 1 its
@@ -1542,6 +1555,37 @@ FUSED_LOSS_GLUE = os.environ.get("EBEN_FUSED_LOSS_GLUE", "1") != "0"
 STFT_GEMM = os.environ.get("EBEN_STFT_GEMM", "1") != "0"
 
 
+def _stft_spectrum(p: StftPlan, math: str, sig: torch.Tensor, t: int, frames: int) -> torch.Tensor:
+    """(1, 2*bins, R*frames) windowed DFT of every row of sig (R, 1, t): eben_stft_frames ("dense") or eben_stft_frames_folded, then
+    the plan's contraction."""
+    lib, st = load(), stream()
+    nrows = sig.shape[0]
+    cols = nrows * frames
+    if math == "dense":
+        fr = torch.empty((1, p.win, cols), dtype=torch.float32, device=sig.device)
+        check(lib.eben_stft_frames(ptr(sig), ptr(fr), nrows, t, p.win, p.hop, p.pad, frames, st), "stft_frames")
+    else:
+        fr = torch.empty((1, p.folded_parts(math)[0].c_in, cols), dtype=torch.float32, device=sig.device)
+        check(lib.eben_stft_frames_folded(ptr(sig), ptr(fr), nrows, t, p.win, p.hop, p.pad, frames, 1 if math == "bf16x3" else 0, st),
+              "stft_frames_folded")
+    return p.dft(math, fr, cols)
+
+
+def _stft_spectrum_adjoint(p: StftPlan, math: str, dspec: torch.Tensor, dsig: torch.Tensor, t: int, frames: int, accumulate: bool) -> None:
+    """dsig (R, 1, t) (+)= the adjoint of ``_stft_spectrum`` applied to dspec (1, 2*bins, R*frames)."""
+    lib, st = load(), stream()
+    rows = dsig.shape[0]
+    xcols = rows * frames
+    # d(frames)[j, (r, f)] = sum_m basis[m, j] dspec[m, (r, f)]: one dense GEMM, then overlap-add
+    dfr = p.dft_t(math, dspec, xcols)
+    if math == "dense":
+        check(lib.eben_overlap_add_ex(ptr(dfr), ptr(dsig), rows, t, p.win, frames, p.hop, p.pad, 1, 1 if accumulate else 0, frames, xcols, st),
+              "overlap_add")
+    else:
+        check(lib.eben_overlap_add_folded(ptr(dfr), ptr(dsig), rows, t, p.win, frames, p.hop, p.pad, 1 if accumulate else 0, frames, xcols, st),
+              "overlap_add_folded")
+
+
 class _MRSTFTFn(torch.autograd.Function):
     """auraloss MultiResolutionSTFTLoss(x, y) as configured by multi_stft.yaml (see mrstft_loss.py).
 
@@ -1570,14 +1614,7 @@ class _MRSTFTFn(torch.autograd.Function):
             frames = p.frames(t)
             cols = 2 * rows * frames
             math = p.math_for(p.math)
-            if math == "dense":
-                fr = torch.empty((1, p.win, cols), dtype=torch.float32, device=x.device)
-                check(lib.eben_stft_frames(ptr(sig), ptr(fr), 2 * rows, t, p.win, p.hop, p.pad, frames, st), "stft_frames")
-            else:
-                fr = torch.empty((1, p.folded_parts(math)[0].c_in, cols), dtype=torch.float32, device=x.device)
-                check(lib.eben_stft_frames_folded(ptr(sig), ptr(fr), 2 * rows, t, p.win, p.hop, p.pad, frames, 1 if math == "bf16x3" else 0, st),
-                      "stft_frames_folded")
-            spec = p.dft(math, fr, cols)
+            spec = _stft_spectrum(p, math, sig, t, frames)
             sums = torch.empty((rows, 3), dtype=torch.float32, device=x.device)
             # y rows: same strides, column offset rows*frames
             ws_bytes = lib.eben_stft_loss_sums_workspace(rows)
@@ -1610,14 +1647,7 @@ class _MRSTFTFn(torch.autograd.Function):
             check(lib.eben_stft_loss_bwd_ex(ptr(spec), ptr(spec) + 4 * xcols, rows, p.bins, frames, frames, cols, p.bins * cols, ctx.eps,
                                             ptr(sums), ptr(gout), 1.0 / len(ctx.plans), ptr(dspec), frames, xcols, p.bins * xcols, st),
                   "stft_loss_bwd")
-            # d(frames)[j, (r, f)] = sum_m basis[m, j] dspec[m, (r, f)]: one dense GEMM, then overlap-add
-            dfr = p.dft_t(math, dspec, xcols)
-            if math == "dense":
-                check(lib.eben_overlap_add_ex(ptr(dfr), ptr(dsig), rows, t, p.win, frames, p.hop, p.pad, 1, 1 if i else 0, frames, xcols, st),
-                      "overlap_add")
-            else:
-                check(lib.eben_overlap_add_folded(ptr(dfr), ptr(dsig), rows, t, p.win, frames, p.hop, p.pad, 1 if i else 0, frames, xcols, st),
-                      "overlap_add_folded")
+            _stft_spectrum_adjoint(p, math, dspec, dsig, t, frames, i > 0)
         if ctx.fir is not None:
             nt = ctx.fir.numel()
             dsig = _fir_interp_sum(dsig, ctx.fir, t, 1, nt, 1, -(nt // 2))
@@ -1626,3 +1656,80 @@ class _MRSTFTFn(torch.autograd.Function):
 
 def mrstft(x: torch.Tensor, y: torch.Tensor, fir: Optional[torch.Tensor], plans: List[StftPlan], eps: float = 1e-8) -> torch.Tensor:
     return _MRSTFTFn.apply(x, y.detach(), fir, plans, eps)
+
+
+#: eben_stft_terms_* term mask bits
+STFT_TERM_SC, STFT_TERM_LOG, STFT_TERM_LIN = 1, 2, 4
+
+
+class _MRSTFTTermsFn(torch.autograd.Function):
+    """auraloss MultiResolutionSTFTLoss(x, y) outside multi_stft.yaml's configuration: any window (through the plans' bases), an
+    optional mel projection per plan (``StftPlan.mel``), the weighted SC / log / lin terms under L1 or L2 (stft_terms.hip).  Framing,
+    windowed DFT, its adjoint, the overlap-add and the FIR are _MRSTFTFn's; only the magnitude terms differ."""
+
+    @staticmethod
+    def forward(ctx, x, y, fir, plans: List[StftPlan], eps: float, weights, l2: bool):
+        lib = load()
+        st = stream()
+        x, y = x.contiguous(), y.contiguous()
+        b, c, t = x.shape
+        rows = b * c
+        w_sc, w_log, w_lin = (float(w) for w in weights)
+        terms = (STFT_TERM_SC if w_sc else 0) | (STFT_TERM_LOG if w_log else 0) | (STFT_TERM_LIN if w_lin else 0)
+        sig = torch.cat((x.reshape(rows, 1, t), y.reshape(rows, 1, t)), dim=0)
+        if fir is not None:
+            nt = fir.numel()
+            sig = _fir_decimate(sig, fir, t, 1, nt, 1, -(nt // 2))
+        saved, inv_counts = [], []
+        ws_bytes = lib.eben_stft_terms_workspace(rows)
+        for p in plans:
+            frames = p.frames(t)
+            math = p.math_for(p.math)
+            spec = _stft_spectrum(p, math, sig, t, frames)
+            sums = torch.empty((rows, 4), dtype=torch.float32, device=x.device)
+            if p.mel is not None:
+                n_out, fb_lo, fb_off, fb_w = p.mel[:4]
+                mags = torch.empty((2, rows, n_out, frames), dtype=torch.float32, device=x.device)
+                mel_ptrs = (_iptr(fb_lo), _iptr(fb_off), ptr(fb_w))
+            else:
+                n_out, mags, mel_ptrs = p.bins, None, (None, None, None)
+            check(lib.eben_stft_terms_fwd(ptr(spec), rows, p.bins, frames, eps, n_out, *mel_ptrs, terms, int(l2), ptr(mags),
+                                          ptr(_empty(ws_bytes, x)), ws_bytes, ptr(sums), st), "stft_terms_fwd")
+            saved.append((spec, sums, frames, math, mags))
+            inv_counts.append(1.0 / float(rows * n_out * frames))
+        ctx.plans, ctx.eps, ctx.geom, ctx.saved, ctx.fir = plans, eps, (b, c, t, rows), saved, fir
+        ctx.terms, ctx.l2, ctx.weights = terms, int(l2), (w_sc, w_log, w_lin)
+        n = len(plans)
+        total = torch.empty((), dtype=torch.float32, device=x.device)
+        check(lib.eben_stft_terms_total((ctypes.c_void_p * n)(*[ptr(sv[1]) for sv in saved]), (ctypes.c_float * n)(*inv_counts), n, rows, terms,
+                                        w_sc, w_log, w_lin, ptr(total), st), "stft_terms_total")
+        return total
+
+    @staticmethod
+    def backward(ctx, gout):
+        lib = load()
+        st = stream()
+        b, c, t, rows = ctx.geom
+        gout = gout.contiguous().reshape(1)
+        dsig = torch.empty((rows, 1, t), dtype=torch.float32, device=gout.device)
+        for i, (p, (spec, sums, frames, math, mags)) in enumerate(zip(ctx.plans, ctx.saved)):
+            dspec = torch.empty((1, 2 * p.bins, rows * frames), dtype=torch.float32, device=gout.device)
+            if p.mel is not None:
+                n_out, bin_m, bin_w = p.mel[0], p.mel[4], p.mel[5]
+                adj = (_iptr(bin_m), ptr(bin_w), ptr(mags))
+            else:
+                n_out, adj = p.bins, (None, None, None)
+            check(lib.eben_stft_terms_bwd(ptr(spec), rows, p.bins, frames, ctx.eps, n_out, *adj, ctx.terms, ctx.l2, *ctx.weights, ptr(sums),
+                                          ptr(gout), 1.0 / len(ctx.plans), ptr(dspec), st), "stft_terms_bwd")
+            _stft_spectrum_adjoint(p, math, dspec, dsig, t, frames, i > 0)
+        if ctx.fir is not None:
+            nt = ctx.fir.numel()
+            dsig = _fir_interp_sum(dsig, ctx.fir, t, 1, nt, 1, -(nt // 2))
+        return dsig.reshape(b, c, t), None, None, None, None, None, None
+
+
+def mrstft_terms(x: torch.Tensor, y: torch.Tensor, fir: Optional[torch.Tensor], plans: List[StftPlan], eps: float, weights: Sequence[float],
+                 l2: bool) -> torch.Tensor:
+    """MultiResolutionSTFTLoss with weights (w_sc, w_log_mag, w_lin_mag), mag_distance L2 (l2) or L1 and the plans' windows and mel
+    projections (eben_stft_terms_*); at least one weight non-zero, at most 16 resolutions."""
+    return _MRSTFTTermsFn.apply(x, y.detach(), fir, plans, eps, tuple(weights), l2)
