@@ -132,6 +132,15 @@ EBEN_API int eben_conv1d_pack_multi(const EbenPackJob* jobs, int n, void* stream
  * long reductions of melgan_discriminator.py:119-145 / eben_discriminator.py:118-140 as persistent whole-panel blocks).  The packed layouts differ;
  * pack / fwd / bwd_dx agree by construction. */
 EBEN_API int eben_conv1d_kernel_generation(const EbenConv1dDesc* d, int which);
+/* The kernel a launch of generation 4 / 6 runs, asked of the host without launching anything (the dispatch's own decision, for tests).
+ * which 0: eben_conv1d_fwd / eben_bl_conv1d_fwd; 1: the input gradient -- eben_conv1d_bwd_dx with mask_on_load = 1 (the fused output
+ * activation differentiated as the gradient is staged: out_slope != 1), eben_conv1d_bwd_dx_ex / eben_bl_conv1d_bwd_dx with 0.
+ * out[0..7] (n >= 8) = generation, then for generations 4 / 6: FM, XRB, IM, NPW, NPX, BL (tap3_kernel's template arguments; XRB = 0
+ * off tap3_kernel), EBEN_VARIANT_*; zeros past out[0] otherwise.  EBEN_EUNSUPPORTED where the launch itself would refuse. */
+#define EBEN_VARIANT_TAP3 1      /* tap3_kernel (tapconv3.hip) */
+#define EBEN_VARIANT_THIN_BL 2   /* thin_bl_kernel (thin_bl.hip) */
+#define EBEN_VARIANT_TAP4 3      /* tap4_kernel (bigtap.hip) */
+EBEN_API int eben_conv1d_variant(const EbenConv1dDesc* d, int which, int mask_on_load, int* out, int n);
 /* pack v (optionally scaled per dim-0 row: weight-norm) into the MFMA-friendly layouts */
 EBEN_API int eben_conv1d_pack(const EbenConv1dDesc* d, const float* v, const float* scale, float* wp_fwd, float* wp_bwd, void* stream);
 /* y = lrelu_out( conv(lrelu_in(x)) + bias ) [+ residual] */
@@ -235,6 +244,10 @@ EBEN_API int eben_bl_conv1d_bwd_dw(const EbenConv1dDesc* d, const void* dy_hi, c
  * ws_bytes[i]): same slabs, bit for bit. */
 EBEN_API int eben_bl_conv1d_bwd_dw_multi(const EbenConv1dDesc* const* descs, const void* const* dy_hi, const void* const* x_hi, int has_bias,
                                 float* const* slabs, const size_t* ws_bytes, int n, void* stream);
+/* The bl_dw kernel the layer's weight gradient runs (host only, the dispatch's own decision): out[0..4] (n >= 5) = FM, FN, XC, WN of
+ * bl_dw_kernel<FM, FN, XC, WN>, and 1 when eben_bl_conv1d_bwd_dw_multi groups the problem (bl_dw_multi_kernel<FM, FN>) or 0 when it
+ * launches it on its own.  EBEN_EUNSUPPORTED for layers outside the kernel. */
+EBEN_API int eben_bl_conv1d_bwd_dw_variant(const EbenConv1dDesc* d, int* out, int n);
 /* Chain heads: ReflectionPad1d(reflect_pad) + Conv1d(c_in -> c_out, ksize, dilation, groups = c_in, zero padding `pad`, stride 1)
  * + bias + LeakyReLU(out_slope), fp32 (batch, c_in, l_in) in, bundle planes out (eben_discriminator.py:66-76 layer 0,
  * melgan_discriminator.py:89-98 layer 0).  `jobs` is a HOST array of up to 4 heads run by ONE launch (the three PQMF-band chains

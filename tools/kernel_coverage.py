@@ -1,10 +1,11 @@
 #!/usr/bin/env python
 """Which kernels of libeben_hip.so were launched: rocprofv3 --kernel-trace --stats summaries (CSV) of the GPU test suite and of
 bench.py against the kernel list of the library (tools/kernel_resources.py).
-Usage: python tools/kernel_coverage.py <kernel_stats.csv> [...]   (prints per source file: kernels, launched, and the ones never launched)"""
+Usage: python tools/kernel_coverage.py <kernel_stats.csv | results.db> [...]   (prints per source file: kernels, launched, and the ones never launched)"""
 import csv
 import os
 import re
+import sqlite3
 import subprocess
 import sys
 
@@ -26,6 +27,12 @@ def norm(name):
 def main():
     used = {}
     for f in sys.argv[1:]:
+        if f.endswith(".db"):   # a rocpd database (rocprofv3's default output): one row per dispatch
+            con = sqlite3.connect(f)
+            col = "name" if "name" in [r[1] for r in con.execute("pragma table_info(kernels)")] else "kernel_name"
+            for (name,) in con.execute(f"select {col} from kernels"):
+                used[norm(name)] = used.get(norm(name), 0) + 1
+            continue
         for r in csv.DictReader(open(f)):
             used[norm(r["Name"])] = used.get(norm(r["Name"]), 0) + int(r["Calls"])
     here = os.path.dirname(os.path.abspath(__file__))

@@ -96,6 +96,7 @@ SIGNATURES = {
     "eben_wn_bwd_multi": (c_int, [POINTER(EbenWnBwdItem), c_int, _P]),
     "eben_conv1d_packed_floats": (c_size_t, [_D, c_int]),
     "eben_conv1d_kernel_generation": (c_int, [_D, c_int]),
+    "eben_conv1d_variant": (c_int, [_D, c_int, c_int, POINTER(c_int), c_int]),
     "eben_conv1d_pack": (c_int, [_D, _P, _P, _P, _P, _P]),
     "eben_conv1d_pack_multi": (c_int, [POINTER(EbenPackJob), c_int, _P]),
     "eben_conv1d_fwd": (c_int, [_D, _P, _P, _P, _P, _P, _P]),
@@ -119,6 +120,7 @@ SIGNATURES = {
     "eben_bl_conv1d_bwd_dw_workspace": (c_size_t, [_D, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "eben_bl_conv1d_bwd_dw": (c_int, [_D, _P, _P, c_int, _P, c_size_t, _P]),
     "eben_bl_conv1d_bwd_dw_multi": (c_int, [POINTER(_D), POINTER(_P), POINTER(_P), c_int, POINTER(_P), POINTER(c_size_t), c_int, _P]),
+    "eben_bl_conv1d_bwd_dw_variant": (c_int, [_D, POINTER(c_int), c_int]),
     "eben_bl_head_fwd": (c_int, [POINTER(EbenBlHeadJob), c_int, c_int, _P]),
     "eben_bl_head_dx": (c_int, [POINTER(EbenBlHeadJob), c_int, c_int, _P, _P]),
     "eben_bl_head_dw_workspace": (c_size_t, [POINTER(EbenBlHeadJob), c_int, POINTER(c_int), POINTER(c_int)]),

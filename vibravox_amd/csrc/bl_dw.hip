@@ -508,6 +508,22 @@ static int launch_bldw(const BlDwArgs& a, const BlDwPlan& p, hipStream_t st) {
   return EBEN_OK;
 }
 
+// The kernel a plan runs: bl_dw_kernel<FM, FN, XC, WN>, and whether eben_bl_conv1d_bwd_dw_multi groups it into bl_dw_multi_kernel<FM, FN>
+// (contiguous-X and eight-wave layers are not grouped: their own launch).  THE decision: both dispatches and the query read it.
+struct BlDwVariant { int FM, FN, XC, WN, grouped; };
+static BlDwVariant bldw_variant(const BlDwPlan& p) {
+  if (p.wide) return BlDwVariant{2, 3, 1, 4, 0};
+  return BlDwVariant{p.FM, p.FN, p.xc, 2, p.xc ? 0 : 1};
+}
+
+static int launch_bldw_variant(const BlDwVariant& v, const BlDwArgs& a, const BlDwPlan& p, hipStream_t st) {
+  if (v.WN == 4) return launch_bldw<2, 3, true, 4>(a, p, st);
+  if (v.XC) return v.FM == 2 ? (v.FN == 4 ? launch_bldw<2, 4, true>(a, p, st) : launch_bldw<2, 3, true>(a, p, st))
+                             : (v.FN == 4 ? launch_bldw<1, 4, true>(a, p, st) : launch_bldw<1, 3, true>(a, p, st));
+  if (v.FM == 2) return v.FN == 4 ? launch_bldw<2, 4>(a, p, st) : v.FN == 3 ? launch_bldw<2, 3>(a, p, st) : v.FN == 2 ? launch_bldw<2, 2>(a, p, st) : launch_bldw<2, 1>(a, p, st);
+  return v.FN == 4 ? launch_bldw<1, 4>(a, p, st) : v.FN == 3 ? launch_bldw<1, 3>(a, p, st) : v.FN == 2 ? launch_bldw<1, 2>(a, p, st) : launch_bldw<1, 1>(a, p, st);
+}
+
 }  // namespace eben
 
 using namespace eben;
@@ -552,12 +568,21 @@ extern "C" int eben_bl_conv1d_bwd_dw(const EbenConv1dDesc* d, const void* dy_hi,
   BlDwPlan p;
   const int rc = bldw_args(d, dy_hi, x_hi, has_bias, slabs, ws_bytes, &a, &p);
   if (rc) return rc;
-  hipStream_t st = as_stream(stream);
-  if (p.wide) return launch_bldw<2, 3, true, 4>(a, p, st);
-  if (p.xc) return p.FM == 2 ? (p.FN == 4 ? launch_bldw<2, 4, true>(a, p, st) : launch_bldw<2, 3, true>(a, p, st))
-                             : (p.FN == 4 ? launch_bldw<1, 4, true>(a, p, st) : launch_bldw<1, 3, true>(a, p, st));
-  if (p.FM == 2) return p.FN == 4 ? launch_bldw<2, 4>(a, p, st) : p.FN == 3 ? launch_bldw<2, 3>(a, p, st) : p.FN == 2 ? launch_bldw<2, 2>(a, p, st) : launch_bldw<2, 1>(a, p, st);
-  return p.FN == 4 ? launch_bldw<1, 4>(a, p, st) : p.FN == 3 ? launch_bldw<1, 3>(a, p, st) : p.FN == 2 ? launch_bldw<1, 2>(a, p, st) : launch_bldw<1, 1>(a, p, st);
+  return launch_bldw_variant(bldw_variant(p), a, p, as_stream(stream));
+}
+
+extern "C" int eben_bl_conv1d_bwd_dw_variant(const EbenConv1dDesc* d, int* out, int n) {
+  EBEN_REQUIRE(out && n >= 5, "eben_bl_conv1d_bwd_dw_variant: 5 output slots");
+  Canon c;
+  const int rc = canon_from_desc(d, &c);
+  if (rc) return rc;
+  EBEN_REQUIRE(!d->transposed, "eben_bl_conv1d_bwd_dw_variant: a Conv1d descriptor");
+  BlDwPlan p;
+  make_bldw_plan(c, &p);
+  if (!p.ok) return fail(EBEN_EUNSUPPORTED, "eben_bl_conv1d_bwd_dw_variant: layer not covered by the bundle-layout weight-gradient kernel");
+  const BlDwVariant v = bldw_variant(p);
+  out[0] = v.FM; out[1] = v.FN; out[2] = v.XC; out[3] = v.WN; out[4] = v.grouped;
+  return EBEN_OK;
 }
 
 namespace eben {
@@ -591,7 +616,7 @@ extern "C" int eben_bl_conv1d_bwd_dw_multi(const EbenConv1dDesc* const* descs, c
       BlDwPlan p;
       const int rc = bldw_args(descs[i], dy_hi[i], x_hi[i], has_bias, slabs[i], ws_bytes[i], &a, &p);
       if (rc) return rc;
-      if (p.xc || p.wide) {   // contiguous-X (stride 4) and eight-wave layers are not grouped: their own launch
+      if (!bldw_variant(p).grouped) {   // contiguous-X (stride 4) and eight-wave layers: their own launch
         if (T.n > 0) break;
         const int rc1 = eben_bl_conv1d_bwd_dw(descs[i], dy_hi[i], x_hi[i], has_bias, slabs[i], ws_bytes[i], stream);
         if (rc1) return rc1;

@@ -59,9 +59,23 @@ struct Tap3Plan {
   int big, WM, WN, TM, TN, RING, XT, PPT, xbuf_stride;
 };
 
+// What of a launch besides its plan decides the kernel that runs it (tap3_call_of: from the arguments tap3_launch builds)
+struct Tap3Call { int bl, in_mode, pr_S, pr_order, reflect, bias, res, eh, accumulate; };
+inline Tap3Call tap3_call_of(const Tap3Args& a, int reflect) {
+  return Tap3Call{a.xh != nullptr, a.in_mode, a.pr_S, a.pr_order, reflect, a.bias != nullptr, a.res != nullptr, a.eh != nullptr, a.accumulate};
+}
+// The kernel a launch runs (EBEN_VARIANT_* of include/eben_hip.h) and its template arguments: tap3_kernel<FM, XRB, IM, NPW, NPX, BL>, the
+// thin_bl_kernel form `thin` (thin_bl.hip, 1-based), or tap4_kernel (p.big).  tap3_variant is THE decision: tap3_launch dispatches on it and
+// eben_conv1d_variant reports it.  EBEN_OK, or EBEN_EUNSUPPORTED for operand forms no instantiation covers.
+struct Tap3Variant { int kernel, FM, XRB, IM, NPW, NPX, BL, thin; };
+int tap3_variant(const Tap3Plan& p, const Tap3Call& k, Tap3Variant* v);
+int tap3_plan_variant(const Canon& c, int dir, const Tap3Call& k, Tap3Variant* v);   // make_plan3 + tap3_variant
+
 // bigtap.hip
 int tap4_launch(const Tap3Plan& p, const Tap3Args& a, hipStream_t st);
-// thin_bl.hip: the thin bundle-layout launches of a tap3 plan, one kernel per direction; 1 (result in *rc) when it took the launch
-int thin_bl_launch(const Tap3Plan& p, const Tap3Args& a, int reflect, int nblocks, hipStream_t st, int* rc);
+// thin_bl.hip: the thin bundle-layout launches of a tap3 plan, one kernel per direction.  thin_bl_form: which one takes the launch (1-based),
+// 0 when it is not one of the thin forms (tap3_kernel runs it); thin_bl_launch runs form `form`.
+int thin_bl_form(const Tap3Plan& p, const Tap3Call& k);
+int thin_bl_launch(const Tap3Plan& p, const Tap3Args& a, int form, int nblocks, hipStream_t st);
 
 }  // namespace eben

@@ -23,6 +23,7 @@
 //   * LeakyReLU on load, bias / LeakyReLU / residual / activation-derivative mask in the epilogue;
 //   * blockIdx -> tile mapping is XCD-aware (tiles sharing a weight panel stay on one XCD's L2).
 #include "common.h"
+#include "tap3.h"
 
 #include <cstdlib>
 
@@ -657,6 +658,25 @@ extern "C" int eben_conv1d_kernel_generation(const EbenConv1dDesc* d, int which)
   const int dir = d->transposed ? 1 - which : which;
   const int gen = tap_generation(c, dir);
   return gen == 4 && tap3_is_big(c, dir) ? 6 : gen;
+}
+
+extern "C" int eben_conv1d_variant(const EbenConv1dDesc* d, int which, int mask_on_load, int* out, int n) {
+  EBEN_REQUIRE(out && n >= 8 && (which == 0 || which == 1), "eben_conv1d_variant: which 0 / 1 and 8 output slots");
+  EBEN_REQUIRE(!mask_on_load || which == 1, "eben_conv1d_variant: the mask is applied on load by input gradients only");
+  Canon c;
+  const int rc = canon_from_desc(d, &c);
+  if (rc) return rc;
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  out[0] = eben_conv1d_kernel_generation(d, which);
+  if (out[0] != 4 && out[0] != 6) return EBEN_OK;
+  // the launch as the entry points build it: the forward's reflect padding is the kernel's; input gradients fold it in a pass of their own
+  const int dir = d->transposed ? 1 - which : which;
+  Tap3Call k{};
+  k.bl = c.bl; k.in_mode = mask_on_load ? 1 : 0; k.reflect = which == 0 && c.reflect && !d->transposed;
+  Tap3Variant v;
+  if (const int e = tap3_plan_variant(c, dir, k, &v)) return e;
+  out[1] = v.FM; out[2] = v.XRB; out[3] = v.IM; out[4] = v.NPW; out[5] = v.NPX; out[6] = v.BL; out[7] = v.kernel;
+  return EBEN_OK;
 }
 
 extern "C" int eben_conv1d_pack(const EbenConv1dDesc* d, const float* v, const float* scale, float* wp_fwd, float* wp_bwd, void* stream) {

@@ -1378,19 +1378,35 @@ static int launch3_im(const Tap3Args& a, int nblocks, size_t lds, hipStream_t st
   return EBEN_OK;
 }
 template <int FM, int XRB>
-static int launch3_cfg(const Tap3Args& a, int nblocks, size_t lds, int npw, int npx, hipStream_t st) {
-  if (a.xh) {   // bundle layout
-    if (a.in_mode || npw != npx || npw > 2) return fail(EBEN_EUNSUPPORTED, "tap3: bundle layout with %d / %d operand pieces", npw, npx);
-    if (npw == 2) return launch3_im<FM, XRB, false, 2, 2, true>(a, nblocks, lds, st);
-    return launch3_im<FM, XRB, false, 1, 1, true>(a, nblocks, lds, st);
-  }
-  if (npx > 1) {
-    if (a.in_mode) return fail(EBEN_EUNSUPPORTED, "tap3: split operand with a mask on load");
-    if (npw == 1) return launch3_im<FM, XRB, false, 1, 2>(a, nblocks, lds, st);
-    if (npw == 2) return launch3_im<FM, XRB, false, 2, 2>(a, nblocks, lds, st);
+static int launch3_cfg(const Tap3Args& a, int nblocks, size_t lds, const Tap3Variant& v, hipStream_t st) {
+  if (v.BL) return v.NPW == 2 ? launch3_im<FM, XRB, false, 2, 2, true>(a, nblocks, lds, st) : launch3_im<FM, XRB, false, 1, 1, true>(a, nblocks, lds, st);
+  if (v.NPX > 1) {
+    if (v.NPW == 1) return launch3_im<FM, XRB, false, 1, 2>(a, nblocks, lds, st);
+    if (v.NPW == 2) return launch3_im<FM, XRB, false, 2, 2>(a, nblocks, lds, st);
     return launch3_im<FM, XRB, false, 3, 3>(a, nblocks, lds, st);
   }
-  return a.in_mode ? launch3_im<FM, XRB, true>(a, nblocks, lds, st) : launch3_im<FM, XRB, false>(a, nblocks, lds, st);
+  return v.IM ? launch3_im<FM, XRB, true>(a, nblocks, lds, st) : launch3_im<FM, XRB, false>(a, nblocks, lds, st);
+}
+
+int tap3_variant(const Tap3Plan& p, const Tap3Call& k, Tap3Variant* v) {
+  *v = Tap3Variant{};
+  if (!p.ok) return fail(EBEN_EUNSUPPORTED, "tap3_launch on a layer the bf16 kernel does not cover");
+  if (k.bl && (k.in_mode || p.npw != p.npx || p.npw > 2))
+    return fail(EBEN_EUNSUPPORTED, "tap3: bundle layout with %d / %d operand pieces or a mask on load", p.npw, p.npx);
+  v->FM = p.FM; v->NPW = p.npw; v->NPX = p.npx; v->BL = k.bl ? 1 : 0;
+  if (p.big) { v->kernel = EBEN_VARIANT_TAP4; return EBEN_OK; }
+  if ((v->thin = thin_bl_form(p, k))) { v->kernel = EBEN_VARIANT_THIN_BL; return EBEN_OK; }
+  v->kernel = EBEN_VARIANT_TAP3;
+  v->XRB = p.XRB == 2 || p.XRB == 3 ? p.XRB : 5;
+  if (!k.bl && p.npx > 1 && k.in_mode) return fail(EBEN_EUNSUPPORTED, "tap3: split operand with a mask on load");
+  v->IM = !k.bl && p.npx == 1 && k.in_mode ? 1 : 0;
+  return EBEN_OK;
+}
+
+int tap3_plan_variant(const Canon& c, int dir, const Tap3Call& k, Tap3Variant* v) {
+  Tap3Plan p;
+  make_plan3(c, dir, &p);
+  return tap3_variant(p, k, v);
 }
 
 int tap3_applicable(const Canon& c, int dir) {
@@ -1565,21 +1581,20 @@ int tap3_launch(const Canon& c, int dir, const TapIO& io, int reflect, hipStream
       a.pg[ph].pad = 0;
     }
   }
-  if (p.big) {
+  Tap3Variant v;
+  if (const int rc = tap3_variant(p, tap3_call_of(a, reflect), &v)) return rc;
+  if (v.kernel == EBEN_VARIANT_TAP4) {
     if (p.nph > 8) return fail(EBEN_EUNSUPPORTED, "tap4: more than 8 output phases");
     return tap4_launch(p, a, st);
   }
-  {
-    int rc = EBEN_OK;
-    if (thin_bl_launch(p, a, reflect, (int)nb, st, &rc)) return rc;
-  }
+  if (v.kernel == EBEN_VARIANT_THIN_BL) return thin_bl_launch(p, a, v.thin, (int)nb, st);
 #define EBEN_T3_CASE(FMV)                                                          \
-  switch (p.XRB) {                                                                 \
-    case 2: return launch3_cfg<FMV, 2>(a, (int)nb, p.lds_bytes, p.npw, p.npx, st);               \
-    case 3: return launch3_cfg<FMV, 3>(a, (int)nb, p.lds_bytes, p.npw, p.npx, st);               \
-    default: return launch3_cfg<FMV, 5>(a, (int)nb, p.lds_bytes, p.npw, p.npx, st);              \
+  switch (v.XRB) {                                                                 \
+    case 2: return launch3_cfg<FMV, 2>(a, (int)nb, p.lds_bytes, v, st);            \
+    case 3: return launch3_cfg<FMV, 3>(a, (int)nb, p.lds_bytes, v, st);            \
+    default: return launch3_cfg<FMV, 5>(a, (int)nb, p.lds_bytes, v, st);           \
   }
-  switch (p.FM) {
+  switch (v.FM) {
     case 1: EBEN_T3_CASE(1)
     case 2: EBEN_T3_CASE(2)
     case 3: EBEN_T3_CASE(3)

@@ -555,36 +555,48 @@ static int launch_fm(int FM, const Tap3Args& a, int nblocks, size_t lds, hipStre
   }
 }
 
+enum { FORM_FWD_NP2_S2 = 1, FORM_FWD_NP1_S4, FORM_DX_PR_S2, FORM_DX_PR_S4, FORM_DX_PS };
+
 }  // namespace thin
 
-// Called by tap3_launch with the finished plan and arguments of a tap3_kernel launch: 1 (and *rc) when a thin_bl kernel took it, 0 when the
-// launch is not one of the thin forms (tap3_kernel runs it).  Nothing here is per launch beyond a few comparisons of the plan.
-int thin_bl_launch(const Tap3Plan& p, const Tap3Args& a, int reflect, int nblocks, hipStream_t st, int* rc) {
+// The finished plan of a tap3_kernel launch and what the launch carries: the thin form that takes it, 0 when the launch is not one of the
+// thin forms (tap3_kernel runs it).  Nothing here is per launch beyond a few comparisons of the plan.
+int thin_bl_form(const Tap3Plan& p, const Tap3Call& k) {
   static const int enabled = getenv("EBEN_THIN_BL") ? atoi(getenv("EBEN_THIN_BL")) : 1;
-  if (!enabled || !a.xh || p.big || reflect || a.in_mode || p.npw != p.npx || p.npw > 2) return 0;
+  if (!enabled || !k.bl || p.big || k.reflect || k.in_mode || p.npw != p.npx || p.npw > 2) return 0;
   // one channel chunk in one input buffer, tap3_kernel's chunking and ring (the packed image and table are the plan's), <= 8 phases
   if (p.ncc != 1 || p.nxbuf != 1 || p.nph > 8 || p.FM < 1 || p.FM > 4 || p.BN != 128) return 0;
   if (p.KSC != thin::ksc_of(p.npw) || p.WCHU != p.KSC * p.npw * p.FM * 64) return 0;
   if (p.lds_bytes != (size_t)thin::RING * p.WCHU * 16 + ((size_t)p.CI_B * p.CSTRIDE * 16 + 16) * p.npx + (size_t)p.BM * 4) return 0;
   // the thin layers: <= 128 reduction channels and <= 256 rows per group
   if (p.Cg > 128 || p.Mg > 256) return 0;
-  const size_t lds = p.lds_bytes;
-  if (p.mode == 0 && a.pr_S == 0) {
-    if (a.eh || a.res || a.accumulate || p.nph != 1) return 0;   // forward: bias + activation only
-    if (p.S == 2 && p.npw == 2) { *rc = thin::launch_fm<2, thin::FWD, 2>(p.FM, a, nblocks, lds, st); return 1; }   // PQMF-band L1-L4
-    if (p.S == 4 && p.npw == 1) { *rc = thin::launch_fm<1, thin::FWD, 4>(p.FM, a, nblocks, lds, st); return 1; }   // MelGAN L1-L2
+  if (p.mode == 0 && k.pr_S == 0) {
+    if (k.eh || k.res || k.accumulate || p.nph != 1) return 0;   // forward: bias + activation only
+    if (p.S == 2 && p.npw == 2) return thin::FORM_FWD_NP2_S2;     // PQMF-band L1-L4
+    if (p.S == 4 && p.npw == 1) return thin::FORM_FWD_NP1_S4;     // MelGAN L1-L2
     return 0;
   }
-  if (p.npw != 1 || a.bias || a.res || a.accumulate) return 0;
+  if (p.npw != 1 || k.bias || k.res || k.accumulate) return 0;
   if (p.mode == 0) {   // phases as rows (the primed stride-1 layer)
-    if (a.pr_order != 1 || p.S != 1 || p.nph != 1) return 0;
-    if (a.pr_S == 2) { *rc = thin::launch_fm<1, thin::DX_PR, 2>(p.FM, a, nblocks, lds, st); return 1; }
-    if (a.pr_S == 4) { *rc = thin::launch_fm<1, thin::DX_PR, 4>(p.FM, a, nblocks, lds, st); return 1; }
+    if (k.pr_order != 1 || p.S != 1 || p.nph != 1) return 0;
+    if (k.pr_S == 2) return thin::FORM_DX_PR_S2;
+    if (k.pr_S == 4) return thin::FORM_DX_PR_S4;
     return 0;
   }
   if (p.S != 1 || p.OS != 2 || p.nph != 2) return 0;   // phase scatter: the stride-2 input gradients that keep it (dilation 3)
-  *rc = thin::launch_fm<1, thin::DX_PS, 1>(p.FM, a, nblocks, lds, st);
-  return 1;
+  return thin::FORM_DX_PS;
+}
+
+int thin_bl_launch(const Tap3Plan& p, const Tap3Args& a, int form, int nblocks, hipStream_t st) {
+  const size_t lds = p.lds_bytes;
+  switch (form) {
+    case thin::FORM_FWD_NP2_S2: return thin::launch_fm<2, thin::FWD, 2>(p.FM, a, nblocks, lds, st);
+    case thin::FORM_FWD_NP1_S4: return thin::launch_fm<1, thin::FWD, 4>(p.FM, a, nblocks, lds, st);
+    case thin::FORM_DX_PR_S2: return thin::launch_fm<1, thin::DX_PR, 2>(p.FM, a, nblocks, lds, st);
+    case thin::FORM_DX_PR_S4: return thin::launch_fm<1, thin::DX_PR, 4>(p.FM, a, nblocks, lds, st);
+    case thin::FORM_DX_PS: return thin::launch_fm<1, thin::DX_PS, 1>(p.FM, a, nblocks, lds, st);
+    default: return fail(EBEN_EINVAL, "thin_bl: no thin form %d", form);
+  }
 }
 
 }  // namespace eben
