@@ -1,13 +1,17 @@
 #!/usr/bin/env python
 """EBEN train-step benchmark (BASELINE.json metric: audio-seconds/sec of the full GAN step).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 One "step" = EBENLightningModule.training_step on one batch of synthetic (32, 1, 32000) float32
 waveforms already resident in HBM (cut to 31968): generator fwd, MRSTFT + feature-matching + hinge,
 EMA loss balancing, generator backward + Adam, discriminator fwd/backward + Adam, and (N > 1) the
 RCCL gradient all-reduces.  Weak scaling: 32 clips per GPU.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps, --dump-outputs, the JSON line.
+--full adds the legs that measure something else, each in the same process: the CPU baseline (first), the roofline launch
+timings (a second run of the steps launched kernel by kernel, then the roofline kernel alone) and the fp32 / fp32-grade legs.
 """
 from __future__ import annotations
 
@@ -214,7 +218,10 @@ def main():
     ap.add_argument("--workload", default="bwe", choices=["bwe", "noisybwe"],
                     help="bwe: BASELINE config 2 (resident synthetic batch); noisybwe: config 4 (every step assembles its batch on the "
                          "device from a resident pool of ragged clips: noise mixing + crop/pad to 2.5 s + time masking, then the same step)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure, run and report the CPU baseline, the roofline launch timings (roofline, "
+                         "roofline_time_dominant, roofline_family) and the fp32 and fp32-grade legs (value_f32, value_fp32_grade)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-batch", type=int, default=32)
     ap.add_argument("--cpu-steps", type=int, default=3)
     ap.add_argument("--force-ddp", action="store_true", help="run the bucketed RCCL gradient path even with one rank")
@@ -228,7 +235,7 @@ def main():
                     help="generator backward contractions (default: bf16 with a bf16 discriminator, else f32)")
     ap.add_argument("--stft-math", default=None, choices=["bf16x3", "folded", "dense", "folded_x3", "folded_x6"],
                     help="MRSTFT windowed-DFT contractions (default: 'folded', exact fp32 on the even / odd parts of the frames)")
-    ap.add_argument("--no-f32-leg", action="store_true", help="skip the extra fp32 timing reported beside a bf16 run")
+    ap.add_argument("--no-f32-leg", action="store_true", help="with --full: skip the extra fp32 timings reported beside a bf16 run")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (returned tensors, logged losses, parameters after its "
                          "Adam updates) as DIR/<name>.npy, at most 64 MB; rank 0 only (e.g. bench_outputs/)")
@@ -278,7 +285,7 @@ def main():
     # The CPU-baseline leg runs FIRST (rank 0, one rank only): everything after it is GPU work, so a sampler watching the device over the
     # run (the driver's rocm-smi trace) sees the timed region and not a host-only tail.
     cpu_rec = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         # torch's intra-op pool.  Measured on the GPU host (2 x EPYC 9575F, 256 hardware threads) at the full batch 32: 8 threads 9.9,
         # 16 threads 14.8, 32 threads 10.6 audio-s/s, 256 threads > 20x slower -- these convolutions do not scale past ~16 threads, so
         # 16 is the setting that is fair to the CPU; the 8-thread leg is comparable with the survey's measurement of the reference.
@@ -351,7 +358,8 @@ def main():
     mel = mod.discriminator.melgan_discriminator.discriminator
     layer, layer_t = mel[4][0], mel[3][0]
     timer, timer_t = ops.KernelTimer(layer.spec, "fwd"), ops.KernelTimer(layer_t.spec, "dx")
-    ops.set_kernel_timers([timer, timer_t])
+    if args.full:
+        ops.set_kernel_timers([timer, timer_t])
 
     def barrier():
         if use_ddp:
@@ -422,13 +430,14 @@ def main():
     # The two roofline launches are bracketed by HIP events on the stream they are launched on.  Events cannot sit between the nodes of
     # a replayed HIP graph, and the timed steps above replay the discriminator chains as graphs (ops.ReplayedChain): the brackets are
     # taken over a second run of the same steps with the chains launched kernel by kernel (same kernels, same streams, same batch)
-    timer.enabled = timer_t.enabled = True
-    timed_steps(max(5, args.steps // 4))
-    timer.enabled = timer_t.enabled = False
+    if args.full:
+        timer.enabled = timer_t.enabled = True
+        timed_steps(max(5, args.steps // 4))
+        timer.enabled = timer_t.enabled = False
 
     # beside a bf16 run: the same K steps in exact fp32 (the arithmetic of the reference), reported as value_f32 -- never as `value`
     dt32 = per32 = None
-    if bf16 and not args.no_f32_leg:
+    if args.full and bf16 and not args.no_f32_leg:
         mod.disc_math = mod.gen_backward_math = "f32"
         mod.stft_math = "folded"
         settle32 = settle_graphs()   # the plan's own launch sequences are captured before its clock starts (as for the bf16 leg)
@@ -438,7 +447,7 @@ def main():
     # contractions with three bf16 pieces per operand, weight gradients and the generator backward in fp32 arithmetic): the plan whose
     # tests run at the fp32 tolerances, reported as value_fp32_grade
     dt6 = per6 = None
-    if bf16 and not args.no_f32_leg:
+    if args.full and bf16 and not args.no_f32_leg:
         mod.disc_math, mod.gen_backward_math, mod.stft_math = "bf16x6", "f32", "folded_x6"
         settle6 = settle_graphs()
         dt6, per6 = timed_steps(args.steps)
@@ -446,7 +455,7 @@ def main():
     # the roofline kernel once more, ALONE on the device (inside the step it shares the GPU with the three other
     # discriminator chains and the MRSTFT GEMMs, which stretches its launch-to-finish time): reported as `isolated`
     iso_ms = None
-    if rank == 0:
+    if args.full and rank == 0:
         import ctypes
         from vibravox_amd._lib import check, load, ptr, stream
         from vibravox_amd.lightning_modules.eben import DISC_MATH_PLANS
@@ -491,55 +500,58 @@ def main():
         value = audio_s / (dt / args.steps)
         peak = MFMA_BF16_PEAK_TFLOPS if bf16 else MFMA_F32_PEAK_TFLOPS
 
-        def launch_record(tm, which, kname):
-            sp = tm.spec
-            lx = cut
-            chain = [(15, 1, 7), (41, 4, 20), (41, 4, 20), (41, 4, 20)]
-            depth = 4 if tm is timer else 3
-            for (k, s_, p_) in chain[:depth]:
-                lx = (lx + 2 * p_ - (k - 1) - 1) // s_ + 1
-            l_out = sp.out_len(lx)
-            items = tm.batch or args.batch
-            flops = 2.0 * items * sp.c_out * (sp.c_in // sp.groups) * sp.ksize * l_out
-            kms = tm.mean_ms()
-            ach = flops / (kms * 1e-3) / 1e12 if kms else None
-            return {"bound": "mfma", "kernel": f"eben::{kname} MelGAN L{depth} {which} ({sp.c_in}->{sp.c_out} k{sp.ksize} s{sp.stride} g{sp.groups}), {items} items per launch",
-                    "achieved": round(ach, 2) if ach else None, "peak": peak, "unit": "TFLOP/s", "frac": round(ach / peak, 4) if ach else None,
-                    "launch_ms": round(kms, 4) if kms else None, "flops_per_launch": flops, "launches_timed": len(tm.events)}, flops
-
         stft_desc = {"folded_x6": "fp32-grade (three bf16 pieces per operand)",
                      "folded_x3": "hi + lo bf16 operands (three MFMAs per product, ~2^-17; the generator gradient against the fp32 step stays at 5.5e-3)"
                      }.get(stft_math, "fp32 (" + stft_math + ")")
-        kn = ("tap4_kernel<2,2,4,2,1,4,3,2> (bigtap.hip: persistent producer / consumer block per CU, v_mfma_f32_32x32x16_bf16, bf16 bundles at rest)" if args.disc_math == "bf16_bl" else
-              "tap3_kernel<4,*> (v_mfma_f32_32x32x16_bf16)" if bf16 else "tap2_kernel<4,4,16> (v_mfma_f32_32x32x2_f32)")
-        roof, flops = launch_record(timer, "fwd", kn)
-        family = pmc_family(args.disc_math) if (timer.batch or 2 * args.batch) == 64 else []
-        roof["traffic"] = next((r["traffic_bytes"] for r in family if r["name"] == "melgan_l4_fwd"), None)
-        # the counters are not collected inside this run (rocprofv3 --pmc passes are separate processes): the figure is the committed profile's
-        roof["traffic_source"] = next((r.get("source") for r in family if r["name"] == "melgan_l4_fwd"), None)
-        roof["launch_ms_note"] = ("HIP events around the launch on its stream, over a second run of the timed steps with the chains launched kernel by "
-                                  "kernel (events cannot sit between the nodes of a replayed graph); `isolated` = the same launch alone; "
-                                  "`profile` = THAT launch's duration inside the graph-replayed step, from the committed rocprofv3 --kernel-trace with "
-                                  "dispatch order (named by its position on MelGAN's queue; the tracer stretches the step)")
-        prof = (named_launch("melgan_l4_fwd") if args.disc_math == "bf16_bl" else None) or profile_average("tap4_kernel<2, 2, 4, 2, 1" if args.disc_math == "bf16_bl" else "tap3_kernel<4")
-        if prof:
-            roof["profile"] = prof
-            if prof.get("launch") and prof.get("avg_ms"):
-                roof["profile"]["achieved"] = round(flops / (prof["avg_ms"] * 1e-3) / 1e12, 2)
-                roof["profile"]["frac"] = round(flops / (prof["avg_ms"] * 1e-3) / 1e12 / peak, 4)
-        if iso_ms:
-            roof["isolated"] = {"launch_ms": round(iso_ms, 4), "achieved": round(flops / (iso_ms * 1e-3) / 1e12, 2),
-                                "frac": round(flops / (iso_ms * 1e-3) / 1e12 / peak, 4),
-                                "note": "same launch alone on the device, 20 back-to-back launches after the timed region"}
-        if roof.get("bound") == "mfma":
-            roof["peak_note"] = ("`peak` is the dense bf16 MFMA figure at 2.4 GHz (MI355X_MICROARCH.md); tools/ubench/clock_probe.hip on this pool: the shader clock is "
-                                 "2.38 GHz idle and 1.82-1.89 GHz with MFMA streams on every SIMD, 1.83-1.94 PFLOP/s of pure MFMA issue")
-        roof_t, flops_t = launch_record(timer_t, "input gradient (two 2B-row passes per step: rows [fm | adv], then rows [fake | real])", kn)
-        prof_t = named_launch("melgan_l3_dx") if args.disc_math == "bf16_bl" else None
-        if prof_t and prof_t.get("avg_ms"):
-            prof_t["achieved"] = round(flops_t / (prof_t["avg_ms"] * 1e-3) / 1e12, 2)
-            prof_t["frac"] = round(flops_t / (prof_t["avg_ms"] * 1e-3) / 1e12 / peak, 4)
-            roof_t["profile"] = prof_t
+        roof_fields = {}   # --full: the launch records of the roofline kernels
+        if args.full:
+            def launch_record(tm, which, kname):
+                sp = tm.spec
+                lx = cut
+                chain = [(15, 1, 7), (41, 4, 20), (41, 4, 20), (41, 4, 20)]
+                depth = 4 if tm is timer else 3
+                for (k, s_, p_) in chain[:depth]:
+                    lx = (lx + 2 * p_ - (k - 1) - 1) // s_ + 1
+                l_out = sp.out_len(lx)
+                items = tm.batch or args.batch
+                flops = 2.0 * items * sp.c_out * (sp.c_in // sp.groups) * sp.ksize * l_out
+                kms = tm.mean_ms()
+                ach = flops / (kms * 1e-3) / 1e12 if kms else None
+                return {"bound": "mfma", "kernel": f"eben::{kname} MelGAN L{depth} {which} ({sp.c_in}->{sp.c_out} k{sp.ksize} s{sp.stride} g{sp.groups}), {items} items per launch",
+                        "achieved": round(ach, 2) if ach else None, "peak": peak, "unit": "TFLOP/s", "frac": round(ach / peak, 4) if ach else None,
+                        "launch_ms": round(kms, 4) if kms else None, "flops_per_launch": flops, "launches_timed": len(tm.events)}, flops
+
+            kn = ("tap4_kernel<2,2,4,2,1,4,3,2> (bigtap.hip: persistent producer / consumer block per CU, v_mfma_f32_32x32x16_bf16, bf16 bundles at rest)" if args.disc_math == "bf16_bl" else
+                  "tap3_kernel<4,*> (v_mfma_f32_32x32x16_bf16)" if bf16 else "tap2_kernel<4,4,16> (v_mfma_f32_32x32x2_f32)")
+            roof, flops = launch_record(timer, "fwd", kn)
+            family = pmc_family(args.disc_math) if (timer.batch or 2 * args.batch) == 64 else []
+            roof["traffic"] = next((r["traffic_bytes"] for r in family if r["name"] == "melgan_l4_fwd"), None)
+            # the counters are not collected inside this run (rocprofv3 --pmc passes are separate processes): the figure is the committed profile's
+            roof["traffic_source"] = next((r.get("source") for r in family if r["name"] == "melgan_l4_fwd"), None)
+            roof["launch_ms_note"] = ("HIP events around the launch on its stream, over a second run of the timed steps with the chains launched kernel by "
+                                      "kernel (events cannot sit between the nodes of a replayed graph); `isolated` = the same launch alone; "
+                                      "`profile` = THAT launch's duration inside the graph-replayed step, from the committed rocprofv3 --kernel-trace with "
+                                      "dispatch order (named by its position on MelGAN's queue; the tracer stretches the step)")
+            prof = (named_launch("melgan_l4_fwd") if args.disc_math == "bf16_bl" else None) or profile_average("tap4_kernel<2, 2, 4, 2, 1" if args.disc_math == "bf16_bl" else "tap3_kernel<4")
+            if prof:
+                roof["profile"] = prof
+                if prof.get("launch") and prof.get("avg_ms"):
+                    roof["profile"]["achieved"] = round(flops / (prof["avg_ms"] * 1e-3) / 1e12, 2)
+                    roof["profile"]["frac"] = round(flops / (prof["avg_ms"] * 1e-3) / 1e12 / peak, 4)
+            if iso_ms:
+                roof["isolated"] = {"launch_ms": round(iso_ms, 4), "achieved": round(flops / (iso_ms * 1e-3) / 1e12, 2),
+                                    "frac": round(flops / (iso_ms * 1e-3) / 1e12 / peak, 4),
+                                    "note": "same launch alone on the device, 20 back-to-back launches after the timed region"}
+            if roof.get("bound") == "mfma":
+                roof["peak_note"] = ("`peak` is the dense bf16 MFMA figure at 2.4 GHz (the MI355X's rated peak); tools/ubench/clock_probe.hip on the MI355X: the shader clock is "
+                                     "2.38 GHz idle and 1.82-1.89 GHz with MFMA streams on every SIMD, 1.83-1.94 PFLOP/s of pure MFMA issue")
+            roof_t, flops_t = launch_record(timer_t, "input gradient (two 2B-row passes per step: rows [fm | adv], then rows [fake | real])", kn)
+            prof_t = named_launch("melgan_l3_dx") if args.disc_math == "bf16_bl" else None
+            if prof_t and prof_t.get("avg_ms"):
+                prof_t["achieved"] = round(flops_t / (prof_t["avg_ms"] * 1e-3) / 1e12, 2)
+                prof_t["frac"] = round(flops_t / (prof_t["avg_ms"] * 1e-3) / 1e12 / peak, 4)
+                roof_t["profile"] = prof_t
+            roof_fields = {"roofline": roof, "roofline_time_dominant": roof_t, "roofline_family": family}
         ideal = step_roofline_ms("f32" if not bf16 else "bf16", scale)
         line = {
             "metric": "EBEN train-step audio-seconds/sec (gen+disc)", "value": round(value, 2), "unit": "audio-seconds/sec",
@@ -562,9 +574,7 @@ def main():
             "step_ms": {"median": round(percentile(per_step, 0.5), 3), "p10": round(percentile(per_step, 0.1), 3),
                         "p90": round(percentile(per_step, 0.9), 3), "max": round(per_step[-1], 3),
                         "mean": round(sum(per_step) / len(per_step), 3), "clock": "HIP events at the step boundaries on the main stream"},
-            "roofline": roof,
-            "roofline_time_dominant": roof_t,
-            "roofline_family": family,
+            **roof_fields,
             "step_roofline": {"ideal_ms": round(ideal, 3), "frac": round(ideal / ms, 4),
                               "note": "sum over the eleven passes of F_min = 2(3G+8D) of max(FLOP / dense MFMA peak of `dtype`, SURVEY 8d bytes / 8 TB/s) / measured ms per "
                                       "step; no credit for the build's own extra products (G = 6.727e8, D = 2.5255e9 MACs per audio-second)"},
