@@ -714,10 +714,10 @@ def test_benchmarked_plan_two_steps_with_mrstft_against_oracle(hip, golden, plan
         np.testing.assert_allclose(torch.stack(mod.last_norms).cpu().numpy(), logs["balancing/norms"].numpy(), rtol=5e-2)
 
 
-def test_prepack_graph_survives_a_forward_at_another_shape(hip, golden):
-    """train x4 (the prepack sequences settle and are captured into HIP graphs) -> validation forward at another batch / length (the
-    shared image caches miss and reallocate) -> train x2: bit-identical to the same sequence with the graphs disabled.  A replay that
-    kept writing the buffers it captured would leave the generator's convolutions on pre-update weights from here on."""
+def test_prepack_graphs_of_both_networks_survive_a_forward_at_another_shape(hip, golden):
+    """train x4 (the prepack sequences, one per network, settle and are captured into HIP graphs) -> validation forward at another batch /
+    length (the shared image caches miss and reallocate) -> train x2: bit-identical to the same sequence with the graphs disabled.  A
+    replay that kept writing the buffers it captured would leave the generator's convolutions on pre-update weights from here on."""
     from vibravox_amd import ops
 
     def run(graphs):
@@ -725,7 +725,7 @@ def test_prepack_graph_survives_a_forward_at_another_shape(hip, golden):
         ops.ReplayedPrepack.enabled = graphs
         try:
             mod, _, _ = make_module(golden, use_mrstft=False)
-            captured = 0
+            captured = []
             for i in range(6):
                 if i == 4:
                     mod.validation_step({"audio_body_conducted": formula_audio("pp/val/bc", 3, 5000).to(DEV),
@@ -733,7 +733,7 @@ def test_prepack_graph_survives_a_forward_at_another_shape(hip, golden):
                 batch = {"audio_body_conducted": formula_audio(f"pp/{i}/bc", 2, 8200).to(DEV), "audio_airborne": formula_audio(f"pp/{i}/air", 2, 8200).to(DEV)}
                 mod.training_step(batch)
                 if i == 3:
-                    captured = sum(g.graph is not None for g in (ops._conv_prepack_graph, mod.generator._engine._prepack_graph, mod._disc_engine._prepack_graph))
+                    captured = [g.graph is not None for g in (mod._prepack_graph, mod._disc_engine._prepack_graph)]   # one per network
             torch.cuda.synchronize()
             out = {f"G.{k}": v.clone() for k, v in mod.generator.state_dict().items()}
             out.update({f"D.{k}": v.clone() for k, v in mod.discriminator.state_dict().items()})
@@ -742,9 +742,8 @@ def test_prepack_graph_survives_a_forward_at_another_shape(hip, golden):
         finally:
             ops.ReplayedPrepack.enabled = prev
 
-    ops._conv_prepack_graph.graph, ops._conv_prepack_graph.sig = None, None
     (a, cap_a), (b, cap_b) = run(True), run(False)
-    assert cap_a == 3 and cap_b == 0, (cap_a, cap_b)   # the three sequences were graph replays before the validation forward
+    assert len(cap_a) == 2 and all(cap_a) and not any(cap_b), (cap_a, cap_b)   # both sequences were graph replays before the validation forward
     assert [k for k in a if not torch.equal(a[k], b[k])] == []
 
 

@@ -166,13 +166,13 @@ def main():
         seeds = torch.randn(r4, 1, cur.length, device=dev)
         gt = Planes(r4, cur.channels, cur.length, dev, lo=False)
         t_f = time_ms(lambda: check(lib.eben_bl_tail_fwd(xin.hi.data_ptr(), xin.lo.data_ptr(), r2, cur.channels, cur.length, sp.ksize, sp.pad_l, ptr(v.detach()),
-                                                         ptr(tail.scale), ptr(bias.detach()), 1.0, ptr(logits), st)), a.iters)
+                                                         ptr(tail.cache.scale), ptr(bias.detach()), 1.0, ptr(logits), st)), a.iters)
         seg_gen, seg_disc = (ctypes.c_int * 4)(0, 0, 0, 0), (ctypes.c_int * 4)(0, 1, 0, 1)
 
         def tail_two_passes():
-            check(lib.eben_bl_tail_dx(ptr(seeds), r2, cur.channels, cur.length, sp.ksize, sp.pad_l, ptr(v.detach()), ptr(tail.scale), xin.hi.data_ptr(),
+            check(lib.eben_bl_tail_dx(ptr(seeds), r2, cur.channels, cur.length, sp.ksize, sp.pad_l, ptr(v.detach()), ptr(tail.cache.scale), xin.hi.data_ptr(),
                                       xin.lo.data_ptr(), 0.2, half, seg_gen, half, half, ptr(sums), 0.1, gt.hi.data_ptr(), None, st))
-            check(lib.eben_bl_tail_dx(ptr(seeds[r2:]), r2, cur.channels, cur.length, sp.ksize, sp.pad_l, ptr(v.detach()), ptr(tail.scale), xin.hi.data_ptr(),
+            check(lib.eben_bl_tail_dx(ptr(seeds[r2:]), r2, cur.channels, cur.length, sp.ksize, sp.pad_l, ptr(v.detach()), ptr(tail.cache.scale), xin.hi.data_ptr(),
                                       xin.lo.data_ptr(), 0.2, half, seg_disc, 0, half, ptr(sums), 0.1, gt.hi[r2:].data_ptr(), None, st))
         t_b = time_ms(tail_two_passes, a.iters)
         t_w = time_ms(lambda: ch.weight_grads([(n - 1, seeds[r2:], xin)], x_in, None, half), a.iters)

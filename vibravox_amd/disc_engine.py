@@ -56,27 +56,21 @@ class _Layer:
         self.math_fwd, self.math_dx, self.math_dw = (math, math, math) if isinstance(math, int) else tuple(math)
         self.spec: ops.ConvSpec = conv.spec
         self.spec_lin = dataclasses.replace(conv.spec, in_slope=1.0, out_slope=1.0)   # gradients arrive pre-masked
-        self.packs: Dict[Tuple[int, int, int], Tuple[tuple, torch.Tensor]] = {}
-        self.used = set()   # slots touched since the last prepack(): the only ones it rebuilds
-        self.scale_key = None
-        self.scale = self.norm = None
-        self.reuse = False   # inside prepack(): rebuild into the buffers already held (ops._buffer)
-        self.keep_scale = False   # the layer's kernels take (v, scale) directly (bundle-layout heads / tails): prepack refreshes the scale
+        #: slots (direction, batch, length) -> images; scale / norm; pruned by prepack to the slots the last step used
+        self.cache = ops.PackedWeights(prune=True)
         self.pr_weights: Dict[tuple, torch.Tensor] = {}   # slot -> primed weights of the phases-as-rows input gradient
         self._pr_descs: Dict[tuple, object] = {}
         self._params = None
 
+    @property
+    def packs(self) -> dict:
+        """The packed images held, by slot (direction, batch, length)."""
+        return self.cache.images
+
     def ensure_scale(self) -> None:
         """Weight-norm scale g / ||v|| and norm ||v|| of the current weights (what ``packed`` computes on the way)."""
-        v, g, _ = self.params()
-        v, g = v.detach(), g.detach()
-        wkey = self._weights_key()
-        if self.scale_key != wkey:
-            rows = v.shape[0]
-            self.scale = ops._buffer(self.scale, rows, v, self.reuse)
-            self.norm = ops._buffer(self.norm, rows, v, self.reuse)
-            check(load().eben_wn_scale(ptr(g), ptr(v), rows, v.numel() // rows, ptr(self.scale), ptr(self.norm), _stream()), "wn_scale")
-            self.scale_key = wkey
+        self.params()
+        self.cache.ensure_scale()
 
     def params(self):
         """(v, g, bias).  Looked up ~440 times a step: the Parameter objects are kept until ``ops.bump_weights_epoch()`` (no arguments)
@@ -86,36 +80,26 @@ class _Layer:
         if hit is None or hit[0] != epoch:
             prm = self.conv.parametrizations["weight"]
             hit = self._params = (epoch, (prm.original1, prm.original0, self.conv.bias))
+            self.cache.params = hit[1][:2]
         return hit[1]
-
-    def _weights_key(self):
-        v, g, _ = self.params()
-        e = ops._storage_epoch
-        return (v.data_ptr(), v._version, e.get(v.data_ptr(), 0), g.data_ptr(), g._version, e.get(g.data_ptr(), 0), e.get(-1, 0))
 
     def packed(self, which: int, batch: int, l_in: int) -> torch.Tensor:
         """MFMA / direct layout of the weights for the forward (0) or input-gradient (1) launch of this
         exact descriptor (the first-generation layout depends on the batch size)."""
         lib = load()
-        v, g, _ = self.params()
-        v, g = v.detach(), g.detach()
-        wkey = self._weights_key()
-        if self.scale_key != wkey:
-            rows = v.shape[0]
-            self.scale = ops._buffer(self.scale, rows, v, self.reuse)
-            self.norm = ops._buffer(self.norm, rows, v, self.reuse)
-            check(lib.eben_wn_scale(ptr(g), ptr(v), rows, v.numel() // rows, ptr(self.scale), ptr(self.norm), _stream()), "wn_scale")
-            self.scale_key = wkey
+        v = self.params()[0].detach()
+        c = self.cache
+        key = c.ensure_scale()
         slot = (which, batch, l_in)
-        self.used.add(slot)
-        hit = self.packs.get(slot)
-        if hit is not None and hit[0] == wkey:
+        c.used.add(slot)
+        hit = c.images.get(slot)
+        if hit is not None and hit[0] == key:
             return hit[1]
-        if hit is None and len(self.packs) >= self.MAX_PACKS:
+        if hit is None and len(c.images) >= self.MAX_PACKS:
             # variable clip lengths / a short last batch: every new (batch, length) would otherwise keep another packed copy of
             # the weights alive and be re-packed after every optimiser step -- drop the slots the current step has not touched
-            for old in [k for k in self.packs if k not in self.used] or list(self.packs)[:1]:
-                del self.packs[old]
+            for old in [k for k in c.images if k not in c.used] or list(c.images)[:1]:
+                del c.images[old]
         d = ops.conv_desc(self.spec, batch, l_in, self.math_fwd if which == 0 else self.math_dx)
         if which == 2:
             # "phases as rows" form of the input gradient (include/eben_hip.h, eben_bl_dx_pr_*): the primed stride-1 layer's weights are a
@@ -125,14 +109,13 @@ class _Layer:
             n_w = dq.c_out * (dq.c_in // dq.groups) * dq.ksize
             if wq is None or wq.numel() != n_w:
                 wq = self.pr_weights[slot] = torch.empty(n_w, dtype=torch.float32, device=v.device)
-            check(lib.eben_bl_dx_pr_weights(ctypes.byref(d), ptr(v), ptr(self.scale), ptr(wq), _stream()), "bl_dx_pr_weights")
-            wp = ops._buffer(None if hit is None else hit[1], lib.eben_conv1d_packed_floats(ctypes.byref(dq), 0), v, self.reuse)
+            check(lib.eben_bl_dx_pr_weights(ctypes.byref(d), ptr(v), ptr(c.scale), ptr(wq), _stream()), "bl_dx_pr_weights")
+            wp = c.buffer(None if hit is None else hit[1], lib.eben_conv1d_packed_floats(ctypes.byref(dq), 0), v)
             ops.conv1d_pack(dq, wq, None, wp, None)
-            self.packs[slot] = (wkey, wp)
-            return wp
-        wp = ops._buffer(None if hit is None else hit[1], lib.eben_conv1d_packed_floats(ctypes.byref(d), which), v, self.reuse)
-        ops.conv1d_pack(d, v, self.scale, wp if which == 0 else None, wp if which == 1 else None)
-        self.packs[slot] = (wkey, wp)
+        else:
+            wp = c.buffer(None if hit is None else hit[1], lib.eben_conv1d_packed_floats(ctypes.byref(d), which), v)
+            ops.conv1d_pack(d, v, c.scale, wp if which == 0 else None, wp if which == 1 else None)
+        c.images[slot] = (key, wp)
         return wp
 
     def pr_desc(self, batch: int, l_in: int):
@@ -331,7 +314,7 @@ class _Chain:
         dg = torch.empty_like(gain) if dg is None else dg
         if bias is not None and dbias is None:
             dbias = torch.empty(wrows, dtype=torch.float32, device=g2.device)
-        wn_jobs.append((slabs, nslab.value, wrows * row_stride.value, wrows, cols, row_stride.value, gain.detach(), v.detach(), lay.norm,
+        wn_jobs.append((slabs, nslab.value, wrows * row_stride.value, wrows, cols, row_stride.value, gain.detach(), v.detach(), lay.cache.norm,
                         dg, dv, dbias))
         return dv, dg, dbias
 
@@ -502,61 +485,11 @@ class DiscriminatorEngine:
     def join(self):
         self._join_streams()
 
-    def prepack(self):
-        """Rebuilds every packed weight image the last step used (forward at 2B rows, input gradients at 4B / 2B rows)
-        on the side stream, right after the discriminator's optimiser step: the ~100 small launches then run under the
-        next step's generator forward instead of at the head of the four chains."""
-        if not self.chains or not any(lay.packs or (lay.keep_scale and lay.scale is not None) for ch in self.chains for lay in ch.layers):
-            return
-        dev = self.chains[0].layers[0].params()[0].device
-        main = torch.cuda.current_stream(dev)
-        side = ops._side_stream(dev)
-        side.wait_stream(main)
-        layers = [lay for ch in self.chains for lay in ch.layers]
-
-        def body():
-            jobs = []
-            for lay in layers:   # weight-norm scales of all layers: one multi-tensor launch
-                wkey = lay._weights_key()
-                if (lay.packs or (lay.keep_scale and lay.scale is not None)) and lay.scale_key != wkey:
-                    v, g, _ = lay.params()
-                    rows = v.shape[0]
-                    lay.scale = ops._buffer(lay.scale, rows, v, True)
-                    lay.norm = ops._buffer(lay.norm, rows, v, True)
-                    lay.scale_key = wkey
-                    jobs.append((g.detach(), v.detach(), rows, v.numel() // rows, lay.scale, lay.norm))
-            ops.wn_scale_multi(jobs)
-            with ops.pack_batch():
-                for lay in layers:
-                    used, lay.used = lay.used, set()
-                    lay.reuse = True
-                    try:
-                        for slot in list(lay.packs):
-                            if slot in used:
-                                lay.packed(*slot)     # what the last step launched: the next step most likely launches it again
-                            else:
-                                del lay.packs[slot]   # a shape of an earlier step: rebuilt on demand if it comes back
-                    finally:
-                        lay.reuse = False
-                    lay.used = set()              # re-packing is not a use: the next step decides what survives the next prepack
-
-        # the launch sequence as a function of everything but the weights' values (ops.ReplayedPrepack): layers, the slots the last
-        # step used (= all the slots held, or the eager path prunes), parameter storage, the image / scale buffers written, and that
-        # every image is stale
-        sig = tuple((id(lay), tuple(sorted(lay.packs)), tuple(sorted(lay.used)) == tuple(sorted(lay.packs)), lay.params()[0].data_ptr(),
-                     tuple(lay.packs[k][1].data_ptr() for k in sorted(lay.packs)), 0 if lay.scale is None else lay.scale.data_ptr(),
-                     0 if lay.norm is None else lay.norm.data_ptr(),
-                     lay.scale_key != lay._weights_key()) for lay in layers) + (ops._storage_epoch.get(-1, 0),)
-        with torch.cuda.stream(side), torch.no_grad():
-            if self._prepack_graph.run(sig, body, side):
-                for lay in layers:   # replayed: images and scales are current, the cache keys are not
-                    wkey = lay._weights_key()
-                    lay.scale_key = wkey
-                    for slot, (_, wp) in list(lay.packs.items()):
-                        lay.packs[slot] = (wkey, wp)
-                    lay.used = set()
-            self._prepack_ev = torch.cuda.Event()
-            self._prepack_ev.record()
+    def image_caches(self) -> list:
+        """``ops.prepack`` entries of every layer: after the discriminator's optimiser step the images the last step used (forward at
+        2B rows, input gradients at 4B / 2B rows) are rebuilt on the side stream, under the next step's generator forward instead of
+        at the head of the four chains."""
+        return [(lay.cache, lambda slot, lay=lay: lay.packed(*slot)) for ch in self.chains for lay in ch.layers]
 
     # ---- the four scalar losses (device tensors) ------------------------------------------------
     @torch.no_grad()

@@ -132,9 +132,7 @@ class _ChainBL:
         for i, conv in enumerate(convs):
             mth = math(i, n) if callable(math) else math
             mth = (mth, mth, mth) if isinstance(mth, int) else tuple(mth)
-            lay = _Layer(conv, tuple(v | BL for v in mth))
-            lay.keep_scale = i == 0 or i == n - 1   # head / tail: no packed image, the kernels take (v, scale)
-            self.layers.append(lay)
+            self.layers.append(_Layer(conv, tuple(v | BL for v in mth)))   # head / tail: no packed image, the kernels take (v, scale)
         head, tail = self.layers[0].spec, self.layers[-1].spec
         if not (head.groups == head.c_in and head.stride == 1 and head.pad_l == head.pad_r and head.c_out % 8 == 0 and head.ksize <= 16 and head.c_in <= 4):
             raise ops._lib.EbenError("bundle-layout engine: unexpected chain head")
@@ -148,7 +146,7 @@ class _ChainBL:
         v, _, bias = lay.params()
         lay.ensure_scale()
         j = EbenBlHeadJob()
-        j.x, j.v, j.scale, j.bias = ptr(x) if x is not None else None, ptr(v.detach()), ptr(lay.scale), ptr(bias.detach()) if bias is not None else None
+        j.x, j.v, j.scale, j.bias = ptr(x) if x is not None else None, ptr(v.detach()), ptr(lay.cache.scale), ptr(bias.detach()) if bias is not None else None
         j.y_hi, j.y_lo = _addr(out.hi), _addr(out.lo)
         j.c_in, j.c_out, j.l_in, j.l_out = sp.c_in, sp.c_out, l_in, out.length
         j.ksize, j.dilation, j.pad, j.reflect_pad, j.out_slope = sp.ksize, sp.dilation, sp.pad_l, self.pad, sp.out_slope
@@ -201,7 +199,7 @@ class _ChainBL:
         tail.ensure_scale()
         l_out = cur.length + sp.pad_l + sp.pad_r - (sp.ksize - 1)
         logits = logits_out if logits_out is not None else torch.empty((rows, 1, l_out), dtype=torch.float32, device=act0.hi.device)
-        check(lib.eben_bl_tail_fwd(_addr(cur.hi), _addr(cur.lo), rows, cur.channels, cur.length, sp.ksize, sp.pad_l, ptr(v.detach()), ptr(tail.scale),
+        check(lib.eben_bl_tail_fwd(_addr(cur.hi), _addr(cur.lo), rows, cur.channels, cur.length, sp.ksize, sp.pad_l, ptr(v.detach()), ptr(tail.cache.scale),
                                    ptr(bias.detach()) if bias is not None else None, sp.out_slope, ptr(logits), _stream()), "bl_tail_fwd")
         return acts, logits
 
@@ -232,7 +230,7 @@ class _ChainBL:
         if want_param_grads:
             jobs.append((n - 1, seeds[d0:], x_in))
         g = Planes(rows, x_in.channels, x_in.length, seeds.device, lo=False)
-        check(lib.eben_bl_tail_dx(ptr(seeds), rows, x_in.channels, x_in.length, sp.ksize, sp.pad_l, ptr(v.detach()), ptr(tail.scale), _addr(x_in.hi),
+        check(lib.eben_bl_tail_dx(ptr(seeds), rows, x_in.channels, x_in.length, sp.ksize, sp.pad_l, ptr(v.detach()), ptr(tail.cache.scale), _addr(x_in.hi),
                                   _addr(x_in.lo), self.layers[n - 2].spec.out_slope, half, seg_map, fm_rows, half, fm_sums_addr + 8 * (n - 2), fm_gs,
                                   _addr(g.hi), None, st), "bl_tail_dx")
         for i in range(n - 2, 0, -1):
@@ -345,7 +343,7 @@ class _ChainBL:
             keep.append((d, slabs))
             dv, dg, dbias = _ChainBL._outputs(lay, sink, g.hi.device)
             rows = v.shape[0]
-            wn_jobs.append((slabs, nslab, rows * row_stride, rows, v.numel() // rows, row_stride, gain.detach(), v.detach(), lay.norm, dg, dv, dbias, perm))
+            wn_jobs.append((slabs, nslab, rows * row_stride, rows, v.numel() // rows, row_stride, gain.detach(), v.detach(), lay.cache.norm, dg, dv, dbias, perm))
             outs.append((dv, dg, dbias))
         check(lib.eben_bl_conv1d_bwd_dw_multi(descs, dys, xs, has_bias, slabs_p, nbs, k, st), "bl_conv1d_bwd_dw_multi")
         return outs
@@ -379,7 +377,7 @@ class _ChainBL:
               "bl_conv1d_bwd_dw")
         dv, dg, dbias = self._outputs(lay, sink, g.hi.device)
         rows = v.shape[0]
-        wn_jobs.append((slabs, nslab, rows * row_stride, rows, v.numel() // rows, row_stride, gain.detach(), v.detach(), lay.norm, dg, dv, dbias, perm))
+        wn_jobs.append((slabs, nslab, rows * row_stride, rows, v.numel() // rows, row_stride, gain.detach(), v.detach(), lay.cache.norm, dg, dv, dbias, perm))
         return dv, dg, dbias
 
     def _head_dw(self, g0: Planes, x_full: torch.Tensor, half: int, st: int, wn_jobs: list, sink=None):
@@ -396,7 +394,7 @@ class _ChainBL:
         check(lib.eben_bl_head_dw(ctypes.byref(job), 2 * half, ptr(slabs), nbytes, st), "bl_head_dw")
         dv, dg, dbias = self._outputs(lay, sink, x_full.device)
         rows = v.shape[0]
-        wn_jobs.append((slabs, nslab.value, rows * row_stride.value, rows, v.numel() // rows, row_stride.value, gain.detach(), v.detach(), lay.norm, dg, dv,
+        wn_jobs.append((slabs, nslab.value, rows * row_stride.value, rows, v.numel() // rows, row_stride.value, gain.detach(), v.detach(), lay.cache.norm, dg, dv,
                         dbias))
         return dv, dg, dbias
 
@@ -418,7 +416,7 @@ class _ChainBL:
         for br in range(2):
             dv, dg = torch.empty_like(v), torch.empty_like(gain)
             dbias = torch.empty(1, dtype=torch.float32, device=seeds.device) if bias is not None else None
-            wn_jobs.append((slabs[br * per:(br + 1) * per], nslab.value, row_stride.value, 1, v.numel(), row_stride.value, gain.detach(), v.detach(), lay.norm,
+            wn_jobs.append((slabs[br * per:(br + 1) * per], nslab.value, row_stride.value, 1, v.numel(), row_stride.value, gain.detach(), v.detach(), lay.cache.norm,
                             dg, dv, dbias))
             outs.append((dv, dg, dbias))
         return outs[0], outs[1]
@@ -479,23 +477,26 @@ class DiscriminatorEngineBL(DiscriminatorEngine):
         return st
 
     @staticmethod
+    def _slots(lay: _Layer, which: int) -> list:
+        """The image slots of direction `which` a layer holds (1 includes the phases-as-rows images, 2)."""
+        return [slot for slot in lay.cache.images if slot[0] == which or (which == 1 and slot[0] == 2)]
+
+    @staticmethod
     def _mark_used(ch: "_ChainBL", which: int) -> None:
-        """A replayed sequence reads the chain's packed images without passing through ``_Layer.packed``: tell ``prepack`` they are in
-        use (it drops the images the last step did not touch)."""
+        """A replayed sequence reads the chain's packed images without passing through ``_Layer.packed``: tell ``ops.prepack`` they are
+        in use (it drops the images the last step did not touch)."""
         for lay in ch.layers:
-            lay.used.update(slot for slot in lay.packs if slot[0] == which or (which == 1 and slot[0] == 2))   # 2: phases-as-rows images
+            lay.cache.used.update(DiscriminatorEngineBL._slots(lay, which))
 
     @staticmethod
     def _chain_sig(ch: "_ChainBL", which: int):
-        """Everything a chain's launches depend on besides tensor values: per layer the parameter storage, the weight-norm scale buffer,
-        the packed images of direction `which` (address + whether they are current) and the arithmetic."""
+        """Everything a chain's launches depend on besides tensor values: per layer the bias and the image cache's state (parameter
+        storage, weight-norm scale buffer, the packed images of direction `which`: address + whether they are current) and the arithmetic."""
         out = []
         for lay in ch.layers:
-            v, g, b = lay.params()
-            wkey = lay._weights_key()
-            imgs = tuple(sorted((slot, wp.data_ptr(), key == wkey) for slot, (key, wp) in lay.packs.items() if slot[0] == which or (which == 1 and slot[0] == 2))) if which >= 0 else ()
-            out.append((v.data_ptr(), g.data_ptr(), 0 if b is None else b.data_ptr(), 0 if lay.scale is None else lay.scale.data_ptr(),
-                        lay.scale_key == wkey, imgs, lay.math_fwd, lay.math_dx, lay.math_dw))
+            b = lay.params()[2]
+            out.append((0 if b is None else b.data_ptr(), lay.cache.state(DiscriminatorEngineBL._slots(lay, which) if which >= 0 else ()),
+                        lay.math_fwd, lay.math_dx, lay.math_dw))
         return tuple(out)
 
     # ---- forward ---------------------------------------------------------------------------------------------------------------

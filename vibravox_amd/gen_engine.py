@@ -126,17 +126,15 @@ class GeneratorEngine:
     def __init__(self, gen):
         self.gen = gen
         self._spec_cache: Dict[tuple, ops.ConvSpec] = {}
-        self._ru_images: Dict[int, dict] = {}   # id(ResidualUnit) -> {key, fwd image, bwd images per math, scales}
+        self._ru_images: Dict[int, ops.PackedWeights] = {}   # id(ResidualUnit) -> its image cache
         self._s2d_images: Dict[int, tuple] = {}  # id(conv) -> (key, image of the space-to-depth form, permuted weights)
-        self._prepack_graph = ops.ReplayedPrepack()
-        self._ru_batch = None
         # the training forward and, per backward segment, the input-gradient and the weight-gradient launches as replayed HIP graphs (ops.ReplayedChain)
         self._fwd_graph = ops.ReplayedChain()
         self._dx_graphs: List[ops.ReplayedChain] = []   # per backward segment (decoder block / latent / encoder block)
         self._dw_graphs: List[ops.ReplayedChain] = []
         self._static: Dict[tuple, torch.Tensor] = {}   # (name, shape) -> buffer the graphs read their per-step input from
         self._dwq: Optional[list] = None               # while the input-gradient chain runs in queue mode: its weight-gradient work items
-        self._core_convs = None
+        self._core_convs = self._core_units = None
 
     # ---- helpers ------------------------------------------------------------------------------------
     def _spec(self, m, in_slope=None, out_slope=None) -> ops.ConvSpec:
@@ -176,8 +174,7 @@ class GeneratorEngine:
         if lib.eben_conv1d_kernel_generation(ctypes.byref(d), 0) != 4:
             return None
         v, g = _params(m)
-        e = ops._storage_epoch
-        key = (v.data_ptr(), v._version, e.get(v.data_ptr(), 0), None if g is None else (g.data_ptr(), g._version), e.get(-1, 0), batch, l_q, math)
+        key = ops.weights_key((v, g), batch, l_q, math)
         hit = self._s2d_images.get(id(m))
         if hit is None or hit[0] != key:
             vv = v.detach().view(rows_out, c, kq, spec.stride).permute(0, 1, 3, 2).reshape(rows_out, c * spec.stride, kq).contiguous()
@@ -220,108 +217,58 @@ class GeneratorEngine:
         the fp32-grade split."""
         return ops.MATH_BF16 if ops._backward_math[0] != ops.MATH_F32 else RU_BWD_F32_MATH
 
+    def _ru_cache(self, ru) -> ops.PackedWeights:
+        c = self._ru_images.get(id(ru))
+        if c is None:
+            c = self._ru_images[id(ru)] = ops.PackedWeights()
+        c.params = _params(ru.dilated_conv) + _params(ru.pointwise_conv)
+        return c
+
     def _ru_image(self, ru, which: int = 0) -> torch.Tensor:
         """Weight images of the fused unit (both convs, weight-norm scales folded in): 0 forward, 1 backward (transposed, in the
-        math of the current backward).  Rebuilt when a parameter changed: the forward image and the backward image of every math
-        this unit has been differentiated in (so that ``prepack``, which runs outside the step's math context, rebuilds the
-        right ones)."""
+        math of the current backward).  Slots: ("fwd", forward math) and ("bwd", math) per backward math."""
+        c = self._ru_cache(ru)
+        slot = ("fwd", ru_forward_math()) if which == 0 else ("bwd", self._ru_bwd_math())
+        if not c.current(slot, ops.weights_key(c.params)):
+            self._ru_rebuild(ru, c, slot)
+        return c.images[slot][1]
+
+    def _ru_rebuild(self, ru, c: ops.PackedWeights, slot) -> None:
+        """Builds image ``slot``.  When the forward image is not current (a parameter or the forward math changed), the weight-norm
+        scales, the forward image and the backward image of every math this unit has been differentiated in are rebuilt with it (so
+        that ``ops.prepack``, which runs outside the step's math context, rebuilds the right ones); inside it (``c.reuse``) the scales
+        are current already and the images go into the buffers held."""
         lib = load()
-        vd, gd = _params(ru.dilated_conv)
-        vp, gp = _params(ru.pointwise_conv)
-        e = ops._storage_epoch
-        key = tuple((t.data_ptr(), t._version, e.get(t.data_ptr(), 0)) for t in (vd, gd, vp, gp)) + (e.get(-1, 0), ru_forward_math())
-        hit = self._ru_images.get(id(ru))
-        bm = self._ru_bwd_math() if which == 1 else None
-        if hit is not None and hit["key"] == key and (bm is None or bm in hit["bwd"]):
-            return hit["fwd"] if which == 0 else hit["bwd"][bm]
-        c = vd.shape[0]
-        dev = vd.device
-        batch = self._ru_batch   # inside prepack(): the launches of all units are gathered into one wn_scale / one pack call
-        reuse = batch is not None   # prepack(): rebuild into the buffers held (a graph replay writes the ones it captured)
-        if hit is None or hit["key"] != key:
-            # scale / norm of the dilated, then of the pointwise conv
-            scales = ops._buffer(None if hit is None else hit["scales"], 4 * c, vd, reuse).view(4, c)
-            wn = [(gd.detach(), vd.detach(), c, vd.numel() // c, scales[0], scales[1]), (gp.detach(), vp.detach(), c, vp.numel() // c, scales[2], scales[3])]
-            if batch is not None:
-                batch["wn"].extend(wn)
-            else:
-                ops.wn_scale_multi(wn)
-            img = ops._buffer(None if hit is None else hit["fwd"], lib.eben_ru_packed_floats_ex(c, ru_forward_math()), vd, reuse)
-            self._ru_pack(c, ru_forward_math(), 0, vd, scales[0], vp, scales[2], img)
-            maths = set(hit["bwd"]) if hit is not None else set()
-            old_bwd = hit["bwd"] if hit is not None else {}
-            hit = self._ru_images[id(ru)] = {"key": key, "fwd": img, "bwd": {}, "scales": scales}
+        vd, _, vp, _ = c.params
+        vd, vp = vd.detach(), vp.detach()
+        ch = vd.shape[0]
+        key = ops.weights_key(c.params)
+        fwd = ("fwd", ru_forward_math())
+        slots = [slot]
+        if not c.current(fwd, key):
+            if not c.reuse:
+                c.scale_key = None
+                c.ensure_scale()
+            old, c.images = c.images, {}
+            bwd = [s for s in old if s[0] == "bwd"]
+            slots = [fwd] + bwd + ([slot] if slot != fwd and slot not in bwd else [])
         else:
-            maths, old_bwd = set(), {}
-        if bm is not None:
-            maths.add(bm)
-        scales = hit["scales"]
-        for m in maths:
-            img_b = ops._buffer(old_bwd.get(m), lib.eben_ru_packed_floats_ex(c, m), vd, reuse)
-            self._ru_pack(c, m, 1, vd, scales[0], vp, scales[2], img_b)
-            hit["bwd"][m] = img_b
-        return hit["fwd"] if which == 0 else hit["bwd"][bm]
+            old = c.images
+        for s in slots:
+            hit = old.get(s)
+            img = c.buffer(None if hit is None else hit[1], lib.eben_ru_packed_floats_ex(ch, s[1]), vd)
+            ops.ru_pack(ch, s[1], 0 if s[0] == "fwd" else 1, vd, c.scale[0], vp, c.scale[2], img)
+            c.images[s] = (key, img)
 
-    def _ru_pack(self, c, math, which, vd, sd, vp, sp, img) -> None:
-        if self._ru_batch is not None and math != ops.MATH_F32:
-            self._ru_batch["packs"].append((c, math, which, vd.detach(), sd, vp.detach(), sp, img))
-            return
-        check(load().eben_ru_pack_ex(c, math, which, ptr(vd.detach()), ptr(sd), ptr(vp.detach()), ptr(sp), ptr(img), stream()), "ru_pack")
+    def image_caches(self) -> list:
+        """``ops.prepack`` entries of the fused units that hold images."""
+        return [(c, lambda slot, ru=ru, c=c: self._ru_rebuild(ru, c, slot))
+                for ru in self._units() if (c := self._ru_images.get(id(ru))) is not None and c.images]
 
-    def _ru_flush(self) -> None:
-        """Issues what ``_ru_image`` gathered: the weight-norm scales of all units as one launch, then their images as one."""
-        batch, self._ru_batch = self._ru_batch, None
-        if batch is None:
-            return
-        ops.wn_scale_multi(batch["wn"])
-        if batch["packs"]:
-            from ._lib import EbenRuPackJob
-
-            table = (EbenRuPackJob * len(batch["packs"]))()
-            for it, (c, math, which, vd, sd, vp, sp, img) in zip(table, batch["packs"]):
-                it.channels, it.math, it.which = c, math, which
-                it.v_dil, it.scale_dil, it.v_pw, it.scale_pw, it.wimg = ptr(vd), ptr(sd), ptr(vp), ptr(sp), ptr(img)
-            check(load().eben_ru_pack_multi(table, len(table), stream()), "ru_pack_multi")
-
-    def prepack(self) -> None:
-        """Rebuilds the fused units' weight images on the side stream (called with ``ops.prepack`` after the optimiser step);
-        replayed as a graph once the sequence has settled (``ops.ReplayedPrepack``)."""
-        if not self._ru_images:
-            return
-        units = [ru for blk in list(self.gen.encoder_blocks) + list(self.gen.decoder_blocks) for ru in blk.residuals]
-        dev = _params(units[0].dilated_conv)[0].device
-        main = torch.cuda.current_stream(dev)
-        side = ops._side_stream(dev)
-        side.wait_stream(main)
-
-        def key_of(ru):
-            e = ops._storage_epoch
-            ts = _params(ru.dilated_conv) + _params(ru.pointwise_conv)
-            return tuple((t.data_ptr(), t._version, e.get(t.data_ptr(), 0)) for t in ts) + (e.get(-1, 0), ru_forward_math())
-
-        def body():
-            self._ru_batch = {"wn": [], "packs": []}
-            try:
-                for ru in units:
-                    self._ru_image(ru)
-            finally:
-                self._ru_flush()
-
-        def entry(ru):
-            # what the launch sequence depends on besides the weights' values, the buffers it writes included (ops.ReplayedPrepack)
-            hit = self._ru_images.get(id(ru))
-            return (id(ru), _params(ru.dilated_conv)[0].data_ptr(),
-                    None if hit is None else (tuple((m, hit["bwd"][m].data_ptr()) for m in sorted(hit["bwd"])), hit["fwd"].data_ptr(),
-                                              hit["scales"].data_ptr(), hit["key"] != key_of(ru)))
-
-        sig = tuple(entry(ru) for ru in units) + (ops._storage_epoch.get(-1, 0),)
-        with torch.cuda.stream(side), torch.no_grad():
-            if self._prepack_graph.run(sig, body, side):
-                for ru in units:   # replayed: the images are current, the cache keys are not
-                    self._ru_images[id(ru)]["key"] = key_of(ru)
-            ev = torch.cuda.Event()
-            ev.record()
-        self._prepacked = ev
+    def _units(self) -> list:
+        if self._core_units is None:
+            self._core_units = [ru for blk in list(self.gen.encoder_blocks) + list(self.gen.decoder_blocks) for ru in blk.residuals]
+        return self._core_units
 
     def _residual_unit(self, ru, x, in_slope, train, recs):
         """y = xin + lrelu(pointwise(dilated(xin))), xin = lrelu(x, in_slope).  Returns y; records (x, h, u) for the backward."""
@@ -376,10 +323,7 @@ class GeneratorEngine:
         """Returns (input of last_conv, first_bands, records for ``backward`` or None)."""
         gen = self.gen
         lib = load()
-        ev = getattr(self, "_prepacked", None)
-        if ev is not None:
-            self._prepacked = None
-            torch.cuda.current_stream().wait_event(ev)
+        ops.join_prepack()   # images rebuilt ahead of time on the side stream
         slope = gen.nl.negative_slope
         first_bands = gen.pqmf(cut_audio, "analysis", bands=gen.p).detach()
         saved = {"enc": [], "dec": [], "misc": []} if train else None
@@ -591,7 +535,7 @@ class GeneratorEngine:
     # GPU-side dispatch but 15-30 us of Python + ctypes on the host: 1.2 + 2.2 + 0.5 ms of host time per step ([MI355X]
     # tools/host_times.py) on a 12 ms step whose host side took 11.3 ms in all.  Every per-step input is copied into a static
     # buffer, every tensor the bodies allocate lives in the graph's pool (rewritten in place by the next replay: valid until then,
-    # which is as long as the step needs it), and the weight images are the ones prepack() rebuilds in place.
+    # which is as long as the step needs it), and the weight images are the ones ops.prepack rebuilds in place.
     @staticmethod
     def _graphs_usable() -> bool:
         return USE_GRAPHS and ops.ReplayedChain.enabled and not ops.ReplayedPrepack._multi_rank() and not ops._timers_enabled()
@@ -606,32 +550,16 @@ class GeneratorEngine:
         return buf
 
     def _fwd_sig(self, buf: torch.Tensor) -> tuple:
-        """Everything the captured forward depends on besides values: input buffer, arithmetic, and per layer the weight-image
-        buffers and whether they are current (a stale image makes the eager path rebuild it -- a replay would not)."""
+        """Everything the captured forward depends on besides values: input buffer, arithmetic, and per layer and fused unit the image
+        cache's buffers and whether they are current (a stale image makes the eager path rebuild it -- a replay would not)."""
         if self._core_convs is None:
             gen = self.gen
             from .torch_modules.utils import HipConv1d
             self._core_convs = [m for part in (gen.first_conv, gen.encoder_blocks, gen.latent_conv, gen.decoder_blocks)
                                 for m in part.modules() if isinstance(m, HipConv1d)]
-            self._core_units = [ru for blk in list(gen.encoder_blocks) + list(gen.decoder_blocks) for ru in blk.residuals]
-        addr = lambda t: 0 if t is None else t.data_ptr()
         parts = [buf.data_ptr(), tuple(buf.shape), ops._backward_math[0], conv_forward_math(), ru_forward_math()]
-        for m in self._core_convs:
-            pw = m._packed
-            if pw is None or pw.last is None:
-                parts.append(None)
-                continue
-            v, g = _params(m)
-            parts.append((addr(pw.wp_fwd), addr(pw.wp_bwd), addr(pw.scale), addr(pw.norm), pw.key == ops._pack_key(v, g, pw.last[1], pw.last[2])))
-        e = ops._storage_epoch
-        for ru in self._core_units:
-            hit = self._ru_images.get(id(ru))
-            if hit is None:
-                parts.append(None)
-                continue
-            ts = _params(ru.dilated_conv) + _params(ru.pointwise_conv)
-            key = tuple((t.data_ptr(), t._version, e.get(t.data_ptr(), 0)) for t in ts) + (e.get(-1, 0), ru_forward_math())
-            parts.append((hit["fwd"].data_ptr(), tuple((k, hit["bwd"][k].data_ptr()) for k in sorted(hit["bwd"])), hit["scales"].data_ptr(), hit["key"] == key))
+        parts += [m._packed.state() for m in self._core_convs]
+        parts += [None if (c := self._ru_images.get(id(ru))) is None else c.state() for ru in self._units()]
         return tuple(parts)
 
     def forward_train(self, x: torch.Tensor):
@@ -646,11 +574,7 @@ class GeneratorEngine:
         self._serial = getattr(self, "_serial", 0) + 1
         if not self._graphs_usable() or self._replay_outstanding():
             return self.forward(x, True)
-        ops.join_prepack()
-        ev = getattr(self, "_prepacked", None)
-        if ev is not None:   # the waits stay outside the graph
-            self._prepacked = None
-            torch.cuda.current_stream().wait_event(ev)
+        ops.join_prepack()   # the wait stays outside the graph
         buf = self._static_buf("x", x)
         buf.copy_(x)
         out = self._fwd_graph.run(self._fwd_sig(buf), lambda: self.forward(buf, True), None)

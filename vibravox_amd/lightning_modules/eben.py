@@ -118,6 +118,7 @@ class EBENLightningModule(BaseSELightningModule):
         self.automatic_optimization = False
         self.last_lambdas = None
         self.last_norms = None
+        self._prepack_graph = ops.ReplayedPrepack()   # the generator's image rebuild (ops.prepack) as a replayed graph
 
     def configure_optimizers(self):
         return [self.generator_optimizer, self.discriminator_optimizer]
@@ -346,10 +347,10 @@ class EBENLightningModule(BaseSELightningModule):
         self._step(generator_optimizer, self._sync_grads(generator_optimizer))
         generator_optimizer.zero_grad()
         self._mark("generator Adam")
-        if self.prepack_weights:
-            ops.prepack(self._hip_convs(self.generator))   # next step's generator images, under the discriminator phase
-            if getattr(self.generator, "_engine", None) is not None:
-                self.generator._engine.prepack()
+        if self.prepack_weights:   # next step's generator images -- conv layers and fused units, one sequence -- under the discriminator phase
+            g_engine = getattr(self.generator, "_engine", None)
+            ops.prepack(ops.conv_images(self._hip_convs(self.generator)) + (g_engine.image_caches() if g_engine is not None else []),
+                        self._prepack_graph)
 
         # ---- discriminator phase: the gradients of real_loss + fake_loss are already there
         if update_discriminator:
@@ -364,8 +365,8 @@ class EBENLightningModule(BaseSELightningModule):
             self._step(discriminator_optimizer, self._sync_grads(discriminator_optimizer))
             discriminator_optimizer.zero_grad()
             self._mark("discriminator Adam")
-            if self.prepack_weights:
-                engine.prepack()   # next step's discriminator images, under the next generator forward
+            if self.prepack_weights:   # next step's discriminator images, under the next generator forward (the chains wait for them)
+                engine._prepack_ev = ops.prepack(engine.image_caches(), engine._prepack_graph, join=False)
         return {"corrupted": corrupted_speech, "enhanced": enhanced_speech.detach(), "reference": reference_speech}
 
     #: run the discriminators on the reference half of the batch underneath the generator forward (it does not depend on the generator).

@@ -12,12 +12,12 @@ import gc
 import os
 import weakref
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
 from . import _lib
-from ._lib import EbenConv1dDesc, EbenPackJob, EbenWnBwdItem, EbenWnScaleItem, check, load, ptr, stream
+from ._lib import EbenConv1dDesc, EbenPackJob, EbenRuPackJob, EbenWnBwdItem, EbenWnScaleItem, check, load, ptr, stream
 
 # Optimisers that write parameters behind autograd's back (FusedAdam) bump the epoch of exactly
 # the storages they touched, so that only those layers' packed-weight caches are rebuilt.
@@ -352,97 +352,188 @@ def conv_desc(spec: ConvSpec, batch: int, l_in: int, math: int = MATH_F32) -> Eb
     return d
 
 
+def weights_key(params, *extra) -> tuple:
+    """When a weight image is current: address, ``_version`` and storage epoch of every tensor in ``params`` (None allowed), the global
+    epoch, and whatever else the caller's image depends on (``extra``).  The one staleness test of every image cache."""
+    e = _storage_epoch
+    return tuple(None if t is None else (t.data_ptr(), t._version, e.get(t.data_ptr(), 0)) for t in params) + (e.get(-1, 0),) + extra
+
+
+def _addrs(image) -> tuple:
+    return (image.data_ptr(),) if isinstance(image, torch.Tensor) else tuple(t.data_ptr() for t in image if isinstance(t, torch.Tensor))
+
+
 class PackedWeights:
-    """Weight-norm scale + MFMA-layout copies of one layer's weights, rebuilt when (v, g) change."""
+    """Image cache of one layer or fused residual unit: its parameter tensors, their weight-norm scale and norm, and MFMA-layout
+    images of the weights (scale folded in) by slot, each with the ``weights_key`` of the parameters it was built from.  What a slot
+    is, how its image is built and which slots are kept belongs to the owner (``pack_weights``: the latest descriptor;
+    ``disc_engine._Layer``: up to MAX_PACKS shapes and directions; ``gen_engine``: a fused unit's forward image and one backward image
+    per arithmetic).  ``prepack`` rebuilds the images of many caches after an optimiser step."""
 
-    __slots__ = ("key", "scale", "norm", "wp_fwd", "wp_bwd", "last")
+    __slots__ = ("params", "scale", "norm", "scale_key", "images", "used", "prune", "reuse")
 
-    def __init__(self):
-        self.key = None
-        self.scale = self.norm = self.wp_fwd = self.wp_bwd = None
-        self.last = None   # (spec, descriptor) of the latest pack: what `prepack` rebuilds ahead of the next step
+    def __init__(self, prune: bool = False):
+        self.params = ()          # (v, g) of a layer (g None without weight norm); (v, g) of each conv of a fused unit
+        self.scale = self.norm = self.scale_key = None
+        self.images = {}          # slot -> (weights_key at build time, image)
+        self.used = set()         # slots read since the last prepack (only tracked where ``prune``)
+        self.prune = prune        # prepack drops the slots not used since the last one (else it rebuilds every slot held)
+        self.reuse = False        # inside prepack: rebuild into the buffers already held (a graph replay writes the ones it captured)
+
+    def current(self, slot, key) -> bool:
+        hit = self.images.get(slot)
+        return hit is not None and hit[0] == key
+
+    def buffer(self, old: Optional[torch.Tensor], numel: int, like: torch.Tensor) -> torch.Tensor:
+        """A float buffer of ``numel`` elements: ``old`` itself while rebuilding in place and it has that size (the step that read the
+        old contents is complete), else a fresh one."""
+        if self.reuse and old is not None and old.numel() == numel and old.device == like.device:
+            return old
+        return torch.empty(numel, dtype=torch.float32, device=like.device)
+
+    def wn_jobs(self) -> list:
+        """``wn_scale_multi`` jobs of every weight-normalised (v, g) pair of ``params``, into the buffers held: (scale, norm) of one
+        pair, or one [scale, norm] block per pair (a fused unit)."""
+        pairs = [(v.detach(), g.detach()) for v, g in zip(self.params[0::2], self.params[1::2]) if g is not None]
+        if not pairs:
+            self.scale = self.norm = None
+            return []
+        rows = pairs[0][0].shape[0]
+        if len(pairs) == 1:
+            self.scale = self.buffer(self.scale, rows, pairs[0][0])
+            self.norm = self.buffer(self.norm, rows, pairs[0][0])
+            bufs = [(self.scale, self.norm)]
+        else:
+            self.scale = self.buffer(self.scale, 2 * len(pairs) * rows, pairs[0][0]).view(2 * len(pairs), rows)
+            bufs = [(self.scale[2 * i], self.scale[2 * i + 1]) for i in range(len(pairs))]
+        return [(g, v, v.shape[0], v.numel() // v.shape[0], s, n) for (v, g), (s, n) in zip(pairs, bufs)]
+
+    def ensure_scale(self) -> tuple:
+        """The weight-norm scale and norm of the current parameters (what the images fold in), launched when stale.  Returns the
+        parameters' ``weights_key``."""
+        key = weights_key(self.params)
+        if self.scale_key == key:
+            return key
+        jobs = self.wn_jobs()
+        if len(jobs) == 1:
+            g, v, rows, cols, scale, norm = jobs[0]
+            check(load().eben_wn_scale(ptr(g), ptr(v), rows, cols, ptr(scale), ptr(norm), stream()), "wn_scale")
+        else:
+            wn_scale_multi(jobs)
+        self.scale_key = key
+        return key
+
+    def state(self, slots=None) -> tuple:
+        """What a launch sequence reading this cache depends on besides values: the parameter storage, where the scale / norm and the
+        images of ``slots`` (default: every slot held) are, and whether each is current."""
+        key = weights_key(self.params)
+        addr = lambda t: 0 if t is None else t.data_ptr()
+        return (tuple(addr(t) for t in self.params), addr(self.scale), addr(self.norm), self.scale_key == key,
+                tuple((s, _addrs(self.images[s][1]), self.images[s][0] == key) for s in (self.images if slots is None else slots)))
 
 
-_pack_batch: List[Optional[list]] = [None]
+class ConvImages(NamedTuple):
+    """What ``pack_weights`` returns: the images of one descriptor (wp_bwd None when not asked for) and the scale / norm they fold in."""
+
+    wp_fwd: torch.Tensor
+    wp_bwd: Optional[torch.Tensor]
+    scale: Optional[torch.Tensor]
+    norm: Optional[torch.Tensor]
+    d: EbenConv1dDesc
+    d_bwd: EbenConv1dDesc
+
+
+_pack_batch: List[Optional[dict]] = [None]
 
 
 def conv1d_pack(d: EbenConv1dDesc, v, scale, wp_fwd, wp_bwd) -> None:
     """``eben_conv1d_pack`` on the current stream -- or, inside ``pack_batch()``, one job of the ``eben_conv1d_pack_multi`` call
     issued when the context closes (the prepack sequences: ~150 images per step in ~15 launches)."""
     if _pack_batch[0] is not None:
-        _pack_batch[0].append((d, v, scale, wp_fwd, wp_bwd))
+        _pack_batch[0]["conv"].append((d, v, scale, wp_fwd, wp_bwd))
         return
     check(load().eben_conv1d_pack(ctypes.byref(d), ptr(v), ptr(scale), ptr(wp_fwd), ptr(wp_bwd), stream()), "conv1d_pack")
 
 
+def ru_pack(c: int, math: int, which: int, vd, sd, vp, sp, img) -> None:
+    """``eben_ru_pack_ex`` (image of a fused residual unit) on the current stream -- or, inside ``pack_batch()`` and for the split
+    arithmetics, one job of the ``eben_ru_pack_multi`` call issued when the context closes."""
+    if _pack_batch[0] is not None and math != MATH_F32:
+        _pack_batch[0]["ru"].append((c, math, which, vd, sd, vp, sp, img))
+        return
+    check(load().eben_ru_pack_ex(c, math, which, ptr(vd), ptr(sd), ptr(vp), ptr(sp), ptr(img), stream()), "ru_pack")
+
+
 @contextlib.contextmanager
 def pack_batch():
-    """Collects the ``conv1d_pack`` calls made inside and issues them as one ``eben_conv1d_pack_multi`` on the current stream at
-    exit (everything the jobs read -- the weight-norm scales -- must have been launched on that stream before)."""
+    """Collects the ``conv1d_pack`` / ``ru_pack`` calls made inside and issues them as one ``eben_conv1d_pack_multi`` and one
+    ``eben_ru_pack_multi`` on the current stream at exit (everything the jobs read -- the weight-norm scales -- must have been
+    launched on that stream before)."""
     if _pack_batch[0] is not None:   # nested: the outer context flushes
         yield
         return
-    _pack_batch[0] = []
+    _pack_batch[0] = {"conv": [], "ru": []}
     try:
         yield
         jobs = _pack_batch[0]
     finally:
         _pack_batch[0] = None
-    if jobs:
-        table = (EbenPackJob * len(jobs))()
-        for it, (d, v, scale, wp_fwd, wp_bwd) in zip(table, jobs):
+    if jobs["conv"]:
+        table = (EbenPackJob * len(jobs["conv"]))()
+        for it, (d, v, scale, wp_fwd, wp_bwd) in zip(table, jobs["conv"]):
             it.desc, it.v, it.scale, it.wp_fwd, it.wp_bwd = d, ptr(v), ptr(scale), ptr(wp_fwd), ptr(wp_bwd)
-        check(load().eben_conv1d_pack_multi(table, len(jobs), stream()), "conv1d_pack_multi")
-
-
-def _pack_key(v, g, d, d_bwd):
-    return (v.data_ptr(), v._version, _storage_epoch.get(v.data_ptr(), 0), _storage_epoch.get(-1, 0),
-            None if g is None else (g.data_ptr(), g._version, _storage_epoch.get(g.data_ptr(), 0)), d.batch, d.l_in, d.math, d_bwd.math)
-
-
-def _buffer(old: Optional[torch.Tensor], numel: int, like: torch.Tensor, reuse: bool) -> torch.Tensor:
-    """A float buffer of ``numel`` elements: ``old`` itself when ``reuse`` and it has that size (``prepack``: the step that read the
-    old contents is complete, and a graph replay needs the buffers it captured to stay the ones in use), else a fresh one."""
-    if reuse and old is not None and old.numel() == numel and old.device == like.device:
-        return old
-    return torch.empty(numel, dtype=torch.float32, device=like.device)
+        check(load().eben_conv1d_pack_multi(table, len(table), stream()), "conv1d_pack_multi")
+    if jobs["ru"]:
+        table = (EbenRuPackJob * len(jobs["ru"]))()
+        for it, (c, math, which, vd, sd, vp, sp, img) in zip(table, jobs["ru"]):
+            it.channels, it.math, it.which = c, math, which
+            it.v_dil, it.scale_dil, it.v_pw, it.scale_pw, it.wimg = ptr(vd), ptr(sd), ptr(vp), ptr(sp), ptr(img)
+        check(load().eben_ru_pack_multi(table, len(table), stream()), "ru_pack_multi")
 
 
 def pack_weights(spec: ConvSpec, d: EbenConv1dDesc, v: torch.Tensor, g: Optional[torch.Tensor],
-                 cache: Optional[PackedWeights], need_bwd: bool, d_bwd: Optional[EbenConv1dDesc] = None, pre_scale=None,
-                 reuse: bool = False) -> PackedWeights:
-    """d_bwd: descriptor of the backward launches when it differs from the forward's (bf16 backward math);
-    pre_scale: (scale, norm) already computed for the current weights (multi-tensor launch in `prepack`);
-    reuse: rebuild into the buffers the cache already holds where their sizes fit (only `prepack` may: nothing reads them any more)."""
+                 cache: Optional[PackedWeights], need_bwd: bool, d_bwd: Optional[EbenConv1dDesc] = None) -> ConvImages:
+    """Images of one conv layer for the forward launch of ``d`` and the backward launches of ``d_bwd`` (when it differs: bf16
+    backward math), from ``cache`` while the parameters and the descriptor's shape and arithmetic are unchanged.  A cache keeps the
+    latest descriptor's images and always holds the backward one (it serves every later pass); the weight-norm scale is rebuilt with
+    them (inside ``prepack``, which has rebuilt it already, into the buffers held)."""
     lib = load()
     d_bwd = d if d_bwd is None else d_bwd
-    key = _pack_key(v, g, d, d_bwd)
     pw = cache if cache is not None else PackedWeights()
     if _side["prepacked"] is not None and torch.cuda.current_stream() != _side["stream"]:
         join_prepack()   # images built ahead of time on the side stream: first consumer waits for them
     need_bwd = need_bwd or cache is not None  # a module-level cache serves every later pass
-    if pw.key == key and (pw.wp_bwd is not None or not need_bwd):
-        return pw
-    st = stream()
-    rows = v.shape[0]
-    if g is not None and pre_scale is not None:
-        pw.scale, pw.norm = pre_scale
-    elif g is not None:
-        pw.scale = _buffer(pw.scale, rows, v, reuse)
-        pw.norm = _buffer(pw.norm, rows, v, reuse)
-        check(lib.eben_wn_scale(ptr(g), ptr(v), rows, v.numel() // rows, ptr(pw.scale), ptr(pw.norm), st), "wn_scale")
-    else:
-        pw.scale = pw.norm = None
-    pw.wp_fwd = _buffer(pw.wp_fwd, lib.eben_conv1d_packed_floats(ctypes.byref(d), 0), v, reuse)
-    pw.wp_bwd = _buffer(pw.wp_bwd, lib.eben_conv1d_packed_floats(ctypes.byref(d_bwd), 1), v, reuse) if need_bwd else None
+    pw.params = (v, g)
+    slot = (d.batch, d.l_in, d.math, d_bwd.math)
+    key = weights_key(pw.params)
+    hit = pw.images.get(slot)
+    if hit is not None and hit[0] == key and (hit[1].wp_bwd is not None or not need_bwd):
+        return hit[1]
+    if not pw.reuse:
+        pw.scale_key = None
+        pw.ensure_scale()
+    old = (None, None) if hit is None else hit[1]
+    wp_fwd = pw.buffer(old[0], lib.eben_conv1d_packed_floats(ctypes.byref(d), 0), v)
+    wp_bwd = pw.buffer(old[1], lib.eben_conv1d_packed_floats(ctypes.byref(d_bwd), 1), v) if need_bwd else None
     if d_bwd is d or not need_bwd:
-        conv1d_pack(d, v, pw.scale, pw.wp_fwd, pw.wp_bwd)
+        conv1d_pack(d, v, pw.scale, wp_fwd, wp_bwd)
     else:
-        conv1d_pack(d, v, pw.scale, pw.wp_fwd, None)
-        conv1d_pack(d_bwd, v, pw.scale, None, pw.wp_bwd)
-    pw.key = key
-    pw.last = (spec, d, d_bwd)
-    return pw
+        conv1d_pack(d, v, pw.scale, wp_fwd, None)
+        conv1d_pack(d_bwd, v, pw.scale, None, wp_bwd)
+    img = ConvImages(wp_fwd, wp_bwd, pw.scale, pw.norm, d, d_bwd)
+    pw.images = {slot: (key, img)}
+    return img
+
+
+def conv_images(modules) -> list:
+    """``prepack`` entries of the HipConv1d layers among ``modules`` that hold images: each rebuilds its latest descriptor."""
+    def entry(pw):
+        def rebuild(slot):
+            img = pw.images[slot][1]
+            pack_weights(None, img.d, *pw.params, pw, True, img.d_bwd)
+        return pw, rebuild
+
+    return [entry(m._packed) for m in modules if m._packed.images]
 
 
 _replayed = weakref.WeakSet()   # every ReplayedPrepack / ReplayedChain alive: graphs_pending() asks them
@@ -585,7 +676,7 @@ class ReplayedPrepack:
     everything the launches depend on besides the weights' values (layers, shapes, parameter storage AND the addresses of the image /
     scale buffers the launches write: a forward at another shape between two train steps -- validation -- reallocates them, and a
     replay would go on filling the orphaned ones); a new signature falls back to eager rounds and a new capture.  The prepack bodies
-    rebuild INTO the buffers the caches hold (``_buffer(reuse=True)``), so the signature settles after one eager round.  Tensors
+    rebuild INTO the buffers the caches hold (``PackedWeights.reuse``), so the signature settles after one eager round.  Tensors
     allocated by the body while capturing live in the graph's pool for as long as the graph."""
 
     enabled = os.environ.get("EBEN_PREPACK_GRAPH", "1") != "0"
@@ -727,59 +818,66 @@ def _timers_enabled() -> bool:
     return any(t.enabled for t in _timers)
 
 
-_conv_prepack_graph = ReplayedPrepack()
-
-
-def prepack(layers) -> None:
-    """Rebuilds the packed weights of ``layers`` (modules with ``_packed`` / ``spec`` / weight-norm parameters, i.e.
-    ``torch_modules.utils.HipConv1d``) for the descriptors of their latest forward, on the side stream: called right
-    after an optimiser step, the ~2 tiny launches per layer (weight-norm scale, pack) leave the next forward's critical
-    path and run underneath whatever the main stream does next.  ``join_prepack`` must precede the next use."""
-    todo = [m for m in layers if getattr(m, "_packed", None) is not None and m._packed.last is not None]
-    if not todo:
-        return
-    dev = todo[0]._packed.wp_fwd.device
+def prepack(entries, graph: ReplayedPrepack, join: bool = True):
+    """Rebuilds the packed weight images of one network on the side stream, right after its optimiser step: the ~2 tiny launches per
+    layer leave the next forward's critical path and run underneath whatever the main stream does next.  entries: (cache,
+    rebuild(slot)) per layer or fused unit (``conv_images``, ``GeneratorEngine.image_caches``, ``DiscriminatorEngine.image_caches``).
+    One ``wn_scale_multi`` for every stale scale, then every slot the cache keeps (``PackedWeights.prune``) rebuilt into the buffers it
+    occupies (conv images as one ``eben_conv1d_pack_multi``, fused-unit images as one ``eben_ru_pack_multi``), replayed by ``graph``
+    once the sequence has settled.  Returns the event recorded behind it; ``join``: ``join_prepack`` waits for it (else the caller's
+    streams do)."""
+    entries = [(c, rebuild) for c, rebuild in entries if c.images or c.scale is not None]
+    if not entries:
+        return None
+    dev = entries[0][0].params[0].device
     main = torch.cuda.current_stream(dev)
     side = _side_stream(dev)
     side.wait_stream(main)   # the step that used the old images (and the optimiser that changed the weights) is complete
-    def params_of(m):
-        v, g = conv_params(m)
-        return v.detach(), None if g is None else g.detach()
+
+    def kept(c):
+        return [s for s in c.images if s in c.used or not c.prune]
 
     def body():
-        scales, jobs = {}, []
-        for m in todo:   # weight-norm scales of every layer: one multi-tensor launch
-            if m.weight_norm:
-                v, g = params_of(m)
-                rows = v.shape[0]
-                sc = _buffer(m._packed.scale, rows, v, True)
-                nm = _buffer(m._packed.norm, rows, v, True)
-                scales[id(m)] = (sc, nm)
-                jobs.append((g, v, rows, v.numel() // rows, sc, nm))
+        jobs = []
+        for c, _ in entries:   # weight-norm scales of every layer: one multi-tensor launch
+            key = weights_key(c.params)
+            if c.scale_key != key:
+                c.reuse = True
+                jobs += c.wn_jobs()
+                c.reuse = False
+                c.scale_key = key
         wn_scale_multi(jobs)
         with pack_batch():
-            for m in todo:
-                spec, d, d_bwd = m._packed.last
-                v, g = params_of(m)
-                pack_weights(spec, d, v, g, m._packed, True, d_bwd, scales.get(id(m)), reuse=True)
+            for c, rebuild in entries:
+                keep = kept(c)
+                for slot in [s for s in c.images if s not in keep]:
+                    del c.images[slot]   # a shape of an earlier step: rebuilt on demand if it comes back
+                c.reuse = True
+                try:
+                    key = weights_key(c.params)
+                    for slot in keep:
+                        if not c.current(slot, key):
+                            rebuild(slot)
+                finally:
+                    c.reuse = False
+                c.used = set()   # re-packing is not a use: the next step decides what survives the next prepack
 
-    # everything the launch sequence depends on besides the weights' values: the layers, their descriptors, the parameter storage,
-    # the buffers the launches write, and WHICH layers are stale (a layer skipped while capturing would never be rebuilt by the replays)
-    def _addr(t):
-        return 0 if t is None else t.data_ptr()
-
-    sig = tuple((id(m), m._packed.last[1].batch, m._packed.last[1].l_in, m._packed.last[1].math, m._packed.last[2].math, params_of(m)[0].data_ptr(),
-                 _addr(m._packed.wp_fwd), _addr(m._packed.wp_bwd), _addr(m._packed.scale), _addr(m._packed.norm),
-                 m._packed.key != _pack_key(*params_of(m), m._packed.last[1], m._packed.last[2])) for m in todo) + (_storage_epoch.get(-1, 0),)
+    # everything the launch sequence depends on besides the weights' values (ReplayedPrepack): the caches, the slots rebuilt, the
+    # parameter storage, the buffers the launches write, and WHICH scales and images are stale (one skipped while capturing would never
+    # be rebuilt by the replays)
+    sig = tuple((id(c), c.state(kept(c)), len(kept(c)) == len(c.images)) for c, _ in entries) + (_storage_epoch.get(-1, 0),)
     with torch.cuda.stream(side), torch.no_grad():
-        if _conv_prepack_graph.run(sig, body, side):
-            for m in todo:   # replayed: the images are current, the cache keys are not
-                spec, d, d_bwd = m._packed.last
-                v, g = params_of(m)
-                m._packed.key = _pack_key(v, g, d, d_bwd)
+        if graph.run(sig, body, side):
+            for c, _ in entries:   # replayed: the images and scales are current, the cache keys are not
+                key = weights_key(c.params)
+                c.scale_key = key
+                c.images = {slot: (key, img) for slot, (_, img) in c.images.items()}
+                c.used = set()
         ev = torch.cuda.Event()
         ev.record()
-    _side["prepacked"] = ev
+    if join:
+        _side["prepacked"] = ev
+    return ev
 
 
 def join_prepack() -> None:
