@@ -514,7 +514,7 @@ def test_bundle_conv_weight_gradient(hip, name):
     check(hip.eben_bl_conv1d_bwd_dw(ctypes.byref(d), dyp.hi.data_ptr(), xp.hi.data_ptr(), 1, slabs.data_ptr(), nbytes, st), "bl_conv1d_bwd_dw")
     wshape = spec.weight_shape()
     dv, dbias = torch.empty(wshape, dtype=torch.float32, device=DEV), torch.empty(wshape[0], dtype=torch.float32, device=DEV)
-    ops.wn_bwd_multi([(slabs, nslab.value, wshape[0] * rs.value, wshape[0], wshape[1] * wshape[2], rs.value, None, dv, None, None, dv, dbias, perm.value)])
+    ops.wn_bwd_multi([ops.wn_job(slabs, nslab.value, rs.value, dv, None, None, (dv, None, dbias), col_perm_k=perm.value)])
     wr = torch.zeros(wshape, dtype=torch.float64, device=DEV).requires_grad_(True)
     br = torch.zeros(wshape[0], dtype=torch.float64, device=DEV).requires_grad_(True)
     out = F.conv1d(bf16_hi(x).double(), wr, br, stride=spec.stride, padding=spec.pad_l, dilation=spec.dilation, groups=spec.groups)
@@ -593,7 +593,7 @@ def test_bundle_conv_weight_gradient_small_tiles(hip, kw, length):
     check(hip.eben_bl_conv1d_bwd_dw(ctypes.byref(d), dyp.hi.data_ptr(), xp.hi.data_ptr(), 1, slabs.data_ptr(), nbytes, st), "bl_conv1d_bwd_dw")
     wshape = spec.weight_shape()
     dv, dbias = torch.empty(wshape, dtype=torch.float32, device=DEV), torch.empty(wshape[0], dtype=torch.float32, device=DEV)
-    ops.wn_bwd_multi([(slabs, nslab.value, wshape[0] * rs.value, wshape[0], wshape[1] * wshape[2], rs.value, None, dv, None, None, dv, dbias, perm.value)])
+    ops.wn_bwd_multi([ops.wn_job(slabs, nslab.value, rs.value, dv, None, None, (dv, None, dbias), col_perm_k=perm.value)])
     wr = torch.zeros(wshape, dtype=torch.float64, device=DEV).requires_grad_(True)
     br = torch.zeros(wshape[0], dtype=torch.float64, device=DEV).requires_grad_(True)
     out = F.conv1d(bf16_hi(x).double(), wr, br, stride=spec.stride, padding=spec.pad_l, dilation=spec.dilation, groups=spec.groups)

@@ -194,7 +194,7 @@ def _dw_reduce(hip, d, slabs, spec):
     hip.eben_bl_conv1d_bwd_dw_workspace(ctypes.byref(d), ctypes.byref(nslab), ctypes.byref(rs), ctypes.byref(perm))
     wshape = spec.weight_shape()
     dv, dbias = torch.empty(wshape, dtype=torch.float32, device=DEV), torch.empty(wshape[0], dtype=torch.float32, device=DEV)
-    ops.wn_bwd_multi([(slabs, nslab.value, wshape[0] * rs.value, wshape[0], wshape[1] * wshape[2], rs.value, None, dv, None, None, dv, dbias, perm.value)])
+    ops.wn_bwd_multi([ops.wn_job(slabs, nslab.value, rs.value, dv, None, None, (dv, None, dbias), col_perm_k=perm.value)])
     return dv, dbias
 
 

@@ -275,12 +275,7 @@ class _Chain:
         logits = None
         for i, g, x_in in jobs:
             lay = self.layers[i]
-            if i == n - 1:
-                # Logits layer: fake and real branches separately, then added -- the reference's structure
-                # (two autograd graphs accumulating into one .grad).  While every hinge term is active the
-                # two bias gradients are -c*N and +c*N summed in the SAME order, i.e. they cancel exactly and
-                # Adam leaves the bias alone; one sum over both branches leaves a rounding residue that Adam
-                # (m / sqrt(v)) turns into a full-size step.
+            if i == n - 1:   # the two hinge branches stay separate sums: ops.add_logits_branches
                 gf = self._weight_grads(lay, g[2 * half:3 * half], x_in[:half], st, wn_jobs)
                 gr = self._weight_grads(lay, g[3 * half:], x_in[half:], st, wn_jobs)
                 logits = (i, gf, gr)
@@ -289,34 +284,21 @@ class _Chain:
         ops.wn_bwd_multi(wn_jobs)
         if logits is not None:
             i, gf, gr = logits
-            outs = [None if sink is None or p is None else sink.grad_buffer(p) for p in self.layers[i].params()]
-            grads[i] = tuple(None if a is None else (a + b if o is None else torch.add(a, b, out=o)) for a, b, o in zip(gf, gr, outs))
+            grads[i] = ops.add_logits_branches(self.layers[i].params(), gf, gr, sink)
         return grads
 
     @staticmethod
     def _weight_grads(lay: _Layer, g2: torch.Tensor, x_in: torch.Tensor, st: int, wn_jobs: list, sink=None):
         """sink (ddp.GradSync): the gradients are written straight into its bucket views."""
-        lib = load()
         v, gain, bias = lay.params()
-        rows_b = g2.shape[0]
-        d = ops.conv_desc(lay.spec_lin, rows_b, x_in.shape[2], lay.math_dw)
-        nslab, row_stride = ctypes.c_int(0), ctypes.c_int(0)
-        ws_bytes = lib.eben_conv1d_bwd_dw_workspace(ctypes.byref(d), ctypes.byref(nslab), ctypes.byref(row_stride))
+        d = ops.conv_desc(lay.spec_lin, g2.shape[0], x_in.shape[2], lay.math_dw)
+        ws_bytes, nslab, row_stride = ops.dw_workspace(d)
         slabs = torch.empty(max(1, (ws_bytes + 3) // 4), dtype=torch.float32, device=g2.device)
-        check(lib.eben_conv1d_bwd_dw(ctypes.byref(d), ptr(g2), None, ptr(x_in), 1 if bias is not None else 0, ptr(slabs), ws_bytes, st),
+        check(load().eben_conv1d_bwd_dw(ctypes.byref(d), ptr(g2), None, ptr(x_in), 1 if bias is not None else 0, ptr(slabs), ws_bytes, st),
               "conv1d_bwd_dw")
-        wrows = v.shape[0]
-        cols = v.numel() // wrows
-        dv = dg = dbias = None
-        if sink is not None:
-            dv, dg, dbias = sink.grad_buffer(v), sink.grad_buffer(gain), (sink.grad_buffer(bias) if bias is not None else None)
-        dv = torch.empty_like(v) if dv is None else dv
-        dg = torch.empty_like(gain) if dg is None else dg
-        if bias is not None and dbias is None:
-            dbias = torch.empty(wrows, dtype=torch.float32, device=g2.device)
-        wn_jobs.append((slabs, nslab.value, wrows * row_stride.value, wrows, cols, row_stride.value, gain.detach(), v.detach(), lay.cache.norm,
-                        dg, dv, dbias))
-        return dv, dg, dbias
+        outs, _ = ops.grad_outputs(v, gain, bias, sink)
+        wn_jobs.append(ops.wn_job(slabs, nslab, row_stride, v, gain, lay.cache.norm, outs))
+        return outs
 
 
 _DIRECT_INJECT = os.environ.get("EBEN_DIRECT_INJECT", "1") != "0"

@@ -258,27 +258,7 @@ class _ChainBL:
         """Weight gradients of every layer (rows [fake | real] of the stacked gradients -- what ``backward_body`` put into the jobs and
         ``g0`` -- against the layer inputs [enhanced | reference]): head from (g0, the chain's fp32 input), tap-conv layers by
         ``eben_bl_conv1d_bwd_dw``, the logits layer per branch."""
-        lib = load()
-        st = _stream()
-        n = len(self.layers)
-        grads = [None] * n
-        wn_jobs = []
-        logits = None
-        for i, g, x_in in jobs:
-            lay = self.layers[i]
-            if i == n - 1:
-                gf, gr = self._tail_dw(lay, g, x_in, half, st, wn_jobs)
-                logits = (i, gf, gr)
-            else:
-                grads[i] = self._mid_dw(lay, g, x_in, half, st, wn_jobs, sink)
-        if g0 is not None:
-            grads[0] = self._head_dw(g0, x_full, half, st, wn_jobs, sink)
-        ops.wn_bwd_multi(wn_jobs)
-        if logits is not None:
-            i, gf, gr = logits
-            outs = [None if sink is None or p is None else sink.grad_buffer(p) for p in self.layers[i].params()]
-            grads[i] = tuple(None if a is None else (a + b if o is None else torch.add(a, b, out=o)) for a, b, o in zip(gf, gr, outs))
-        return grads
+        return self._weight_grads([self], [jobs], [x_full], [g0], half, sink, grouped=False)[0]
 
     @staticmethod
     def weight_grads_group(chains, jobs_list, x_fulls, g0s, half: int, sink=None):
@@ -286,7 +266,12 @@ class _ChainBL:
         own dilation and lengths) in one launch sequence: the mid layers of one index as ONE ``eben_bl_conv1d_bwd_dw_multi`` launch (a
         thin layer's weight gradient is mostly fixed cost: [MI355X] 64 rows 37-40 us, 192 rows 66-87 us), one slab reduction / weight-norm
         pass for all of them.  Same slabs, same results as chain by chain.  Returns the chains' gradient lists."""
-        lib = load()
+        return _ChainBL._weight_grads(chains, jobs_list, x_fulls, g0s, half, sink, grouped=True)
+
+    @staticmethod
+    def _weight_grads(chains, jobs_list, x_fulls, g0s, half: int, sink, grouped: bool):
+        """The walk behind both: logits layers, mid layers from the last index down, heads, ONE slab-sum / weight-norm launch, the logits
+        layers' branch sums.  ``grouped`` selects the launch of a mid-layer index (a group of one is still the ``_multi`` launch)."""
         st = _stream()
         n = len(chains[0].layers)
         assert all(len(ch.layers) == n for ch in chains)
@@ -295,90 +280,62 @@ class _ChainBL:
         for ci, (ch, jobs) in enumerate(zip(chains, jobs_list)):
             for i, g, x_in in jobs:
                 if i == n - 1:
-                    gf, gr = ch._tail_dw(ch.layers[i], g, x_in, half, st, wn_jobs)
-                    logits.append((ci, i, gf, gr))
+                    logits.append((ci,) + ch._tail_dw(ch.layers[i], g, x_in, half, st, wn_jobs))
                 else:
                     by_layer.setdefault(i, []).append((ci, g, x_in))
         for i in sorted(by_layer, reverse=True):
             items = by_layer[i]
-            outs = _ChainBL._mid_dw_multi([(chains[ci].layers[i], g, x_in) for ci, g, x_in in items], half, st, wn_jobs, sink)
+            outs = _ChainBL._mid_dw([(chains[ci].layers[i], g, x_in) for ci, g, x_in in items], half, st, wn_jobs, sink, grouped)
             for (ci, _, _), o in zip(items, outs):
                 grads[ci][i] = o
         for ci, ch in enumerate(chains):
             if g0s[ci] is not None:
                 grads[ci][0] = ch._head_dw(g0s[ci], x_fulls[ci], half, st, wn_jobs, sink)
         ops.wn_bwd_multi(wn_jobs)
-        for ci, i, gf, gr in logits:
-            outs = [None if sink is None or p is None else sink.grad_buffer(p) for p in chains[ci].layers[i].params()]
-            grads[ci][i] = tuple(None if a is None else (a + b if o is None else torch.add(a, b, out=o)) for a, b, o in zip(gf, gr, outs))
+        for ci, gf, gr in logits:
+            grads[ci][n - 1] = ops.add_logits_branches(chains[ci].layers[n - 1].params(), gf, gr, sink)
         return grads
 
     @staticmethod
-    def _mid_dw_multi(items, half: int, st: int, wn_jobs: list, sink=None):
-        """items: (layer, gradient planes rows [fake | real], input planes) of the SAME layer index of several chains."""
-        lib = load()
-        k = len(items)
-        descs = (ctypes.POINTER(ops.EbenConv1dDesc) * k)()
-        dys, xs, slabs_p = (ctypes.c_void_p * k)(), (ctypes.c_void_p * k)(), (ctypes.c_void_p * k)()
-        nbs = (ctypes.c_size_t * k)()
-        keep, outs = [], []
-        has_bias = None
-        for j, (lay, g, x_in) in enumerate(items):
-            v, gain, bias = lay.params()
-            hb = 1 if bias is not None else 0
-            assert has_bias in (None, hb)
-            has_bias = hb
-            d = ops.conv_desc(lay.spec_lin, 2 * half, x_in.length, lay.math_dw)
-            ws = getattr(d, "_bl_dw_ws", None)
-            if ws is None:
-                nslab, row_stride, perm = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
-                nbytes = lib.eben_bl_conv1d_bwd_dw_workspace(ctypes.byref(d), ctypes.byref(nslab), ctypes.byref(row_stride), ctypes.byref(perm))
-                if nbytes == 0:
-                    raise ops._lib.EbenError(f"bundle-layout weight gradient does not cover {lay.spec}")
-                ws = d._bl_dw_ws = (nbytes, nslab.value, row_stride.value, perm.value)
-            nbytes, nslab, row_stride, perm = ws
-            slabs = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=g.hi.device)
-            descs[j] = ctypes.pointer(d)
-            dys[j], xs[j], slabs_p[j], nbs[j] = _addr(g.hi), _addr(x_in.hi), slabs.data_ptr(), nbytes
-            keep.append((d, slabs))
-            dv, dg, dbias = _ChainBL._outputs(lay, sink, g.hi.device)
-            rows = v.shape[0]
-            wn_jobs.append((slabs, nslab, rows * row_stride, rows, v.numel() // rows, row_stride, gain.detach(), v.detach(), lay.cache.norm, dg, dv, dbias, perm))
-            outs.append((dv, dg, dbias))
-        check(lib.eben_bl_conv1d_bwd_dw_multi(descs, dys, xs, has_bias, slabs_p, nbs, k, st), "bl_conv1d_bwd_dw_multi")
-        return outs
-
-    @staticmethod
-    def _outputs(lay: _Layer, sink, device):
-        v, gain, bias = lay.params()
-        dv = dg = dbias = None
-        if sink is not None:
-            dv, dg, dbias = sink.grad_buffer(v), sink.grad_buffer(gain), (sink.grad_buffer(bias) if bias is not None else None)
-        dv = torch.empty_like(v) if dv is None else dv
-        dg = torch.empty_like(gain) if dg is None else dg
-        if bias is not None and dbias is None:
-            dbias = torch.empty(v.shape[0], dtype=torch.float32, device=device)
-        return dv, dg, dbias
-
-    def _mid_dw(self, lay: _Layer, g: Planes, x_in: Planes, half: int, st: int, wn_jobs: list, sink=None):
-        lib = load()
-        v, gain, bias = lay.params()
-        d = ops.conv_desc(lay.spec_lin, 2 * half, x_in.length, lay.math_dw)
+    def _dw_workspace(d, spec) -> tuple:
+        """(bytes, slabs, row stride, column permutation) of ``eben_bl_conv1d_bwd_dw``'s workspace: asked once, kept on the descriptor."""
         ws = getattr(d, "_bl_dw_ws", None)
         if ws is None:
             nslab, row_stride, perm = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
-            nbytes = lib.eben_bl_conv1d_bwd_dw_workspace(ctypes.byref(d), ctypes.byref(nslab), ctypes.byref(row_stride), ctypes.byref(perm))
+            nbytes = load().eben_bl_conv1d_bwd_dw_workspace(ctypes.byref(d), ctypes.byref(nslab), ctypes.byref(row_stride), ctypes.byref(perm))
             if nbytes == 0:
-                raise ops._lib.EbenError(f"bundle-layout weight gradient does not cover {lay.spec}")
+                raise ops._lib.EbenError(f"bundle-layout weight gradient does not cover {spec}")
             ws = d._bl_dw_ws = (nbytes, nslab.value, row_stride.value, perm.value)
-        nbytes, nslab, row_stride, perm = ws
-        slabs = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=g.hi.device)
-        check(lib.eben_bl_conv1d_bwd_dw(ctypes.byref(d), _addr(g.hi), _addr(x_in.hi), 1 if bias is not None else 0, ptr(slabs), nbytes, st),
-              "bl_conv1d_bwd_dw")
-        dv, dg, dbias = self._outputs(lay, sink, g.hi.device)
-        rows = v.shape[0]
-        wn_jobs.append((slabs, nslab, rows * row_stride, rows, v.numel() // rows, row_stride, gain.detach(), v.detach(), lay.cache.norm, dg, dv, dbias, perm))
-        return dv, dg, dbias
+        return ws
+
+    @staticmethod
+    def _mid_dw(items, half: int, st: int, wn_jobs: list, sink, grouped: bool):
+        """items: (layer, gradient planes rows [fake | real], input planes) of the SAME layer index of several chains, as ONE
+        ``eben_bl_conv1d_bwd_dw_multi`` launch (``grouped``), else each by its own ``eben_bl_conv1d_bwd_dw``."""
+        lib = load()
+        launches, outs = [], []
+        for lay, g, x_in in items:
+            v, gain, bias = lay.params()
+            d = ops.conv_desc(lay.spec_lin, 2 * half, x_in.length, lay.math_dw)
+            nbytes, nslab, row_stride, perm = _ChainBL._dw_workspace(d, lay.spec)
+            slabs = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=g.hi.device)
+            launches.append((d, _addr(g.hi), _addr(x_in.hi), 1 if bias is not None else 0, slabs, nbytes))
+            outs.append(ops.grad_outputs(v, gain, bias, sink)[0])
+            wn_jobs.append(ops.wn_job(slabs, nslab, row_stride, v, gain, lay.cache.norm, outs[-1], col_perm_k=perm))
+        if not grouped:
+            for d, dy, x, has_bias, slabs, nbytes in launches:
+                check(lib.eben_bl_conv1d_bwd_dw(ctypes.byref(d), dy, x, has_bias, ptr(slabs), nbytes, st), "bl_conv1d_bwd_dw")
+            return outs
+        k = len(launches)
+        descs = (ctypes.POINTER(ops.EbenConv1dDesc) * k)()
+        dys, xs, slabs_p = (ctypes.c_void_p * k)(), (ctypes.c_void_p * k)(), (ctypes.c_void_p * k)()
+        nbs = (ctypes.c_size_t * k)()
+        for j, (d, dy, x, has_bias, slabs, nbytes) in enumerate(launches):
+            assert has_bias == launches[0][3]
+            descs[j] = ctypes.pointer(d)
+            dys[j], xs[j], slabs_p[j], nbs[j] = dy, x, slabs.data_ptr(), nbytes
+        check(lib.eben_bl_conv1d_bwd_dw_multi(descs, dys, xs, launches[0][3], slabs_p, nbs, k, st), "bl_conv1d_bwd_dw_multi")
+        return outs
 
     def _head_dw(self, g0: Planes, x_full: torch.Tensor, half: int, st: int, wn_jobs: list, sink=None):
         lib = load()
@@ -392,16 +349,14 @@ class _ChainBL:
         nbytes = lib.eben_bl_head_dw_workspace(ctypes.byref(job), 2 * half, ctypes.byref(nslab), ctypes.byref(row_stride))
         slabs = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x_full.device)
         check(lib.eben_bl_head_dw(ctypes.byref(job), 2 * half, ptr(slabs), nbytes, st), "bl_head_dw")
-        dv, dg, dbias = self._outputs(lay, sink, x_full.device)
-        rows = v.shape[0]
-        wn_jobs.append((slabs, nslab.value, rows * row_stride.value, rows, v.numel() // rows, row_stride.value, gain.detach(), v.detach(), lay.cache.norm, dg, dv,
-                        dbias))
-        return dv, dg, dbias
+        outs, _ = ops.grad_outputs(v, gain, bias, sink)
+        wn_jobs.append(ops.wn_job(slabs, nslab.value, row_stride.value, v, gain, lay.cache.norm, outs))
+        return outs
 
     @staticmethod
     def _tail_dw(lay: _Layer, seeds: torch.Tensor, x_in: Planes, half: int, st: int, wn_jobs: list):
         """Logits layer, the two hinge branches by ONE launch: seed rows [fake | real] (2 half rows) against embedding rows [enhanced |
-        reference]; the branches stay separate results (the engine adds them: see ``disc_engine._Chain.weight_grads``)."""
+        reference]; the branches stay separate results (the engine adds them: see ``ops.add_logits_branches``)."""
         lib = load()
         v, gain, bias = lay.params()
         sp = lay.spec
@@ -413,12 +368,9 @@ class _ChainBL:
               "bl_tail_dw")
         outs = []
         per = nslab.value * row_stride.value
-        for br in range(2):
-            dv, dg = torch.empty_like(v), torch.empty_like(gain)
-            dbias = torch.empty(1, dtype=torch.float32, device=seeds.device) if bias is not None else None
-            wn_jobs.append((slabs[br * per:(br + 1) * per], nslab.value, row_stride.value, 1, v.numel(), row_stride.value, gain.detach(), v.detach(), lay.cache.norm,
-                            dg, dv, dbias))
-            outs.append((dv, dg, dbias))
+        for br in range(2):   # one output channel: v is one row of v.numel() columns, a branch's slabs are row_stride apart
+            outs.append(ops.grad_outputs(v, gain, bias)[0])
+            wn_jobs.append(ops.wn_job(slabs[br * per:(br + 1) * per], nslab.value, row_stride.value, v, gain, lay.cache.norm, outs[-1]))
         return outs[0], outs[1]
 
 

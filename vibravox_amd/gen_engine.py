@@ -389,45 +389,56 @@ class GeneratorEngine:
         if self._dwq is not None:
             self._dwq.append(("conv", rec, dy))
             return
-        v, g = _params(rec.m)
-        if not v.requires_grad:
-            return
-        grads = ops.weight_grads(rec.d, dy, rec.y, rec.x, v, g, rec.m.bias, rec.norm)
-        for p, t in zip((v, g, rec.m.bias), grads):   # not deferred (no side-stream context): accumulate like autograd would
+        if _params(rec.m)[0].requires_grad:
+            self._accumulate(self._conv_grads(rec, dy))
+
+    @staticmethod
+    def _accumulate(pairs) -> None:
+        for p, t in pairs:   # not deferred (no side-stream context): accumulate like autograd would
             if p is not None and t is not None and p.requires_grad:
                 p.grad = t if p.grad is None else p.grad.add_(t)
                 for hook in list((getattr(p, "_post_accumulate_grad_hooks", None) or {}).values()):
                     hook(p)   # e.g. ddp.GradSync's bucket accounting
 
     @staticmethod
-    def _accumulate(params, grads) -> None:
-        for p, t in zip(params, grads):   # not deferred (no side-stream context): accumulate like autograd would
-            if p is not None and t is not None and p.requires_grad:
-                p.grad = t if p.grad is None else p.grad.add_(t)
-                for hook in list((getattr(p, "_post_accumulate_grad_hooks", None) or {}).values()):
-                    hook(p)   # e.g. ddp.GradSync's bucket accounting
+    def _conv_grads(rec: _ConvRec, dy) -> list:
+        """One conv's weight gradients as (parameter, gradient) pairs; none for what was deferred."""
+        v, g = _params(rec.m)
+        grads = ops.weight_grads(rec.d, dy, rec.y, rec.x, v, g, rec.m.bias, rec.norm)
+        return [(p, t) for p, t in zip((v, g, rec.m.bias), grads) if p is not None and t is not None]
+
+    @staticmethod
+    def _unit_pairs(dil: _ConvRec, pwc: _ConvRec, res) -> list:
+        """(parameter, gradient) pairs of ``ops.weight_grads_ru`` / ``weight_grads_ru_bl``'s result for the unit's two convs."""
+        return list(zip(_params(pwc.m), res[0][:2])) + list(zip(_params(dil.m), res[1][:2]))
+
+    def _unit_grads(self, dil: _ConvRec, pwc: _ConvRec, gy, gh, bm: int, trainable_only: bool) -> list:
+        """Weight gradients of both convs of a fused unit as (parameter, gradient) pairs: one ``eben_ru_dw`` launch (reduction along
+        time, operands straight from the activation tensors) where both are weight-normalised bias-free parameters, else layer by
+        layer.  ``trainable_only``: nothing is launched for a conv that does not require a gradient."""
+        (vd, gd), (vp, gp) = _params(dil.m), _params(pwc.m)
+        wanted = lambda *ps: not trainable_only or all(p.requires_grad for p in ps)
+        if (USE_FUSED_RU_DW and gd is not None and gp is not None and dil.m.bias is None and pwc.m.bias is None and wanted(vd, vp, gd, gp)
+                and bm in (ops.MATH_BF16, ops.MATH_BF16X6)):
+            res = ops.weight_grads_ru(bm, dil.spec.dilation, gy, pwc.y, float(pwc.spec.out_slope), pwc.x, gh, dil.x, float(dil.spec.in_slope),
+                                      (vp, gp, pwc.norm), (vd, gd, dil.norm))
+            if res is not False:
+                return self._unit_pairs(dil, pwc, res)
+        return [pair for rec, dy in ((pwc, gy), (dil, gh)) if wanted(_params(rec.m)[0]) for pair in self._conv_grads(rec, dy)]
+
+    def _unit_grads_bl(self, dil: _ConvRec, pwc: _ConvRec, gzb, hb, ghb, xb):
+        """``_unit_grads`` of a bundle-layout unit (``eben_rubl_dw``); False where its two convs are routed differently."""
+        (vd, gd), (vp, gp) = _params(dil.m), _params(pwc.m)
+        res = ops.weight_grads_ru_bl(dil.spec.dilation, gzb, hb, ghb, xb, (vp, gp, pwc.norm), (vd, gd, dil.norm))
+        return False if res is False else self._unit_pairs(dil, pwc, res)
 
     def _ru_dw(self, dil: _ConvRec, pwc: _ConvRec, gy, gh, bm: int) -> None:
-        """Weight gradients of both convs of a fused unit: one ``eben_ru_dw`` launch (reduction along time, operands straight from
-        the activation tensors) where both are weight-normalised bias-free parameters, else layer by layer."""
         if ops._skip_weight_grads[0]:
             return
         if self._dwq is not None:
             self._dwq.append(("ru", dil, pwc, gy, gh, bm))
             return
-        (vd, gd), (vp, gp) = _params(dil.m), _params(pwc.m)
-        fusable = (USE_FUSED_RU_DW and gd is not None and gp is not None and dil.m.bias is None and pwc.m.bias is None
-                   and vd.requires_grad and vp.requires_grad and gd.requires_grad and gp.requires_grad and bm in (ops.MATH_BF16, ops.MATH_BF16X6))
-        res = False
-        if fusable:
-            res = ops.weight_grads_ru(bm, dil.spec.dilation, gy, pwc.y, float(pwc.spec.out_slope), pwc.x, gh, dil.x, float(dil.spec.in_slope),
-                                      (vp, gp, pwc.norm), (vd, gd, dil.norm))
-        if res is False:
-            self._dw(pwc, gy)
-            self._dw(dil, gh)
-            return
-        self._accumulate((vp, gp, None), res[0])
-        self._accumulate((vd, gd, None), res[1])
+        self._accumulate(self._unit_grads(dil, pwc, gy, gh, bm, trainable_only=True))
 
     @staticmethod
     def _ru_bl_params_ok(ru, length: int) -> bool:
@@ -455,13 +466,11 @@ class GeneratorEngine:
             if self._dwq is not None:
                 self._dwq.append(("rubl", dil, pwc, gzb, hb, ghb, xb))
             else:
-                (vd, gd), (vp, gp) = _params(dil.m), _params(pwc.m)
-                res = ops.weight_grads_ru_bl(dil.spec.dilation, gzb, hb, ghb, xb, (vp, gp, pwc.norm), (vd, gd, dil.norm))
+                res = self._unit_grads_bl(dil, pwc, gzb, hb, ghb, xb)
                 if res is False:
                     raise RuntimeError("bundle-layout ResidualUnit: the two convs' weight gradients are routed differently (one of them holds a gradient "
                                        "or a hook the other does not); set EBEN_RU_BL=0 for this pattern")
-                self._accumulate((vp, gp, None), res[0])
-                self._accumulate((vd, gd, None), res[1])
+                self._accumulate(res)
         return gx
 
     def _ru_backward(self, rec, gy, res_post=None):
@@ -622,34 +631,15 @@ class GeneratorEngine:
         Returns [(parameter, gradient)] (with a data-parallel ``sink``: the gradients are its bucket views)."""
         jobs, assign = [], []
         with ops.collect_wn_jobs(jobs, sink):
-            for item in queue:
-                if item[0] == "conv":
-                    _, rec, dy = item
-                    v, g = _params(rec.m)
-                    grads = ops.weight_grads(rec.d, dy, rec.y, rec.x, v, g, rec.m.bias, rec.norm)
-                    assign.extend((p, t) for p, t in zip((v, g, rec.m.bias), grads) if p is not None and t is not None)
-                elif item[0] == "rubl":
-                    _, dil, pwc, gzb, hb, ghb, xb = item
-                    (vd, gd), (vp, gp) = _params(dil.m), _params(pwc.m)
-                    res = ops.weight_grads_ru_bl(dil.spec.dilation, gzb, hb, ghb, xb, (vp, gp, pwc.norm), (vd, gd, dil.norm))
+            for kind, *item in queue:
+                if kind == "conv":
+                    assign += self._conv_grads(*item)
+                elif kind == "rubl":
+                    res = self._unit_grads_bl(*item)
                     assert res is not False
-                    assign.extend(zip((vp, gp), res[0][:2]))
-                    assign.extend(zip((vd, gd), res[1][:2]))
+                    assign += res
                 else:
-                    _, dil, pwc, gy, gh, bm = item
-                    (vd, gd), (vp, gp) = _params(dil.m), _params(pwc.m)
-                    res = False
-                    if USE_FUSED_RU_DW and gd is not None and gp is not None and dil.m.bias is None and pwc.m.bias is None and bm in (ops.MATH_BF16, ops.MATH_BF16X6):
-                        res = ops.weight_grads_ru(bm, dil.spec.dilation, gy, pwc.y, float(pwc.spec.out_slope), pwc.x, gh, dil.x, float(dil.spec.in_slope),
-                                                  (vp, gp, pwc.norm), (vd, gd, dil.norm))
-                    if res is False:
-                        for rec, dy in ((pwc, gy), (dil, gh)):
-                            v, g = _params(rec.m)
-                            grads = ops.weight_grads(rec.d, dy, rec.y, rec.x, v, g, rec.m.bias, rec.norm)
-                            assign.extend((p, t) for p, t in zip((v, g, rec.m.bias), grads) if p is not None and t is not None)
-                    else:
-                        assign.extend(zip((vp, gp), res[0][:2]))
-                        assign.extend(zip((vd, gd), res[1][:2]))
+                    assign += self._unit_grads(*item, trainable_only=False)   # _deferrable() has checked requires_grad
         ops.wn_bwd_multi(jobs)
         return assign
 

@@ -203,20 +203,49 @@ def _side_stream(device, deal: bool = False) -> "torch.cuda.Stream":
     return aux_stream(SIDE_STREAMS[k], device)
 
 
+class WnJob(NamedTuple):
+    """One slab-sum / weight-norm job: the arguments of ``eben_wn_bwd`` for one layer (built by ``wn_job``)."""
+    slabs: torch.Tensor
+    nslab: int
+    slab_stride: int
+    rows: int
+    cols: int
+    row_stride: int
+    g: Optional[torch.Tensor]
+    v: torch.Tensor
+    norm: Optional[torch.Tensor]
+    dg: object       # outputs: tensors or raw device pointers
+    dv: object
+    dbias: object
+    col_perm_k: int = 0
+
+
+def wn_job(slabs, nslab: int, row_stride: int, v, g, norm, outs, *, col_perm_k: int = 0) -> WnJob:
+    """The job that sums ``nslab`` split-K slabs of ``v``'s shape (rows of ``row_stride`` floats) and applies the weight-norm chain rule
+    into ``outs`` = (dv, dg, dbias).  The logits layer (one output channel) is the one-row case, its two branches two jobs over views
+    of one slab buffer; without ``g`` the sums are written as they are.  col_perm_k: the slabs' columns are in the bundle-major order
+    of ``eben_bl_conv1d_bwd_dw``."""
+    dv, dg, dbias = outs
+    rows = v.shape[0]
+    has_g = g is not None
+    return WnJob(slabs, nslab, rows * row_stride, rows, v.numel() // rows, row_stride, g.detach() if has_g else None, v.detach(),
+                 norm if has_g else None, dg, dv, dbias, col_perm_k)
+
+
 def wn_bwd_multi(jobs) -> None:
-    """jobs: (slabs, nslab, slab_stride, rows, cols, row_stride, g, v, norm, dg, dv, dbias[, col_perm_k]) per layer -- the arguments
-    of ``eben_wn_bwd`` (col_perm_k: the slabs' columns are in the bundle-major order of ``eben_bl_conv1d_bwd_dw``) -- on the current
-    stream, as one multi-tensor call."""
+    """jobs: one ``WnJob`` per layer (or a plain sequence of its fields in order, the form this call took before the record), on the
+    current stream, as one multi-tensor call."""
     if not jobs:
         return
     items = (EbenWnBwdItem * len(jobs))()
     p = lambda t: t if t is None or isinstance(t, int) else ptr(t)   # outputs may arrive as raw device pointers
     for it, job in zip(items, jobs):
-        slabs, nslab, slab_stride, rows, cols, row_stride, g, v, norm, dg, dv, dbias = job[:12]
-        it.col_perm_k = job[12] if len(job) > 12 else 0
-        it.slabs, it.g, it.v, it.norm = ptr(slabs), ptr(g), ptr(v), ptr(norm)
-        it.dg, it.dv, it.dbias = p(dg), p(dv), p(dbias)
-        it.slab_stride, it.nslab, it.rows, it.cols, it.row_stride = slab_stride, nslab, rows, cols, row_stride
+        if not isinstance(job, WnJob):
+            job = WnJob(*job)
+        it.col_perm_k = job.col_perm_k
+        it.slabs, it.g, it.v, it.norm = ptr(job.slabs), ptr(job.g), ptr(job.v), ptr(job.norm)
+        it.dg, it.dv, it.dbias = p(job.dg), p(job.dv), p(job.dbias)
+        it.slab_stride, it.nslab, it.rows, it.cols, it.row_stride = job.slab_stride, job.nslab, job.rows, job.cols, job.row_stride
     check(load().eben_wn_bwd_multi(items, len(jobs), stream()), "wn_bwd_multi")
 
 
@@ -893,6 +922,15 @@ def join_prepack() -> None:
 PREMASK_TRANSPOSED_DW = os.environ.get("EBEN_PREMASK_DW", "1") != "0"
 
 
+def dw_workspace(d: EbenConv1dDesc) -> tuple:
+    """(bytes, slabs, row stride) of ``eben_conv1d_bwd_dw``'s workspace for this descriptor: asked once, kept on the descriptor."""
+    ws = getattr(d, "_dw_ws", None)
+    if ws is None:
+        nslab, row_stride = ctypes.c_int(0), ctypes.c_int(0)
+        ws = d._dw_ws = (load().eben_conv1d_bwd_dw_workspace(ctypes.byref(d), ctypes.byref(nslab), ctypes.byref(row_stride)), nslab.value, row_stride.value)
+    return ws
+
+
 def weight_grads(d: EbenConv1dDesc, dy: torch.Tensor, y: Optional[torch.Tensor], x: torch.Tensor, v: torch.Tensor,
                  g: Optional[torch.Tensor], bias: Optional[torch.Tensor], norm: Optional[torch.Tensor]):
     """Weight (+ bias) gradient of one conv layer: ``eben_conv1d_bwd_dw`` into split-K slabs, then the slab sum and the
@@ -903,8 +941,7 @@ def weight_grads(d: EbenConv1dDesc, dy: torch.Tensor, y: Optional[torch.Tensor],
     or assigned to ``.grad`` by ``join()`` (never handed to autograd: it may clone what it is given, and the deferred
     kernels would then fill a tensor nobody reads)."""
     lib = load()
-    has_g, has_bias = g is not None, bias is not None
-    use_side, sunk = _wg_route(v, g, bias)
+    use_side, outs, sunk = _wg_route(v, g, bias)
     premask = None
     if PREMASK_TRANSPOSED_DW and d.transposed and d.out_slope != 1.0 and y is not None and d.math in (MATH_BF16, MATH_BF16X2):
         # ConvTranspose1d with a fused output activation: the bf16 weight-gradient kernel takes no mask on that operand (the layer
@@ -914,37 +951,20 @@ def weight_grads(d: EbenConv1dDesc, dy: torch.Tensor, y: Optional[torch.Tensor],
         if plain is None:
             plain = d._dw_plain = type(d).from_buffer_copy(d)
             plain.out_slope = 1.0
-        premask, d = (dy, y, d.out_slope), plain
-    ws = getattr(d, "_dw_ws", None)   # (bytes, slabs, row stride) of this descriptor: asked once
-    if ws is None:
-        nslab, row_stride = ctypes.c_int(0), ctypes.c_int(0)
-        ws = d._dw_ws = (lib.eben_conv1d_bwd_dw_workspace(ctypes.byref(d), ctypes.byref(nslab), ctypes.byref(row_stride)), nslab.value, row_stride.value)
-    ws_bytes, nslab, row_stride = ws
+        premask, slope, d = (dy, y), d.out_slope, plain
+    ws_bytes, nslab, row_stride = dw_workspace(d)
     # Every buffer is allocated on the CURRENT stream's pool; on the deferred path the kernels are launched on the side stream through
     # its raw handle (no torch stream switch) and everything they touch stays referenced until join(), after which the current
     # stream -- which waits for the side stream there -- may reuse it.
     slabs = _empty(ws_bytes, x)
-    job, outs = _wg_job(slabs, nslab, row_stride, v, g, bias, norm, sunk, x.device)
-    raw = None
-    if use_side:
-        side = _side_stream(x.device, deal=True)
-        side.wait_stream(torch.cuda.current_stream(x.device))   # dy (and everything saved by the forward) is complete on the main stream
-        raw = side.cuda_stream
+    job = wn_job(slabs, nslab, row_stride, v, g, norm, outs)
+    st = _wg_stream(use_side, x.device)
     if premask is not None:
         gm = torch.empty_like(dy)
-        check(lib.eben_lrelu_bwd(ptr(dy), ptr(y), ptr(gm), dy.numel(), premask[2], raw if use_side else stream()), "lrelu_bwd")
+        check(lib.eben_lrelu_bwd(ptr(dy), ptr(y), ptr(gm), dy.numel(), slope, st), "lrelu_bwd")
         dy, y = gm, None
-    if use_side:
-        check(lib.eben_conv1d_bwd_dw(ctypes.byref(d), ptr(dy), ptr(y), ptr(x), 1 if has_bias else 0, ptr(slabs), ws_bytes, raw), "conv1d_bwd_dw")
-        _side["keep"].append((dy, x, y, norm, slabs) + (premask[:2] if premask is not None else ()))
-        _wg_defer(job, outs, v, g, bias, sunk)
-        return None, None, None
-    check(lib.eben_conv1d_bwd_dw(ctypes.byref(d), ptr(dy), ptr(y), ptr(x), 1 if has_bias else 0, ptr(slabs), ws_bytes, stream()), "conv1d_bwd_dw")
-    if _wn_collect[0] is not None:
-        _wn_collect[0].append(job)
-    else:
-        wn_bwd_multi([job])
-    return outs
+    check(lib.eben_conv1d_bwd_dw(ctypes.byref(d), ptr(dy), ptr(y), ptr(x), 1 if bias is not None else 0, ptr(slabs), ws_bytes, st), "conv1d_bwd_dw")
+    return _wg_finish(use_side, (dy, x, y, norm, slabs) + (premask or ()), [(job, (v, g, bias), sunk)])[0]
 
 
 _wn_collect = [None, None]   # inside collect_wn_jobs(): the list the immediate path appends its slab-sum / weight-norm jobs to, the sink
@@ -967,118 +987,112 @@ class collect_wn_jobs:
         _wn_collect[0], _wn_collect[1], _side["enabled"] = self.prev
 
 
+def grad_outputs(v, g, bias, sink=None, whole_layer: bool = False):
+    """Where a layer's three weight gradients are written: ((dv, dg, dbias), sunk).  With a data-parallel ``sink`` (``ddp.GradSync``)
+    p.grad is a view of a gradient bucket and the results go there directly, a parameter the sink holds no buffer for gets a fresh
+    tensor; ``whole_layer``: the sink is used only when it has a buffer for every parameter of the layer.  sunk: every output is a
+    view of the sink."""
+    params = (v, g, bias)
+    outs = [None if sink is None or p is None else sink.grad_buffer(p) for p in params]
+    sunk = sink is not None and all(o is not None for p, o in zip(params, outs) if p is not None)
+    if whole_layer and not sunk:
+        outs = [None, None, None]
+    dv, dg, dbias = outs
+    if dv is None:
+        dv = torch.empty_like(v)
+    if dg is None and g is not None:
+        dg = torch.empty_like(g)
+    if dbias is None and bias is not None:
+        dbias = torch.empty(v.shape[0], dtype=torch.float32, device=v.device)
+    return (dv, dg, dbias), sunk
+
+
+def add_logits_branches(params, gf, gr, sink=None):
+    """Logits layer: the fake and the real branch are separate weight gradients, then added (into the sink's buffers, where it has
+    them) -- the reference's structure (two autograd graphs accumulating into one .grad).  While every hinge term is active the
+    two bias gradients are -c*N and +c*N summed in the SAME order, i.e. they cancel exactly and Adam leaves the bias alone; one sum
+    over both branches leaves a rounding residue that Adam (m / sqrt(v)) turns into a full-size step."""
+    outs, _ = grad_outputs(*params, sink)
+    return tuple(None if a is None else torch.add(a, b, out=o) for a, b, o in zip(gf, gr, outs))
+
+
 def _wg_route(v, g, bias):
-    """Where a layer's weight gradients go: (issue on the side stream?, bucket views of a data-parallel sink or None)."""
-    has_g, has_bias = g is not None, bias is not None
+    """Where a layer's weight gradients go: (issue on the side stream?, the outputs, are they bucket views of a data-parallel sink?)."""
     is_param = isinstance(v, torch.nn.Parameter)
     use_side = (_side["enabled"] and is_param and v.grad is None and (g is None or g.grad is None) and (bias is None or bias.grad is None)
                 and _no_grad_hooks(v) and _no_grad_hooks(g) and _no_grad_hooks(bias))
-    sunk = None
     sk = _side["sink"] if _side["enabled"] and not use_side else (_wn_collect[1] if _wn_collect[0] is not None else None)
+    outs, sunk = grad_outputs(v, g, bias, sk, whole_layer=True)
     if sk is not None:
-        # data-parallel run: p.grad is a view of a gradient bucket -- write the results there directly
-        sunk = (sk.grad_buffer(v), sk.grad_buffer(g) if has_g else None, sk.grad_buffer(bias) if has_bias else None)
-        if sunk[0] is None or (has_g and sunk[1] is None) or (has_bias and sunk[2] is None):
-            sunk = None
-        use_side = sunk is not None and _wn_collect[0] is None   # collecting: the caller has made the producing stream current
-    return use_side, sunk
+        use_side = sunk and _wn_collect[0] is None   # collecting: the caller has made the producing stream current
+    return use_side, outs, sunk
 
 
-def _wg_job(slabs, nslab, row_stride, v, g, bias, norm, sunk, device):
-    """The ``eben_wn_bwd`` job that sums a layer's split-K slabs and applies the weight-norm chain rule, and its outputs."""
-    has_g, has_bias = g is not None, bias is not None
-    rows = v.shape[0]
-    cols = v.numel() // rows
-    if sunk is not None:
-        dv, dg, dbias = sunk
+def _wg_stream(use_side: bool, device) -> int:
+    """The raw handle of the stream a weight-gradient kernel is launched on: the current one, or the side stream behind it."""
+    if not use_side:
+        return stream()
+    side = _side_stream(device, deal=True)
+    side.wait_stream(torch.cuda.current_stream(device))   # dy (and everything saved by the forward) is complete on the main stream
+    return side.cuda_stream
+
+
+def _wg_finish(use_side: bool, keep: tuple, layers) -> list:
+    """What follows the weight-gradient launch of ``layers`` = [(job, (v, g, bias), sunk)]: deferred (the slab sums and the weight-norm
+    chain rule of ALL layers are one multi-tensor launch at join(), which also assigns or reports the results; ``keep`` is what the
+    launch reads), collected by ``collect_wn_jobs``, or run here.  Returns (dv, dg, dbias) per layer, Nones where deferred."""
+    jobs = [job for job, _, _ in layers]
+    if use_side:
+        _side["keep"].append(keep)
+        _side["wn_jobs"].extend(jobs)
+        for job, params, sunk in layers:
+            if sunk:
+                _side["sunk"].extend(p for p in params if p is not None)
+            else:
+                _side["assign"].extend((p, t) for p, t in zip(params, (job.dv, job.dg, job.dbias)) if p is not None and t is not None)
+        return [(None, None, None)] * len(layers)
+    if _wn_collect[0] is not None:
+        _wn_collect[0].extend(jobs)
     else:
-        dv = torch.empty_like(v)
-        dg = torch.empty_like(g) if has_g else None
-        dbias = torch.empty(rows, dtype=torch.float32, device=device) if has_bias else None
-    job = (slabs, nslab, rows * row_stride, rows, cols, row_stride, g.detach() if has_g else None, v.detach(), norm if has_g else None, dg, dv, dbias)
-    return job, (dv, dg, dbias)
+        wn_bwd_multi(jobs)
+    return [(job.dv, job.dg, job.dbias) for job in jobs]
 
 
-def _wg_defer(job, outs, v, g, bias, sunk) -> None:
-    """Deferred path: the slab sums and the weight-norm chain rule of ALL layers are one multi-tensor launch at join()."""
-    _side["wn_jobs"].append(job)
-    if sunk is None:
-        _side["assign"].extend((p, t) for p, t in zip((v, g, bias), outs) if p is not None and t is not None)
-    else:
-        _side["sunk"].extend(p for p in (v, g, bias) if p is not None)
+def _weight_grads_unit(launch, what: str, c: int, nslab: int, device, keep: tuple, pw_params, dil_params):
+    """Both weight gradients of a fused ResidualUnit of ``c`` channels by one launch ``launch(slabs_p, slabs_d, stream)`` that reads
+    ``keep``: ``*_params`` = (v, g, norm) of the pointwise / dilated conv (weight-normalised, no bias).  Routed like ``weight_grads``
+    (side stream / gradient buckets / immediate); returns False when the two layers would be routed differently, else a pair of
+    (dv, dg, None) results -- Nones where deferred."""
+    (vp, gp, np_), (vd, gd, nd) = pw_params, dil_params
+    (use_side, outs_p, sunk_p), (side_d, outs_d, sunk_d) = _wg_route(vp, gp, None), _wg_route(vd, gd, None)
+    if use_side != side_d or sunk_p != sunk_d:
+        return False
+    slabs_p = torch.empty(nslab * c * c, dtype=torch.float32, device=device)
+    slabs_d = torch.empty(nslab * c * 3 * c, dtype=torch.float32, device=device)
+    job_p = wn_job(slabs_p, nslab, c, vp, gp, np_, outs_p)
+    job_d = wn_job(slabs_d, nslab, 3 * c, vd, gd, nd, outs_d)
+    check(launch(ptr(slabs_p), ptr(slabs_d), _wg_stream(use_side, device)), what)
+    return tuple(_wg_finish(use_side, keep + (np_, nd, slabs_p, slabs_d), [(job_p, (vp, gp, None), sunk_p), (job_d, (vd, gd, None), sunk_d)]))
 
 
 def weight_grads_ru(math: int, dilation: int, gy: torch.Tensor, u: torch.Tensor, out_slope: float, h: torch.Tensor, gh: torch.Tensor,
                     x: torch.Tensor, in_slope: float, pw_params, dil_params):
     """Both weight gradients of a fused ResidualUnit in one launch (``eben_ru_dw``: the reduction runs along time, no packing
-    pass): ``*_params`` = (v, g, norm) of the pointwise / dilated conv (weight-normalised, no bias).  Routed like ``weight_grads``
-    (side stream / gradient buckets / immediate); returns False when the two layers would be routed differently (the caller then
-    takes the per-layer path), else a pair of (dv, dg, None) results -- Nones where deferred."""
+    pass); see ``_weight_grads_unit`` (False: the caller takes the per-layer path)."""
     lib = load()
-    (vp, gp, np_), (vd, gd, nd) = pw_params, dil_params
-    route_p, route_d = _wg_route(vp, gp, None), _wg_route(vd, gd, None)
-    if route_p[0] != route_d[0] or (route_p[1] is None) != (route_d[1] is None):
-        return False
-    use_side = route_p[0]
     b, c, l = gy.shape
-    nslab = lib.eben_ru_dw_slabs(b, c, l)
-    slabs_p = torch.empty(nslab * c * c, dtype=torch.float32, device=gy.device)
-    slabs_d = torch.empty(nslab * c * 3 * c, dtype=torch.float32, device=gy.device)
-    job_p, outs_p = _wg_job(slabs_p, nslab, c, vp, gp, None, np_, route_p[1], gy.device)
-    job_d, outs_d = _wg_job(slabs_d, nslab, 3 * c, vd, gd, None, nd, route_d[1], gy.device)
-    if use_side:
-        side = _side_stream(gy.device, deal=True)
-        side.wait_stream(torch.cuda.current_stream(gy.device))
-        st = side.cuda_stream
-    else:
-        st = stream()
-    check(lib.eben_ru_dw(math, b, c, l, dilation, ptr(gy), ptr(u), float(out_slope), ptr(h), ptr(gh), ptr(x), float(in_slope), ptr(slabs_p), ptr(slabs_d), st),
-          "ru_dw")
-    if use_side:
-        _side["keep"].append((gy, u, h, gh, x, np_, nd, slabs_p, slabs_d))
-        _wg_defer(job_p, outs_p, vp, gp, None, route_p[1])
-        _wg_defer(job_d, outs_d, vd, gd, None, route_d[1])
-        return (None, None, None), (None, None, None)
-    if _wn_collect[0] is not None:
-        _wn_collect[0].extend((job_p, job_d))
-    else:
-        wn_bwd_multi([job_p, job_d])
-    return outs_p, outs_d
+    launch = lambda sp, sd, st: lib.eben_ru_dw(math, b, c, l, dilation, ptr(gy), ptr(u), float(out_slope), ptr(h), ptr(gh), ptr(x), float(in_slope), sp, sd, st)
+    return _weight_grads_unit(launch, "ru_dw", c, lib.eben_ru_dw_slabs(b, c, l), gy.device, (gy, u, h, gh, x), pw_params, dil_params)
 
 
 def weight_grads_ru_bl(dilation: int, gzb: torch.Tensor, hb: torch.Tensor, ghb: torch.Tensor, xb: torch.Tensor, pw_params, dil_params):
     """``weight_grads_ru`` on the four bf16 bundle planes of a unit (``eben_rubl_dw``, csrc/ru_bl.hip): g_z and g_h as written by
     ``eben_rubl_bwd``, h and xin as saved by ``eben_rubl_fwd`` -- planes of shape (batch, C / 8, L, 8)."""
     lib = load()
-    (vp, gp, np_), (vd, gd, nd) = pw_params, dil_params
-    route_p, route_d = _wg_route(vp, gp, None), _wg_route(vd, gd, None)
-    if route_p[0] != route_d[0] or (route_p[1] is None) != (route_d[1] is None):
-        return False
-    use_side = route_p[0]
     b, cb, l, _ = gzb.shape
     c = 8 * cb
-    nslab = lib.eben_rubl_dw_slabs(b, c, l)
-    slabs_p = torch.empty(nslab * c * c, dtype=torch.float32, device=gzb.device)
-    slabs_d = torch.empty(nslab * c * 3 * c, dtype=torch.float32, device=gzb.device)
-    job_p, outs_p = _wg_job(slabs_p, nslab, c, vp, gp, None, np_, route_p[1], gzb.device)
-    job_d, outs_d = _wg_job(slabs_d, nslab, 3 * c, vd, gd, None, nd, route_d[1], gzb.device)
-    if use_side:
-        side = _side_stream(gzb.device, deal=True)
-        side.wait_stream(torch.cuda.current_stream(gzb.device))
-        st = side.cuda_stream
-    else:
-        st = stream()
-    check(lib.eben_rubl_dw(b, c, l, dilation, gzb.data_ptr(), hb.data_ptr(), ghb.data_ptr(), xb.data_ptr(), ptr(slabs_p), ptr(slabs_d), st), "rubl_dw")
-    if use_side:
-        _side["keep"].append((gzb, hb, ghb, xb, np_, nd, slabs_p, slabs_d))
-        _wg_defer(job_p, outs_p, vp, gp, None, route_p[1])
-        _wg_defer(job_d, outs_d, vd, gd, None, route_d[1])
-        return (None, None, None), (None, None, None)
-    if _wn_collect[0] is not None:
-        _wn_collect[0].extend((job_p, job_d))
-    else:
-        wn_bwd_multi([job_p, job_d])
-    return outs_p, outs_d
+    launch = lambda sp, sd, st: lib.eben_rubl_dw(b, c, l, dilation, gzb.data_ptr(), hb.data_ptr(), ghb.data_ptr(), xb.data_ptr(), sp, sd, st)
+    return _weight_grads_unit(launch, "rubl_dw", c, lib.eben_rubl_dw_slabs(b, c, l), gzb.device, (gzb, hb, ghb, xb), pw_params, dil_params)
 
 
 class _ConvLayerFn(torch.autograd.Function):
