@@ -643,3 +643,60 @@ def test_stride4_weight_gradient_forms_agree(hip, kw, rows, length, same_split):
     else:
         sa, sb = a.double().sum(0), b.double().sum(0)
         assert float((sa - sb).abs().max()) <= 1e-5 * float(sb.abs().max())
+
+
+class _RecordingSink:
+    """The two methods of ``ddp.GradSync`` the discriminator engine uses: one persistent gradient buffer per parameter, and a log of
+    which parameters were reported in which phase of the step."""
+
+    def __init__(self):
+        self.buffers, self.reports, self.phase = {}, [], None
+
+    def grad_buffer(self, p):
+        if id(p) not in self.buffers:
+            self.buffers[id(p)] = torch.zeros_like(p)
+        return self.buffers[id(p)]
+
+    def mark_ready(self, params):
+        self.reports += [(id(p), self.phase) for p in params]
+
+
+def test_grouped_weight_gradients_report_to_the_sink_like_chain_by_chain(hip, golden):
+    """Data-parallel runs hand the engine a sink: the weight gradients are written into its buffers and, with ``defer_mark_ready`` (the
+    default), reported only when ``collect_param_grads`` has joined them -- for the PQMF-band chains' grouped launch sequence
+    (``group_weight_grads``) as for chain by chain: no report before the join, every trainable parameter exactly once, the same bits."""
+    from formula import formula_audio
+    from tests.test_gpu_models import build_discriminator
+    from vibravox_amd.disc_engine import DiscriminatorEngine
+    from vibravox_amd.disc_engine_bl import DiscriminatorEngineBL
+    from vibravox_amd.lightning_modules.eben import DISC_MATH_PLANS
+
+    bands = formula_audio("d_bands", 8, 2016, amp=0.5).reshape(2, 4, 2016).to(DEV)
+    audio = formula_audio("d_audio", 2, 4 * 2016 - 32).reshape(2, 1, -1).to(DEV)
+    bands_b = formula_audio("d_bands_b", 8, 2016, amp=0.5).reshape(2, 4, 2016).to(DEV)
+    audio_b = formula_audio("d_audio_b", 2, 4 * 2016 - 32).reshape(2, 1, -1).to(DEV)
+    assert DiscriminatorEngineBL.defer_mark_ready
+    saved = DiscriminatorEngineBL.group_weight_grads
+    runs = []
+    try:
+        for group in (False, True):
+            DiscriminatorEngineBL.group_weight_grads = group
+            disc, _ = build_discriminator(golden)
+            engine = DiscriminatorEngine(disc, DISC_MATH_PLANS["bf16_bl"])
+            assert type(engine) is DiscriminatorEngineBL
+            sink = _RecordingSink()
+            for phase, call in (("forward", lambda: engine.forward(bands, audio, bands_b, audio_b)), ("losses", engine.losses),
+                                ("backward_launch", lambda: engine.backward_launch(True, sink)), ("backward_finish", engine.backward_finish),
+                                ("collect_param_grads", engine.collect_param_grads)):
+                sink.phase = phase
+                call()
+            torch.cuda.synchronize()
+            params = [p for p in disc.parameters() if p.requires_grad]
+            early = [phase for _, phase in sink.reports if phase != "collect_param_grads"]
+            assert not early, (group, sorted(set(early)))
+            assert sorted(i for i, _ in sink.reports) == sorted(id(p) for p in params), group
+            runs.append([sink.buffers[id(p)].clone() for p in params])
+    finally:
+        DiscriminatorEngineBL.group_weight_grads = saved
+    assert all(torch.isfinite(g).all() for g in runs[0]) and all(g.abs().max() > 0 for g in runs[0] if g.dim() == 3)   # every weight was written
+    assert all(torch.equal(a, b) for a, b in zip(*runs))

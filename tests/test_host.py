@@ -349,3 +349,5 @@ def test_bundle_layout_engine_falls_back_for_heads_it_has_no_kernel_for():
     with pytest.warns(UserWarning, match="fp32 tensors at rest"):
         eng = DiscriminatorEngine(d3, plan)
     assert type(eng) is DiscriminatorEngine and eng.math is plan   # the step does not rebuild it every call
+    for e in (DiscriminatorEngine(d4), DiscriminatorEngine(d4, plan)):   # both engine types read the module tree alike
+        assert [len(c.layers) for c in e.chains] == [8, 8, 8, 7] and [c.pad for c in e.chains] == [1, 1, 1, 7]

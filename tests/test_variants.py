@@ -194,3 +194,37 @@ def test_grouped_weight_gradients_equal_chain_by_chain(hip, golden):
         DiscriminatorEngineBL.group_weight_grads, DiscriminatorEngineBL.split_backward = saved
     for other in outs[1:]:
         assert all(torch.equal(outs[0][k], other[k]) for k in outs[0]), [k for k in outs[0] if not torch.equal(outs[0][k], other[k])]
+
+
+@pytest.mark.gpu
+def test_whole_and_split_discriminator_forward_agree(hip, golden):
+    """The bundle-layout engine's forward as one pass over all 2B rows (``split_discriminator_forward = False``) and as the reference half
+    underneath the generator forward followed by the enhanced half, with MelGAN's reference half run behind the generator ("0"), beside
+    it ("1") or its thin layers only ("thin"): after six steps -- every launch sequence captured and replayed -- both networks and the
+    feature-matching loss are bit-identical.  A forward launch computes each row from that row alone, and the weight gradients run on
+    all 2B rows in every run; only the launches the rows travel in differ."""
+    from vibravox_amd import disc_engine_bl
+
+    fm_key = "train/generator/feature_matching_loss"
+    outs = []
+    saved = disc_engine_bl.SPLIT_MELGAN
+    try:
+        for split, melgan in ((False, saved), (True, "thin"), (True, "0"), (True, "1")):
+            disc_engine_bl.SPLIT_MELGAN = melgan
+            mod, _, dev = _make_module(golden, {})
+            mod.disc_math, mod.gen_backward_math = "bf16_bl", "bf16"
+            mod.split_discriminator_forward = split
+            torch.manual_seed(3)
+            for bc, air in variant_batches("none", 6):
+                mod.training_step({"audio_body_conducted": bc.to(dev), "audio_airborne": air.to(dev)})
+            torch.cuda.synchronize()
+            assert type(mod._disc_engine).__name__ == "DiscriminatorEngineBL"
+            out = {f"D/{k}": v.clone() for k, v in mod.discriminator.state_dict().items()}
+            out.update({f"G/{k}": v.clone() for k, v in mod.generator.state_dict().items()})
+            out[fm_key] = mod.logged[fm_key].detach().clone()
+            outs.append(out)
+    finally:
+        disc_engine_bl.SPLIT_MELGAN = saved
+    for other in outs[1:]:
+        assert outs[0].keys() == other.keys()
+        assert all(torch.equal(outs[0][k], other[k]) for k in outs[0]), [k for k in outs[0] if not torch.equal(outs[0][k], other[k])]

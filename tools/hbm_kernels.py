@@ -10,7 +10,7 @@ rows = {r["Name"]: r for r in csv.DictReader(open(sys.argv[1]))}
 B, T = 32, 31968
 R2 = 2 * B   # discriminator rows (enhanced + reference)
 # embedding elements per row that enter the feature-matching loss, per chain (the feature-matching sums run as ONE launch per chain:
-# disc_engine_bl.forward, body(i)) -- layers 0 .. n - 2 of each sub-discriminator
+# disc_engine_bl._forward_rows, body(i)) -- layers 0 .. n - 2 of each sub-discriminator
 mel = [16 * 31968, 64 * 7992, 256 * 1998, 1024 * 500, 1024 * 125, 1024 * 125]
 pq = [[24 * 7992, 48 * 3997, 96 * 1999, 192 * 1000, 384 * 500, 768 * 250, 768 * 250],
       [24 * 7992, 48 * 3993, 96 * 1994, 192 * 994, 384 * 494, 768 * 244, 768 * 244],

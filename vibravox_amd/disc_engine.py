@@ -30,7 +30,7 @@ from __future__ import annotations
 import ctypes
 import dataclasses
 import os
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -133,26 +133,27 @@ class _Layer:
         return self._pr_descs[key]
 
 
+def chain_convs(modules) -> Tuple[int, list]:
+    """(reflection padding, the convs in order) of a sub-discriminator's ``discriminator`` list: every entry is a conv or a
+    Sequential of an optional ReflectionPad1d and a conv (eben_discriminator.py:40-49, melgan_discriminator.py:48-57)."""
+    pad, convs = 0, []
+    for m in modules:
+        for sub in (m if isinstance(m, torch.nn.Sequential) else [m]):
+            if hasattr(sub, "padding") and not hasattr(sub, "spec"):
+                pad = int(sub.padding)
+            else:
+                convs.append(sub)
+    return pad, convs
+
+
 class _Chain:
     """A sub-discriminator: ReflectionPad1d(pad) followed by the conv stack (last conv = logits)."""
 
     def __init__(self, modules, math=ops.MATH_F32):
         """math: EBEN_MATH_* or (forward, input gradient, weight gradient), or a callable layer index -> one of those."""
-        self.layers: List[_Layer] = []
-        self.pad = 0
+        self.pad, convs = chain_convs(modules)
+        self.layers: List[_Layer] = [_Layer(conv, math(i, len(convs)) if callable(math) else math) for i, conv in enumerate(convs)]
         self._fm_ok: Dict[tuple, bool] = {}
-        convs = []
-        for m in modules:
-            if isinstance(m, torch.nn.Sequential):
-                for sub in m:
-                    if hasattr(sub, "padding") and not hasattr(sub, "spec"):
-                        self.pad = int(sub.padding)
-                    else:
-                        convs.append(sub)
-            else:
-                convs.append(m)
-        for i, conv in enumerate(convs):
-            self.layers.append(_Layer(conv, math(i, len(convs)) if callable(math) else math))
 
     # ---- forward on a (2B, C, L) batch: returns [input, out_0, ..., logits] and the padded input
     def forward(self, x: torch.Tensor):
@@ -337,6 +338,50 @@ def inject_grads(params: Sequence[torch.nn.Parameter], grads: Sequence[torch.Ten
     _InjectGrads.apply(list(gs), *ps).backward()
 
 
+@dataclasses.dataclass(slots=True)
+class ForwardState:
+    """What the forward passes of a step leave for ``losses`` and the backward (fp32 tensors at rest)."""
+
+    half: int
+    emb: list           # per chain [input, out_0, ..., logits], 2 half rows: [enhanced | reference]
+    xp: list            # per chain the reflection-padded input
+    bands_shape: tuple
+    # the feature-matching operands, added by ``losses`` and read again by the backward
+    fm_a: Optional[list] = None
+    fm_sums: Optional[torch.Tensor] = None
+    fm_inv: float = 0.0
+    fm_numel: object = None
+    fm_ptrs: object = None
+
+
+class ChainBackward(NamedTuple):
+    """What the stacked backward of ONE chain left on its stream: handed from ``backward_launch`` to whatever follows it."""
+
+    dx: object                   # gradient at the chain's input: a tensor (fp32 at rest) or the ``Planes`` at the head's output
+    jobs: Optional[list]         # (layer index, stacked gradient at the layer's output, layer input): the weight gradients still to run
+    g0: object                   # bundle layout: rows [fake | real] of ``dx``, the head's weight-gradient operand
+    seeds: torch.Tensor          # the stacked seed rows [fm | adv | fake | real]
+    stream: "torch.cuda.Stream"  # the stream the chain was launched on (``spread_backward`` moves one chain off its home stream)
+    done: "torch.cuda.Event"     # recorded behind the chain on that stream
+
+
+class BackwardLaunch(NamedTuple):
+    """``backward_launch`` -> ``backward_finish``."""
+
+    chains: List[ChainBackward]
+    want_param_grads: bool
+    split: bool    # two passes (bundle layout): only rows [fm | adv] are behind ``done``, rows [fake | real] and the weight gradients follow
+    keep: tuple    # main-stream tensors the chains read: referenced until the join
+
+
+class PendingGrads(NamedTuple):
+    """Weight-gradient work left running on the chains' streams until ``collect_param_grads`` joins it."""
+
+    grads: list    # per chain, per layer (dv, dg, dbias)
+    ready: list    # parameters whose report to the data-parallel sink waits for the join (``defer_mark_ready``)
+    keep: list     # the saved activations and stacked gradients: alive until the kernels have run
+
+
 class DiscriminatorEngine:
     def __new__(cls, disc, math=ops.MATH_F32):
         if cls is DiscriminatorEngine and isinstance(math, dict) and math.get("layout") == "bl":
@@ -352,6 +397,11 @@ class DiscriminatorEngine:
             warnings.warn(f"bundle-layout discriminator engine: {why}; running the same plan on fp32 tensors at rest ('bf16')")
         return super().__new__(cls)
 
+    chain_type = _Chain
+    #: whether running the reference half of the batch ahead of time (``forward_reference``, underneath the generator forward) has been
+    #: measured to pay: the train step splits the forward of such an engine by default, of any engine under EBEN_SPLIT_D_FWD=1
+    split_forward_pays = False
+
     def __init__(self, disc, math=ops.MATH_F32):
         """math: what the contractions of the layers tapconv3.hip / conv_dw3.hip cover compute in (fp32 accumulation, storage
         and element-wise stages either way) -- one EBEN_MATH_* for everything, a (forward, input gradient, weight gradient)
@@ -361,11 +411,17 @@ class DiscriminatorEngine:
         self.q = disc.q
         self.math = math
         per = math if isinstance(math, dict) else {"pqmf": math, "melgan": math}
-        self.chains = [_Chain(d.discriminator, per["pqmf"]) for d in disc.pqmf_discriminators] + [
-            _Chain(disc.melgan_discriminator.discriminator, per["melgan"])]
-        self._streams = None
-        self._state = None
+        self.chains = [self.chain_type(d.discriminator, per["pqmf"]) for d in disc.pqmf_discriminators] + [
+            self.chain_type(disc.melgan_discriminator.discriminator, per["melgan"])]
+        self._streams = None    # each chain's home stream (made by the first launch, per device)
+        self._launched = []     # the stream each chain's LAST launch ran on
+        self._state = None      # the step's forward state, from ``forward`` to ``backward_finish``
+        self._partial = None    # what ``forward_reference`` left for ``forward``
+        self._bwd: Optional[BackwardLaunch] = None
+        self._pending: Optional[PendingGrads] = None
+        self._sink = None       # the step's data-parallel gradient sink (``ddp.GradSync``), from ``backward_launch`` on
         self._prepack_graph = ops.ReplayedPrepack()
+        self._prepack_ev = None   # behind the last ``prepack``: every chain launch waits for it
         #: weights of the (adversarial, fake, real) hinge seeds of the stacked backward: (1, 1, 1) is the train step; (1, 1, 0) /
         #: (1, 0, 1) give the discriminator gradient of fake_loss / real_loss alone (the parity tests bound each branch
         #: separately -- their sum cancels to a fraction of a percent at initialisation)
@@ -384,42 +440,62 @@ class DiscriminatorEngine:
     #: writes it into buffers the epilogues then read
     fm_in_epilogue = os.environ.get("EBEN_FM_EPILOGUE", "1") != "0"
     spread_backward = os.environ.get("EBEN_D_BWD_SPREAD", "1") != "0"   # [MI355X] 19.6 -> 19.35 ms/step (the input-gradient phase shortens by 0.4 ms, the generator backward, which then shares the GPU with more weight-gradient work, lengthens by 0.15)
+    #: data-parallel runs: report a chain's gradients to the sink when ``collect_param_grads`` has joined them instead of from the
+    #: chain's stream right behind its launches (the bundle-layout engine's default: see there)
+    defer_mark_ready = False
 
+    # ---- the chains' streams ---------------------------------------------------------------------------
     def _launch_on_streams(self, fn, forward: bool = False, order=None):
         """fn(i) for each sub-discriminator on its own HIP stream, the longest chain (MelGAN, last) first so that it
-        is never queued behind a short one (or in ``order``); results in chain order.  The caller joins with ``_join_streams``."""
+        is never queued behind a short one (or in ``order``); results in chain order.  The streams used are kept in
+        ``_launched`` (fn(i) may read its own); the caller joins with ``_join_streams``."""
         main = torch.cuda.current_stream()
         dev = main.device
+        n = len(self.chains)
         if self._streams is None or self._streams[0].device != dev:
             # MelGAN chain on one stream, the three (shorter, equal) PQMF-band chains in series on another: with the main
             # and the side stream that is four streams = four hardware queues, none shared (ops.aux_stream)
             pq, mel = ops.aux_stream(1, dev), ops.aux_stream(0, dev)
-            self._streams = [pq] * (len(self.chains) - 1) + [mel]
+            self._streams = [pq] * (n - 1) + [mel]
         streams = list(self._streams)
-        if (self.spread_forward if forward else self.spread_backward) and len(self.chains) >= 3:
-            streams[len(self.chains) - 2] = ops.aux_stream(2, dev)
-        self._used_streams = set(streams) | set(self._streams)
-        results = [None] * len(self.chains)
-        n = len(self.chains)
-        ev = getattr(self, "_prepack_ev", None)
+        if (self.spread_forward if forward else self.spread_backward) and n >= 3:
+            streams[n - 2] = ops.aux_stream(2, dev)
+        self._launched = streams
+        results = [None] * n
         for i in (order if order is not None else [n - 1] + list(range(n - 1))):
             st = streams[i]
             st.wait_stream(main)
-            if ev is not None:
-                st.wait_event(ev)   # weight images rebuilt ahead of time on the side stream (prepack)
+            if self._prepack_ev is not None:
+                st.wait_event(self._prepack_ev)   # weight images rebuilt ahead of time on the side stream (prepack)
             with torch.cuda.stream(st):
                 results[i] = fn(i)
         return results
 
     def _join_streams(self):
+        """The current stream waits for everything on the chains' streams: those of the last launch and the home streams."""
         main = torch.cuda.current_stream()
-        for st in getattr(self, "_used_streams", None) or set(self._streams):
+        for st in set(self._launched) | set(self._streams or ()):
             main.wait_stream(st)
 
-    def _on_streams(self, fn):
-        results = self._launch_on_streams(fn)
+    def _behind(self, r: ChainBackward, st: "torch.cuda.Stream"):
+        """Context: ``st`` is the current stream, for work that follows chain ``r``'s backward -- ordered behind it by the stream
+        itself when the chain was launched there, by its ``done`` event otherwise."""
+        if st != r.stream:
+            st.wait_event(r.done)
+        return torch.cuda.stream(st)
+
+    def _report(self, pend: PendingGrads, chains) -> None:
+        """Data-parallel run: the gradients of ``chains`` are in the sink's buckets once the current stream gets here.  Reported now,
+        from this stream, the buckets they complete (MelGAN's 75 MB first) are exchanged underneath the other chains' weight
+        gradients and the generator backward instead of in front of Adam; ``defer_mark_ready``: after the join."""
+        ready = [p for ch in chains for lay in ch.layers for p in lay.params() if p is not None and p.requires_grad]
+        if self.defer_mark_ready:
+            pend.ready.extend(ready)
+        else:
+            self._sink.mark_ready(ready)
+
+    def join(self):
         self._join_streams()
-        return results
 
     # ---- the two forwards: one batch-2B pass, or the reference half ahead of time ----------------------
     def _inputs(self, half, bands_like, audio_like):
@@ -439,33 +515,29 @@ class DiscriminatorEngine:
         wav[half:].copy_(audio_ref)
         inputs = [sub] * (len(self.chains) - 1) + [wav]
         bufs = self._launch_on_streams(lambda i: self.chains[i].forward_rows(inputs[i], None, half, 2 * half), forward=True)
-        self._partial = dict(half=half, sub=sub, wav=wav, bufs=bufs)
+        self._partial = (half, sub, wav, bufs)
 
     @torch.no_grad()
     def forward(self, bands: torch.Tensor, audio: torch.Tensor, bands_ref: torch.Tensor, audio_ref: torch.Tensor, join: bool = True):
         """join=False leaves the chains running (the caller overlaps independent work on the main stream and calls
         ``join()`` before anything reads the embeddings).  After ``forward_reference`` only the enhanced half is run."""
         half = bands.shape[0]
-        part = getattr(self, "_partial", None)
-        self._partial = None
-        if part is not None and part["half"] == half:
-            sub, wav = part["sub"], part["wav"]
+        part, self._partial = self._partial, None
+        if part is not None and part[0] == half:
+            _, sub, wav, bufs = part
             sub[:half].copy_(bands[:, -self.q:, :])
             wav[:half].copy_(audio)
-            inputs = [sub] * (len(self.chains) - 1) + [wav]
-            res = self._launch_on_streams(lambda i: self.chains[i].forward_rows(inputs[i], part["bufs"][i], 0, half), forward=True)
+            r1 = half
         else:
             sub = torch.cat((bands[:, -self.q:, :], bands_ref[:, -self.q:, :]), dim=0).contiguous()
             wav = torch.cat((audio, audio_ref), dim=0).contiguous()
-            inputs = [sub] * (len(self.chains) - 1) + [wav]
-            res = self._launch_on_streams(lambda i: self.chains[i].forward_rows(inputs[i], None, 0, 2 * half), forward=True)
+            bufs, r1 = [None] * len(self.chains), 2 * half
+        inputs = [sub] * (len(self.chains) - 1) + [wav]
+        res = self._launch_on_streams(lambda i: self.chains[i].forward_rows(inputs[i], bufs[i], 0, r1), forward=True)
         if join:
             self._join_streams()
-        self._state = dict(half=half, emb=[r["emb"] for r in res], xp=[r["xp"] for r in res], bands_shape=tuple(bands.shape))
-        return self._state["emb"]
-
-    def join(self):
-        self._join_streams()
+        self._state = ForwardState(half, [r["emb"] for r in res], [r["xp"] for r in res], tuple(bands.shape))
+        return self._state.emb
 
     def image_caches(self) -> list:
         """``ops.prepack`` entries of every layer: after the discriminator's optimiser step the images the last step used (forward at
@@ -473,12 +545,17 @@ class DiscriminatorEngine:
         at the head of the four chains."""
         return [(lay.cache, lambda slot, lay=lay: lay.packed(*slot)) for ch in self.chains for lay in ch.layers]
 
+    def prepack(self) -> None:
+        """Rebuilds those images now (``ops.prepack``, after the discriminator's optimiser step) and keeps the event recorded behind
+        them: the chains' launches wait for it, nothing else does."""
+        self._prepack_ev = ops.prepack(self.image_caches(), self._prepack_graph, join=False)
+
     # ---- the four scalar losses (device tensors) ------------------------------------------------
     @torch.no_grad()
     def losses(self) -> Dict[str, torch.Tensor]:
         lib = load()
         s = self._state
-        half, emb = s["half"], s["emb"]
+        half, emb = s.half, s.emb
         dev = emb[0][0].device
         a = [t[:half] for scale in emb for t in scale[1:-1]]
         b = [t[half:] for scale in emb for t in scale[1:-1]]
@@ -492,7 +569,7 @@ class DiscriminatorEngine:
         sums = torch.empty(2 * n, dtype=torch.float32, device=dev)
         check(lib.eben_fm_sums(ptrs, numel, n, ptr(ws), ws_bytes, ptr(sums), _stream()), "fm_sums")
         inv = 1.0 / (len(emb) * len(emb[-1][1:-1]))
-        s.update(fm_a=a, fm_b=b, fm_sums=sums, fm_inv=inv, fm_numel=numel, fm_ptrs=ptrs)
+        s.fm_a, s.fm_sums, s.fm_inv, s.fm_numel, s.fm_ptrs = a, sums, inv, numel, ptrs
         hinge = torch.empty(3 * len(emb), dtype=torch.float32, device=dev)
         terms = [(rows, target) for scale in emb for rows, target in ((scale[-1][:half], 1.0), (scale[-1][:half], -1.0), (scale[-1][half:], 1.0))]
         nt = len(terms)
@@ -522,16 +599,15 @@ class DiscriminatorEngine:
         self._sink = sink
         lib = load()
         s = self._state
-        half, emb = s["half"], s["emb"]
+        half, emb = s.half, s.emb
         dev = emb[0][0].device
-        n = len(s["fm_a"])
         one = torch.ones(1, dtype=torch.float32, device=dev)
         # feature-matching gradient: formed in the input-gradient epilogues where every launch of a chain can (no buffers, no extra
         # pass over the embeddings), by one eben_fm_bwd launch per chain otherwise
-        fused = [self.fm_in_epilogue and ch.fm_epilogue_ok(emb[i], s["xp"][i], half) for i, ch in enumerate(self.chains)]
+        fused = [self.fm_in_epilogue and ch.fm_epilogue_ok(emb[i], s.xp[i], half) for i, ch in enumerate(self.chains)]
         da, k = [], 0
         for i, scale in enumerate(emb):
-            for t in s["fm_a"][k:k + len(scale) - 2]:
+            for t in s.fm_a[k:k + len(scale) - 2]:
                 da.append(None if fused[i] else torch.empty_like(t))
             k += len(scale) - 2
         # feature-matching gradients per chain, aligned with out_0 .. out_{L-2}; each chain forms its own on its own stream (one
@@ -543,7 +619,7 @@ class DiscriminatorEngine:
             first.append(k)
             k += cnt
         inv_scales = 1.0 / len(emb)
-        fm_all, numel_all, sums_ptr = s["fm_ptrs"], s["fm_numel"], ptr(s["fm_sums"])
+        fm_all, numel_all, sums_ptr = s.fm_ptrs, s.fm_numel, ptr(s.fm_sums)
 
         def run(i):
             k0, cnt = first[i], len(fm_per_chain[i])
@@ -551,7 +627,7 @@ class DiscriminatorEngine:
                 pairs = (ctypes.c_void_p * (2 * cnt))(*fm_all[2 * k0:2 * (k0 + cnt)])
                 outs = (ctypes.c_void_p * cnt)(*[ptr(t) for t in fm_per_chain[i]])
                 numel = (ctypes.c_int64 * cnt)(*numel_all[k0:k0 + cnt])
-                check(lib.eben_fm_bwd(pairs, outs, numel, cnt, sums_ptr + 8 * k0, ptr(one), s["fm_inv"], _stream()), "fm_bwd")
+                check(lib.eben_fm_bwd(pairs, outs, numel, cnt, sums_ptr + 8 * k0, ptr(one), s.fm_inv, _stream()), "fm_bwd")
             scale = emb[i]
             lg = scale[-1]
             seeds = torch.zeros((4 * half,) + tuple(lg.shape[1:]), dtype=torch.float32, device=dev)
@@ -560,68 +636,66 @@ class DiscriminatorEngine:
             for k2, (rows, target) in enumerate(((lg[:half], 1.0), (lg[:half], -1.0), (lg[half:], 1.0))):
                 check(lib.eben_hinge_bwd(ptr(rows), rows.numel(), target, ptr(one), inv_scales * self.seed_weights[k2],
                                          ptr(flat[(k2 + 1) * per:]), _stream()), "hinge_bwd")
-            return self.chains[i].backward(scale, s["xp"][i], fm_per_chain[i], seeds, half, want_param_grads,
-                                           (sums_ptr + 8 * k0, s["fm_inv"]) if fused[i] and cnt else None)
+            dx, jobs = self.chains[i].backward(scale, s.xp[i], fm_per_chain[i], seeds, half, want_param_grads,
+                                               (sums_ptr + 8 * k0, s.fm_inv) if fused[i] and cnt else None)
+            done = torch.cuda.Event()
+            done.record()
+            return ChainBackward(dx, jobs, None, seeds, self._launched[i], done)
 
         # `da` / `one` live on the main stream's pool and are read by the chains: keep them referenced until the join
-        self._bwd = (self._launch_on_streams(run), want_param_grads, (da, one, fm_per_chain))
+        self._bwd = BackwardLaunch(self._launch_on_streams(run), want_param_grads, False, (da, one, fm_per_chain))
 
     @torch.no_grad()
     def backward_finish(self):
         """Returns (d fm / d bands, d fm / d audio, d adv / d bands, d adv / d audio).  With ``want_param_grads`` the
         weight gradients of real_loss + fake_loss are launched behind the input-gradient chains and left running
         (``collect_param_grads`` joins them)."""
-        res, want_param_grads, _keep = self._bwd
+        bw, self._bwd = self._bwd, None
         self._join_streams()
-        self._bwd = _keep = None
-        s = self._state
-        half = s["half"]
-        dev = s["emb"][0][0].device
+        res, want_param_grads = bw.chains, bw.want_param_grads
+        del bw   # with it the main-stream tensors the chains read
+        s, self._state = self._state, None
+        half = s.half
+        dev = s.emb[0][0].device
         main = torch.cuda.current_stream()
         for r in res:
             # allocated on a chain stream, read on the main stream from here on: without this the allocator may hand
             # the block to the chain's next allocation (the weight-gradient workspaces below) while it is still read
-            r[0].record_stream(main)
+            r.dx.record_stream(main)
         # input gradients: the PQMF-band chains share the `bands[:, -q:]` input, the MelGAN chain reads the waveform
-        bshape = s["bands_shape"]
-        gb = torch.zeros((2 * half,) + bshape[1:], dtype=torch.float32, device=dev)
-        acc = res[0][0]
+        gb = torch.zeros((2 * half,) + s.bands_shape[1:], dtype=torch.float32, device=dev)
+        acc = res[0].dx
         for r in res[1:-1]:
-            acc = acc + r[0]
+            acc = acc + r.dx
         gb[:, -self.q:, :] = acc
-        ga = res[-1][0]
+        ga = res[-1].dx
         self._pending = None
         if want_param_grads:
-            # phase B: weight gradients on the chains' streams, NOT joined here -- see collect_param_grads()
-            pend = [None] * len(self.chains)
+            # phase B: weight gradients on the chains' home streams, NOT joined here -- see collect_param_grads()
             n = len(self.chains)
+            pend = self._pending = PendingGrads([None] * n, [], [s])
             for i in [n - 1] + list(range(n - 1)):   # the longest chain first
-                with torch.cuda.stream(self._streams[i]):
-                    pend[i] = self.chains[i].weight_grads(res[i][1], half, self._sink)
+                with self._behind(res[i], self._streams[i]):
+                    pend.grads[i] = self.chains[i].weight_grads(res[i].jobs, half, self._sink)
                     if self._sink is not None:
-                        # data-parallel run: this chain's gradients are in the buckets once its stream gets here -- report them
-                        # now, from this stream, so that the buckets they complete (MelGAN's 75 MB first) are exchanged underneath
-                        # the other chains' weight gradients and the generator backward instead of in front of Adam
-                        self._sink.mark_ready([p for lay in self.chains[i].layers for p in lay.params() if p is not None and p.requires_grad])
-            self._pending = (pend, s)   # keeps the saved activations alive until the kernels have run
-        self._state = None
+                        self._report(pend, [self.chains[i]])
         return gb[:half], ga[:half], gb[half:], ga[half:]
 
     def collect_param_grads(self):
         """Joins the weight-gradient work launched by ``backward`` and returns the gradients of
         real_loss + fake_loss aligned with ``list(disc.parameters())`` (None if none were requested)."""
-        if getattr(self, "_pending", None) is None:
+        pend, self._pending = self._pending, None
+        if pend is None:
             return None
-        pend, *_keep = self._pending
+        self._join_streams()
         main = torch.cuda.current_stream()
-        for st in set(self._streams) | set(getattr(self, "_used_streams", None) or ()):
-            main.wait_stream(st)
-        sink = getattr(self, "_sink", None)
-        if sink is not None:   # already in the gradient buckets and reported chain by chain (backward_finish): nothing to inject
-            self._pending = self._sink = None
+        sink, self._sink = self._sink, None
+        if sink is not None:   # already in the gradient buckets: nothing to inject; what was not reported chain by chain is now
+            if pend.ready:
+                sink.mark_ready(pend.ready)
             return None
         by_param = {}
-        for ch, grads in zip(self.chains, pend):
+        for ch, grads in zip(self.chains, pend.grads):
             for lay, (dv, dg, dbias) in zip(ch.layers, grads):
                 v, gain, bias = lay.params()
                 by_param[id(v)], by_param[id(gain)] = dv, dg
@@ -630,5 +704,4 @@ class DiscriminatorEngine:
                 for t in (dv, dg, dbias):
                     if t is not None:
                         t.record_stream(main)
-        self._pending = None
         return [by_param.get(id(p)) for p in ops.parameters_of(self.disc)]

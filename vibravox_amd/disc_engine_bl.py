@@ -20,30 +20,30 @@ where two embeddings agree to 16 bits).
 from __future__ import annotations
 
 import ctypes
-import dataclasses
-from typing import Dict, List, Optional
+import os
+from typing import Dict, List, NamedTuple, Optional
 
 import torch
 
 from . import ops
 from ._lib import EbenBlHeadJob, check, load, ptr
 from ._lib import stream as _stream
-from .disc_engine import DiscriminatorEngine, _Layer
+from .disc_engine import BackwardLaunch, ChainBackward, DiscriminatorEngine, PendingGrads, _Layer, chain_convs
 
 BL = 0x100   # EBEN_LAYOUT_BL
 #: split forward (forward_reference): how much of MelGAN's reference half runs underneath the generator forward.  "0": none (MelGAN whole,
 #: behind the generator: rounds 4-5); "1": all of it ([MI355X, same box, 3 x alternated, 100 steps] 9.03 / 9.08 / 8.99 -> 8.96 / 9.03 /
 #: 8.94 ms per step, 8.90 / 8.92 / 8.88 together with EBEN_D_BWD_SPREAD=0 -- but layers 3-5 then run as two 32-row launches at 0.26 of
 #: the MFMA peak instead of one at 0.47); "thin" (default): its head and thin layers only
-SPLIT_MELGAN = __import__("os").environ.get("EBEN_SPLIT_MELGAN", "thin")
+SPLIT_MELGAN = os.environ.get("EBEN_SPLIT_MELGAN", "thin")
 #: "thin": MelGAN's head and layers 1 .. MELGAN_SPLIT_DEPTH - 1 (the HBM-bound ones) run per half like the PQMF-band chains; the MFMA-bound
 #: layers behind them keep ONE 2B-row launch (the persistent tile kernel fills the machine exactly once at 64 rows)
-MELGAN_SPLIT_DEPTH = int(__import__("os").environ.get("EBEN_SPLIT_MELGAN_DEPTH", "3"))
+MELGAN_SPLIT_DEPTH = int(os.environ.get("EBEN_SPLIT_MELGAN_DEPTH", "3"))
 #: the four stacked seed blocks of a chain's backward from one launch (eben_hinge_bwd_stacked); 0: a memset + three launches
-STACKED_SEEDS = __import__("os").environ.get("EBEN_STACKED_SEEDS", "1") != "0"
+STACKED_SEEDS = os.environ.get("EBEN_STACKED_SEEDS", "1") != "0"
 #: the feature-matching rows of the stacked input gradients read a one-byte code plane of each embedding (signs of a - r and of a, written by
 #: the feature-matching sums pass) instead of three more operand planes; 0: the four-operand form (bit-identical results either way)
-FM_CODES = __import__("os").environ.get("EBEN_FM_CODES", "1") != "0"
+FM_CODES = os.environ.get("EBEN_FM_CODES", "1") != "0"
 
 
 def _fm_sums(lib, acts, half: int, sums_out: torch.Tensor) -> None:
@@ -117,17 +117,7 @@ class _ChainBL:
 
     def __init__(self, modules, math):
         self.layers: List[_Layer] = []
-        self.pad = 0
-        convs = []
-        for m in modules:
-            if isinstance(m, torch.nn.Sequential):
-                for sub in m:
-                    if hasattr(sub, "padding") and not hasattr(sub, "spec"):
-                        self.pad = int(sub.padding)
-                    else:
-                        convs.append(sub)
-            else:
-                convs.append(m)
+        self.pad, convs = chain_convs(modules)
         n = len(convs)
         for i, conv in enumerate(convs):
             mth = math(i, n) if callable(math) else math
@@ -374,15 +364,42 @@ class _ChainBL:
         return outs[0], outs[1]
 
 
+class StaticBL(NamedTuple):
+    """Persistent buffers of one (batch, lengths) shape: what the replayed launch sequences read and write at fixed addresses."""
+
+    sub: torch.Tensor              # the PQMF-band chains' input, rows [enhanced | reference]
+    wav: torch.Tensor              # MelGAN's
+    inputs: List[torch.Tensor]     # per chain: one of the two
+    act0: List[Planes]             # per chain the head's output, 2B rows
+    planes: List[List[Planes]]     # per chain the embeddings behind it: two launch sequences write their halves (row views)
+    logits: List[torch.Tensor]
+    one: torch.Tensor
+    fm_sums: torch.Tensor          # (s1, s2) per embedding pair, filled chain by chain at the end of each forward body
+
+
+class ForwardStateBL(NamedTuple):
+    """What the forward passes of a step leave for ``losses`` and the backward (bundle layout)."""
+
+    half: int
+    acts: List[List[Planes]]       # per chain [head output, embeddings behind it]
+    logits: List[torch.Tensor]
+    inputs: List[torch.Tensor]
+    bands_shape: tuple
+    static: StaticBL
+
+
 class DiscriminatorEngineBL(DiscriminatorEngine):
     """``DiscriminatorEngine`` over bundle-layout tensors (selected by ``math = {..., "layout": "bl"}``)."""
+
+    chain_type = _ChainBL
+    split_forward_pays = True   # [MI355X, same box, interleaved] 10.25 -> 10.05 ms per step
 
     @staticmethod
     def unsupported(disc) -> Optional[str]:
         """Why this discriminator cannot run in the bundle layout (None: it can): the chain heads / logits layers have dedicated kernels
         built for EBEN's configured shapes (4 -> 24 k 3 and 1 -> 16 k 15 heads, C -> 1 k <= 8 logits layers)."""
         for m in list(disc.pqmf_discriminators) + [disc.melgan_discriminator]:
-            convs = [sub for part in m.discriminator for sub in (part if isinstance(part, torch.nn.Sequential) else [part]) if hasattr(sub, "spec")]
+            _, convs = chain_convs(m.discriminator)
             if len(convs) < 3:
                 return "a sub-discriminator with fewer than three conv layers"
             head, tail = convs[0].spec, convs[-1].spec
@@ -395,23 +412,18 @@ class DiscriminatorEngineBL(DiscriminatorEngine):
         return None
 
     def __init__(self, disc, math):
-        self.disc = disc
-        self.q = disc.q
-        self.math = math
-        self.chains = [_ChainBL(d.discriminator, math["pqmf"]) for d in disc.pqmf_discriminators] + [
-            _ChainBL(disc.melgan_discriminator.discriminator, math["melgan"])]
-        self._streams = None
-        self._state = None
-        self._prepack_graph = ops.ReplayedPrepack()
-        self.seed_weights = (1.0, 1.0, 1.0)
+        super().__init__(disc, math)
         n = len(self.chains)
-        # graph replay of each chain's three launch sequences (ops.ReplayedChain) and the buffers they start from, per input shape
-        self._graphs = {k: [ops.ReplayedChain() for _ in range(n)] for k in ("fwd", "bwd", "dw")}
-        self._static: Dict[tuple, dict] = {}
+        # graph replay of each chain's launch sequences (ops.ReplayedChain: one that is never run is never captured) and the buffers
+        # they start from, per input shape
+        self._graphs = {k: [ops.ReplayedChain() for _ in range(n)] for k in ("fwd", "fwd_ref", "fwd_enh", "bwd", "bwd_d", "dw")}
+        self._graphs["dw_group"] = [ops.ReplayedChain()]
+        self._static: Dict[tuple, StaticBL] = {}
+        # where each chain's embedding pairs start among all of them, and the feature-matching loss's 1 / (chains * pairs per chain)
+        self._fm_first = [sum(len(c.layers) - 1 for c in self.chains[:i]) for i in range(n)]
+        self._fm_inv = 1.0 / (n * (len(self.chains[-1].layers) - 1))
 
-    def _static_for(self, half: int, bands, audio) -> dict:
-        """Persistent buffers of one (batch, lengths) shape: the chain inputs [enhanced | reference], the heads' outputs, the
-        feature-matching sums -- what the replayed launch sequences read at fixed addresses."""
+    def _static_for(self, half: int, bands, audio) -> StaticBL:
         key = (half, tuple(bands.shape[1:]), tuple(audio.shape[1:]), str(audio.device))
         st = self._static.get(key)
         if st is None:
@@ -422,10 +434,14 @@ class DiscriminatorEngineBL(DiscriminatorEngine):
             sub = torch.empty((rows, self.q) + tuple(bands.shape[2:]), dtype=torch.float32, device=dev)
             wav = torch.empty((rows,) + tuple(audio.shape[1:]), dtype=torch.float32, device=dev)
             inputs = [sub] * (len(self.chains) - 1) + [wav]
-            act0 = [Planes(rows, ch.layers[0].spec.c_out, ch.head_out_len(inputs[i].shape[2]), dev) for i, ch in enumerate(self.chains)]
-            npairs = sum(len(ch.layers) - 1 for ch in self.chains)
-            st = self._static[key] = dict(sub=sub, wav=wav, inputs=inputs, act0=act0, one=torch.ones(1, dtype=torch.float32, device=dev),
-                                          fm_sums=torch.empty(2 * npairs, dtype=torch.float32, device=dev))
+            act0, planes, logits = [], [], []
+            for ch, x in zip(self.chains, inputs):
+                act0.append(Planes(rows, ch.layers[0].spec.c_out, ch.head_out_len(x.shape[2]), dev))
+                shapes, l_logits = ch.out_shapes(act0[-1].length)
+                planes.append([Planes(rows, c, l, dev) for c, l in shapes])
+                logits.append(torch.empty((rows, 1, l_logits), dtype=torch.float32, device=dev))
+            st = self._static[key] = StaticBL(sub, wav, inputs, act0, planes, logits, torch.ones(1, dtype=torch.float32, device=dev),
+                                              torch.empty(2 * sum(len(ch.layers) - 1 for ch in self.chains), dtype=torch.float32, device=dev))
         return st
 
     @staticmethod
@@ -452,29 +468,14 @@ class DiscriminatorEngineBL(DiscriminatorEngine):
         return tuple(out)
 
     # ---- forward ---------------------------------------------------------------------------------------------------------------
-    def _split_planes(self, st: dict, half: int):
-        """Planes of every embedding / the logits of the full 2B-row batch, allocated once per shape: with the forward split into its
-        reference and enhanced halves two launch sequences write into them (row views)."""
-        if "planes" not in st:
-            dev = st["wav"].device
-            planes, logits = [], []
-            for i, ch in enumerate(self.chains):
-                shapes, l_logits = ch.out_shapes(st["act0"][i].length)
-                planes.append([Planes(2 * half, c, l, dev) for c, l in shapes])
-                logits.append(torch.empty((2 * half, 1, l_logits), dtype=torch.float32, device=dev))
-            st["planes"], st["logits"] = planes, logits
-        return st["planes"], st["logits"]
-
-    def _forward_rows(self, st: dict, half: int, r0: int, r1: int, fm: bool, key: str):
-        """Heads + chain bodies of batch rows [r0, r1) on the chains' streams (not joined).  fm: the feature-matching sums of each chain's
-        embedding pairs behind its layers (the second of the two halves)."""
+    def _forward_rows(self, st: StaticBL, half: int, r0: int, r1: int, fm: bool, key: str) -> None:
+        """Heads + chain bodies of batch rows [r0, r1) on the chains' streams (not joined), into the static planes.  fm: the
+        feature-matching sums of each chain's embedding pairs behind its layers (all 2B rows are there: the second of the two halves, or
+        the whole batch)."""
         lib = load()
-        sub, wav, act0 = st["sub"], st["wav"], st["act0"]
-        planes, logits = self._split_planes(st, half)
+        sub, wav, act0, planes, logits, fm_sums = st.sub, st.wav, st.act0, st.planes, st.logits, st.fm_sums
         n = len(self.chains)
         nrows = r1 - r0
-        fm_first = [sum(len(c.layers) - 1 for c in self.chains[:i]) for i in range(n)]
-        fm_sums = st["fm_sums"]
         head_done = [None]
 
         # MelGAN (the last chain) keeps ONE 2B-row launch per layer, behind the generator: its heavy layers fill the machine exactly once at
@@ -491,6 +492,9 @@ class DiscriminatorEngineBL(DiscriminatorEngine):
             return r0, r1
 
         def body(i):
+            # the chain's layers, then the feature-matching sums of ITS embedding pairs on its own stream: the HBM-bound pass over the
+            # embeddings (1.6 GB at 64 rows) runs beside the other chains' MFMA-bound layers instead of alone behind the join
+            # ([MI355X] one launch over all 35 pairs after the join: 0.27 ms of the step's critical path)
             q0, q1 = rng(i)
             a0 = act0[i].rows_slice(q0, q1)
             if i == n - 1 and depth is not None:
@@ -500,13 +504,15 @@ class DiscriminatorEngineBL(DiscriminatorEngine):
             else:
                 self.chains[i].forward_body(a0, [p.rows_slice(q0, q1) for p in planes[i]], logits[i][q0:q1])
             if fm:
-                _fm_sums(lib, [act0[i]] + planes[i], half, fm_sums[2 * fm_first[i]:])
+                _fm_sums(lib, [act0[i]] + planes[i], half, fm_sums[2 * self._fm_first[i]:])
             return True
 
         def run(i):
+            # heads (eager, so that the chains that share one can be released by an event): the PQMF-band chains' in one launch on the
+            # stream of the first of them, MelGAN's on its own stream; then the chain's body, replayed as a graph once it has settled
             ch = self.chains[i]
             if rng(i) is None:   # MelGAN in the reference pass: nothing yet
-                return [act0[i]] + planes[i], logits[i]
+                return
             if i == n - 1:
                 q0, q1 = rng(i)
                 jobs = (EbenBlHeadJob * 1)(ch.head_job(wav[q0:q1], wav.shape[2], act0[i].rows_slice(q0, q1)))
@@ -517,26 +523,20 @@ class DiscriminatorEngineBL(DiscriminatorEngine):
                 head_done[0] = torch.cuda.Event()
                 head_done[0].record()
             else:
-                torch.cuda.current_stream().wait_event(head_done[0])
+                torch.cuda.current_stream().wait_event(head_done[0])   # chains 1, 2 may run on another stream than chain 0
             sig = (rng(i), fm, act0[i].hi.data_ptr(), act0[i].lo.data_ptr(), act0[i].length, fm_sums.data_ptr(), planes[i][0].hi.data_ptr(),
                    self._chain_sig(ch, 0))
             self._graphs[key][i].run(sig, lambda: body(i), torch.cuda.current_stream())
             self._mark_used(ch, 0)
-            return [act0[i]] + planes[i], logits[i]
 
-        return self._launch_on_streams(run, forward=True, order=[n - 1] + list(range(n - 1)))
+        self._launch_on_streams(run, forward=True, order=[n - 1] + list(range(n - 1)))
 
     def _join_pending(self):
         """Weight-gradient work of an earlier step that nobody collected (an exception between ``backward_finish`` and
         ``collect_param_grads``, a skipped batch): its kernels still read the static planes -- the current stream waits for the chains'
         streams and the work is dropped, instead of failing every later step."""
-        if getattr(self, "_pending", None) is not None:
-            main = torch.cuda.current_stream()
-            for st in set(self._streams or ()):
-                main.wait_stream(st)
-            if getattr(self, "_used_streams", None):
-                for st in self._used_streams:
-                    main.wait_stream(st)
+        if self._pending is not None:
+            self._join_streams()
             self._pending = None
 
     @torch.no_grad()
@@ -549,75 +549,29 @@ class DiscriminatorEngineBL(DiscriminatorEngine):
         # the planes are static per shape: every consumer of the previous step's embeddings (stacked input gradients, weight gradients)
         # must have been joined before they are rewritten
         self._join_pending()
-        st["sub"][half:].copy_(bands_ref[:, -self.q:, :])
-        st["wav"][half:].copy_(audio_ref)
-        if "fwd_ref" not in self._graphs:
-            n = len(self.chains)
-            self._graphs["fwd_ref"] = [ops.ReplayedChain() for _ in range(n)]
-            self._graphs["fwd_enh"] = [ops.ReplayedChain() for _ in range(n)]
+        st.sub[half:].copy_(bands_ref[:, -self.q:, :])
+        st.wav[half:].copy_(audio_ref)
         self._forward_rows(st, half, half, 2 * half, False, "fwd_ref")
-        self._ref_done = (half, st)
+        self._partial = (half, st)
 
     @torch.no_grad()
     def forward(self, bands, audio, bands_ref, audio_ref, join: bool = True):
-        lib = load()
+        """The enhanced rows and the feature-matching sums behind them when the reference rows are on their way (``forward_reference``
+        at this shape), all 2B rows otherwise -- the same launch sequences over other rows, into the same static planes."""
         half = bands.shape[0]
         st = self._static_for(half, bands, audio)
-        sub, wav, inputs, act0 = st["sub"], st["wav"], st["inputs"], st["act0"]
-        pre = getattr(self, "_ref_done", None)
-        self._ref_done = None
+        pre, self._partial = self._partial, None
         if pre is None:
             self._join_pending()
-        if pre is not None and pre[0] == half and pre[1] is st:
-            # the reference rows are on their way (forward_reference): the enhanced rows + the feature-matching sums behind them
-            sub[:half].copy_(bands[:, -self.q:, :])
-            wav[:half].copy_(audio)
-            res = self._forward_rows(st, half, 0, half, True, "fwd_enh")
-            if join:
-                self._join_streams()
-            self._state = dict(half=half, acts=[r[0] for r in res], logits=[r[1] for r in res], inputs=inputs, bands_shape=tuple(bands.shape), static=st)
-            return self._state
-        sub[:half].copy_(bands[:, -self.q:, :])
-        sub[half:].copy_(bands_ref[:, -self.q:, :])
-        wav[:half].copy_(audio)
-        wav[half:].copy_(audio_ref)
-        n = len(self.chains)
-        rows = 2 * half
-        self._head_done = None
-        fm_first = [sum(len(c.layers) - 1 for c in self.chains[:i]) for i in range(n)]
-        fm_sums = st["fm_sums"]
-
-        def body(i):
-            # the chain's layers, then the feature-matching sums of ITS embedding pairs on its own stream: the HBM-bound pass over the
-            # embeddings (1.6 GB at 64 rows) runs beside the other chains' MFMA-bound layers instead of alone behind the join
-            # ([MI355X] one launch over all 35 pairs after the join: 0.27 ms of the step's critical path)
-            acts, logits = self.chains[i].forward_body(act0[i])
-            _fm_sums(lib, acts, half, fm_sums[2 * fm_first[i]:])
-            return acts, logits
-
-        def run(i):
-            # heads (eager, so that the chains that share one can be released by an event): the PQMF-band chains' in one launch on the
-            # stream of the first of them, MelGAN's on its own stream; then the chain's body, replayed as a graph once it has settled
-            ch = self.chains[i]
-            if i == n - 1:
-                jobs = (EbenBlHeadJob * 1)(ch.head_job(wav, wav.shape[2], act0[i]))
-                check(lib.eben_bl_head_fwd(jobs, 1, rows, _stream()), "bl_head_fwd")
-            elif i == 0:
-                jobs = (EbenBlHeadJob * (n - 1))(*[self.chains[k].head_job(sub, sub.shape[2], act0[k]) for k in range(n - 1)])
-                check(lib.eben_bl_head_fwd(jobs, n - 1, rows, _stream()), "bl_head_fwd")
-                self._head_done = torch.cuda.Event()
-                self._head_done.record()
-            else:
-                torch.cuda.current_stream().wait_event(self._head_done)   # chains 1, 2 may run on another stream than chain 0
-            sig = (rows, act0[i].hi.data_ptr(), act0[i].lo.data_ptr(), act0[i].length, fm_sums.data_ptr(), self._chain_sig(ch, 0))
-            out = self._graphs["fwd"][i].run(sig, lambda: body(i), torch.cuda.current_stream())
-            self._mark_used(ch, 0)
-            return out
-
-        res = self._launch_on_streams(run, forward=True, order=[n - 1] + list(range(n - 1)))
+        enhanced_only = pre is not None and pre[0] == half and pre[1] is st
+        for dst, new, ref in ((st.sub, bands[:, -self.q:, :], bands_ref[:, -self.q:, :]), (st.wav, audio, audio_ref)):
+            dst[:half].copy_(new)
+            if not enhanced_only:
+                dst[half:].copy_(ref)
+        self._forward_rows(st, half, 0, half if enhanced_only else 2 * half, True, "fwd_enh" if enhanced_only else "fwd")
         if join:
             self._join_streams()
-        self._state = dict(half=half, acts=[r[0] for r in res], logits=[r[1] for r in res], inputs=inputs, bands_shape=tuple(bands.shape), static=st)
+        self._state = ForwardStateBL(half, [[a] + p for a, p in zip(st.act0, st.planes)], st.logits, st.inputs, tuple(bands.shape), st)
         return self._state
 
     # ---- losses ----------------------------------------------------------------------------------------------------------------
@@ -625,20 +579,17 @@ class DiscriminatorEngineBL(DiscriminatorEngine):
     def losses(self) -> Dict[str, torch.Tensor]:
         lib = load()
         s = self._state
-        half = s["half"]
-        dev = s["logits"][0].device
-        n = sum(len(acts) for acts in s["acts"])                  # embedding pairs: every embedding but the inputs and the logits
-        sums = s["static"]["fm_sums"]   # fixed address, filled chain by chain at the end of each forward body
+        half = s.half
+        dev = s.logits[0].device
+        n = sum(len(acts) for acts in s.acts)                  # embedding pairs: every embedding but the inputs and the logits
         nch = len(self.chains)
-        inv = 1.0 / (nch * len(s["acts"][-1]))
-        s.update(fm_sums=sums, fm_inv=inv, fm_first=[sum(len(a) for a in s["acts"][:i]) for i in range(nch)])
         hinge = torch.empty(3 * nch, dtype=torch.float32, device=dev)
-        terms = [(rows, target) for lg in s["logits"] for rows, target in ((lg[:half], 1.0), (lg[:half], -1.0), (lg[half:], 1.0))]
+        terms = [(rows, target) for lg in s.logits for rows, target in ((lg[:half], 1.0), (lg[:half], -1.0), (lg[half:], 1.0))]
         nt = len(terms)
         check(lib.eben_hinge_fwd_multi((ctypes.c_void_p * nt)(*[ptr(r) for r, _ in terms]), (ctypes.c_int64 * nt)(*[r.numel() for r, _ in terms]),
                                        (ctypes.c_float * nt)(*[t for _, t in terms]), nt, ptr(hinge), _stream()), "hinge_fwd_multi")
         vals = torch.empty(4, dtype=torch.float32, device=dev)
-        check(lib.eben_disc_losses(ptr(sums), n, inv, ptr(hinge), nch, ptr(vals), _stream()), "disc_losses")
+        check(lib.eben_disc_losses(ptr(s.static.fm_sums), n, self._fm_inv, ptr(hinge), nch, ptr(vals), _stream()), "disc_losses")
         return {"feature_matching_loss": vals[0], "adv_loss_gen": vals[1], "fake_loss": vals[2], "real_loss": vals[3]}
 
     # ---- backward --------------------------------------------------------------------------------------------------------------
@@ -647,17 +598,27 @@ class DiscriminatorEngineBL(DiscriminatorEngine):
     #: them on the same chain streams, joined only in front of the discriminator's Adam.  Same launches, same values (every row of a
     #: stacked pass is independent of the others); the second half of the input-gradient work (config 2: ~1.2 of 2.4 ms) moves underneath
     #: the generator backward.  EBEN_SPLIT_BWD=0: one 4B-row pass (rounds 2-5).
-    split_backward: bool = __import__("os").environ.get("EBEN_SPLIT_BWD", "1") != "0"
+    split_backward: bool = os.environ.get("EBEN_SPLIT_BWD", "1") != "0"
     #: with the two-pass backward the three PQMF-band chains stay in series on ONE stream (the fp32-at-rest engines move the last of them
     #: to the side stream): [MI355X, same box, 3 x alternated] 9.03 / 9.08 / 8.99 -> 8.97 / 8.98 / 8.93 ms per step
-    spread_backward = __import__("os").environ.get("EBEN_D_BWD_SPREAD", "0") != "0"
+    spread_backward = os.environ.get("EBEN_D_BWD_SPREAD", "0") != "0"
+    #: data-parallel runs: report the discriminator's gradients to the bucket exchange when the main stream joins the weight gradients
+    #: (``collect_param_grads``) instead of from each chain's stream right behind its launches.  Reported early, a bucket's collective sits
+    #: on the communication stream WAITING for the chain's events for ~3 ms (second backward pass + weight gradients), and a waiting stream
+    #: stalls whatever shares its hardware queue: [MI355X, single-rank RCCL, 7 queues] the main stream did not start the generator's seeds
+    #: until the discriminator's last weight gradient had run -- 10.07 ms per step against 9.18 deferred (9.06 with the generator's deferred
+    #: too, 8.7 without the exchange).  The price at N > 1 is the discriminator's exchange (92.6 MB) exposed in front of its Adam instead
+    #: of under the tail of its weight gradients.  EBEN_D_DEFER_READY=0: the early form.
+    defer_mark_ready: bool = os.environ.get("EBEN_D_DEFER_READY", "1") != "0"
+    #: weight gradients of the three PQMF-band chains as one launch sequence (``_ChainBL.weight_grads_group``); 0: chain by chain
+    group_weight_grads: bool = os.environ.get("EBEN_DW_GROUP", "0") != "0"
 
     def _seeds(self, lib, s, i, dev):
         """rows [fm | adv | fake | real] of chain i: zeros and the three hinge derivatives (targets +1, -1 on the enhanced rows, +1 on the
         reference rows)"""
-        half = s["half"]
-        lg = s["logits"][i]
-        one = s["static"]["one"]
+        half = s.half
+        lg = s.logits[i]
+        one = s.static.one
         inv_scales = 1.0 / len(self.chains)
         per = lg[:half].numel()
         if STACKED_SEEDS:
@@ -672,189 +633,125 @@ class DiscriminatorEngineBL(DiscriminatorEngine):
                                          _stream()), "hinge_bwd")
         return seeds
 
-    def _launch_weight_grads(self, s, i, jobs, g0, half):
-        """Chain i's weight gradients on the current (the chain's) stream; returns what ``collect_param_grads`` reads."""
+    def _launch_weight_grads(self, s: ForwardStateBL, group: List[int], res: List[ChainBackward], pend: PendingGrads) -> None:
+        """The weight gradients of the chains ``group`` -- one chain, or the PQMF-band chains (one stream, one structure: their mid
+        layers layer index by layer index) -- from their records in ``res`` on the current stream as ONE replayed sequence, into
+        ``pend.grads``."""
         # with a data-parallel sink the launches write straight into its gradient buckets: static addresses, part of the signature
-        sink = self._sink
-        sink_sig = None if sink is None else tuple(0 if (b := sink.grad_buffer(p)) is None else b.data_ptr()
-                                                   for lay in self.chains[i].layers for p in lay.params() if p is not None)
-        jobs_sig = tuple((k, (g.hi.data_ptr() if isinstance(g, Planes) else g.data_ptr()), x.hi.data_ptr(), x.lo.data_ptr()) for k, g, x in jobs)
-        sig = (half, s["inputs"][i].data_ptr(), g0.hi.data_ptr(), jobs_sig, self._chain_sig(self.chains[i], -1), sink_sig)
-        dw_body = lambda: self.chains[i].weight_grads(jobs, s["inputs"][i], g0, half, sink)
-        # A replay rewrites the gradients of the previous replay in place, and without a sink those tensors BECOME ``.grad``
-        # (inject_grads): while a parameter still holds a gradient (accumulation over steps, zero_grad(set_to_none=False), a
-        # caller that does not zero) the launches run eagerly into fresh tensors, as gen_engine._deferrable has it.
-        held = sink is None and any(p.grad is not None for lay in self.chains[i].layers for p in lay.params() if p is not None)
-        out = dw_body() if held else self._graphs["dw"][i].run(sig, dw_body, torch.cuda.current_stream())
-        if sink is not None:
-            ready = [p for lay in self.chains[i].layers for p in lay.params() if p is not None and p.requires_grad]
-            if self.defer_mark_ready:
-                self._deferred_ready = (getattr(self, "_deferred_ready", None) or []) + ready
-            else:
-                sink.mark_ready(ready)
-        return out
-
-    #: data-parallel runs: report the discriminator's gradients to the bucket exchange when the main stream joins the weight gradients
-    #: (``collect_param_grads``) instead of from each chain's stream right behind its launches.  Reported early, a bucket's collective sits
-    #: on the communication stream WAITING for the chain's events for ~3 ms (second backward pass + weight gradients), and a waiting stream
-    #: stalls whatever shares its hardware queue: [MI355X, single-rank RCCL, 7 queues] the main stream did not start the generator's seeds
-    #: until the discriminator's last weight gradient had run -- 10.07 ms per step against 9.18 deferred (9.06 with the generator's deferred
-    #: too, 8.7 without the exchange).  The price at N > 1 is the discriminator's exchange (92.6 MB) exposed in front of its Adam instead
-    #: of under the tail of its weight gradients.  EBEN_D_DEFER_READY=0: the early form.
-    defer_mark_ready: bool = __import__("os").environ.get("EBEN_D_DEFER_READY", "1") != "0"
-
-    def collect_param_grads(self):
-        sink = getattr(self, "_sink", None)
-        ready, self._deferred_ready = getattr(self, "_deferred_ready", None), None
-        if ready and sink is not None and getattr(self, "_pending", None) is not None:
-            main = torch.cuda.current_stream()
-            for st in set(self._streams) | set(getattr(self, "_used_streams", None) or ()):
-                main.wait_stream(st)
-            sink.mark_ready(ready)
-        return super().collect_param_grads()
-
-    #: weight gradients of the three PQMF-band chains as one launch sequence (``_ChainBL.weight_grads_group``); 0: chain by chain
-    group_weight_grads: bool = __import__("os").environ.get("EBEN_DW_GROUP", "0") != "0"
-
-    def _launch_weight_grads_group(self, s, group, keep, half):
-        """``_launch_weight_grads`` for the chains ``group`` (one stream, one structure) as ONE replayed sequence."""
-        sink = self._sink
+        sink, half = self._sink, s.half
         chains = [self.chains[i] for i in group]
         params = [p for ch in chains for lay in ch.layers for p in lay.params() if p is not None]
         sink_sig = None if sink is None else tuple(0 if (b := sink.grad_buffer(p)) is None else b.data_ptr() for p in params)
-        jobs_sig = tuple(tuple((k, (g.hi.data_ptr() if isinstance(g, Planes) else g.data_ptr()), x.hi.data_ptr(), x.lo.data_ptr()) for k, g, x in keep[i][1])
+        jobs_sig = tuple(tuple((k, (g.hi.data_ptr() if isinstance(g, Planes) else g.data_ptr()), x.hi.data_ptr(), x.lo.data_ptr()) for k, g, x in res[i].jobs)
                          for i in group)
-        sig = (half, tuple(s["inputs"][i].data_ptr() for i in group), tuple(keep[i][2].hi.data_ptr() for i in group), jobs_sig,
+        sig = (half, tuple(s.inputs[i].data_ptr() for i in group), tuple(res[i].g0.hi.data_ptr() for i in group), jobs_sig,
                tuple(self._chain_sig(ch, -1) for ch in chains), sink_sig)
-        body = lambda: _ChainBL.weight_grads_group(chains, [keep[i][1] for i in group], [s["inputs"][i] for i in group], [keep[i][2] for i in group],
-                                                   half, sink)
+        body = lambda: _ChainBL._weight_grads(chains, [res[i].jobs for i in group], [s.inputs[i] for i in group], [res[i].g0 for i in group],
+                                              half, sink, grouped=len(group) > 1)
+        # A replay rewrites the gradients of the previous replay in place, and without a sink those tensors BECOME ``.grad``
+        # (inject_grads): while a parameter still holds a gradient (accumulation over steps, zero_grad(set_to_none=False), a
+        # caller that does not zero) the launches run eagerly into fresh tensors, as gen_engine._deferrable has it.
         held = sink is None and any(p.grad is not None for p in params)
-        if "dw_group" not in self._graphs:
-            self._graphs["dw_group"] = [ops.ReplayedChain()]
-        out = body() if held else self._graphs["dw_group"][0].run(sig, body, torch.cuda.current_stream())
+        graph = self._graphs["dw"][group[0]] if len(group) == 1 else self._graphs["dw_group"][0]
+        for i, grads in zip(group, body() if held else graph.run(sig, body, torch.cuda.current_stream())):
+            pend.grads[i] = grads
         if sink is not None:
-            sink.mark_ready([p for p in params if p.requires_grad])
-        return out
+            self._report(pend, chains)
 
     @torch.no_grad()
     def backward_launch(self, want_param_grads: bool = True, sink=None):
         self._sink = sink
         lib = load()
         s = self._state
-        half = s["half"]
-        dev = s["logits"][0].device
-        one = s["static"]["one"]
-        sums_ptr = ptr(s["fm_sums"])
+        half = s.half
+        dev = s.logits[0].device
+        sums_ptr = ptr(s.static.fm_sums)
         split = self.split_backward
         n = len(self.chains)
-
         chain_sigs = {}   # both passes of a chain see the same weights and images: one walk of its layers per step
 
         def sig_of(i, tag):
             if i not in chain_sigs:
                 chain_sigs[i] = self._chain_sig(self.chains[i], 1)
-            return (half, tag, tuple(self.seed_weights), s["fm_inv"], sums_ptr, s["logits"][i].data_ptr(),
-                    tuple((a.hi.data_ptr(), a.lo.data_ptr(), a.length, None if a.codes is None else a.codes.data_ptr()) for a in s["acts"][i]),
+            return (half, tag, tuple(self.seed_weights), self._fm_inv, sums_ptr, s.logits[i].data_ptr(),
+                    tuple((a.hi.data_ptr(), a.lo.data_ptr(), a.length, None if a.codes is None else a.codes.data_ptr()) for a in s.acts[i]),
                     chain_sigs[i])
 
-        def body(i):
+        def body(i, seeds, part):
+            return self.chains[i].backward_body(s.acts[i], seeds, half, want_param_grads, sums_ptr + 8 * self._fm_first[i], self._fm_inv, part)
+
+        def first_pass(i):
             seeds = self._seeds(lib, s, i, dev)
             if split:
-                g, _, _ = self.chains[i].backward_body(s["acts"][i], seeds[:2 * half], half, False, sums_ptr + 8 * s["fm_first"][i], s["fm_inv"], "gen")
-                return g, [], None, seeds
-            return self.chains[i].backward_body(s["acts"][i], seeds, half, want_param_grads, sums_ptr + 8 * s["fm_first"][i], s["fm_inv"]) + (seeds,)
+                return body(i, seeds[:2 * half], "gen")[0], [], None, seeds
+            return body(i, seeds, "all") + (seeds,)
 
         def run(i):
-            out = self._graphs["bwd"][i].run(sig_of(i, (want_param_grads, split)), lambda: body(i), torch.cuda.current_stream())
+            out = self._graphs["bwd"][i].run(sig_of(i, (want_param_grads, split)), lambda: first_pass(i), torch.cuda.current_stream())
             self._mark_used(self.chains[i], 1)
-            if split:
-                ev = torch.cuda.Event()
-                ev.record()
-                return out + (ev,)
-            return out
+            done = torch.cuda.Event()
+            done.record()
+            return ChainBackward(*out, self._launched[i], done)
 
         res = self._launch_on_streams(run)
+        self._bwd = BackwardLaunch(res, want_param_grads, split, ())
         self._pending = None
         if split and want_param_grads:
-            # second pass, not waited for by the main stream: rows [fake | real] down every chain, then the chain's weight gradients
-            if "bwd_d" not in self._graphs:
-                self._graphs["bwd_d"] = [ops.ReplayedChain() for _ in range(n)]
-            pend = [None] * n
-            keep = [None] * n
-
-            def body_d(i):
-                seeds = res[i][3]
-                g, jobs, g0 = self.chains[i].backward_body(s["acts"][i], seeds[2 * half:], half, True, sums_ptr + 8 * s["fm_first"][i], s["fm_inv"], "disc")
-                return g, jobs, g0
-
-            group = list(range(n - 1)) if (self.group_weight_grads and n >= 3 and len({self._second_pass_stream(i, res[i][4]) for i in range(n - 1)}) == 1) else []
+            # second pass, not waited for by the main stream: rows [fake | real] down every chain on the stream of its first pass ([MI355X]
+            # streams of their own, at either HIP priority, cost more than any ordering gave: 9.18 -> 9.44 ms per step at the default
+            # priority, 16.8 at the high one -- more streams than hardware queues), then the chain's weight gradients
+            second = list(res)
+            pend = self._pending = PendingGrads([None] * n, [], [s, res, second])
+            # the PQMF-band chains share a structure: where they also share a stream, their weight gradients as one sequence
+            group = list(range(n - 1)) if (self.group_weight_grads and n >= 3 and len({r.stream for r in res[:-1]}) == 1) else []
             for i in [n - 1] + list(range(n - 1)):
-                with torch.cuda.stream(self._second_pass_stream(i, res[i][4])):
-                    sig = sig_of(i, "disc") + (res[i][3].data_ptr(),)
-                    out = self._graphs["bwd_d"][i].run(sig, lambda i=i: body_d(i), torch.cuda.current_stream())
-                    keep[i] = out
+                with torch.cuda.stream(res[i].stream):
+                    sig = sig_of(i, "disc") + (res[i].seeds.data_ptr(),)
+                    out = self._graphs["bwd_d"][i].run(sig, lambda i=i: body(i, res[i].seeds[2 * half:], "disc"), torch.cuda.current_stream())
+                    second[i] = res[i]._replace(dx=out[0], jobs=out[1], g0=out[2])
                     if i not in group:
-                        pend[i] = self._launch_weight_grads(s, i, out[1], out[2], half)
+                        self._launch_weight_grads(s, [i], second, pend)
             if group:
-                # the PQMF-band chains share a stream and a structure: their weight gradients layer index by layer index
-                with torch.cuda.stream(self._second_pass_stream(group[0], res[group[0]][4])):
-                    for i, grads in zip(group, self._launch_weight_grads_group(s, group, keep, half)):
-                        pend[i] = grads
-            self._pending = (pend, s, res, keep)   # keeps the saved activations and the stacked gradients alive until the kernels have run
-        self._bwd = (res, want_param_grads, (one,))
-
-    def _second_pass_stream(self, i, after: "torch.cuda.Event"):
-        """The stream chain i's second pass runs on: the chain's own ([MI355X] streams of their own, at either HIP priority, cost more than
-        any ordering gave: 9.18 -> 9.44 ms per step at the default priority, 16.8 at the high one -- more streams than hardware queues)."""
-        return self._chain_stream(i)
-
-    def _chain_stream(self, i):
-        """The stream chain i's backward was launched on by the last ``_launch_on_streams`` (spread_backward may move one chain)."""
-        streams = list(self._streams)
-        if self.spread_backward and len(self.chains) >= 3:
-            streams[len(self.chains) - 2] = ops.aux_stream(2, streams[0].device)
-        return streams[i]
+                with torch.cuda.stream(res[group[0]].stream):
+                    self._launch_weight_grads(s, group, second, pend)
 
     @torch.no_grad()
     def backward_finish(self):
         lib = load()
-        res, want_param_grads, _keep = self._bwd
-        split = len(res[0]) == 5
+        bw, self._bwd = self._bwd, None
+        res = bw.chains
         main = torch.cuda.current_stream()
-        if split:
+        if bw.split:
             for r in res:
-                main.wait_event(r[4])   # rows [fm | adv] of every chain; what follows on the chains' streams is joined by collect_param_grads
+                main.wait_event(r.done)   # rows [fm | adv] of every chain; what follows on the chains' streams is joined by collect_param_grads
         else:
             self._join_streams()
-        self._bwd = _keep = None
-        s = self._state
-        half = s["half"]
-        dev = s["logits"][0].device
+        s, self._state = self._state, None
+        half = s.half
+        dev = s.logits[0].device
         n = len(self.chains)
         for r in res:
-            r[0].hi.record_stream(main)
-            if r[0].lo is not None:
-                r[0].lo.record_stream(main)
+            r.dx.hi.record_stream(main)
+            if r.dx.lo is not None:
+                r.dx.lo.record_stream(main)
         # input gradients of the heads, rows [fm | adv]: the PQMF-band chains share the bands (one launch sums them), MelGAN reads the waveform
         rows = 2 * half
-        sub, wav = s["inputs"][0], s["inputs"][-1]
-        bshape = s["bands_shape"]
+        sub, wav = s.inputs[0], s.inputs[-1]
+        bshape = s.bands_shape
         gb = torch.zeros((rows,) + bshape[1:], dtype=torch.float32, device=dev) if bshape[1] != self.q else None
         gsub = torch.empty((rows, self.q, sub.shape[2]), dtype=torch.float32, device=dev)
-        jobs = (EbenBlHeadJob * (n - 1))(*[self.chains[k].head_job(None, sub.shape[2], res[k][0]) for k in range(n - 1)])
+        jobs = (EbenBlHeadJob * (n - 1))(*[self.chains[k].head_job(None, sub.shape[2], res[k].dx) for k in range(n - 1)])
         check(lib.eben_bl_head_dx(jobs, n - 1, rows, ptr(gsub), _stream()), "bl_head_dx")
         if gb is None:
             gb = gsub
         else:
             gb[:, -self.q:, :] = gsub
         ga = torch.empty((rows, 1, wav.shape[2]), dtype=torch.float32, device=dev)
-        jobs = (EbenBlHeadJob * 1)(self.chains[-1].head_job(None, wav.shape[2], res[-1][0]))
+        jobs = (EbenBlHeadJob * 1)(self.chains[-1].head_job(None, wav.shape[2], res[-1].dx))
         check(lib.eben_bl_head_dx(jobs, 1, rows, ptr(ga), _stream()), "bl_head_dx")
-        if want_param_grads and not split:
-            pend = [None] * n
-            for i in [n - 1] + list(range(n - 1)):   # the longest chain first
-                with torch.cuda.stream(self._streams[i]):
-                    pend[i] = self._launch_weight_grads(s, i, res[i][1], res[i][2], half)
-            self._pending = (pend, s, res)   # keeps the saved activations and the stacked gradients alive until the kernels have run
-        self._state = None
+        if bw.want_param_grads and not bw.split:
+            pend = self._pending = PendingGrads([None] * n, [], [s, res])
+            for i in [n - 1] + list(range(n - 1)):   # the longest chain first, each on its home stream
+                with self._behind(res[i], self._streams[i]):
+                    self._launch_weight_grads(s, [i], res, pend)
         return gb[:half], ga[:half], gb[half:], ga[half:]

@@ -265,7 +265,7 @@ class EBENLightningModule(BaseSELightningModule):
         self._mark("start")
         with torch.no_grad():
             bands_ref = self.generator.pqmf.forward(reference_speech, "analysis")
-        if self.split_discriminator_forward and (type(engine).__name__ == "DiscriminatorEngineBL" or self._split_forward_forced):
+        if self.split_discriminator_forward and (engine.split_forward_pays or self._split_forward_forced):
             # the reference half of the discriminator batch does not depend on the generator: it runs on the chains'
             # streams underneath the generator forward (a chain of small launches that leaves most of the GPU idle).
             # Measured for the bundle-layout engine only (0.2 ms of a 10 ms step); the fp32-at-rest engines keep the
@@ -366,7 +366,7 @@ class EBENLightningModule(BaseSELightningModule):
             discriminator_optimizer.zero_grad()
             self._mark("discriminator Adam")
             if self.prepack_weights:   # next step's discriminator images, under the next generator forward (the chains wait for them)
-                engine._prepack_ev = ops.prepack(engine.image_caches(), engine._prepack_graph, join=False)
+                engine.prepack()
         return {"corrupted": corrupted_speech, "enhanced": enhanced_speech.detach(), "reference": reference_speech}
 
     #: run the discriminators on the reference half of the batch underneath the generator forward (it does not depend on the generator).
