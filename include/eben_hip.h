@@ -79,7 +79,8 @@ typedef struct EbenConv1dDesc {
 
 EBEN_API const char* eben_last_error(void);
 /* Bumped whenever a POD structure, an entry point's signature or a table stride changes (2: EbenWnBwdItem.col_perm_k; 3: eben_rubl_*; 4: eben_si_sdr / eben_stoi;
- * 5: eben_multirate_down* / eben_resample_adjoint).
+ * 5: eben_multirate_down* / eben_resample_adjoint).  eben_fir_plan was added without a bump: it changes none of those, and a binding
+ * that needs it finds out by looking the symbol up.
  * eben_version() returns the value the library was built with; bindings compare it with the header they were written against. */
 #define EBEN_ABI_VERSION 5
 EBEN_API int eben_version(void);
@@ -362,14 +363,29 @@ EBEN_API int eben_rubl_dw_slabs(int batch, int channels, int length);
 EBEN_API int eben_rubl_dw(int batch, int channels, int length, int dilation, const void* gzb, const void* hb, const void* ghb, const void* xb,
                           float* slabs_pw, float* slabs_dil, void* stream);
 
-/* ---- PQMF (vibravox/torch_modules/dsp/pqmf.py:194-213, eben_generator.py:209-211) ---------- */
+/* ---- PQMF / FIR banks (vibravox/torch_modules/dsp/pqmf.py:17-232, eben_generator.py:209-211; auraloss FIRFilter) ---------- */
+/* Exact fp32 products, fp32 accumulation in a fixed order (bitwise reproducible), any off0 (floor division for negative offsets),
+ * any lengths, 64-bit row offsets.  Domain: every bank of 1 <= bands <= 64, 1 <= ntaps <= 4096, 1 <= stride <= 64 -- the class
+ * defaults of PseudoQMFBanks (32 bands x 1024 taps) included -- plus the small banks of up to 1024 weights in all that the
+ * whole-bank-in-LDS kernels take at other band counts / strides.  Four kernels serve it (eben_fir_plan tells which):
+ *   1  the M = 4, N = 32 PQMF banks of every EBEN configuration (1, 2 or 4 bands, stride 4): polyphase form on wave shuffles;
+ *   2  one band, stride 1, >= 4 taps (the A-weighting prefilter): register-window FIR;
+ *   3  any other bank of <= 1024 weights whose tile fits 64 KB of LDS beside the whole bank;
+ *   4  everything else inside the domain: tap-tiled kernels (fir_bank.hip) that stage the input span of 128 output positions once
+ *      and stream the bank through LDS in chunks of 64 taps onto v_mfma_f32_32x32x2_f32.
+ * Outside the domain: EBEN_EUNSUPPORTED with a message, nothing launched. */
 /* decimating FIR bank: y[b,k,t] = sum_j w[k*ntaps+j] * x[b,0,t*stride+off0+j], zero outside [0,lx) */
 EBEN_API int eben_fir_decimate(const float* x, const float* w, float* y, int batch, int lx, int ly, int bands, int ntaps,
                       int stride, int off0, void* stream);
 /* interpolating FIR bank summed over bands (adjoint of the above):
- *   x[b,0,u] (+)= sum_k sum_{t,j : t*stride+off0+j == u} w[k*ntaps+j] * y[b,k,t] */
+ *   x[b,0,u] = sum_k sum_{t,j : t*stride+off0+j == u} w[k*ntaps+j] * y[b,k,t], zero outside [0,ly) */
 EBEN_API int eben_fir_interp_sum(const float* y, const float* w, float* x, int batch, int lx, int ly, int bands, int ntaps,
                         int stride, int off0, void* stream);
+/* The kernel a launch of eben_fir_decimate (which = 0) / eben_fir_interp_sum (which = 1) runs, asked of the host without launching
+ * anything (the dispatch's own decision).  out[0..3] (n >= 4) = kernel (1 .. 4 above), output positions per block, taps (reduction
+ * steps) per LDS chunk (0 off kernel 4), bands per block (kernel 4, which = 1: bands whose input tile is staged at a time; the block
+ * sums them all).  EBEN_EUNSUPPORTED where the launch itself would refuse. */
+EBEN_API int eben_fir_plan(int bands, int ntaps, int stride, int which, int* out, int n);
 
 /* ---- elementwise ------------------------------------------------------------------------ */
 EBEN_API int eben_lrelu_fwd(const float* x, float* y, size_t n, float slope, void* stream);

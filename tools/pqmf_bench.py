@@ -3,13 +3,20 @@ achieved HBM rate of each shape (vibravox/torch_modules/dsp/pqmf.py:194-213 -- a
 `pqmf_synthesis_kernel`: the polyphase forms on wave shuffles; EBEN_PQMF_SHUFFLE=0 selects the LDS forms `fir_decimate_kernel` /
 `fir_interp_sum_kernel`) and of their adjoints (the backward of the generator's synthesis / the balancing seeds).
 Algorithmic bytes: every input sample read once, every output sample written once (4 B each).  Peak 8 TB/s (6.3 measured for a copy).
-Usage: python tools/pqmf_bench.py [--iters 50]"""
+Usage: python tools/pqmf_bench.py [--iters 50]
+
+With --bank M N: the M-band x N-tap bank instead (the tap-tiled kernels of csrc/fir_bank.hip; PseudoQMFBanks' class defaults are 32 1024),
+at --batch x (1024 M - N) samples = 1024 frames: analysis, synthesis + band sum and their two adjoints as ONE launch each, with the fraction
+of the fp32 roof (2 M N frames batch FLOP at 157.3 TFLOP/s) and of the byte roof, beside the baseline a library without those kernels is
+left with -- M single-band launches of the whole-bank-in-LDS kernels (plus one add of the M outputs for the band sum).  --baseline-only
+times only that baseline and needs nothing newer than the single-band launches."""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from vibravox_amd.torch_modules.dsp.pqmf import PseudoQMFBanks
 
 ap = argparse.ArgumentParser(); ap.add_argument("--iters", type=int, default=50); ap.add_argument("--batch", type=int, default=32)
+ap.add_argument("--bank", type=int, nargs=2, metavar=("M", "N"), default=None); ap.add_argument("--baseline-only", action="store_true")
 args = ap.parse_args()
 dev = torch.device("cuda")
 pq = PseudoQMFBanks(decimation=4, kernel_size=32).to(dev)
@@ -25,6 +32,44 @@ def timed(fn):
     return e0.elapsed_time(e1) / args.iters * 1e3
 
 
+def bank_rows(m, n):
+    """One large bank: (name, us of the one-launch form or None, us of the m-launch baseline) per direction."""
+    from vibravox_amd import ops
+    pqb = PseudoQMFBanks(decimation=m, kernel_size=n).to(dev)
+    frames, off = 1024, -(n - 1)
+    t = frames * m - n
+    wa, ws = (w.detach().reshape(m, n).contiguous() for w in (pqb.analysis_weights, pqb.synthesis_weights))
+    x = 0.1 * torch.randn(B, 1, t, device=dev)
+    y = 0.1 * torch.randn(B, m, frames, device=dev)
+    ys = [y[:, k:k + 1].contiguous() for k in range(m)]
+    rows = []
+    with torch.no_grad():
+        for name, w in (("analysis", wa), ("synthesis adjoint (analysis-form kernel)", ws)):
+            wk = [w[k:k + 1].contiguous() for k in range(m)]
+            base = timed(lambda: [ops._fir_decimate(x, wk[k], frames, 1, n, m, off) for k in range(m)])
+            one = None if args.baseline_only else timed(lambda: ops._fir_decimate(x, w, frames, m, n, m, off))
+            rows.append((f"{name} ({B},1,{t}) -> ({B},{m},{frames})", one, base))
+        for name, w in (("synthesis + band sum", ws), ("analysis adjoint (synthesis-form kernel)", wa)):
+            wk = [w[k:k + 1].contiguous() for k in range(m)]
+            base = timed(lambda: torch.stack([ops._fir_interp_sum(ys[k], wk[k], t, 1, n, m, off) for k in range(m)]).sum(0))
+            one = None if args.baseline_only else timed(lambda: ops._fir_interp_sum(y, w, t, m, n, m, off))
+            rows.append((f"{name} ({B},{m},{frames}) -> ({B},1,{t})", one, base))
+    flop, nbytes = 2.0 * m * n * frames * B, 4.0 * (B * t + B * m * frames + m * n)
+    print(f"bank {m} x {n}, {B} x {t} samples = {frames} frames: {flop / 1e9:.2f} GFLOP = {flop / 157.3e6:.1f} us at 157.3 TFLOP/s fp32, "
+          f"{nbytes / 1e6:.1f} MB = {nbytes / 8e6:.1f} us at 8 TB/s")
+    print(f"{'launch':72s} {'us':>8s} {'of fp32':>8s} {'of 8TB/s':>8s} {f'{m} launches us':>15s} {'ratio':>6s}")
+    for name, one, base in rows:
+        if one is None:
+            print(f"{name:72s} {'-':>8s} {'-':>8s} {'-':>8s} {base:15.1f} {'-':>6s}")
+        else:
+            print(f"{name:72s} {one:8.1f} {flop / 157.3e6 / one:8.3f} {nbytes / 8e6 / one:8.3f} {base:15.1f} {base / one:6.2f}")
+
+
+if args.bank:
+    bank_rows(*args.bank)
+    if args.baseline_only:
+        sys.exit(0)
+    print()
 x = 0.1 * torch.randn(B, 1, T, device=dev)
 print(f"{'launch':64s} {'us':>7s} {'MB':>7s} {'TB/s':>6s} {'of 8':>5s}")
 rows = []

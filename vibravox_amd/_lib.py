@@ -153,6 +153,7 @@ SIGNATURES = {
     "eben_rubl_dw": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
     "eben_fir_decimate": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "eben_fir_interp_sum": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "eben_fir_plan": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int), c_int]),
     "eben_lrelu_fwd": (c_int, [_P, _P, c_size_t, c_float, _P]),
     "eben_lrelu_bwd": (c_int, [_P, _P, _P, c_size_t, c_float, _P]),
     "eben_space_to_depth": (c_int, [_P, _P, c_float, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),

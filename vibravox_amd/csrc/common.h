@@ -190,6 +190,23 @@ __host__ __device__ inline PhaseGeom phase_geom(int mode, int ph, int J0, int of
   return q;
 }
 
+// tap-tiled FIR banks (fir_bank.hip): the banks of eben_fir_decimate (which 0) / eben_fir_interp_sum (which 1) too large for the
+// whole-bank-in-LDS kernels of direct.hip.  fir_bank_geom is the launch's own geometry (and eben_fir_plan's answer); it fails with
+// EBEN_EUNSUPPORTED outside 1 <= bands <= 64, 1 <= ntaps <= 4096, 1 <= stride <= 64.
+struct FirBankGeom {
+  int P;          // output frames (which 0) / input frames q = floor((u - off0) / stride) (which 1) per block
+  int chunk;      // reduction steps per LDS weight chunk
+  int rows;       // MFMA rows in use per block: bands (which 0) / output phases (which 1) of one 32-row tile
+  int row_tiles;  // 32-row tiles (grid.z)
+  int G;          // which 1: bands whose input tile is staged at a time
+  int Mp, TT;     // which 1: taps per phase rounded up to even, staged frames per band
+  int in_floats;  // LDS floats of the staged input
+  size_t lds;     // dynamic LDS bytes of the launch
+};
+int fir_bank_geom(int bands, int ntaps, int stride, int which, FirBankGeom* g);
+int fir_bank_launch(int which, const float* in, const float* w, float* out, int batch, int lx, int ly, int bands, int ntaps, int stride,
+                    int off0, hipStream_t st);
+
 // second-generation tap-conv (tapconv2.hip): 32x32x2 MFMA tiles, LDS-DMA weight stream
 int tap2_applicable(const Canon& c, int dir);
 size_t tap2_packed_floats(const Canon& c, int dir);

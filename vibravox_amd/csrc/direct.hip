@@ -778,12 +778,54 @@ static int fir1_launch(const float* in, const float* w, float* out, int batch, i
 }
 }  // namespace eben
 
+namespace eben {
+// Which kernel serves a bank (the launches' own decision; eben_fir_plan reports it).  Whatever the three kernels of this file took
+// before the tap-tiled ones existed goes where it went; only what they refuse goes to fir_bank.hip.
+struct FirPlan { int kernel, positions, chunk, bands_per_block; FirBankGeom g; };
+static int fir_plan(int bands, int ntaps, int stride, int which, FirPlan* p) {
+  static const bool shuffles = !(getenv("EBEN_PQMF_SHUFFLE") && atoi(getenv("EBEN_PQMF_SHUFFLE")) == 0);
+  if (bands <= 0 || ntaps <= 0 || stride <= 0 || which < 0 || which > 1) return fail(EBEN_EINVAL, "bad fir bank %d x %d taps, stride %d", bands, ntaps, stride);
+  *p = FirPlan{};
+  if ((long long)bands * ntaps <= FIR_MAX_W) {
+    if (shuffles && stride == 4 && ntaps == 32 && (bands == 1 || bands == 2 || bands == 4)) {   // the PQMF banks: polyphase form on wave shuffles
+      p->kernel = 1; p->positions = which ? 4 * 4 * 57 : 4 * 57; p->bands_per_block = bands;
+      return EBEN_OK;
+    }
+    if (fir1_enabled && stride == 1 && bands == 1 && ntaps >= 4) {
+      p->kernel = 2; p->positions = FIR1_BLOCK; p->bands_per_block = 1;
+      return EBEN_OK;
+    }
+    const size_t lds = which ? sizeof(float) * (FIR_MAX_W + (size_t)bands * ((255 + ntaps - 1) / stride + 3))
+                             : sizeof(float) * (FIR_MAX_W + (size_t)255 * stride + ntaps);
+    if (lds <= 64 * 1024) {
+      p->kernel = 3; p->positions = 256; p->bands_per_block = bands;
+      return EBEN_OK;
+    }
+  }
+  const int rc = fir_bank_geom(bands, ntaps, stride, which, &p->g);
+  if (rc != EBEN_OK) return rc;
+  p->kernel = 4; p->positions = which ? p->g.P * p->g.rows : p->g.P; p->chunk = p->g.chunk; p->bands_per_block = which ? p->g.G : p->g.rows;
+  return EBEN_OK;
+}
+}  // namespace eben
+
+extern "C" int eben_fir_plan(int bands, int ntaps, int stride, int which, int* out, int n) {
+  EBEN_REQUIRE(out && n >= 4, "eben_fir_plan needs room for 4 ints");
+  FirPlan p;
+  const int rc = fir_plan(bands, ntaps, stride, which, &p);
+  if (rc != EBEN_OK) return rc;
+  for (int i = 0; i < n; ++i) out[i] = 0;
+  out[0] = p.kernel; out[1] = p.positions; out[2] = p.chunk; out[3] = p.bands_per_block;
+  return EBEN_OK;
+}
+
 extern "C" int eben_fir_decimate(const float* x, const float* w, float* y, int batch, int lx, int ly, int bands, int ntaps,
                                  int stride, int off0, void* stream) {
   EBEN_REQUIRE(x && w && y && batch > 0 && lx > 0 && ly > 0 && bands > 0 && ntaps > 0 && stride > 0, "bad fir_decimate arguments");
-  EBEN_REQUIRE(bands * ntaps <= FIR_MAX_W, "fir bank of %d x %d taps exceeds %d", bands, ntaps, FIR_MAX_W);
-  static const bool shuffles = !(getenv("EBEN_PQMF_SHUFFLE") && atoi(getenv("EBEN_PQMF_SHUFFLE")) == 0);
-  if (shuffles && stride == 4 && ntaps == 32 && (bands == 1 || bands == 2 || bands == 4)) {   // the PQMF banks: polyphase form on wave shuffles
+  FirPlan p;
+  const int rc = fir_plan(bands, ntaps, stride, 0, &p);
+  if (rc != EBEN_OK) return rc;
+  if (p.kernel == 1) {
     const dim3 grid(ceil_div(ly, 4 * 57), batch);
     if (bands == 1) hipLaunchKernelGGL(pqmf_analysis_kernel<1>, grid, dim3(256), 0, as_stream(stream), x, w, y, lx, ly, off0);
     else if (bands == 2) hipLaunchKernelGGL(pqmf_analysis_kernel<2>, grid, dim3(256), 0, as_stream(stream), x, w, y, lx, ly, off0);
@@ -791,9 +833,9 @@ extern "C" int eben_fir_decimate(const float* x, const float* w, float* y, int b
     EBEN_CHECK_LAUNCH("pqmf_analysis_kernel");
     return EBEN_OK;
   }
-  if (fir1_enabled && stride == 1 && bands == 1 && ntaps >= 4) return fir1_launch<1>(x, w, y, batch, lx, ly, ntaps, off0, as_stream(stream));
+  if (p.kernel == 2) return fir1_launch<1>(x, w, y, batch, lx, ly, ntaps, off0, as_stream(stream));
+  if (p.kernel == 4) return fir_bank_launch(0, x, w, y, batch, lx, ly, bands, ntaps, stride, off0, as_stream(stream));
   const size_t lds = sizeof(float) * (FIR_MAX_W + (size_t)255 * stride + ntaps);
-  EBEN_REQUIRE(lds <= 64 * 1024, "fir_decimate stride %d too large", stride);
   hipLaunchKernelGGL(fir_decimate_kernel, dim3(ceil_div(ly, 256), batch), dim3(256), lds, as_stream(stream), x, w, y, lx, ly,
                      bands, ntaps, stride, off0);
   EBEN_CHECK_LAUNCH("fir_decimate_kernel");
@@ -803,9 +845,10 @@ extern "C" int eben_fir_decimate(const float* x, const float* w, float* y, int b
 extern "C" int eben_fir_interp_sum(const float* y, const float* w, float* x, int batch, int lx, int ly, int bands, int ntaps,
                                    int stride, int off0, void* stream) {
   EBEN_REQUIRE(x && w && y && batch > 0 && lx > 0 && ly > 0 && bands > 0 && ntaps > 0 && stride > 0, "bad fir_interp_sum arguments");
-  EBEN_REQUIRE(bands * ntaps <= FIR_MAX_W, "fir bank of %d x %d taps exceeds %d", bands, ntaps, FIR_MAX_W);
-  static const bool shuffles = !(getenv("EBEN_PQMF_SHUFFLE") && atoi(getenv("EBEN_PQMF_SHUFFLE")) == 0);
-  if (shuffles && stride == 4 && ntaps == 32 && (bands == 1 || bands == 2 || bands == 4)) {
+  FirPlan p;
+  const int rc = fir_plan(bands, ntaps, stride, 1, &p);
+  if (rc != EBEN_OK) return rc;
+  if (p.kernel == 1) {
     // u - off0 = 4 q + r covers u = 0 .. lx - 1 for q = floor(-off0 / 4) .. floor((lx - 1 - off0) / 4)
     auto fdiv = [](long long a, long long d) { long long qq = a / d; return (a % d != 0 && ((a < 0) != (d < 0))) ? qq - 1 : qq; };
     const int qmin = (int)fdiv(-(long long)off0, 4), qmax = (int)fdiv((long long)lx - 1 - off0, 4);
@@ -816,10 +859,10 @@ extern "C" int eben_fir_interp_sum(const float* y, const float* w, float* x, int
     EBEN_CHECK_LAUNCH("pqmf_synthesis_kernel");
     return EBEN_OK;
   }
-  if (fir1_enabled && stride == 1 && bands == 1 && ntaps >= 4) return fir1_launch<-1>(y, w, x, batch, ly, lx, ntaps, -off0, as_stream(stream));
+  if (p.kernel == 2) return fir1_launch<-1>(y, w, x, batch, ly, lx, ntaps, -off0, as_stream(stream));
+  if (p.kernel == 4) return fir_bank_launch(1, y, w, x, batch, lx, ly, bands, ntaps, stride, off0, as_stream(stream));
   const int tile_t = (255 + ntaps - 1) / stride + 3;
   const size_t lds = sizeof(float) * (FIR_MAX_W + (size_t)bands * tile_t);
-  EBEN_REQUIRE(lds <= 64 * 1024, "fir_interp_sum tile too large");
   hipLaunchKernelGGL(fir_interp_sum_kernel, dim3(ceil_div(lx, 256), batch), dim3(256), lds, as_stream(stream), y, w, x, lx, ly,
                      bands, ntaps, stride, off0, tile_t);
   EBEN_CHECK_LAUNCH("fir_interp_sum_kernel");

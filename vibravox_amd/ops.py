@@ -1197,7 +1197,8 @@ def add(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
 
 
 class _TanhLiftFn(torch.autograd.Function):
-    """tanh(x + cat(lift, 0)) -- eben_generator.py:203-208; ``lift`` carries no gradient."""
+    """tanh(x + cat(lift, 0)) -- eben_generator.py:203-208; ``lift`` receives a gradient (the first channels of x's) only where it
+    asks for one: the generator's input is data in training, and the first bands of an input that does require a gradient carry it."""
 
     @staticmethod
     def forward(ctx, x, lift):
@@ -1206,6 +1207,7 @@ class _TanhLiftFn(torch.autograd.Function):
         out = torch.empty_like(x)
         check(load().eben_tanh_lift_fwd(ptr(x), ptr(lift), ptr(out), b, c, lift.shape[1], l, stream()), "tanh_lift_fwd")
         ctx.save_for_backward(out)
+        ctx.lift_channels = lift.shape[1]
         return out
 
     @staticmethod
@@ -1214,11 +1216,11 @@ class _TanhLiftFn(torch.autograd.Function):
         dout = dout.contiguous()
         dx = torch.empty_like(out)
         check(load().eben_tanh_bwd(ptr(dout), ptr(out), ptr(dx), out.numel(), stream()), "tanh_bwd")
-        return dx, None
+        return dx, (dx[:, : ctx.lift_channels].clone() if ctx.needs_input_grad[1] else None)
 
 
 def tanh_lift(x: torch.Tensor, lift: torch.Tensor) -> torch.Tensor:
-    return _TanhLiftFn.apply(x, lift.detach())
+    return _TanhLiftFn.apply(x, lift)
 
 
 class _ReflectPadFn(torch.autograd.Function):

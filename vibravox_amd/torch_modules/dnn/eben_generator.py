@@ -119,7 +119,8 @@ class EBENGenerator(nn.Module, PyTorchModelHubMixin):
     use_engine: bool = os.environ.get("EBEN_GEN_ENGINE", "1") != "0"
 
     def forward(self, cut_audio):
-        if self.use_engine and cut_audio.is_cuda:
+        # (the engine differentiates w.r.t. the parameters only: an input that asks for its own gradient goes module by module)
+        if self.use_engine and cut_audio.is_cuda and not (cut_audio.requires_grad and torch.is_grad_enabled()):
             from ... import gen_engine
 
             x, first_bands = gen_engine.core(self, cut_audio)

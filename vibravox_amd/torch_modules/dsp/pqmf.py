@@ -5,6 +5,8 @@ constructor, ``forward(signal, stage, bands)``, ``kernel_size`` / ``decimation``
 frozen ``analysis_weights`` / ``synthesis_weights`` parameters of shape (M, 1, N).
 The bank design (Kaiser prototype, cutoff by 5 LBFGS outer steps) runs once on the CPU at
 construction; the filtering itself is ``eben_fir_decimate`` / ``eben_fir_interp_sum``.
+Any bank of up to 64 bands x 4096 taps runs (the class defaults are 32 x 1024): the (4, 32) banks of the EBEN configurations on
+the polyphase shuffle kernels, larger ones on the tap-tiled kernels of ``csrc/fir_bank.hip``.
 """
 from __future__ import annotations
 
