@@ -80,7 +80,8 @@ typedef struct EbenConv1dDesc {
 EBEN_API const char* eben_last_error(void);
 /* Bumped whenever a POD structure, an entry point's signature or a table stride changes (2: EbenWnBwdItem.col_perm_k; 3: eben_rubl_*; 4: eben_si_sdr / eben_stoi;
  * 5: eben_multirate_down* / eben_resample_adjoint).  eben_fir_plan was added without a bump: it changes none of those, and a binding
- * that needs it finds out by looking the symbol up.
+ * that needs it finds out by looking the symbol up.  The same holds for the data front end (eben_clip_powers*, eben_noisy_collate_scaled,
+ * eben_biquad*, EbenClip): functions and a new POD type only.
  * eben_version() returns the value the library was built with; bindings compare it with the header they were written against. */
 #define EBEN_ABI_VERSION 5
 EBEN_API int eben_version(void);
@@ -554,6 +555,37 @@ typedef struct EbenCollateItem {
   int64_t shift;
 } EbenCollateItem;
 EBEN_API int eben_noisy_collate(const EbenCollateItem* items, int nitems, int samples, float* body_conducted, float* airborne, void* stream);
+
+/* ---- SNR-controlled mixing (mix_speech_and_noise_with_rescaling, vibravox/utils.py:118-193) --------------------------
+ * eben_clip_powers: powers[i] = float32(sum(x^2) / length_i) of ragged clips (1 <= length_i); products and sums in float64, per-block
+ *   partials and one fixed-order final pass, no atomics: two calls give the same bits.  `clips` is a HOST array (device pointers
+ *   inside, 4-byte aligned), passed by value 48 per launch; `workspace` (device, 8-byte aligned) holds
+ *   eben_clip_powers_workspace(nclips) bytes.
+ * eben_noisy_collate_scaled: eben_noisy_collate with the per-item gain g = sqrt(speech_power / (noise_power * snr_linear)) read
+ *   from DEVICE arrays of nitems floats:  ns = noise[noise_start + u] * g,  body_conducted = speech[u] + ns, every step rounded
+ *   to float32 (utils.py:183-188; never one FMA).  Every item needs a noise clip.  noise_scaled (nullable) receives ns as
+ *   (nitems, 1, samples) with the same zero fill. */
+typedef struct EbenClip {
+  const float* data;
+  int64_t length;
+} EbenClip;
+EBEN_API size_t eben_clip_powers_workspace(int nclips);
+EBEN_API int eben_clip_powers(const EbenClip* clips, int nclips, float* powers, void* workspace, size_t ws_bytes, void* stream);
+EBEN_API int eben_noisy_collate_scaled(const EbenCollateItem* items, int nitems, int samples, const float* speech_power, const float* noise_power,
+                                       const float* snr_linear, float* body_conducted, float* airborne, float* noise_scaled, void* stream);
+
+/* ---- biquad (torchaudio.functional.lfilter of one second-order section, as lowpass_biquad / remove_hf use it, utils.py:84-116) ----
+ * y[r, m] for the padded row xp[r, m] = x[r, reflect(m - pad)], m in [0, t_in + 2*pad) (ReflectionPad1d's index mapping on the
+ * read; pad < t_in; nothing is materialised):  v[n] = b0 u[n] + b1 u[n-1] + b2 u[n-2] - a1 v[n-1] - a2 v[n-2] from a zero state,
+ * with u[n] = xp[n], y[n] = v[n], or, when `reversed`, u[n] = xp[T-1-n], y[T-1-n] = v[n] (the row is filtered from its last
+ * sample to its first and stored in the input's orientation, so no flip is ever made).  coef (HOST) = b0 b1 b2 a1 a2, already
+ * divided by a0.  clamp != 0: the STORED value is clamped to [-1, 1], never the state (lfilter clamp=True).  State and
+ * accumulation are float64, x and y float32; parallel along time (chunks of 4096 samples, csrc/frontend.hip).  x and y are
+ * (rows, t_in) and (rows, t_in + 2*pad), not aliased; `workspace` (device, 8-byte aligned, may be NULL when the query returns
+ * 0) holds eben_biquad_workspace(rows, t_in + 2*pad) bytes. */
+EBEN_API size_t eben_biquad_workspace(int rows, int t_padded);
+EBEN_API int eben_biquad(const float* x, float* y, int rows, int t_in, int pad, const double* coef, int reversed, int clamp, void* workspace,
+                         size_t ws_bytes, void* stream);
 
 /* ---- waveform augmentation (vibravox/torch_modules/dsp/data_augmentation.py:38-71) -------------------------------
  * time masking (dsp/time_masking_waveform.py:18-36): x[r, first : first+count] = 0 in place for r < rows;

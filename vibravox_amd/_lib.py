@@ -82,6 +82,10 @@ class EbenCollateItem(ctypes.Structure):
                 ("shift", c_int64)]
 
 
+class EbenClip(ctypes.Structure):
+    _fields_ = [("data", c_void_p), ("length", c_int64)]
+
+
 _P = c_void_p
 _D = POINTER(EbenConv1dDesc)
 
@@ -202,6 +206,11 @@ SIGNATURES = {
     "eben_stft_terms_total": (c_int, [POINTER(c_void_p), POINTER(c_float), c_int, c_int, c_int, c_float, c_float, c_float, _P, _P]),
     "eben_adam_step": (c_int, [POINTER(EbenAdamTensor), c_int, c_int64, c_float, c_float, c_float, c_float, c_float, c_int, c_float, _P]),
     "eben_noisy_collate": (c_int, [POINTER(EbenCollateItem), c_int, c_int, _P, _P, _P]),
+    "eben_clip_powers_workspace": (c_size_t, [c_int]),
+    "eben_clip_powers": (c_int, [POINTER(EbenClip), c_int, _P, _P, c_size_t, _P]),
+    "eben_noisy_collate_scaled": (c_int, [POINTER(EbenCollateItem), c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "eben_biquad_workspace": (c_size_t, [c_int, c_int]),
+    "eben_biquad": (c_int, [_P, _P, c_int, c_int, c_int, POINTER(ctypes.c_double), c_int, c_int, _P, c_size_t, _P]),
     "eben_l2norm": (c_int, [_P, c_size_t, _P, _P]),
     "eben_si_sdr": (c_int, [_P, _P, c_int, c_int, _P, _P]),
     "eben_stoi_workspace": (c_size_t, [c_int, c_int, c_int]),
