@@ -614,6 +614,19 @@ EBEN_API int eben_multirate_down_adjoint(const float* g0, const float* const* gs
 EBEN_API int eben_resample_adjoint(const float* g, const float* kernels, float* dx, int rows, int t_in, int t_out, int orig, int nw,
                                    int width, int accumulate, void* stream);
 
+/* ---- ragged batches (csrc/ragged.hip): rows of different lengths in one (rows, channels, l_buf) buffer ------------------------
+ * In place, one launch for every (row, channel); lens (DEVICE, rows int32) holds each row's own length at this tensor's rate.
+ * eben_edge_fill: the `count` samples behind each row's end become what the row's own edge rule supplies to the next layer --
+ *   EBEN_FILL_ZERO x[r, c, len + j] = 0, EBEN_FILL_MIRROR x[r, c, len + j] = x[r, c, len - 2 - j] (ReflectionPad1d), j < count.
+ *   1 <= count < l_buf, else EBEN_EINVAL before any launch.  The kernel leaves a row alone when len == l_buf (no slack) and
+ *   skips it when len + count > l_buf, len < 0 or, mirroring, count > len - 1: a bad table writes nothing out of bounds.
+ * eben_edge_zero: the whole slack [len, l_buf) of every row becomes 0 (tensors handed back to the caller).
+ * Added without a version bump, like eben_fir_plan: functions only. */
+#define EBEN_FILL_ZERO 0
+#define EBEN_FILL_MIRROR 1
+EBEN_API int eben_edge_fill(float* x, const int32_t* lens, int rows, int channels, int l_buf, int mode, int count, void* stream);
+EBEN_API int eben_edge_zero(float* x, const int32_t* lens, int rows, int channels, int l_buf, void* stream);
+
 /* ---- misc ------------------------------------------------------------------------------- */
 /* out[0] = sqrt(sum x^2) (torch.norm at eben.py:226); `out` must hold 257 floats (scratch) */
 EBEN_API int eben_l2norm(const float* x, size_t n, float* out, void* stream);

@@ -218,6 +218,8 @@ SIGNATURES = {
     "eben_multirate_down": (c_int, [_P, _P, POINTER(c_int), POINTER(c_void_p), c_int, c_int, c_int, _P]),
     "eben_multirate_down_adjoint": (c_int, [_P, POINTER(c_void_p), _P, POINTER(c_int), _P, c_int, c_int, c_int, _P]),
     "eben_resample_adjoint": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "eben_edge_fill": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "eben_edge_zero": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

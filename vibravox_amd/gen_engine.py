@@ -319,40 +319,101 @@ class GeneratorEngine:
         return y
 
     # ---- forward -------------------------------------------------------------------------------------
-    def forward(self, cut_audio: torch.Tensor, train: bool):
-        """Returns (input of last_conv, first_bands, records for ``backward`` or None)."""
+    def forward(self, cut_audio: torch.Tensor, train: bool, fill=None):
+        """Returns (input of last_conv, first_bands, records for ``backward`` or None).  ``fill(layer path, x)``, inference only: called
+        on the input of every layer with taps along time right before its launch (``forward_ragged`` writes the rows' own edges there)."""
         gen = self.gen
         lib = load()
         ops.join_prepack()   # images rebuilt ahead of time on the side stream
         slope = gen.nl.negative_slope
         first_bands = gen.pqmf(cut_audio, "analysis", bands=gen.p).detach()
         saved = {"enc": [], "dec": [], "misc": []} if train else None
+        if fill is not None:
+            fill("first_conv", first_bands)
         a = self._conv(gen.first_conv, first_bands, train, recs=saved["misc"] if train else None)
         skips = []
-        for blk in gen.encoder_blocks:
+        for i, blk in enumerate(gen.encoder_blocks):
             recs = [] if train else None
             cur = a
             for k, ru in enumerate(blk.residuals):
+                if fill is not None:
+                    fill(f"encoder_blocks.{i}.residuals.{k}", cur)
                 cur = self._residual_unit(ru, cur, slope if k == 0 else 1.0, train, recs)
+            if fill is not None:
+                fill(f"encoder_blocks.{i}.conv", cur)
             a = self._conv(blk.conv, cur, train, recs=recs)
             skips.append(a)
             if train:
                 saved["enc"].append(recs)
         lat = [] if train else None
+        if fill is not None:
+            fill("latent_conv.1", a)
         l1 = self._conv(gen.latent_conv[1], a, train, in_slope=slope, recs=lat)
+        if fill is not None:
+            fill("latent_conv.3", l1)
         cur = self._conv(gen.latent_conv[3], l1, train, recs=lat)
         if train:
             saved["latent"] = lat
-        for blk, skip in zip(gen.decoder_blocks, reversed(skips)):
+        for i, (blk, skip) in enumerate(zip(gen.decoder_blocks, reversed(skips))):
             recs = [] if train else None
             s = torch.empty_like(cur)
             check(lib.eben_add(ptr(cur), ptr(skip), ptr(s), cur.numel(), stream()), "add")
+            if fill is not None:
+                fill(f"decoder_blocks.{i}.conv_trans", s)
             cur = self._conv(blk.conv_trans, s, train, recs=recs)
-            for ru in blk.residuals:
+            for k, ru in enumerate(blk.residuals):
+                if fill is not None:
+                    fill(f"decoder_blocks.{i}.residuals.{k}", cur)
                 cur = self._residual_unit(ru, cur, 1.0, train, recs)
             if train:
                 saved["dec"].append(recs)
         return cur, first_bands, saved
+
+    # ---- ragged batches: rows of different lengths, inference only (vibravox_amd/ragged.py) ---------------------------------------
+    @staticmethod
+    def _edge_fill(x: torch.Tensor, table: torch.Tensor, f) -> None:
+        """Fill ``f`` of the plan on ``x`` in place; ``table``: the plan's row lengths on the device, (resolutions, rows) int32."""
+        rows, channels, l_buf = x.shape
+        lens = table.data_ptr() + 4 * rows * f.level
+        if f.mode == "zero_all":
+            check(load().eben_edge_zero(ptr(x), lens, rows, channels, l_buf, stream()), "edge_zero")
+        else:
+            check(load().eben_edge_fill(ptr(x), lens, rows, channels, l_buf, 1 if f.mode == "mirror" else 0, f.count, stream()), "edge_fill")
+
+    def forward_ragged(self, padded_audio: torch.Tensor, plan):
+        """(enhanced (B,1,l_buf), bands (B,m,l_buf of the bands)) of zero-padded rows of ``plan.cut`` samples each, every row equal to its
+        own batch-1 forward on [0, its length) and zero behind: ``forward(.., train=False)`` launch for launch, with the plan's edge fill
+        in front of each layer.  Equal rows need no fill: the call is the batched forward.  Inference only (no backward exists)."""
+        if torch.is_grad_enabled():
+            raise RuntimeError("EBEN generator engine: forward_ragged has no backward; call it under torch.no_grad()")
+        gen = self.gen
+        b, c, l = padded_audio.shape
+        if c != 1 or b != len(plan.cut) or l != plan.l_buf:
+            raise ValueError(f"forward_ragged: expected a ({len(plan.cut)}, 1, {plan.l_buf}) buffer for this plan, got {tuple(padded_audio.shape)}")
+        x = padded_audio.contiguous()
+        if not plan.fills:
+            pre, first_bands, _ = self.forward(x, False)
+            bands = ops.tanh_lift(gen.last_conv(pre), first_bands)
+            return gen.pqmf.synthesis_sum(bands), bands
+        table = torch.tensor(plan.row_lengths, dtype=torch.int32).to(x.device, non_blocking=True)   # the one upload of the batch
+        todo = iter(plan.fills)
+
+        def fill(path, t):
+            f = next(todo)
+            if f.layer != path or t.shape[2] != plan.buffer_lengths[f.level]:
+                raise RuntimeError(f"ragged plan out of step with the forward: {f} in front of {path} on {tuple(t.shape)}")
+            self._edge_fill(t, table, f)
+
+        if x is padded_audio:
+            x = x.clone()   # the caller's buffer stays as it is
+        fill("pqmf.analysis", x)
+        pre, first_bands, _ = self.forward(x, False, fill)
+        fill("last_conv", pre)
+        bands = ops.tanh_lift(gen.last_conv(pre), first_bands)
+        fill("pqmf.synthesis", bands)
+        enhanced = gen.pqmf.synthesis_sum(bands)
+        fill("enhanced", enhanced)
+        return enhanced, bands
 
     # ---- backward ------------------------------------------------------------------------------------
     def _dx(self, rec: _ConvRec, dy, res_pre=None, res_post=None):
@@ -733,12 +794,17 @@ class _CoreFn(torch.autograd.Function):
         return (None, None) + (None,) * (len(ctx.needs_input_grad) - 2)
 
 
-def core(gen, cut_audio: torch.Tensor):
-    """(input of ``gen.last_conv``, first_bands) through the engine; differentiable w.r.t. the generator's parameters."""
+def engine_of(gen) -> GeneratorEngine:
     engine = getattr(gen, "_engine", None)
     if engine is None:
         engine = GeneratorEngine(gen)
         object.__setattr__(gen, "_engine", engine)   # not a submodule / buffer: invisible to state_dict
+    return engine
+
+
+def core(gen, cut_audio: torch.Tensor):
+    """(input of ``gen.last_conv``, first_bands) through the engine; differentiable w.r.t. the generator's parameters."""
+    engine = engine_of(gen)
     # the parameters the core owns: NOT last_conv's -- the balancing passes differentiate the losses w.r.t. last_conv.weight alone
     # (eben.py:223-227) and must not reach into the core
     params = [p for m in (gen.first_conv, gen.encoder_blocks, gen.latent_conv, gen.decoder_blocks) for p in ops.parameters_of(m) if p.requires_grad]

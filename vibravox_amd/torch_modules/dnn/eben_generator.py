@@ -144,6 +144,23 @@ class EBENGenerator(nn.Module, PyTorchModelHubMixin):
         enhanced_speech = self.pqmf.synthesis_sum(enhanced_speech_decomposed)
         return enhanced_speech, enhanced_speech_decomposed
 
+    def forward_ragged(self, padded, lengths):
+        """Clips of different lengths in one pass (inference, under ``torch.no_grad()``): ``padded`` (B,1,L) holds clip r in
+        ``padded[r, 0, :lengths[r]]`` (what lies behind is ignored).  Returns (enhanced (B,1,l_buf), bands (B,m,.)): with ``plan =
+        vibravox_amd.ragged.plan(self, lengths)``, row r equals ``self(cut_to_valid_length(clip r))`` on ``[0, plan.cut[r])`` --
+        ``plan.row_lengths[1][r]`` band samples -- and is zero behind; ``l_buf`` is the longest cut length plus the plan's margin, or
+        that length alone when all are equal."""
+        from ... import gen_engine, ragged
+
+        plan = ragged.plan(self, lengths)
+        if padded.dim() != 3 or padded.shape[:2] != (len(plan.cut), 1) or padded.shape[2] < max(plan.cut):
+            raise ValueError(f"forward_ragged: expected ({len(plan.cut)}, 1, >= {max(plan.cut)}) audio, got {tuple(padded.shape)}")
+        if padded.shape[2] >= plan.l_buf:
+            buf = padded[:, :, : plan.l_buf]
+        else:
+            buf = torch.nn.functional.pad(padded, (0, plan.l_buf - padded.shape[2]))
+        return gen_engine.engine_of(self).forward_ragged(buf, plan)
+
     def cut_to_valid_length(self, tensor):
         old_len = tensor.shape[2]
         new_len = old_len - (old_len + self.pqmf.kernel_size) % self.multiple
