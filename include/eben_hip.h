@@ -186,6 +186,17 @@ EBEN_API int eben_conv1d_bwd_dx_fm(const EbenConv1dDesc* d, const float* g, cons
  * finish with eben_wn_bwd. */
 EBEN_API int eben_conv1d_bwd_dw(const EbenConv1dDesc* d, const float* dy, const float* y, const float* x, int has_bias,
                        float* slabs, size_t ws_bytes, void* stream);
+/* The kernel family eben_conv1d_bwd_dw runs for the layer, asked of the host without launching anything (the dispatch's own decision,
+ * which eben_conv1d_bwd_dw_workspace reads too; for tests).  out[0] (n >= 13) = EBEN_DW_ROUTE_*; on the conv_dw3 route out[1..12] =
+ * FM, FN, WAVES_M, XRB, SP of conv_dw3_kernel, MT of dw3_pack_a_kernel, then the plan: BKT (time steps per chunk), nsplit (split-K
+ * slabs), nchunks ((batch group, time chunk) pairs: block z owns chunks z, z + nsplit, ...), nnt / nmt (column / row tiles), nbg
+ * (groups of 16 batch items).  Zeros past out[0] on the other routes. */
+#define EBEN_DW_ROUTE_TINY 0       /* tiny_dw_kernel: at most 4 slab columns over a long row */
+#define EBEN_DW_ROUTE_ONE_ROW 1    /* m1_dw_kernel: the c_out = 1 logits layers */
+#define EBEN_DW_ROUTE_DW3 2        /* conv_dw3.hip: bf16 operands */
+#define EBEN_DW_ROUTE_DW2 3        /* conv_dw2.hip: fp32, pre-transposed A image */
+#define EBEN_DW_ROUTE_FALLBACK 4   /* conv_dw_kernel (conv_dw.hip) */
+EBEN_API int eben_conv1d_bwd_dw_variant(const EbenConv1dDesc* d, int* out, int n);
 
 /* ---- bf16 BUNDLE LAYOUT of the discriminator engine ------------------------------------------------------------------------
  * A (batch, channels, length) tensor, channels a multiple of 8, at rest as bf16 [batch][channels / 8][length][8]: one 16-byte UNIT =

@@ -255,6 +255,9 @@ int dw2_launch(const Canon& c, Dw2Args a, float* workspace, size_t ws_bytes, hip
 
 // bf16-operand weight-gradient kernel (conv_dw3.hip): k-step = one time step x 16 batch items
 int dw3_applicable(const Canon& c);
+// the instantiations a covered layer runs -- conv_dw3_kernel<FM, FN, WAVES_M, XRB, SP>, dw3_pack_a_kernel<MT> -- and its plan
+struct Dw3Variant { int FM, FN, WAVES_M, XRB, SP, MT, BKT, nsplit, nchunks, nnt, nmt, nbg; };
+int dw3_variant(const Canon& c, Dw3Variant* v);   // 0: not covered (v untouched)
 size_t dw3_workspace(const Canon& c, int* nslab, int* row_stride);
 int dw3_launch(const Canon& c, const float* a, const float* amask, float a_slope, const float* x, float x_slope, int has_bias, float* workspace,
                size_t ws_bytes, hipStream_t st);

@@ -691,23 +691,50 @@ extern "C" int eben_wn_bwd(const float* dw_slabs, int nslab, size_t slab_stride,
   return EBEN_OK;
 }
 
+// The kernel family a layer's weight gradient runs on (EBEN_DW_ROUTE_*).  THE decision: the workspace size, the launch and the query
+// (eben_conv1d_bwd_dw_variant) read it.
+static int dw_route(const Canon& c, const EbenConv1dDesc* d) {
+  if (tiny_dw_applicable(c, d)) return EBEN_DW_ROUTE_TINY;
+  if (m1_dw_applicable(c, d)) return EBEN_DW_ROUTE_ONE_ROW;
+  if ((d->out_slope == 1.f || !d->transposed) && dw3_applicable(c)) return EBEN_DW_ROUTE_DW3;   // bf16 math (no mask on the X operand)
+  if (dw2_applicable(c)) return EBEN_DW_ROUTE_DW2;
+  return EBEN_DW_ROUTE_FALLBACK;
+}
+
+extern "C" int eben_conv1d_bwd_dw_variant(const EbenConv1dDesc* d, int* out, int n) {
+  EBEN_REQUIRE(out && n >= 13, "eben_conv1d_bwd_dw_variant: 13 output slots");
+  Canon c;
+  const int rc = canon_from_desc(d, &c);
+  if (rc) return rc;
+  for (int i = 0; i < 13; ++i) out[i] = 0;
+  out[0] = dw_route(c, d);
+  if (out[0] == EBEN_DW_ROUTE_DW3) {
+    Dw3Variant v;
+    if (!dw3_variant(c, &v)) return fail(EBEN_EUNSUPPORTED, "eben_conv1d_bwd_dw_variant: no conv_dw3 plan for a layer routed there");
+    const int f[12] = {v.FM, v.FN, v.WAVES_M, v.XRB, v.SP, v.MT, v.BKT, v.nsplit, v.nchunks, v.nnt, v.nmt, v.nbg};
+    for (int i = 0; i < 12; ++i) out[1 + i] = f[i];
+  }
+  return EBEN_OK;
+}
+
 extern "C" size_t eben_conv1d_bwd_dw_workspace(const EbenConv1dDesc* d, int* nslab, int* row_stride) {
   Canon c;
   if (canon_from_desc(d, &c) != EBEN_OK) return 0;
-  if (tiny_dw_applicable(c, d)) {
+  const int route = dw_route(c, d);
+  if (route == EBEN_DW_ROUTE_TINY) {
     const int rs = (c.Cin / c.g) * c.k + 1;
     if (nslab) *nslab = c.B;
     if (row_stride) *row_stride = rs;
     return sizeof(float) * (size_t)c.B * c.Cout * rs;
   }
-  if (m1_dw_applicable(c, d)) {
+  if (route == EBEN_DW_ROUTE_ONE_ROW) {
     const int rs = c.Cin * c.k + 1;
     if (nslab) *nslab = c.B;
     if (row_stride) *row_stride = rs;
     return sizeof(float) * (size_t)c.B * rs;
   }
-  if ((d->out_slope == 1.f || !d->transposed) && dw3_applicable(c)) return dw3_workspace(c, nslab, row_stride);   // bf16 math (no mask on the X operand)
-  if (dw2_applicable(c)) return dw2_workspace(c, nslab, row_stride);
+  if (route == EBEN_DW_ROUTE_DW3) return dw3_workspace(c, nslab, row_stride);
+  if (route == EBEN_DW_ROUTE_DW2) return dw2_workspace(c, nslab, row_stride);
   DwPlan p;
   make_dw_plan(c, &p);
   if (nslab) *nslab = p.nsplit;
@@ -723,7 +750,8 @@ extern "C" int eben_conv1d_bwd_dw(const EbenConv1dDesc* d, const float* dy, cons
   EBEN_REQUIRE(dy && x && slabs, "null pointer in conv1d_bwd_dw");
   EBEN_REQUIRE(d->out_slope == 1.f || y, "y is required to differentiate the fused output activation");
   EBEN_REQUIRE(!(d->transposed && has_bias), "ConvTranspose1d bias gradient is not provided by this kernel");
-  if (tiny_dw_applicable(c, d)) {
+  const int route = dw_route(c, d);
+  if (route == EBEN_DW_ROUTE_TINY) {
     DwArgs a{};
     a.a = dy; a.amask = y; a.a_mode = d->out_slope != 1.f ? 1 : 0; a.a_slope = a.a_mode ? d->out_slope : 1.f;
     a.x = x; a.xmask = nullptr; a.x_mode = 0; a.x_slope = d->in_slope;
@@ -739,7 +767,7 @@ extern "C" int eben_conv1d_bwd_dw(const EbenConv1dDesc* d, const float* dy, cons
     EBEN_CHECK_LAUNCH("tiny_dw_kernel");
     return EBEN_OK;
   }
-  if (m1_dw_applicable(c, d)) {
+  if (route == EBEN_DW_ROUTE_ONE_ROW) {
     DwArgs a{};
     a.a = dy; a.amask = y; a.a_mode = d->out_slope != 1.f ? 1 : 0; a.a_slope = a.a_mode ? d->out_slope : 1.f;
     a.x = x; a.xmask = nullptr; a.x_mode = 0; a.x_slope = d->in_slope;
@@ -753,12 +781,12 @@ extern "C" int eben_conv1d_bwd_dw(const EbenConv1dDesc* d, const float* dy, cons
     EBEN_CHECK_LAUNCH("m1_dw_kernel");
     return EBEN_OK;
   }
-  if ((d->out_slope == 1.f || !d->transposed) && dw3_applicable(c)) {
+  if (route == EBEN_DW_ROUTE_DW3) {
     if (!d->transposed)   // the gradient operand carries the activation derivative of the fused output stage
       return dw3_launch(c, dy, d->out_slope != 1.f ? y : nullptr, d->out_slope, x, d->in_slope, has_bias ? 1 : 0, slabs, ws_bytes, as_stream(stream));
     return dw3_launch(c, x, nullptr, d->in_slope, dy, 1.f, 0, slabs, ws_bytes, as_stream(stream));
   }
-  if (dw2_applicable(c)) {
+  if (route == EBEN_DW_ROUTE_DW2) {
     Dw2Args a2;
     if (!d->transposed) {
       a2.a = dy; a2.amask = y; a2.a_mode = d->out_slope != 1.f ? 1 : 0; a2.a_slope = d->out_slope;

@@ -395,8 +395,23 @@ static void make_dw3_plan(const Canon& c, Dw3Plan* p) {
   p->ok = 1;
 }
 
+// The kernels a plan runs: conv_dw3_kernel<FM, FN, WAVES_M, XRB, SP> behind dw3_pack_a_kernel<MT>.  THE decision: the launch and the
+// query (eben_conv1d_bwd_dw_variant) read it.  Row configuration = the plan's row-tile height (128 / 96 / 64 / 32 rows), eight X-tile
+// units per thread where the tile needs them, hi + lo X tiles for a split operand (whose plans keep to four units).
+static Dw3Variant dw3_variant_of(const Dw3Plan& p) {
+  static const int rows[4][3] = {{2, 2, 2}, {3, 1, 1}, {2, 1, 1}, {1, 1, 1}};   // FM, FN, WAVES_M of cfg 0..3
+  Dw3Variant v;
+  v.FM = rows[p.cfg][0]; v.FN = rows[p.cfg][1]; v.WAVES_M = rows[p.cfg][2];
+  v.XRB = p.xrb == 8 ? 8 : 4;
+  v.SP = (v.XRB <= 4 && p.split) ? 1 : 0;
+  v.MT = v.FM * v.WAVES_M;
+  v.BKT = p.BKT; v.nsplit = p.nsplit; v.nchunks = p.nchunks; v.nnt = p.nnt; v.nmt = p.nmt; v.nbg = p.nbg;
+  return v;
+}
+
 template <int FM, int FN, int WAVES_M, int XRB, bool SP>
-static int launch_dw3_sp(const Dw3Args& a, const Dw3Plan& p, hipStream_t st) {
+static int launch_dw3_sp(const Dw3Variant& v, const Dw3Args& a, const Dw3Plan& p, hipStream_t st) {
+  EBEN_REQUIRE(v.FM == FM && v.FN == FN && v.WAVES_M == WAVES_M && v.XRB == XRB && (v.SP != 0) == SP, "conv_dw3: launch and variant disagree");
   static LdsAttrOnce attr_once;
   auto kern = conv_dw3_kernel<FM, FN, WAVES_M, XRB, SP>;
   {
@@ -413,17 +428,31 @@ static int launch_dw3_sp(const Dw3Args& a, const Dw3Plan& p, hipStream_t st) {
   return EBEN_OK;
 }
 
-template <int FM, int FN, int WAVES_M, int XRB>
-static int launch_dw3(const Dw3Args& a, const Dw3Plan& p, hipStream_t st) {
-  if constexpr (XRB <= 4) {
-    if (p.split) return launch_dw3_sp<FM, FN, WAVES_M, XRB, true>(a, p, st);
+template <int XRB, bool SP>
+static int launch_dw3_rows(const Dw3Variant& v, const Dw3Args& a, const Dw3Plan& p, hipStream_t st) {
+  switch (v.MT) {
+    case 4: return launch_dw3_sp<2, 2, 2, XRB, SP>(v, a, p, st);
+    case 3: return launch_dw3_sp<3, 1, 1, XRB, SP>(v, a, p, st);
+    case 2: return launch_dw3_sp<2, 1, 1, XRB, SP>(v, a, p, st);
+    default: return launch_dw3_sp<1, 1, 1, XRB, SP>(v, a, p, st);
   }
-  return launch_dw3_sp<FM, FN, WAVES_M, XRB, false>(a, p, st);
+}
+
+static int launch_dw3_variant(const Dw3Variant& v, const Dw3Args& a, const Dw3Plan& p, hipStream_t st) {
+  if (v.XRB == 8) return launch_dw3_rows<8, false>(v, a, p, st);
+  return v.SP ? launch_dw3_rows<4, true>(v, a, p, st) : launch_dw3_rows<4, false>(v, a, p, st);
 }
 
 int dw3_applicable(const Canon& c) {
   Dw3Plan p;
   make_dw3_plan(c, &p);
+  return p.ok;
+}
+
+int dw3_variant(const Canon& c, Dw3Variant* v) {
+  Dw3Plan p;
+  make_dw3_plan(c, &p);
+  if (p.ok) *v = dw3_variant_of(p);
   return p.ok;
 }
 
@@ -453,20 +482,7 @@ int dw3_launch(const Canon& c, const float* a, const float* amask, float a_slope
   k.nsplit = p.nsplit; k.nct = p.nct; k.nbg = p.nbg; k.nchunks = p.nchunks; k.nnt = p.nnt; k.nmt = p.nmt;
   k.XSTR = p.XSTR; k.HS = p.HS; k.nch_max = p.nch_max; k.BKT = p.BKT;
   k.slab_stride = p.slab_stride;
-  if (p.xrb == 8) {
-    switch (p.cfg) {
-      case 0: return launch_dw3<2, 2, 2, 8>(k, p, st);
-      case 1: return launch_dw3<3, 1, 1, 8>(k, p, st);
-      case 2: return launch_dw3<2, 1, 1, 8>(k, p, st);
-      default: return launch_dw3<1, 1, 1, 8>(k, p, st);
-    }
-  }
-  switch (p.cfg) {
-    case 0: return launch_dw3<2, 2, 2, 4>(k, p, st);
-    case 1: return launch_dw3<3, 1, 1, 4>(k, p, st);
-    case 2: return launch_dw3<2, 1, 1, 4>(k, p, st);
-    default: return launch_dw3<1, 1, 1, 4>(k, p, st);
-  }
+  return launch_dw3_variant(dw3_variant_of(p), k, p, st);
 }
 
 }  // namespace eben
