@@ -638,6 +638,17 @@ EBEN_API int eben_resample_adjoint(const float* g, const float* kernels, float* 
 EBEN_API int eben_edge_fill(float* x, const int32_t* lens, int rows, int channels, int l_buf, int mode, int count, void* stream);
 EBEN_API int eben_edge_zero(float* x, const int32_t* lens, int rows, int channels, int l_buf, void* stream);
 
+/* ---- streaming inference (csrc/stream.hip): a layer's input for this push from the previous push's buffer and fresh output ------
+ * dst[rc, j] = prev[rc, prev_off + j] for j < n_carry; dst[rc, n_carry + j] = src[rc, src_off + j] (+ add[rc, add_off + j]) for
+ * j < n_new; rc < rows_channels.  fp32 [row][C][L] tensors, each with its own row pitch (in floats); offsets and counts are
+ * arbitrary.  prev may be NULL when n_carry == 0, src when n_new == 0, add always (no second source).  EBEN_EINVAL before any launch
+ * for a null or misaligned-to-4 pointer, a negative offset or count, n_carry + n_new == 0, an offset plus its count past its pitch,
+ * n_carry + n_new past dst_pitch, or a dst extent (rows_channels * dst_pitch floats) that overlaps the extent of a source in use.
+ * Added without a version bump: a function only. */
+EBEN_API int eben_stream_splice(float* dst, int dst_pitch, const float* prev, int prev_pitch, int prev_off, int n_carry, const float* src,
+                                int src_pitch, int src_off, int n_new, const float* add, int add_pitch, int add_off, int rows_channels,
+                                void* stream);
+
 /* ---- misc ------------------------------------------------------------------------------- */
 /* out[0] = sqrt(sum x^2) (torch.norm at eben.py:226); `out` must hold 257 floats (scratch) */
 EBEN_API int eben_l2norm(const float* x, size_t n, float* out, void* stream);

@@ -221,6 +221,7 @@ SIGNATURES = {
     "eben_resample_adjoint": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "eben_edge_fill": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "eben_edge_zero": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
+    "eben_stream_splice": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -415,6 +415,84 @@ class GeneratorEngine:
         fill("enhanced", enhanced)
         return enhanced, bands
 
+    # ---- streaming: one push of a stream schedule, inference only (vibravox_amd/streaming.py) -----------------------------------------
+    def stream_state(self, plan, streams: int, device) -> "StreamState":
+        """The plan's state tensors for ``streams`` rows on ``device``: two buffers per tensor, allocated here once."""
+        return StreamState(plan, streams, device)
+
+    def _stream_node(self, name: str, x: torch.Tensor) -> torch.Tensor:
+        """Node ``name`` of the stream on its buffer: the launch ``forward(.., train=False)`` makes for that layer."""
+        gen = self.gen
+        slope = gen.nl.negative_slope
+        if name == "pqmf.analysis":
+            return gen.pqmf(x, "analysis", bands=gen.p)
+        if name == "pqmf.synthesis":
+            return gen.pqmf.synthesis_sum(x)
+        if name == "first_conv":
+            return self._conv(gen.first_conv, x, False)
+        if name == "last_conv":
+            return gen.last_conv(x)
+        part, *rest = name.split(".")
+        if part == "latent_conv":
+            return self._conv(gen.latent_conv[int(rest[0])], x, False, in_slope=slope if rest[0] == "1" else None)
+        blk = (gen.encoder_blocks if part == "encoder_blocks" else gen.decoder_blocks)[int(rest[0])]
+        if rest[1] == "residuals":
+            first_of_encoder = part == "encoder_blocks" and rest[2] == "0"
+            return self._residual_unit(blk.residuals[int(rest[2])], x, slope if first_of_encoder else 1.0, False, None)
+        return self._conv(getattr(blk, rest[1]), x, False)
+
+    def stream_run(self, state: "StreamState", operations, chunk: Optional[torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """Executes one push's operations (``streaming.Schedule.push``) on ``state``; returns the tensors emitted, by output name.
+        Every input is spliced by ``eben_stream_splice`` and every layer launched as ``forward`` launches it; nothing waits."""
+        from .streaming import Splice
+
+        if torch.is_grad_enabled():
+            raise RuntimeError("EBEN generator engine: stream_run has no backward; call it under torch.no_grad()")
+        lib = load()
+        ops.join_prepack()
+        rows = state.rows
+        outs: Dict[str, torch.Tensor] = {}
+        emitted: Dict[str, torch.Tensor] = {}
+
+        def operand(name):
+            if name is None:
+                return None
+            if name == "input":
+                return chunk
+            kind, key = name.split(":", 1)
+            return outs[key] if kind == "out" else state.view(key)
+
+        for op in operations:
+            if not isinstance(op, Splice):
+                if op.node == "lift":
+                    y = ops.tanh_lift(outs["last_conv"], state.view("lift.operand"))
+                else:
+                    x = state.view(op.node)
+                    if x.shape[2] != op.l_in:
+                        raise RuntimeError(f"stream state out of step with the schedule: {op} on a buffer of {x.shape[2]}")
+                    y = self._stream_node(op.node, x)
+                if y.shape[2] != op.l_out:
+                    raise RuntimeError(f"stream schedule out of step with the kernels: {op} gave {y.shape[2]} samples")
+                outs[op.node] = y
+                continue
+            total = op.n_carry + op.n_new
+            kind, key = op.dst.split(":", 1)
+            if total == 0:
+                state.length[key] = 0
+                continue
+            prev, src, add = operand(op.prev), operand(op.src), operand(op.add)
+            channels = (prev if prev is not None else src).shape[1]
+            if kind == "emit":
+                dst = emitted[key] = torch.empty((rows, channels, total), dtype=torch.float32, device=state.device)
+            else:
+                dst = state.twin(key, total)
+            pitch = lambda t: 0 if t is None else t.shape[2]
+            check(lib.eben_stream_splice(ptr(dst), total, ptr(prev), pitch(prev), op.prev_off, op.n_carry, ptr(src), pitch(src), op.src_off, op.n_new,
+                                         ptr(add), pitch(add), op.add_off, rows * channels, stream()), "stream_splice")
+            if kind == "tape":
+                state.flip(key, total)
+        return emitted
+
     # ---- backward ------------------------------------------------------------------------------------
     def _dx(self, rec: _ConvRec, dy, res_pre=None, res_post=None):
         lib = load()
@@ -771,6 +849,40 @@ class GeneratorEngine:
                 else:
                     with torch.cuda.stream(side):
                         sink.mark_ready([p for p, _ in assign])
+
+
+class StreamState:
+    """Device state of one ``StreamingEnhancer``: per tensor of the plan two flat buffers of ``capacity`` samples per (row, channel) --
+    a splice reads one and writes the other -- and the length the current one holds, as a contiguous (rows, channels, length) view."""
+
+    def __init__(self, plan, streams: int, device):
+        self.plan, self.rows = plan, int(streams)
+        self.device = torch.empty(0, device=device).device   # with its index, as tensors report it
+        self.channels = {t.name: t.channels for t in plan.tensors}
+        self.capacity = {t.name: t.capacity for t in plan.tensors}
+        self.buffers = {t.name: [torch.empty(self.rows * t.channels * t.capacity, dtype=torch.float32, device=self.device) for _ in range(2)]
+                        for t in plan.tensors}
+        self.reset()
+
+    def reset(self) -> None:
+        self.current = {name: 0 for name in self.buffers}
+        self.length = {name: 0 for name in self.buffers}
+
+    def _shaped(self, name: str, which: int, length: int) -> torch.Tensor:
+        c = self.channels[name]
+        return self.buffers[name][which][: self.rows * c * length].view(self.rows, c, length)
+
+    def view(self, name: str) -> torch.Tensor:
+        return self._shaped(name, self.current[name], self.length[name])
+
+    def twin(self, name: str, length: int) -> torch.Tensor:
+        """The buffer a splice writes: the one the current view does not live in."""
+        if length > self.capacity[name]:
+            raise RuntimeError(f"stream state: {name} needs {length} samples, the plan allots {self.capacity[name]}")
+        return self._shaped(name, 1 - self.current[name], length)
+
+    def flip(self, name: str, length: int) -> None:
+        self.current[name], self.length[name] = 1 - self.current[name], length
 
 
 class _CoreFn(torch.autograd.Function):

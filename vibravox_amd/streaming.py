@@ -1,0 +1,465 @@
+"""Streaming inference of the EBEN generator: audio that is still arriving, enhanced chunk by chunk with carried state.
+
+The generator is a finite-context network.  A layer's output at position o reads only the input samples its taps reach, so once a
+tensor is exact up to some frontier, every consumer can be run on ``[carry | new]`` -- the samples in front of the new ones that its
+first new output still reaches, then the new ones -- and each sample of each layer is computed exactly once.  The conv kernels are
+the whole-clip ones: they apply their edge rule at both ends of whatever buffer they get, so the outputs next to a buffer's ends
+are junk unless the end is the stream's own (position 0, or the cut length after ``finish``), and the schedule keeps only the
+outputs whose taps stay inside the buffer.
+
+Everything here is arithmetic on positions (host only, no GPU needed):
+
+  * ``Schedule`` tracks, per tensor, the stream positions ``[S, F)`` its buffer holds and from where the next push still needs it, and
+    turns one push into a list of ``Splice`` / ``Launch`` operations with buffer-relative offsets.  Warm-up (growing buffers with a
+    true left edge), the steady state and ``finish`` (a true right edge) are the same rules; in the steady state the list repeats.
+  * ``plan`` runs a schedule to its steady state and reads off, per tensor: rate, new samples per push, frontier lag, carry, buffer
+    length and capacity; and ``lookahead`` / ``latency``.
+  * ``StreamingEnhancer`` executes the operations on the device through ``GeneratorEngine``; ``tests/stream_oracle.py`` executes the
+    same operations in float64 on poisoned buffers.
+
+Audio hold-back: ``cut_to_valid_length`` drops up to ``multiple - 1`` samples from the end of a clip, so a sample pushed now may turn
+out to lie behind the stream's valid length.  The analysis bank therefore treats only ``ragged.cut_length(pushed)`` samples as
+final (for pushes of whole multiples that is ``pushed - n % multiple``): nothing computed ever depends on a sample that is dropped.
+"""
+from __future__ import annotations
+
+import dataclasses
+from typing import Dict, List, Optional, Tuple
+
+from . import ragged
+
+
+@dataclasses.dataclass(frozen=True)
+class Node:
+    name: str        # module path, as in ragged.plan; its input tape has the same name
+    kind: str        # "analysis" | "conv" | "unit" | "convT" | "lift" | "synthesis"
+    c_in: int
+    c_out: int
+    ksize: int
+    stride: int
+    dilation: int
+    pad_l: int
+    pad_r: int
+    reflect: bool
+    rate: int                    # audio samples per sample of its INPUT
+    add: Optional[str] = None    # hold tape added to the new samples of its input (the decoder's skip add)
+    feeds: Tuple[str, ...] = ()  # hold / output tapes that receive its new exact outputs
+
+
+@dataclasses.dataclass(frozen=True)
+class Splice:
+    """dst := [prev[prev_off : prev_off + n_carry] | src[src_off : src_off + n_new] (+ add[add_off : ...])]; the dst buffer is
+    n_carry + n_new long afterwards (0: emptied, nothing runs).  Names: ``tape:X`` a state buffer (written through its ping-pong
+    twin), ``out:X`` the latest output of node X, ``input`` the pushed chunk, ``emit:X`` a tensor handed to the caller."""
+    dst: str
+    prev: Optional[str]
+    prev_off: int
+    n_carry: int
+    src: Optional[str]
+    src_off: int
+    n_new: int
+    add: Optional[str] = None
+    add_off: int = 0
+
+
+@dataclasses.dataclass(frozen=True)
+class Launch:
+    """Node ``node`` on its tape of ``l_in`` samples (``lift``: on ``out:last_conv`` and ``tape:lift.operand``) -> ``out:node`` of
+    ``l_out``; its outputs [lo, hi) are the new exact ones, everything outside is junk or was delivered before."""
+    node: str
+    l_in: int
+    l_out: int
+    lo: int
+    hi: int
+
+
+@dataclasses.dataclass
+class _Tape:
+    name: str
+    channels: int
+    rate: int
+    S: int = 0      # stream position of the buffer's first sample
+    F: int = 0      # ... behind its last one: the tensor's exact frontier as delivered here
+    keep: int = 0   # the next splice keeps [keep, F)
+
+
+def _ceil(a: int, b: int) -> int:
+    return -((-a) // b)
+
+
+def nodes_of(gen) -> List[Node]:
+    """The generator as stream nodes: ``ragged``'s layer walk with the two PQMF banks and the tanh lift added."""
+    m, n, p = gen.pqmf.decimation, gen.pqmf.kernel_size, gen.p
+    n_enc = len(gen.encoder_blocks)
+    out = [Node("pqmf.analysis", "analysis", 1, p, n, m, 1, n - 1, n - 1, False, 1, feeds=("first_bands",))]
+    levels, steps = ragged._walk(gen, (gen.multiple * 64 - n,), 0)
+    rate = [1] + [m * (levels[1][0] // lv[0]) for lv in levels[1:]]
+    for path, spec, lv in steps:
+        unit = ".residuals." in path
+        kind = "convT" if spec.transposed else "unit" if unit else "conv"
+        add, feeds = None, ()
+        if path.startswith("encoder_blocks.") and path.endswith(".conv"):
+            feeds = (f"skip.{int(path.split('.')[1])}",)
+        if path.startswith("decoder_blocks.") and path.endswith(".conv_trans"):
+            add = f"skip.{n_enc - 1 - int(path.split('.')[1])}"
+        out.append(Node(path, kind, spec.c_in, spec.c_in if unit else spec.c_out, spec.ksize, spec.stride, spec.dilation, spec.pad_l,
+                        spec.pad_l if spec.transposed else spec.pad_r, bool(spec.reflect), rate[lv], add, feeds))
+    out.append(Node("lift", "lift", m, m, 1, 1, 1, 0, 0, False, m, feeds=("bands",)))
+    out.append(Node("pqmf.synthesis", "synthesis", m, 1, n, m, 1, 0, 0, False, m, feeds=("enhanced",)))
+    return out
+
+
+class Schedule:
+    """Positions of one stream (all rows advance in lockstep).  ``push(n)`` / ``push(n, final=True)`` return the operations of that
+    push; the executor owns the buffers.  After a final push the schedule is spent until ``reset()``."""
+
+    def __init__(self, gen, chunk_samples: int):
+        chunk_samples = int(chunk_samples)
+        if chunk_samples <= 0 or chunk_samples % gen.multiple:
+            raise ValueError(f"chunk_samples must be a positive multiple of {gen.multiple}, got {chunk_samples}")
+        self.gen, self.chunk = gen, chunk_samples
+        self.m, self.n = gen.pqmf.decimation, gen.pqmf.kernel_size
+        self.nodes = nodes_of(gen)
+        self.by_name = {nd.name: nd for nd in self.nodes}
+        self.out_chunk = {"enhanced": chunk_samples, "bands": chunk_samples // self.m}
+        self.reset()
+
+    def reset(self) -> None:
+        self.pushed, self.finished = 0, False
+        self.tapes: Dict[str, _Tape] = {}
+        for nd in self.nodes:
+            if nd.kind != "lift":
+                self.tapes[nd.name] = _Tape(nd.name, nd.c_in, nd.rate)
+            for f in nd.feeds:   # holds and outputs: at the rate of the producing node's OUTPUT
+                self.tapes[f] = _Tape(f, nd.c_out, self.out_rate(nd))
+        self.tapes["lift.operand"] = _Tape("lift.operand", self.gen.p, self.m)
+        self.out_f = {nd.name: 0 for nd in self.nodes}   # exact frontier of each node's output
+        self.emitted = {"enhanced": 0, "bands": 0}
+
+    def out_rate(self, nd: Node) -> int:
+        if nd.kind == "analysis":
+            return self.m
+        if nd.kind == "synthesis":
+            return 1
+        return nd.rate // nd.stride if nd.kind == "convT" else nd.rate * nd.stride
+
+    # ---- one node on the tape [S, F): (base, l_out, lo, hi, keep) or None when it cannot run ----------------------------------------
+    def _geometry(self, nd: Node, S: int, F: int, end: bool):
+        """``base``: stream position of output 0; [lo, hi): the exact outputs; ``keep``: the first input the output ``hi`` reads (for a
+        strided conv rounded down to its stride, where the next buffer may start)."""
+        L, k, s, d, pl = F - S, nd.ksize, nd.stride, nd.dilation, nd.pad_l
+        if L <= 0:
+            return None
+        if nd.kind in ("analysis", "conv", "unit"):
+            if S % s:
+                raise RuntimeError(f"stream schedule: {nd.name} starts at {S}, not a multiple of its stride {s}")
+            span = (k - 1) * d
+            if L + pl + nd.pad_r - span < 1 or (nd.reflect and max(pl, nd.pad_r) >= L) or (nd.kind == "unit" and d >= L):
+                return None
+            base, l_out = S // s, (L + pl + nd.pad_r - span - 1) // s + 1
+            lo = base + _ceil(pl, s)
+        elif nd.kind == "convT":   # output o sums the inputs i with 0 <= o + pad - i stride <= k - 1
+            base, l_out = S * s, (L - 1) * s - 2 * pl + k
+            lo = base + k - s - pl
+        else:                      # synthesis: x[u] sums the frames t with u <= t m <= u + n - 1; m L - n outputs, none reads in front of S
+            base, l_out = S * s, s * L - k
+            lo = base
+        if l_out < 1:
+            return None
+        # the analysis bank treats only cut_length(pushed) samples as final
+        hi = base + l_out if end else min(base + l_out, _frontier(nd, ragged.cut_length(self.gen, F) if nd.kind == "analysis" else F))
+        if nd.kind == "convT":
+            keep = _ceil(hi + pl - k + 1, s)
+        elif nd.kind == "synthesis":
+            keep = _ceil(hi, s)
+        else:
+            keep = (hi * s - pl) // s * s
+        return base, l_out, 0 if S == 0 else lo, hi, max(0, keep)
+
+    def _feed(self, ops: list, tape: _Tape, src: Optional[str], base: int, lo: int, hi: int, add: Optional[_Tape] = None) -> None:
+        """The new exact samples [lo, hi) of ``src`` (whose sample 0 sits at ``base``) behind what the tape keeps."""
+        if lo != tape.F or not tape.S <= tape.keep <= tape.F:
+            raise RuntimeError(f"stream schedule: {tape.name} holds [{tape.S}, {tape.F}), keeps from {tape.keep}, fed [{lo}, {hi})")
+        n_carry, n_new = tape.F - tape.keep, hi - lo
+        if n_new == 0 and tape.keep == tape.S:
+            return
+        add_off = 0
+        if add is not None and n_new:
+            if not (add.S <= lo and hi <= add.F):
+                raise RuntimeError(f"stream schedule: {add.name} holds [{add.S}, {add.F}), {tape.name} adds [{lo}, {hi})")
+            add_off = lo - add.S
+        ops.append(Splice("tape:" + tape.name, "tape:" + tape.name if n_carry else None, tape.keep - tape.S if n_carry else 0, n_carry,
+                          src if n_new else None, lo - base if n_new else 0, n_new,
+                          "tape:" + add.name if add is not None and n_new else None, add_off))
+        tape.S, tape.F = tape.keep, hi
+        if add is not None:
+            add.keep = hi
+
+    def _emit(self, ops: list, name: str, src: str, base: int, lo: int, hi: int, final: bool) -> None:
+        """Output ``name`` leaves in whole chunks (everything at the end); what is not out yet waits in its tape."""
+        tape, c = self.tapes[name], self.out_chunk[name]
+        held, n_new, off = tape.F - tape.S, hi - lo, lo - base
+        if lo != tape.F:
+            raise RuntimeError(f"stream schedule: output {name} holds up to {tape.F}, fed [{lo}, {hi})")
+        if final or held + n_new >= c:
+            take = n_new if final else c - held
+            if held + take:
+                ops.append(Splice("emit:" + name, "tape:" + name if held else None, 0, held, src if take else None, off if take else 0, take))
+            rest = n_new - take
+            ops.append(Splice("tape:" + name, None, 0, 0, src if rest else None, off + take if rest else 0, rest))
+            self.emitted[name] += held + take
+            tape.S, tape.F = hi - rest, hi
+        elif n_new:
+            ops.append(Splice("tape:" + name, "tape:" + name if held else None, 0, held, src, off, n_new))
+            tape.F = hi
+        tape.keep = tape.S
+
+    def push(self, n_in: int, final: bool = False) -> List[object]:
+        if self.finished:
+            raise RuntimeError("this stream has finished; reset() starts a new one")
+        if n_in < 0 or (not final and n_in != self.chunk) or (final and n_in >= self.chunk):
+            raise ValueError(f"a push takes {self.chunk} samples, the final one fewer, got {n_in}")
+        total = self.pushed + n_in
+        end_audio = total
+        if final:
+            ragged.plan(self.gen, [total])   # refuses a stream below the shortest clip, in the words of the batch forward
+            end_audio = ragged.cut_length(self.gen, total)
+            self.finished = True
+        ops: List[object] = []
+        a = self.tapes["pqmf.analysis"]
+        if end_audio < a.keep:
+            raise RuntimeError(f"stream schedule: the stream ends at {end_audio}, in front of what the analysis keeps ({a.keep})")
+        n_carry, n_new = min(a.F, end_audio) - a.keep, max(0, end_audio - a.F)
+        if n_new or a.keep != a.S or end_audio < a.F:
+            ops.append(Splice("tape:pqmf.analysis", "tape:pqmf.analysis" if n_carry else None, a.keep - a.S if n_carry else 0, n_carry,
+                              "input" if n_new else None, 0, n_new))
+        a.S, a.F = a.keep, end_audio
+        self.pushed = total
+        fresh = ("input", 0, 0, 1)   # (name, base, lo, hi) of the producer's new exact outputs; None: nothing new
+        last_len = 0
+        for i, nd in enumerate(self.nodes):
+            if nd.kind == "lift":
+                if fresh is None:
+                    continue
+                _, base, lo, hi = fresh
+                fb, lc = self.tapes["first_bands"], self.tapes["last_conv"]
+                if not (fb.S <= base and base + last_len <= fb.F):
+                    raise RuntimeError(f"stream schedule: first_bands holds [{fb.S}, {fb.F}), the lift reads [{base}, {base + last_len})")
+                ops.append(Splice("tape:lift.operand", None, 0, 0, "tape:first_bands", base - fb.S, last_len))
+                ops.append(Launch("lift", last_len, last_len, lo - base, hi - base))
+                op = self.tapes["lift.operand"]
+                op.S = op.keep = base
+                op.F = base + last_len
+                fb.keep = lc.keep   # where last_conv's next output starts
+                fresh = ("out:lift", base, lo, hi)
+                self.out_f["lift"] = hi
+                self._emit(ops, "bands", "out:lift", base, lo, hi, final)
+                continue
+            tape = self.tapes[nd.name]
+            if i > 0 and fresh is not None:
+                self._feed(ops, tape, *fresh, add=self.tapes[nd.add] if nd.add else None)
+            if fresh is None and not final:
+                continue
+            g = self._geometry(nd, tape.S, tape.F, final)
+            done = self.out_f[nd.name]
+            if g is None or g[3] <= done:
+                if final and g is None:
+                    raise RuntimeError(f"stream schedule: {nd.name} cannot run on the last {tape.F - tape.S} samples")
+                fresh = None
+                continue
+            base, l_out, lo, hi, keep = g
+            if lo > done:
+                raise RuntimeError(f"stream schedule: {nd.name} delivered up to {done}, its buffer yields [{lo}, {hi})")
+            ops.append(Launch(nd.name, tape.F - tape.S, l_out, done - base, hi - base))
+            fresh = ("out:" + nd.name, base, done, hi)
+            self.out_f[nd.name], tape.keep, last_len = hi, max(tape.S, min(keep, tape.F)), l_out
+            for f in nd.feeds:
+                if f in self.out_chunk:
+                    self._emit(ops, f, *fresh, final)
+                else:
+                    self._feed(ops, self.tapes[f], *fresh)
+        if final:   # an output whose producer had nothing new at the end still hands over what it holds
+            for name in self.out_chunk:
+                t = self.tapes[name]
+                if t.F > t.S:
+                    self._emit(ops, name, None, t.F, t.F, t.F, True)
+        return ops
+
+
+def _frontier(nd: Node, f: int) -> int:
+    """Outputs of ``nd`` that read nothing but its first ``f`` inputs (the left edge is the stream's own)."""
+    if f <= 0:
+        return 0
+    if nd.kind in ("analysis", "conv", "unit"):   # o stride - pad_l + (k - 1) dil <= f - 1
+        return max(0, (f - 1 - (nd.ksize - 1) * nd.dilation + nd.pad_l) // nd.stride + 1)
+    if nd.kind == "convT":                        # floor((o + pad) / stride) <= f - 1
+        return max(0, f * nd.stride - nd.pad_l)
+    if nd.kind == "synthesis":                    # of the m f - n outputs a buffer of f frames yields
+        return max(0, f * nd.stride - nd.ksize)
+    return f
+
+
+def exact_frontier(gen, audio: int) -> int:
+    """Enhanced samples that depend on nothing but the first ``audio`` input samples, by the schedule's rules (no hold-back)."""
+    f = audio
+    for nd in nodes_of(gen):
+        f = _frontier(nd, f)
+    return f
+
+
+@dataclasses.dataclass(frozen=True)
+class TensorPlan:
+    name: str        # the layer whose input it is, or first_bands / skip.i (holds), lift.operand, bands / enhanced (outputs)
+    channels: int
+    rate: int        # audio samples per sample
+    new: int         # samples gained per push in the steady state
+    lag: int         # pushed / rate - exact frontier, in its own samples
+    carry: int       # samples in front of the new ones that the next push still needs
+    length: int      # carry + new: the steady-state buffer
+    capacity: int    # samples per (row, channel) of its two state buffers: covers warm-up and finish
+
+
+@dataclasses.dataclass(frozen=True)
+class StreamPlan:
+    chunk_samples: int
+    multiple: int
+    hold: int                          # pushed samples the analysis bank does not treat as final yet
+    lookahead: int                     # input samples past an output sample that its value depends on (the largest over the phases)
+    latency: int                       # pushed - emitted in the steady state
+    warmup_pushes: int                 # pushes before the first one that returns samples
+    tensors: Tuple[TensorPlan, ...]
+    steady: Tuple[object, ...]         # the operations of a steady-state push
+    state_floats: int                  # floats of state per stream (both buffers of every tensor)
+
+    def tensor(self, name: str) -> TensorPlan:
+        return next(t for t in self.tensors if t.name == name)
+
+
+def plan(gen, chunk_samples: int) -> StreamPlan:
+    """The steady state of ``Schedule(gen, chunk_samples)``.  ``ValueError`` unless ``chunk_samples`` is a positive multiple of
+    ``gen.multiple``: then every tensor gains a constant count per push and every strided layer keeps its phase."""
+    sch = Schedule(gen, chunk_samples)
+    chunk, n = sch.chunk, sch.n
+    prev, warm = None, None
+    for j in range(4096):
+        ops = sch.push(chunk)
+        if warm is None and any(isinstance(o, Splice) and o.dst == "emit:enhanced" for o in ops):
+            warm = j
+        if warm is not None and ops == prev:
+            break
+        prev = ops
+    else:
+        raise RuntimeError("the stream schedule did not settle")
+    steady = tuple(ops)
+    new = {o.dst[5:]: (o.n_carry, o.n_new) for o in steady if isinstance(o, Splice) and o.dst.startswith("tape:")}
+    tensors = []
+    for name, t in sch.tapes.items():
+        carry, fresh = new[name]
+        lag = sch.pushed // t.rate - t.F
+        if name in sch.out_chunk:   # an output leaves in whole chunks; its tape holds what does not fill the next one yet
+            held, c = t.F - t.S, sch.out_chunk[name]
+            tensors.append(TensorPlan(name, t.channels, t.rate, c, lag, held, held, c))
+            continue
+        # finish() delivers everything up to the stream's end at once: the lag, the last chunk and the banks' span on top of the carry
+        cap = carry + fresh + lag + n // t.rate + 4
+        tensors.append(TensorPlan(name, t.channels, t.rate, fresh, lag, carry, carry + fresh, cap))
+    base = 64 * gen.multiple
+    lookahead = max(a - exact_frontier(gen, a) for a in range(base, base + gen.multiple))
+    return StreamPlan(chunk, gen.multiple, chunk - ragged.cut_length(gen, chunk), lookahead, sch.pushed - sch.emitted["enhanced"], warm,
+                      tuple(tensors), steady, sum(2 * t.channels * t.capacity for t in tensors))
+
+
+# ---- the public driver ----------------------------------------------------------------------------------------------------------------
+class StreamingEnhancer:
+    """``generator`` on audio that is still arriving: ``push`` a ``(streams, 1, chunk_samples)`` float32 device tensor, get the newly
+    final enhanced samples ``(streams, 1, k)`` -- k is 0 during warm-up and exactly ``chunk_samples`` from the first non-empty return on;
+    ``finish()`` (optionally with the last, shorter chunk) returns the rest, up to ``ragged.cut_length(generator, total pushed)``.  The
+    concatenation is what ``generator(cut_to_valid_length(whole clip))`` returns.  Rows advance in lockstep.  ``return_bands``: every
+    call returns ``(enhanced, bands)``, the bands with the same semantics at their rate.  Nothing here waits for the device."""
+
+    def __init__(self, generator, chunk_samples: int, streams: int = 1, return_bands: bool = False):
+        if int(streams) < 1:
+            raise ValueError(f"streams must be positive, got {streams}")
+        self.generator, self.streams, self.return_bands = generator, int(streams), bool(return_bands)
+        self.plan = plan(generator, chunk_samples)
+        self.chunk_samples = self.plan.chunk_samples
+        self._schedule = Schedule(generator, chunk_samples)
+        self.state = None   # device buffers: allocated at the first push, on the chunk's device
+
+    @property
+    def latency(self) -> int:
+        return self.plan.latency
+
+    @property
+    def lookahead(self) -> int:
+        return self.plan.lookahead
+
+    def prepare(self, device) -> "StreamingEnhancer":
+        """Allocates the state on ``device`` now instead of at the first push (it is allocated once either way)."""
+        import torch
+
+        from . import gen_engine
+
+        device = torch.empty(0, device=device).device   # "cuda" -> cuda:0
+        if self.state is None or self.state.device != device:
+            self.state = gen_engine.engine_of(self.generator).stream_state(self.plan, self.streams, device)
+        return self
+
+    def reset(self) -> None:
+        """Ready for a new stream; the state buffers stay."""
+        self._schedule.reset()
+        if self.state is not None:
+            self.state.reset()
+
+    def _check(self, chunk, length_ok, what: str):
+        import torch
+
+        if torch.is_grad_enabled():
+            raise RuntimeError(f"StreamingEnhancer: {what} has no backward; call it under torch.no_grad()")
+        if (not isinstance(chunk, torch.Tensor) or chunk.dim() != 3 or tuple(chunk.shape[:2]) != (self.streams, 1) or not length_ok(chunk.shape[2])
+                or chunk.dtype is not torch.float32):
+            got = f"{chunk.dtype} {tuple(chunk.shape)}" if isinstance(chunk, torch.Tensor) else type(chunk).__name__
+            raise ValueError(f"StreamingEnhancer: {what} expects a float32 ({self.streams}, 1, {self.chunk_samples}) tensor"
+                             f"{' or a shorter last one' if what == 'finish' else ''}, got {got}")
+        if not chunk.is_cuda:
+            from ._lib import EbenError
+
+            raise EbenError(f"StreamingEnhancer runs only on an MI355X HIP device (got a tensor on '{chunk.device}'); there is no CPU path")
+
+    def _run(self, chunk, n_in: int, final: bool):
+        from . import gen_engine
+
+        engine = gen_engine.engine_of(self.generator)
+        device = chunk.device if chunk is not None else self.state.device if self.state is not None else next(self.generator.parameters()).device
+        self.prepare(device)
+        ops = self._schedule.push(n_in, final)
+        out = engine.stream_run(self.state, ops, chunk)
+        import torch
+
+        enhanced = out.get("enhanced")
+        if enhanced is None:
+            enhanced = torch.empty((self.streams, 1, 0), dtype=torch.float32, device=device)
+        if not self.return_bands:
+            return enhanced
+        bands = out.get("bands")
+        if bands is None:
+            bands = torch.empty((self.streams, self.generator.pqmf.decimation, 0), dtype=torch.float32, device=device)
+        return enhanced, bands
+
+    def push(self, chunk):
+        self._check(chunk, lambda l: l == self.chunk_samples, "push")
+        return self._run(chunk.contiguous(), self.chunk_samples, False)
+
+    def finish(self, tail=None):
+        """The rest of the stream.  ``tail``: the last ``(streams, 1, r)`` samples, ``r < chunk_samples`` (what did not fill a chunk).
+        ``ValueError`` when everything pushed is shorter than the shortest clip the generator accepts."""
+        import torch
+
+        if torch.is_grad_enabled():
+            raise RuntimeError("StreamingEnhancer: finish has no backward; call it under torch.no_grad()")
+        if tail is not None and tail.shape[-1] == 0:
+            tail = None
+        if tail is not None:
+            self._check(tail, lambda l: l < self.chunk_samples, "finish")
+            tail = tail.contiguous()
+        return self._run(tail, 0 if tail is None else tail.shape[2], True)
