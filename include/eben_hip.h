@@ -649,6 +649,38 @@ EBEN_API int eben_stream_splice(float* dst, int dst_pitch, const float* prev, in
                                 int src_pitch, int src_off, int n_new, const float* add, int add_pitch, int add_off, int rows_channels,
                                 void* stream);
 
+/* eben_stream_splice_rows: the splice with a slot dimension, for independent sessions that share one state (streaming.StreamPool).
+ * rows_channels = slots * channels, slots <= EBEN_STREAM_MAX_SLOTS.  `active`: (slots + 63) / 64 HOST words, bit r of the mask = slot r
+ * advances in this call; the entry copies them into a by-value kernel argument (no device mask, no copy engine: the caller may reuse
+ * its words at once).  With a = popcount(active bits below r):
+ *   active slot r:   what eben_stream_splice does for that row: prev is read at row r; src and add at row a when src_compact (they
+ *                    hold one row per ACTIVE slot, in slot order), else at row r; dst is written at row a when dst_compact, else at r;
+ *   inactive slot r: dst_compact: writes nothing; else with idle != NULL: dst[r, c, j] = idle[r, c, j] for j < n_carry + n_new (the
+ *                    slot's state moves to the twin buffer unchanged); else writes nothing.
+ * idle (nullable) has its own pitch and is not prev: a tensor rewritten whole every push (n_carry == 0) still holds a session's state.
+ * EBEN_EINVAL before any launch, nothing written, for: what eben_stream_splice refuses; a null `active`; a null or misaligned idle;
+ * n_carry + n_new past idle_pitch; channels <= 0 or rows_channels % channels != 0; more than EBEN_STREAM_MAX_SLOTS slots; a set bit
+ * at or above `slots`; dst's extent overlapping prev, src, add or idle (a compact tensor's extent counts the active slots only).
+ * No bit set with idle (and dst not compact) copies every slot; no bit set and nothing to write returns EBEN_OK without a launch.
+ *
+ * eben_copy_segments: dst[i][0 : floats) = src[i][0 : floats) for `count` <= EBEN_COPY_MAX_SEGMENTS segments read from HOST memory
+ * (passed to the kernel by value), one launch.  EBEN_EINVAL before any launch for a null or misaligned-to-4 pointer, a negative count
+ * of segments or of floats, more than EBEN_COPY_MAX_SEGMENTS segments, or a dst extent overlapping any src extent or another dst.
+ * Segments of 0 floats are legal; nothing to copy returns EBEN_OK without a launch.
+ * Added without a version bump: functions only. */
+#define EBEN_STREAM_MAX_SLOTS 256
+#define EBEN_COPY_MAX_SEGMENTS 64
+typedef struct EbenCopySegment {
+  float* dst;
+  const float* src;
+  long long floats;
+} EbenCopySegment;
+EBEN_API int eben_stream_splice_rows(float* dst, int dst_pitch, const float* prev, int prev_pitch, int prev_off, int n_carry, const float* src,
+                                     int src_pitch, int src_off, int n_new, const float* add, int add_pitch, int add_off, const float* idle,
+                                     int idle_pitch, int rows_channels, int channels, const unsigned long long* active, int src_compact,
+                                     int dst_compact, void* stream);
+EBEN_API int eben_copy_segments(const EbenCopySegment* segments, int count, void* stream);
+
 /* ---- misc ------------------------------------------------------------------------------- */
 /* out[0] = sqrt(sum x^2) (torch.norm at eben.py:226); `out` must hold 257 floats (scratch) */
 EBEN_API int eben_l2norm(const float* x, size_t n, float* out, void* stream);

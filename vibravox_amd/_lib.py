@@ -82,6 +82,10 @@ class EbenCollateItem(ctypes.Structure):
                 ("shift", c_int64)]
 
 
+class EbenCopySegment(ctypes.Structure):
+    _fields_ = [("dst", c_void_p), ("src", c_void_p), ("floats", c_int64)]
+
+
 class EbenClip(ctypes.Structure):
     _fields_ = [("data", c_void_p), ("length", c_int64)]
 
@@ -222,6 +226,9 @@ SIGNATURES = {
     "eben_edge_fill": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "eben_edge_zero": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "eben_stream_splice": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P]),
+    "eben_stream_splice_rows": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P, c_int, c_int, _P, c_int, c_int, c_int,
+                                        POINTER(ctypes.c_uint64), c_int, c_int, _P]),
+    "eben_copy_segments": (c_int, [POINTER(EbenCopySegment), c_int, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -441,6 +441,19 @@ class GeneratorEngine:
             return self._residual_unit(blk.residuals[int(rest[2])], x, slope if first_of_encoder else 1.0, False, None)
         return self._conv(getattr(blk, rest[1]), x, False)
 
+    def _stream_launch(self, state: "StreamState", op, outs: Dict[str, torch.Tensor]) -> torch.Tensor:
+        """One ``streaming.Launch`` on every row of ``state``: the node's output."""
+        if op.node == "lift":
+            y = ops.tanh_lift(outs["last_conv"], state.view("lift.operand"))
+        else:
+            x = state.view(op.node)
+            if x.shape[2] != op.l_in:
+                raise RuntimeError(f"stream state out of step with the schedule: {op} on a buffer of {x.shape[2]}")
+            y = self._stream_node(op.node, x)
+        if y.shape[2] != op.l_out:
+            raise RuntimeError(f"stream schedule out of step with the kernels: {op} gave {y.shape[2]} samples")
+        return y
+
     def stream_run(self, state: "StreamState", operations, chunk: Optional[torch.Tensor]) -> Dict[str, torch.Tensor]:
         """Executes one push's operations (``streaming.Schedule.push``) on ``state``; returns the tensors emitted, by output name.
         Every input is spliced by ``eben_stream_splice`` and every layer launched as ``forward`` launches it; nothing waits."""
@@ -464,16 +477,7 @@ class GeneratorEngine:
 
         for op in operations:
             if not isinstance(op, Splice):
-                if op.node == "lift":
-                    y = ops.tanh_lift(outs["last_conv"], state.view("lift.operand"))
-                else:
-                    x = state.view(op.node)
-                    if x.shape[2] != op.l_in:
-                        raise RuntimeError(f"stream state out of step with the schedule: {op} on a buffer of {x.shape[2]}")
-                    y = self._stream_node(op.node, x)
-                if y.shape[2] != op.l_out:
-                    raise RuntimeError(f"stream schedule out of step with the kernels: {op} gave {y.shape[2]} samples")
-                outs[op.node] = y
+                outs[op.node] = self._stream_launch(state, op, outs)
                 continue
             total = op.n_carry + op.n_new
             kind, key = op.dst.split(":", 1)
@@ -492,6 +496,84 @@ class GeneratorEngine:
             if kind == "tape":
                 state.flip(key, total)
         return emitted
+
+    def stream_run_pooled(self, state: "StreamState", steady, chunks: torch.Tensor, mask, n_active: int) -> Dict[str, torch.Tensor]:
+        """One steady-state push (``plan.steady``) of the slots whose bit is set in ``mask`` (64-bit words), on the shared ``state`` of a
+        ``streaming.StreamPool``.  ``chunks``: the ``n_active`` pushed chunks in slot order, one row each.  Every layer runs over all
+        slots as in ``stream_run``; every splice is an ``eben_stream_splice_rows``: the analysis tape reads the compact input, every
+        tape that holds state carries its idle slots over to the twin buffer, and the emits come back compact, a row per active slot
+        in slot order."""
+        from .streaming import Splice
+
+        if torch.is_grad_enabled():
+            raise RuntimeError("EBEN generator engine: stream_run_pooled has no backward; call it under torch.no_grad()")
+        if tuple(chunks.shape[:2]) != (n_active, 1) or n_active != sum(bin(w).count("1") for w in mask) or n_active < 1:
+            raise ValueError(f"stream_run_pooled: {tuple(chunks.shape)} chunks for {n_active} active slots of mask {mask}")
+        lib = load()
+        ops.join_prepack()
+        rows = state.rows
+        words = (ctypes.c_uint64 * 4)(*mask)
+        outs: Dict[str, torch.Tensor] = {}
+        emitted: Dict[str, torch.Tensor] = {}
+        pitch = lambda t: 0 if t is None else t.shape[2]
+
+        def operand(name):
+            if name is None or name == "input":
+                return chunks if name else None
+            kind, key = name.split(":", 1)
+            return outs[key] if kind == "out" else state.view(key)
+
+        for op in steady:
+            if not isinstance(op, Splice):
+                outs[op.node] = self._stream_launch(state, op, outs)
+                continue
+            total = op.n_carry + op.n_new
+            kind, key = op.dst.split(":", 1)
+            if total == 0:
+                state.length[key] = 0
+                continue
+            prev, src, add = operand(op.prev), operand(op.src), operand(op.add)
+            channels = (prev if prev is not None else src).shape[1]
+            idle = None
+            if kind == "emit":
+                dst = emitted[key] = torch.empty((n_active, channels, total), dtype=torch.float32, device=state.device)
+            else:
+                dst = state.twin(key, total)
+                if key != "lift.operand":   # rewritten whole from another tape every push: it holds no state
+                    idle = state.view(key)
+                    if idle.shape[2] != total:
+                        raise RuntimeError(f"pool state out of step with the steady list: {op} on a buffer of {idle.shape[2]}")
+            check(lib.eben_stream_splice_rows(ptr(dst), total, ptr(prev), pitch(prev), op.prev_off, op.n_carry, ptr(src), pitch(src), op.src_off,
+                                              op.n_new, ptr(add), pitch(add), op.add_off, ptr(idle), pitch(idle), rows * channels, channels, words,
+                                              1 if op.src == "input" else 0, 1 if kind == "emit" else 0, stream()), "stream_splice_rows")
+            if kind == "tape":
+                state.flip(key, total)
+        return emitted
+
+    def stream_move(self, pool: "StreamState", slot: int, private: "StreamState", names, into_pool: bool) -> None:
+        """A session's steady-state buffers (tensors ``names`` of the plan) between the batch-1 state ``private`` and row ``slot`` of the
+        shared state ``pool``: a (channels, length) block is contiguous on both sides, so it is one ``eben_copy_segments`` launch per
+        64 tensors.  Out of the pool, ``private`` is set to the steady lengths first."""
+        from ._lib import EbenCopySegment
+
+        if not 0 <= slot < pool.rows or private.rows != 1:
+            raise ValueError(f"stream_move: slot {slot} of {pool.rows}, a private state of {private.rows} rows")
+        lib = load()
+        lengths = pool.steady_lengths
+        if not into_pool:
+            private.reset()
+            for name in names:
+                private.length[name] = lengths[name]
+        table = []
+        for name in names:   # addresses by arithmetic: building ~40 pairs of tensor views costs more host time than the launch
+            n = lengths[name]
+            if private.length[name] != n or pool.length[name] != n:
+                raise RuntimeError(f"stream_move: {name} holds {private.length[name]} and {pool.length[name]} samples, its steady length is {n}")
+            mine, row = private.address(name, 0), pool.address(name, slot)
+            table.append(EbenCopySegment(row, mine, pool.channels[name] * n) if into_pool else EbenCopySegment(mine, row, pool.channels[name] * n))
+        for i in range(0, len(table), 64):
+            part = table[i : i + 64]
+            check(lib.eben_copy_segments((EbenCopySegment * len(part))(*part), len(part), stream()), "copy_segments")
 
     # ---- backward ------------------------------------------------------------------------------------
     def _dx(self, rec: _ConvRec, dy, res_pre=None, res_post=None):
@@ -862,6 +944,8 @@ class StreamState:
         self.capacity = {t.name: t.capacity for t in plan.tensors}
         self.buffers = {t.name: [torch.empty(self.rows * t.channels * t.capacity, dtype=torch.float32, device=self.device) for _ in range(2)]
                         for t in plan.tensors}
+        self.base = {name: [t.data_ptr() for t in pair] for name, pair in self.buffers.items()}
+        self.steady_lengths = {t.name: t.length for t in plan.tensors}
         self.reset()
 
     def reset(self) -> None:
@@ -874,6 +958,10 @@ class StreamState:
 
     def view(self, name: str) -> torch.Tensor:
         return self._shaped(name, self.current[name], self.length[name])
+
+    def address(self, name: str, row: int) -> int:
+        """Device address of row ``row`` of the current view: its (channels, length) block is contiguous."""
+        return self.base[name][self.current[name]] + 4 * row * self.channels[name] * self.length[name]
 
     def twin(self, name: str, length: int) -> torch.Tensor:
         """The buffer a splice writes: the one the current view does not live in."""

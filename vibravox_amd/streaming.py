@@ -16,6 +16,10 @@ Everything here is arithmetic on positions (host only, no GPU needed):
     length and capacity; and ``lookahead`` / ``latency``.
   * ``StreamingEnhancer`` executes the operations on the device through ``GeneratorEngine``; ``tests/stream_oracle.py`` executes the
     same operations in float64 on poisoned buffers.
+  * ``PoolBook`` keeps independent sessions -- streams that begin, pause and end whenever they like -- in the slots of one shared state:
+    the steady-state list is position-free and every position of a ``Schedule`` moves by a constant per steady push
+    (``Schedule.advance``), so all sessions that push in a tick share ONE run of ``plan.steady`` with a mask of the slots that advance.
+    ``StreamPool`` executes its per-tick lists on the device; ``tests/pool_oracle.py`` executes them in float64.
 
 Audio hold-back: ``cut_to_valid_length`` drops up to ``multiple - 1`` samples from the end of a clip, so a sample pushed now may turn
 out to lie behind the stream's valid length.  The analysis bank therefore treats only ``ragged.cut_length(pushed)`` samples as
@@ -122,10 +126,12 @@ class Schedule:
         self.nodes = nodes_of(gen)
         self.by_name = {nd.name: nd for nd in self.nodes}
         self.out_chunk = {"enhanced": chunk_samples, "bands": chunk_samples // self.m}
+        self._steady: Optional[tuple] = None   # plan.steady, once advance() has asked for it
         self.reset()
 
     def reset(self) -> None:
         self.pushed, self.finished = 0, False
+        self._last: Optional[tuple] = None   # the operations of the latest push
         self.tapes: Dict[str, _Tape] = {}
         for nd in self.nodes:
             if nd.kind != "lift":
@@ -283,7 +289,30 @@ class Schedule:
                 t = self.tapes[name]
                 if t.F > t.S:
                     self._emit(ops, name, None, t.F, t.F, t.F, True)
+        self._last = tuple(ops)
         return ops
+
+    def advance(self, k: int) -> None:
+        """The state ``k`` further pushes would have left, without their operations.  Only in the steady state (the latest push returned
+        ``plan.steady``): from there on a push moves every position by a constant -- one chunk at the tensor's own rate -- and repeats
+        its list, so the pushes of a session that lives in a ``StreamPool`` slot need no host arithmetic until it leaves."""
+        k = int(k)
+        if k < 0:
+            raise ValueError(f"advance takes a number of pushes, got {k}")
+        if self.finished:
+            raise RuntimeError("this stream has finished; reset() starts a new one")
+        if self._steady is None:
+            self._steady = plan(self.gen, self.chunk).steady
+        if self._last != self._steady:
+            raise RuntimeError("advance: the schedule is not in its steady state (its latest push did not return plan.steady)")
+        for t in self.tapes.values():
+            d = k * (self.chunk // t.rate)
+            t.S, t.F, t.keep = t.S + d, t.F + d, t.keep + d
+        for nd in self.nodes:
+            self.out_f[nd.name] += k * (self.chunk // self.out_rate(nd))
+        for name, c in self.out_chunk.items():
+            self.emitted[name] += k * c
+        self.pushed += k * self.chunk
 
 
 def _frontier(nd: Node, f: int) -> int:
@@ -463,3 +492,284 @@ class StreamingEnhancer:
             self._check(tail, lambda l: l < self.chunk_samples, "finish")
             tail = tail.contiguous()
         return self._run(tail, 0 if tail is None else tail.shape[2], True)
+
+
+# ---- independent sessions in the slots of one shared state ---------------------------------------------------------------------------
+@dataclasses.dataclass(frozen=True)
+class PrivatePush:
+    """Session ``session`` pushes alone: ``ops`` on the batch-1 state ``private`` (``fresh``: the state starts a new stream first)."""
+    session: "Session"
+    private: int
+    ops: Tuple[object, ...]
+    fresh: bool
+
+
+@dataclasses.dataclass(frozen=True)
+class PooledRun:
+    """One run of ``plan.steady`` over all slots: bit r of ``mask`` (64-bit words) = slot r advances; ``order``: the sessions of the set
+    bits in slot order, which is the row order of the compact input and of the compact emits."""
+    mask: Tuple[int, ...]
+    order: Tuple["Session", ...]
+
+
+@dataclasses.dataclass(frozen=True)
+class Move:
+    """``into_pool``: the steady-state buffers of state ``private`` go to row ``slot`` of the pool's state; else the other way round, into a
+    state that is set to the steady lengths first."""
+    session: "Session"
+    private: int
+    slot: int
+    into_pool: bool
+
+
+class Session:
+    """Handle of one stream in a ``StreamPool``: ``phase`` is "warming", "pooled" or "closed"."""
+
+    def __init__(self, book: "PoolBook", slot: int, private: int, schedule: Schedule):
+        self.book, self.slot, self.schedule = book, slot, schedule
+        self.private = private   # id of the batch-1 state it warms up or finishes on; -1 while it needs none
+        self.phase = "warming"
+        self.pushes = 0          # private pushes so far
+        self.pooled_pushes = 0   # pushes made in the slot that ``schedule`` has not been advanced by yet
+
+    def __repr__(self) -> str:
+        return f"Session(slot {self.slot}, {self.phase})"
+
+
+class PoolBook:
+    """Who is where (host only, no GPU needed): slots, private states, mask words and compact order, and per tick the list of
+    ``PooledRun`` / ``PrivatePush`` / ``Move`` entries that ``StreamPool`` executes on the device and ``tests/pool_oracle.py`` in float64.
+    A session warms up and finishes on a private batch-1 state with its own ``Schedule`` and lives in a slot in between; a pooled push
+    costs a counter increment here."""
+
+    def __init__(self, gen, chunk_samples: int, slots: int = 64, stream_plan: Optional[StreamPlan] = None):
+        slots = int(slots)
+        if not 1 <= slots <= 256:
+            raise ValueError(f"slots must lie in 1 ... 256, got {slots}")
+        self.gen, self.slots = gen, slots
+        self.plan = stream_plan if stream_plan is not None else plan(gen, chunk_samples)
+        self.chunk = self.plan.chunk_samples
+        self.words = (slots + 63) // 64
+        self.free_slots = list(range(slots))
+        self.free_private: List[int] = []
+        self.n_private = 0            # private states handed out so far: ids 0 ... n_private - 1
+        self.spare: List[Schedule] = []
+        self.moved = tuple(t.name for t in self.plan.tensors if t.length and t.name != "lift.operand")   # the tensors that hold state
+
+    def _take_private(self) -> int:
+        if self.free_private:
+            return self.free_private.pop(0)
+        self.n_private += 1
+        return self.n_private - 1
+
+    def _give_private(self, i: int) -> None:
+        self.free_private.append(i)
+        self.free_private.sort()
+
+    def open(self) -> Session:
+        if not self.free_slots:
+            raise RuntimeError(f"StreamPool: all {self.slots} slots hold an open session")
+        if self.spare:
+            schedule = self.spare.pop()
+            schedule.reset()
+        else:
+            schedule = Schedule(self.gen, self.chunk)
+            schedule._steady = self.plan.steady
+        return Session(self, self.free_slots.pop(0), -1, schedule)   # a private state is taken at the first push, the slot now
+
+    def check(self, sessions) -> None:
+        seen = set()
+        for s in sessions:
+            if not isinstance(s, Session) or s.book is not self:
+                raise ValueError("StreamPool: not a session of this pool")
+            if s.phase == "closed":
+                raise RuntimeError("StreamPool: this session is closed")
+            if id(s) in seen:
+                raise ValueError("StreamPool: a session is named twice")
+            seen.add(id(s))
+
+    def tick(self, sessions) -> List[object]:
+        """The entries of a tick in which exactly ``sessions`` push one chunk each; the others stay where they are."""
+        sessions = list(sessions)
+        self.check(sessions)
+        entries: List[object] = []
+        pooled = sorted((s for s in sessions if s.phase == "pooled"), key=lambda s: s.slot)
+        if pooled:
+            mask = [0] * self.words
+            for s in pooled:
+                mask[s.slot >> 6] |= 1 << (s.slot & 63)
+                s.pooled_pushes += 1
+            entries.append(PooledRun(tuple(mask), tuple(pooled)))
+        for s in sessions:
+            if s.phase != "warming":
+                continue
+            ops = tuple(s.schedule.push(self.chunk))
+            if s.private < 0:
+                s.private = self._take_private()
+            entries.append(PrivatePush(s, s.private, ops, s.pushes == 0))
+            s.pushes += 1
+            if ops == self.plan.steady:
+                entries.append(Move(s, s.private, s.slot, True))
+                self._give_private(s.private)
+                s.private, s.phase = -1, "pooled"
+        return entries
+
+    def close(self, session: Session, n_tail: int = 0) -> List[object]:
+        """The entries that finish ``session`` with a tail of ``n_tail`` samples; its slot is free afterwards.  A refusal of the final push
+        (a tail of a chunk or more, a stream below the shortest clip) leaves the session open."""
+        self.check([session])
+        s, entries = session, []
+        if s.phase == "pooled":
+            s.schedule.advance(s.pooled_pushes)
+            s.pooled_pushes = 0
+            ops = tuple(s.schedule.push(n_tail, final=True))
+            s.private = self._take_private()
+            entries.append(Move(s, s.private, s.slot, False))
+            entries.append(PrivatePush(s, s.private, ops, False))
+        else:
+            ops = tuple(s.schedule.push(n_tail, final=True))
+            if s.private < 0:
+                s.private = self._take_private()
+            entries.append(PrivatePush(s, s.private, ops, s.pushes == 0))
+        self._give_private(s.private)
+        self.free_slots.append(s.slot)
+        self.free_slots.sort()
+        self.spare.append(s.schedule)
+        s.phase, s.private = "closed", -1
+        return entries
+
+
+class StreamPool:
+    """Independent streams through one ``generator``: ``open()`` a session whenever a stream begins, ``step({session: chunk})`` with the
+    ``(1, 1, chunk_samples)`` float32 device chunks of the sessions that have one this tick, ``close(session, tail)`` when it ends.  Per
+    session the returns are those of ``StreamingEnhancer.push`` / ``finish`` on a stream of its own.  A session warms up and finishes
+    alone on a private batch-1 state; in between it lives in one of ``slots`` rows of a shared state, and every session that pushed in a
+    tick is served by ONE run of the steady-state list over all rows, with masked splices (``eben_stream_splice_rows``) that leave the
+    rows of the others as they are.  Nothing here waits for the device."""
+
+    def __init__(self, generator, chunk_samples: int, slots: int = 64, return_bands: bool = False):
+        self.generator, self.return_bands = generator, bool(return_bands)
+        self.plan = plan(generator, chunk_samples)
+        self.chunk_samples = self.plan.chunk_samples
+        self.book = PoolBook(generator, chunk_samples, slots, self.plan)
+        self.slots = self.book.slots
+        self.state = None      # the shared state: allocated by prepare() or at the first step
+        self.private = {}      # id -> batch-1 StreamState, allocated when the book first hands the id out and kept
+
+    @property
+    def latency(self) -> int:
+        return self.plan.latency
+
+    @property
+    def lookahead(self) -> int:
+        return self.plan.lookahead
+
+    def prepare(self, device, private: int = 0) -> "StreamPool":
+        """Allocates the shared state on ``device`` now instead of at the first step, and ``private`` batch-1 states for sessions that
+        warm up or finish at the same time (further ones are allocated when first needed, and kept)."""
+        import torch
+
+        from . import gen_engine
+
+        device = torch.empty(0, device=device).device
+        if self.state is None or self.state.device != device:
+            self.state = gen_engine.engine_of(self.generator).stream_state(self.plan, self.slots, device)
+            for t in self.plan.tensors:
+                self.state.length[t.name] = t.length
+            self.private = {}
+        for i in range(min(int(private), self.slots)):
+            self._private_state(i)
+        return self
+
+    def open(self) -> Session:
+        return self.book.open()
+
+    def _check(self, chunk, length_ok, what: str):
+        import torch
+
+        if (not isinstance(chunk, torch.Tensor) or chunk.dim() != 3 or tuple(chunk.shape[:2]) != (1, 1) or not length_ok(chunk.shape[2])
+                or chunk.dtype is not torch.float32):
+            got = f"{chunk.dtype} {tuple(chunk.shape)}" if isinstance(chunk, torch.Tensor) else type(chunk).__name__
+            raise ValueError(f"StreamPool: {what} expects a float32 (1, 1, {self.chunk_samples}) tensor per session"
+                             f"{' or a shorter last one' if what == 'close' else ''}, got {got}")
+        if not chunk.is_cuda:
+            from ._lib import EbenError
+
+            raise EbenError(f"StreamPool runs only on an MI355X HIP device (got a tensor on '{chunk.device}'); there is no CPU path")
+
+    def _private_state(self, i: int):
+        from . import gen_engine
+
+        if i not in self.private:
+            self.private[i] = gen_engine.engine_of(self.generator).stream_state(self.plan, 1, self.state.device)
+        return self.private[i]
+
+    def _results(self, out, sessions, results: dict) -> None:
+        """The emitted tensors, a row per session, as what each session's call returns (rows are split in one call: a view per session
+        built one by one costs more host time at 64 sessions than the mask does)."""
+        import torch
+
+        m = self.generator.pqmf.decimation
+        per_name = []
+        for name, c in (("enhanced", 1), ("bands", m))[: 2 if self.return_bands else 1]:
+            t = out.get(name)
+            if t is None:
+                t = torch.empty((len(sessions), c, 0), dtype=torch.float32, device=self.state.device)
+            per_name.append(t.split(1, dim=0) if len(sessions) > 1 else (t,))
+        for a, s in enumerate(sessions):
+            results[s] = (per_name[0][a], per_name[1][a]) if self.return_bands else per_name[0][a]
+
+    def _execute(self, entries, chunks) -> dict:
+        import torch
+
+        from . import gen_engine
+
+        engine = gen_engine.engine_of(self.generator)
+        results = {}
+        for e in entries:
+            if isinstance(e, PooledRun):
+                compact = chunks[e.order[0]] if len(e.order) == 1 else torch.cat([chunks[s] for s in e.order], dim=0)
+                self._results(engine.stream_run_pooled(self.state, self.plan.steady, compact, e.mask, len(e.order)), e.order, results)
+            elif isinstance(e, PrivatePush):
+                state = self._private_state(e.private)
+                if e.fresh:
+                    state.reset()
+                self._results(engine.stream_run(state, e.ops, chunks.get(e.session)), (e.session,), results)
+            else:
+                engine.stream_move(self.state, e.slot, self._private_state(e.private), self.book.moved, e.into_pool)
+        return results
+
+    def step(self, chunks: dict) -> dict:
+        """One tick: ``{session: chunk}`` -> ``{session: newly final samples}`` (``(enhanced, bands)`` with ``return_bands``)."""
+        import torch
+
+        if torch.is_grad_enabled():
+            raise RuntimeError("StreamPool: step has no backward; call it under torch.no_grad()")
+        if not isinstance(chunks, dict):
+            raise ValueError(f"StreamPool: step expects a dict of session -> chunk, got {type(chunks).__name__}")
+        self.book.check(chunks)
+        for chunk in chunks.values():
+            self._check(chunk, lambda l: l == self.chunk_samples, "step")
+        if not chunks:
+            return {}
+        chunks = {s: c.contiguous() for s, c in chunks.items()}
+        self.prepare(next(iter(chunks.values())).device)
+        results = self._execute(self.book.tick(chunks), chunks)
+        return {s: results[s] for s in chunks}
+
+    def close(self, session: Session, tail=None):
+        """The rest of ``session``'s stream, as ``StreamingEnhancer.finish``; its slot is free for the next ``open()``."""
+        import torch
+
+        if torch.is_grad_enabled():
+            raise RuntimeError("StreamPool: close has no backward; call it under torch.no_grad()")
+        self.book.check([session])
+        if tail is not None and isinstance(tail, torch.Tensor) and tail.shape[-1] == 0:
+            tail = None
+        if tail is not None:
+            self._check(tail, lambda l: l < self.chunk_samples, "close")
+            tail = tail.contiguous()
+        self.prepare(tail.device if tail is not None else self.state.device if self.state is not None
+                     else next(self.generator.parameters()).device)
+        entries = self.book.close(session, 0 if tail is None else tail.shape[2])
+        return self._execute(entries, {} if tail is None else {session: tail})[session]
