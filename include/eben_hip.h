@@ -698,6 +698,21 @@ EBEN_API size_t eben_stoi_workspace(int rows, int t, int fs);
 EBEN_API int eben_stoi(const float* clean, const float* processed, int rows, int t, int fs, const float* resample_table, int taps,
               void* workspace, size_t ws_bytes, float* out, void* stream);
 
+/* ---- the same metrics over rows of different lengths (corpus evaluation in ragged batches) ------------------------------------
+ * Rows are t_max floats apart; row r is the signal [0, lengths[r]) and what lies behind it is never read.  lengths (DEVICE, rows
+ * int32) is never seen by the host: grids and the workspace are sized from t_max (eben_stoi_ragged_workspace(rows, t_max, fs) bytes,
+ * every row at full length with all frames kept) and a row's surplus workgroups return at once.  out[r] has the bits of the dense
+ * entry on row r alone (preds[r, :lengths[r]] as a (1, lengths[r]) call): the same kernels with the row's own length, loop order and
+ * reduction order.  A lengths[r] outside [1, t_max] cannot be refused by the host: that row reads nothing and gets out[r] = NaN, the
+ * other rows are unaffected.  EBEN_EINVAL before any launch for a null pointer, rows outside [1, 65535], t_max <= 0, fs <= 0 or, at
+ * fs != 10000, a missing or even-length table; EBEN_EWORKSPACE for a short workspace.  Any 4-byte-aligned base and any t_max.
+ * Added without a version bump: functions only. */
+EBEN_API int eben_si_sdr_ragged(const float* preds, const float* target, int rows, int t_max, const int32_t* lengths, float* out,
+                                void* stream);
+EBEN_API size_t eben_stoi_ragged_workspace(int rows, int t_max, int fs);
+EBEN_API int eben_stoi_ragged(const float* clean, const float* processed, int rows, int t_max, const int32_t* lengths, int fs,
+                              const float* resample_table, int taps, void* workspace, size_t ws_bytes, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,11 @@
 //                             bins the third-octave bands cover, folded into the 15 band envelopes
 //   4. stoi_corr_kernel       one workgroup per row: the 30-frame segment correlations and d
 // Buffers are sized for the all-frames-kept case; rows whose kept count is smaller leave the tail workgroups idle.
+//
+// Ragged batches (eben_si_sdr_ragged / eben_stoi_ragged): the same kernels with a DEVICE table of row lengths.  Rows are t_max apart,
+// grids and buffers are sized for a row of t_max samples, and every kernel derives the row's own shape from its length (stoi_shape_of,
+// shared with the host), so a row runs the loops of the dense call on that row alone, in the same order.  The dense entries pass
+// lengths == nullptr: every row is t_max long.  A length outside [1, t_max] reads nothing and yields NaN.
 #include <cmath>
 
 #include "common.h"
@@ -45,13 +50,26 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
   return red[0] + red[1] + red[2] + red[3];
 }
 
+// samples of row r: t_max without a table (the dense entries), else lengths[r], or 0 when that is outside [1, t_max] (uniform over
+// the workgroup)
+__device__ __forceinline__ int row_length(const int* __restrict__ lengths, long long r, int t_max) {
+  if (!lengths) return t_max;
+  const int n = lengths[r];
+  return n >= 1 && n <= t_max ? n : 0;
+}
+
 // ---- SI-SDR -------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void si_sdr_kernel(const float* __restrict__ preds, const float* __restrict__ target, int t,
-                                                     float* __restrict__ out) {
+__global__ __launch_bounds__(256) void si_sdr_kernel(const float* __restrict__ preds, const float* __restrict__ target, int t_max,
+                                                     const int* __restrict__ lengths, float* __restrict__ out) {
   __shared__ double red[4];
   const long long r = blockIdx.x;
-  const float* p = preds + r * t;
-  const float* g = target + r * t;
+  const int t = row_length(lengths, r, t_max);
+  if (t == 0) {
+    if (threadIdx.x == 0) out[r] = NAN;
+    return;
+  }
+  const float* p = preds + r * t_max;
+  const float* g = target + r * t_max;
   double pt = 0.0, tt = 0.0;
   for (int i = threadIdx.x; i < t; i += 256) {
     const double a = p[i], b = g[i];
@@ -71,6 +89,29 @@ __global__ __launch_bounds__(256) void si_sdr_kernel(const float* __restrict__ p
 }
 
 // ---- STOI ---------------------------------------------------------------------------------------------------------------
+struct StoiShape {
+  int p, q, t10, nf, fmax;
+};
+
+int gcd_int(int a, int b) {
+  while (b) {
+    const int c = a % b;
+    a = b;
+    b = c;
+  }
+  return a;
+}
+
+// a signal of t samples at 10000 q / p Hz (p / q reduced; 1 / 1 at 10 kHz): t10 samples at 10 kHz, nf frames at range(0, t10 - 256, 128),
+// at most nf - 1 STFT frames of the silence-removed signal (fmax, >= 1 as a buffer pitch).  The one place host and kernels get it from.
+__host__ __device__ inline StoiShape stoi_shape_of(int t, int p, int q) {
+  StoiShape s{p, q, 0, 0, 1};
+  s.t10 = (int)(((long long)t * p + q - 1) / q);
+  s.nf = s.t10 > kFrame ? (s.t10 - kFrame + kHop - 1) / kHop : 0;
+  s.fmax = s.nf > 1 ? s.nf - 1 : 1;
+  return s;
+}
+
 struct StoiBands {
   int lo[kBands];  // [lo, hi) FFT bins of each third-octave band (thirdoct(10000, 512, 15, 150))
   int hi[kBands];
@@ -78,14 +119,17 @@ struct StoiBands {
 };
 
 // out[n] = sum_m x[m] * table[half + n*q - m*p], m in [0, t_in): scipy resample_poly's zero-padded, centred polyphase sum
-// (table = up * h, 2*half+1 taps).  blockIdx.z selects the signal (0 clean, 1 processed).
+// (table = up * h, 2*half+1 taps).  blockIdx.z selects the signal (0 clean, 1 processed).  Rows are t_max apart on the way in and
+// t10_max apart on the way out; a row of t_in samples produces its own ceil(t_in p / q) outputs.
 __global__ __launch_bounds__(256) void stoi_resample_kernel(const float* __restrict__ clean, const float* __restrict__ processed,
-                                                            const float* __restrict__ table, int half, int p, int q, int t_in,
-                                                            int t_out, int rows, float* __restrict__ out) {
+                                                            const float* __restrict__ table, int half, int p, int q, int t_max,
+                                                            const int* __restrict__ lengths, int t10_max, int rows,
+                                                            float* __restrict__ out) {
   const int n = blockIdx.x * 256 + threadIdx.x;
-  if (n >= t_out) return;
   const long long r = blockIdx.y;
-  const float* x = (blockIdx.z ? processed : clean) + r * t_in;
+  const int t_in = row_length(lengths, r, t_max);
+  if (t_in == 0 || n >= stoi_shape_of(t_in, p, q).t10) return;
+  const float* x = (blockIdx.z ? processed : clean) + r * t_max;
   const long long c = (long long)n * q;
   const long long lo_num = c - half;
   int m0 = lo_num <= 0 ? 0 : (int)((lo_num + p - 1) / p);
@@ -93,7 +137,7 @@ __global__ __launch_bounds__(256) void stoi_resample_kernel(const float* __restr
   if (m1 > t_in - 1) m1 = t_in - 1;
   float acc = 0.f;
   for (int m = m0; m <= m1; ++m) acc = fmaf(x[m], table[c + half - (long long)m * p], acc);
-  out[((long long)blockIdx.z * rows + r) * t_out + n] = acc;
+  out[((long long)blockIdx.z * rows + r) * t10_max + n] = acc;
 }
 
 __device__ __forceinline__ double hann258(int j) {  // np.hanning(258)[1:-1][j]
@@ -101,16 +145,25 @@ __device__ __forceinline__ double hann258(int j) {  // np.hanning(258)[1:-1][j]
 }
 
 // one workgroup per row: energies 20*log10(||w*frame|| + EPS) of the clean frames at range(0, t - 256, 128), the mask
-// max - 40 - e < 0 and the kept-frame table kept[row, 0:count[row]] in frame order
-__global__ __launch_bounds__(256) void stoi_frames_kernel(const float* __restrict__ clean, int t, int nf, double* __restrict__ energy,
+// max - 40 - e < 0 and the kept-frame table kept[row, 0:count[row]] in frame order.  `clean` is at 10 kHz, rows pitch10 apart; the
+// tables are nf_max apart and the row's own frame count comes from its length (t_max, lengths: at the caller's rate).  A row whose
+// length is out of range gets count = -1, which stoi_corr_kernel turns into NaN.
+__global__ __launch_bounds__(256) void stoi_frames_kernel(const float* __restrict__ clean, int pitch10, int nf_max, int t_max,
+                                                          const int* __restrict__ lengths, int p, int q, double* __restrict__ energy,
                                                           int* __restrict__ kept, int* __restrict__ count) {
   __shared__ double win[kFrame];
   __shared__ double red[4];
   __shared__ int wave_cnt[4];
   const long long r = blockIdx.x;
-  const float* x = clean + r * t;
-  double* e = energy + r * nf;
-  int* k = kept + r * nf;
+  const int len = row_length(lengths, r, t_max);
+  if (len == 0) {
+    if (threadIdx.x == 0) count[r] = -1;
+    return;
+  }
+  const int nf = stoi_shape_of(len, p, q).nf;
+  const float* x = clean + r * pitch10;
+  double* e = energy + r * nf_max;
+  int* k = kept + r * nf_max;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   win[threadIdx.x] = hann258(threadIdx.x);
   __syncthreads();
@@ -150,7 +203,8 @@ __global__ __launch_bounds__(256) void stoi_frames_kernel(const float* __restric
 
 // one workgroup per (STFT frame i, row).  With kept frames k_0..k_{K-1} (k_m[u] = w[u] * sig[128*kept[m] + u]) the
 // overlap-added signal has K+1 hops and K-1 STFT frames; frame i is w * [k_i[0:128] + k_{i-1}[128:256], k_i[128:256] + k_{i+1}[0:128]]
-// (k_{-1} = 0).  tob[row, s, band, i] = sqrt(sum over the band's bins of |rfft(frame, 512)|^2).
+// (k_{-1} = 0).  tob[row, s, band, i] = sqrt(sum over the band's bins of |rfft(frame, 512)|^2).  t and nf are the row pitches of the
+// 10 kHz signals and of the kept-frame table; the row's own extent is count[row] (-1: nothing to do).
 __global__ __launch_bounds__(256) void stoi_bands_kernel(const float* __restrict__ sx, const float* __restrict__ sy, int t, int nf, const int* __restrict__ kept,
                                                          const int* __restrict__ count, StoiBands bands, int fmax, double* __restrict__ tob) {
   __shared__ float win[kFrame];
@@ -206,8 +260,8 @@ __global__ __launch_bounds__(256) void stoi_corr_kernel(const double* __restrict
   __shared__ double red[4];
   const long long r = blockIdx.x;
   const int frames = count[r] - 1;
-  if (frames < kSeg) {  // uniform over the workgroup
-    if (threadIdx.x == 0) out[r] = 1e-5f;
+  if (frames < kSeg) {  // uniform over the workgroup; count = -1: the row's length was out of range
+    if (threadIdx.x == 0) out[r] = count[r] < 0 ? NAN : 1e-5f;
     return;
   }
   const int J = frames - kSeg + 1;
@@ -243,30 +297,14 @@ __global__ __launch_bounds__(256) void stoi_corr_kernel(const double* __restrict
   if (threadIdx.x == 0) out[r] = (float)(acc / ((double)J * kBands));
 }
 
-struct StoiShape {
-  int p, q, t10, nf, fmax;
-};
-
-int gcd_int(int a, int b) {
-  while (b) {
-    const int c = a % b;
-    a = b;
-    b = c;
-  }
-  return a;
-}
-
 StoiShape stoi_shape(int t, int fs) {
-  StoiShape s{1, 1, t, 0, 1};
+  int p = 1, q = 1;
   if (fs != kFs) {
     const int g = gcd_int(kFs, fs);
-    s.p = kFs / g;
-    s.q = fs / g;
-    s.t10 = (int)(((long long)t * s.p + s.q - 1) / s.q);
+    p = kFs / g;
+    q = fs / g;
   }
-  s.nf = s.t10 > kFrame ? (s.t10 - kFrame + kHop - 1) / kHop : 0;
-  s.fmax = s.nf > 1 ? s.nf - 1 : 1;
-  return s;
+  return stoi_shape_of(t, p, q);
 }
 
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -322,22 +360,18 @@ StoiBands stoi_bands() {
 
 using namespace eben;
 
-extern "C" int eben_si_sdr(const float* preds, const float* target, int rows, int t, float* out, void* stream) {
-  EBEN_REQUIRE(preds && target && out && rows > 0 && t > 0, "bad si_sdr arguments");
-  hipLaunchKernelGGL(si_sdr_kernel, dim3(rows), dim3(256), 0, as_stream(stream), preds, target, t, out);
+namespace {
+
+int launch_si_sdr(const float* preds, const float* target, int rows, int t_max, const int* lengths, float* out, void* stream) {
+  hipLaunchKernelGGL(si_sdr_kernel, dim3(rows), dim3(256), 0, as_stream(stream), preds, target, t_max, lengths, out);
   EBEN_CHECK_LAUNCH("si_sdr_kernel");
   return EBEN_OK;
 }
 
-extern "C" size_t eben_stoi_workspace(int rows, int t, int fs) {
-  if (rows <= 0 || t <= 0 || fs <= 0) return 0;
-  return stoi_ws(rows, stoi_shape(t, fs), fs).total;
-}
-
-extern "C" int eben_stoi(const float* clean, const float* processed, int rows, int t, int fs, const float* resample_table, int taps,
-                         void* workspace, size_t ws_bytes, float* out, void* stream) {
-  EBEN_REQUIRE(clean && processed && out && workspace && rows > 0 && rows <= 65535 && t > 0 && fs > 0, "bad stoi arguments");
-  const StoiShape s = stoi_shape(t, fs);
+// the four STOI stages over rows t_max apart; lengths == nullptr: every row is t_max long (the dense entry)
+int launch_stoi(const float* clean, const float* processed, int rows, int t_max, const int* lengths, int fs, const float* resample_table,
+                int taps, void* workspace, size_t ws_bytes, float* out, void* stream) {
+  const StoiShape s = stoi_shape(t_max, fs);
   const StoiWs w = stoi_ws(rows, s, fs);
   if (ws_bytes < w.total) return fail(EBEN_EWORKSPACE, "stoi needs %zu workspace bytes", w.total);
   char* ws = static_cast<char*>(workspace);
@@ -348,7 +382,7 @@ extern "C" int eben_stoi(const float* clean, const float* processed, int rows, i
     EBEN_REQUIRE(resample_table && taps > 0 && (taps & 1), "stoi at fs != 10000 needs the odd-length resampling table");
     float* rs = reinterpret_cast<float*>(ws + w.sig);
     hipLaunchKernelGGL(stoi_resample_kernel, dim3(ceil_div(s.t10, 256), rows, 2), dim3(256), 0, st, clean, processed, resample_table,
-                       (taps - 1) / 2, s.p, s.q, t, s.t10, rows, rs);
+                       (taps - 1) / 2, s.p, s.q, t_max, lengths, s.t10, rows, rs);
     EBEN_CHECK_LAUNCH("stoi_resample_kernel");
     sx = rs;
     sy = rs + (size_t)rows * s.t10;
@@ -357,7 +391,7 @@ extern "C" int eben_stoi(const float* clean, const float* processed, int rows, i
   int* kept = reinterpret_cast<int*>(ws + w.kept);
   int* count = reinterpret_cast<int*>(ws + w.count);
   double* tob = reinterpret_cast<double*>(ws + w.tob);
-  hipLaunchKernelGGL(stoi_frames_kernel, dim3(rows), dim3(256), 0, st, sx, s.t10, s.nf, energy, kept, count);
+  hipLaunchKernelGGL(stoi_frames_kernel, dim3(rows), dim3(256), 0, st, sx, s.t10, s.nf, t_max, lengths, s.p, s.q, energy, kept, count);
   EBEN_CHECK_LAUNCH("stoi_frames_kernel");
   if (s.nf > 1) {
     hipLaunchKernelGGL(stoi_bands_kernel, dim3(s.fmax, rows), dim3(256), 0, st, sx, sy, s.t10, s.nf, kept, count, stoi_bands(), s.fmax,
@@ -367,4 +401,40 @@ extern "C" int eben_stoi(const float* clean, const float* processed, int rows, i
   hipLaunchKernelGGL(stoi_corr_kernel, dim3(rows), dim3(256), 0, st, tob, count, s.fmax, out);
   EBEN_CHECK_LAUNCH("stoi_corr_kernel");
   return EBEN_OK;
+}
+
+}  // namespace
+
+extern "C" int eben_si_sdr(const float* preds, const float* target, int rows, int t, float* out, void* stream) {
+  EBEN_REQUIRE(preds && target && out && rows > 0 && t > 0, "bad si_sdr arguments");
+  return launch_si_sdr(preds, target, rows, t, nullptr, out, stream);
+}
+
+extern "C" int eben_si_sdr_ragged(const float* preds, const float* target, int rows, int t_max, const int32_t* lengths, float* out,
+                                  void* stream) {
+  EBEN_REQUIRE(preds && target && lengths && out, "si_sdr_ragged: null pointer");
+  EBEN_REQUIRE(rows > 0 && rows <= 65535 && t_max > 0, "si_sdr_ragged: rows = %d outside [1, 65535] or t_max = %d <= 0", rows, t_max);
+  return launch_si_sdr(preds, target, rows, t_max, lengths, out, stream);
+}
+
+extern "C" size_t eben_stoi_workspace(int rows, int t, int fs) {
+  if (rows <= 0 || t <= 0 || fs <= 0) return 0;
+  return stoi_ws(rows, stoi_shape(t, fs), fs).total;
+}
+
+// every row at full length with all frames kept: what the dense call on (rows, t_max) takes
+extern "C" size_t eben_stoi_ragged_workspace(int rows, int t_max, int fs) { return eben_stoi_workspace(rows, t_max, fs); }
+
+extern "C" int eben_stoi(const float* clean, const float* processed, int rows, int t, int fs, const float* resample_table, int taps,
+                         void* workspace, size_t ws_bytes, float* out, void* stream) {
+  EBEN_REQUIRE(clean && processed && out && workspace && rows > 0 && rows <= 65535 && t > 0 && fs > 0, "bad stoi arguments");
+  return launch_stoi(clean, processed, rows, t, nullptr, fs, resample_table, taps, workspace, ws_bytes, out, stream);
+}
+
+extern "C" int eben_stoi_ragged(const float* clean, const float* processed, int rows, int t_max, const int32_t* lengths, int fs,
+                                const float* resample_table, int taps, void* workspace, size_t ws_bytes, float* out, void* stream) {
+  EBEN_REQUIRE(clean && processed && lengths && out && workspace, "stoi_ragged: null pointer");
+  EBEN_REQUIRE(rows > 0 && rows <= 65535 && t_max > 0 && fs > 0, "stoi_ragged: rows = %d outside [1, 65535], t_max = %d or fs = %d <= 0", rows,
+               t_max, fs);
+  return launch_stoi(clean, processed, rows, t_max, lengths, fs, resample_table, taps, workspace, ws_bytes, out, stream);
 }

@@ -3,14 +3,21 @@
 What the reference does clip by clip (``scripts/eben_enhanced_vibravox.py``: ``cut_to_valid_length``, one batch-1 forward each) runs
 here as a few batched forwards: the clips are sorted by length, dealt into batches of at most ``max_batch_samples`` buffer samples and
 each batch goes through ``EBENGenerator.forward_ragged`` -- every clip's result is the one its own forward gives.
+
+``evaluate_clips`` scores such a corpus against its references the same way (the reference's ``trainer.test`` does it with batches of
+one): per batch one ragged forward and the SI-SDR / STOI kernels with a length per row, straight from the padded buffers.
 """
 from __future__ import annotations
 
-from typing import List, Sequence
+import math
+from typing import Dict, List, Sequence
 
 import torch
 
 from . import ragged
+
+#: the rate ``base_se.py`` evaluates SI-SDR and STOI at
+EVAL_RATE = 16000
 
 #: buffer samples (rows x padded length) per batch: 262 s at 16 kHz.  The widest activations (32 channels at 1/4 of the audio rate,
 #: 64 at 1/8) take 32 bytes per audio sample each, 128 MiB a tensor at this budget
@@ -78,3 +85,72 @@ def enhance_clips(generator, clips: Sequence[torch.Tensor], *, max_batch_samples
                 bands.append(bnd[r, :, : plan.row_lengths[1][r]].clone())
     enhanced = [enhanced[p] for p in back]
     return (enhanced, [bands[p] for p in back]) if return_bands else enhanced
+
+
+def resampled_length(length: int, orig_freq: int, new_freq: int) -> int:
+    """Samples ``augment.resample`` returns for a signal of ``length``: ceil(new * length / orig) over the reduced ratio, in integers."""
+    g = math.gcd(int(orig_freq), int(new_freq))
+    orig, new = int(orig_freq) // g, int(new_freq) // g
+    return -(-new * int(length) // orig)
+
+
+def _check_clip(c, what: str) -> None:
+    if not torch.is_tensor(c) or c.dim() not in (1, 2, 3) or c.numel() != c.shape[-1] or c.dtype is not torch.float32:
+        got = f"{c.dtype} {tuple(c.shape)}" if torch.is_tensor(c) else type(c).__name__
+        raise ValueError(f"{what}: expected a float32 tensor of shape (T,), (1, T) or (1, 1, T), got {got}")
+
+
+@torch.no_grad()
+def evaluate_clips(generator, corrupted: Sequence[torch.Tensor], reference: Sequence[torch.Tensor], *, sample_rate: int = EVAL_RATE,
+                   max_batch_samples: int = MAX_BATCH_SAMPLES, return_enhanced: bool = False) -> Dict[str, object]:
+    """Per-clip SI-SDR and STOI of the enhanced ``corrupted[i]`` against ``reference[i]``, at 16 kHz as ``base_se.py`` logs them:
+    ``{"si_sdr": (N,) float32, "stoi": (N,) float32}`` on the device, in input order; with ``return_enhanced`` also ``"enhanced"``, the
+    list ``enhance_clips`` returns.  Clips as for ``enhance_clips``; a pair has one length, and both are scored on their first
+    ``cut_to_valid_length`` samples (a reference may carry anything behind them).  Batches as in ``enhance_clips``: per batch one
+    ``forward_ragged`` and the metric kernels with ``lengths = plan.cut`` on the padded buffers -- nothing is unpacked unless
+    ``return_enhanced`` asks for it, and nothing here waits for the device."""
+    from . import metrics
+
+    corrupted, reference = list(corrupted), list(reference)
+    if len(corrupted) != len(reference):
+        raise ValueError(f"evaluate_clips: {len(corrupted)} corrupted clips and {len(reference)} references")
+    for i, (c, g) in enumerate(zip(corrupted, reference)):
+        _check_clip(c, f"corrupted clip {i}")
+        _check_clip(g, f"reference clip {i}")
+        if c.shape[-1] != g.shape[-1]:
+            raise ValueError(f"pair {i}: the corrupted clip has {c.shape[-1]} samples, its reference {g.shape[-1]}")
+    sample_rate = int(sample_rate)
+    if sample_rate <= 0:
+        raise ValueError(f"evaluate_clips: sample_rate must be positive, got {sample_rate}")
+    lengths = [c.shape[-1] for c in corrupted]
+    batches, back = ragged.compose_batches(generator, lengths, max_batch_samples)   # refuses a clip that is too short, by index
+    si_sdr: List[torch.Tensor] = []
+    stoi: List[torch.Tensor] = []
+    enhanced: List[torch.Tensor] = []
+    for idx in batches:
+        plan = ragged.plan(generator, [lengths[i] for i in idx])
+        dev = corrupted[idx[0]].device
+        buf = torch.zeros((len(idx), 1, plan.l_buf), dtype=torch.float32, device=dev)
+        ref = torch.zeros((len(idx), plan.l_buf), dtype=torch.float32, device=dev)
+        for r, i in enumerate(idx):
+            buf[r, 0, : plan.cut[r]].copy_(corrupted[i].reshape(-1)[: plan.cut[r]])
+            ref[r, : plan.cut[r]].copy_(reference[i].reshape(-1)[: plan.cut[r]])
+        enh, _ = generator.forward_ragged(buf, [lengths[i] for i in idx])   # zero behind every row, like ref
+        if return_enhanced:
+            for r, i in enumerate(idx):
+                enhanced.append(enh[r, 0, : plan.cut[r]].reshape(corrupted[i].shape[:-1] + (plan.cut[r],)).clone())
+        enh, rows = enh.reshape(len(idx), plan.l_buf), plan.cut
+        if sample_rate != EVAL_RATE:
+            from .augment import resample
+
+            # the resampler's taps reach a few samples past a row's end: they find the zeros the row alone is padded with
+            enh, ref = resample(enh, sample_rate, EVAL_RATE), resample(ref, sample_rate, EVAL_RATE)
+            rows = [resampled_length(t, sample_rate, EVAL_RATE) for t in rows]
+        lens = torch.tensor(rows, dtype=torch.int32).to(dev, non_blocking=True)   # 1 <= each <= the buffer's length by construction
+        si_sdr.append(metrics.si_sdr(enh, ref, lens))
+        stoi.append(metrics.stoi(enh, ref, EVAL_RATE, lens))
+    order = torch.tensor(back, dtype=torch.int64).to(si_sdr[0].device, non_blocking=True)
+    out: Dict[str, object] = {"si_sdr": torch.cat(si_sdr).index_select(0, order), "stoi": torch.cat(stoi).index_select(0, order)}
+    if return_enhanced:
+        out["enhanced"] = [enhanced[p] for p in back]
+    return out

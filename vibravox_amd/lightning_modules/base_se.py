@@ -98,18 +98,54 @@ class BaseSELightningModule(_Base):
 
         return resample(x.contiguous(), int(self.sample_rate), 16000)
 
+    def _ragged_to_16k(self, enhanced: torch.Tensor, reference: torch.Tensor, lengths):
+        """A padded batch whose row r is ``[..., :lengths[r]]`` (one length per row of the flattened leading dimensions), at 16 kHz:
+        each row's resampling is the one the row alone gets.  The resampler's taps reach past a row's end, where the row alone is
+        zero-padded, so what lies behind each row is zeroed first, on a copy.  At 16 kHz nothing is touched or read behind a row."""
+        if int(self.sample_rate) == 16000:
+            return enhanced, reference, lengths
+        import math
+
+        from .. import metrics
+        from .._lib import check, load, ptr, stream
+
+        if enhanced.shape != reference.shape or enhanced.dim() < 1:
+            raise ValueError(f"common_eval_logging: enhanced {tuple(enhanced.shape)} and reference {tuple(reference.shape)} must have one shape")
+        t = enhanced.shape[-1]
+        lead = tuple(enhanced.shape[:-1])
+        rows = math.prod(lead)
+        host = metrics._host_lengths(lengths, rows, t, "common_eval_logging")
+        lens = (host.to(enhanced.device, non_blocking=True) if host is not None
+                else metrics._device_lengths(lengths, rows, lead, enhanced.device, "common_eval_logging"))
+        out = []
+        for x in (enhanced, reference):
+            x = x.detach().to(torch.float32).reshape(rows, 1, t).clone(memory_format=torch.contiguous_format)
+            check(load().eben_edge_zero(ptr(x), lens.data_ptr(), rows, 1, t, stream()), "edge_zero")
+            out.append(self._to_16k(x.reshape(lead + (t,))))
+        g = math.gcd(int(self.sample_rate), 16000)
+        orig, new = int(self.sample_rate) // g, 16000 // g
+        lens16 = ((lens.to(torch.int64) * new + (orig - 1)) // orig).to(torch.int32)   # augment.resample's length of the row alone
+        lens16 = torch.where((lens >= 1) & (lens <= t), lens16, torch.zeros_like(lens16))   # an out-of-range row stays out of range: NaN
+        return out[0], out[1], lens16
+
     def common_eval_logging(self, stage: str, outputs, batch_idx: int, dataloader_idx: int = 0) -> None:
         """base_se.py:67-130: with a reference, SI-SDR and STOI of the enhanced speech at 16 kHz, batch means logged as
         ``{stage}/torchmetrics_si_sdr{suffix}`` and ``{stage}/torchmetrics_stoi{suffix}`` (the metric objects also accumulate,
         as torchmetrics' forward does).  Without a reference the reference logs only model-based scores, which are out of
-        scope: nothing is logged."""
+        scope: nothing is logged.  ``outputs["lengths"]`` (optional, as ``metrics.si_sdr`` takes it) makes the batch a padded one:
+        row r is scored on its first ``lengths[r]`` samples alone."""
         if "reference" not in outputs:
             return
         names = getattr(self, "dataloader_names", None)
         suffix = f"/{names[dataloader_idx]}" if names is not None else ""
-        enhanced, reference = self._to_16k(outputs["enhanced"]), self._to_16k(outputs["reference"])
+        lengths = outputs.get("lengths")
+        if lengths is None:
+            enhanced, reference = self._to_16k(outputs["enhanced"]), self._to_16k(outputs["reference"])
+        else:
+            enhanced, reference, lengths = self._ragged_to_16k(outputs["enhanced"], outputs["reference"], lengths)
         for key, metric in self.metrics.items():
-            self.log(f"{stage}/{key}{suffix}", metric(enhanced, reference), sync_dist=True, prog_bar=True, add_dataloader_idx=False)
+            self.log(f"{stage}/{key}{suffix}", metric(enhanced, reference, lengths=lengths), sync_dist=True, prog_bar=True,
+                     add_dataloader_idx=False)
 
     def on_validation_batch_end(self, outputs, batch, batch_idx: int, dataloader_idx: int = 0) -> None:
         self.common_eval_logging("validation", outputs, batch_idx, dataloader_idx)

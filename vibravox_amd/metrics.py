@@ -14,11 +14,17 @@ kernels is test code under ``tests/``).
 ``ScaleInvariantSignalDistortionRatio`` and ``ShortTimeObjectiveIntelligibility`` mirror the torchmetrics classes
 (``update`` / ``compute`` / ``reset``; ``forward`` returns the batch mean and accumulates).  Their running sum and count
 live on the device as plain attributes, not buffers, so a module that holds them keeps its ``state_dict`` keys.
+
+Rows of different lengths: every entry point takes ``lengths``, one value per row of the flattened leading dimensions.  Row ``r`` is
+then the signal ``[..., :lengths[r]]`` -- what lies behind it is never read -- and its value has the bits of the call on that row
+alone (``eben_si_sdr_ragged`` / ``eben_stoi_ragged``: the same kernels with a length per row).  A sequence of ints or a CPU integer
+tensor is validated (``ValueError`` naming the row) and uploaded; an ``int32`` tensor on the signals' device is used as it is, without
+synchronisation, and a value outside ``[1, T]`` in it makes that row NaN.
 """
 from __future__ import annotations
 
 import math
-from typing import Dict, Optional, Tuple
+from typing import Dict, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -28,26 +34,72 @@ from ._lib import EbenError, check, load, ptr, stream
 STOI_FS = 10000
 
 
-def _rows(preds: torch.Tensor, target: torch.Tensor, what: str) -> Tuple[torch.Tensor, torch.Tensor, Tuple[int, ...]]:
+Lengths = Union[None, Sequence[int], torch.Tensor]
+
+
+def _host_lengths(lengths, rows: int, t: int, what: str) -> Optional[torch.Tensor]:
+    """A host-side ``lengths`` checked and as a CPU int32 tensor; None for a device tensor (``_device_lengths`` takes those)."""
+    if torch.is_tensor(lengths):
+        if lengths.is_cuda:
+            return None
+        if lengths.dtype in (torch.bool,) or lengths.is_floating_point() or lengths.is_complex():
+            raise ValueError(f"{what}: lengths must be integers, got a {lengths.dtype} tensor")
+        values = [int(v) for v in lengths.reshape(-1).tolist()]
+    else:
+        values = []
+        for r, v in enumerate(lengths):
+            if isinstance(v, bool) or int(v) != v:
+                raise ValueError(f"{what}: lengths[{r}] = {v!r} is not an integer")
+            values.append(int(v))
+    if len(values) != rows:
+        raise ValueError(f"{what}: {len(values)} lengths for {rows} rows")
+    for r, v in enumerate(values):
+        if not 1 <= v <= t:
+            raise ValueError(f"{what}: row {r} has length {v}, outside [1, {t}]")
+    return torch.tensor(values, dtype=torch.int32)
+
+
+def _device_lengths(lengths: torch.Tensor, rows: int, lead: Tuple[int, ...], dev: torch.device, what: str) -> torch.Tensor:
+    """A ``lengths`` that already lives on a device: taken as it is (nobody reads its values on the host)."""
+    if lengths.device != dev:
+        raise ValueError(f"{what}: lengths is on '{lengths.device}', the signals are on '{dev}'")
+    if lengths.dtype is not torch.int32:
+        raise ValueError(f"{what}: a device lengths tensor must be int32, got {lengths.dtype}")
+    if tuple(lengths.shape) not in ((rows,), lead):
+        raise ValueError(f"{what}: a device lengths tensor must have shape {(rows,)} or {lead}, got {tuple(lengths.shape)}")
+    return lengths.contiguous().reshape(-1)
+
+
+def _rows(preds: torch.Tensor, target: torch.Tensor, what: str, lengths: Lengths = None):
+    """(preds, target) as contiguous float32 (rows, T), the leading shape and ``lengths`` as a device int32 (rows,) tensor or None."""
     if preds.shape != target.shape:
         raise ValueError(f"{what}: preds and target must have the same shape, got {tuple(preds.shape)} and {tuple(target.shape)}")
     if preds.dim() < 1 or preds.shape[-1] < 1:
         raise ValueError(f"{what}: expected (..., time) signals, got shape {tuple(preds.shape)}")
-    for t in (preds, target):
-        if not t.is_cuda:
-            raise EbenError(f"{what} runs only on an MI355X HIP device (got a tensor on '{t.device}'); there is no CPU path")
     lead = tuple(preds.shape[:-1])
     t = preds.shape[-1]
+    rows = math.prod(lead)
+    host = _host_lengths(lengths, rows, t, what) if lengths is not None else None   # refused before anything touches a device
+    for x in (preds, target):
+        if not x.is_cuda:
+            raise EbenError(f"{what} runs only on an MI355X HIP device (got a tensor on '{x.device}'); there is no CPU path")
     p2 = preds.detach().to(torch.float32).contiguous().reshape(-1, t)
     g2 = target.detach().to(torch.float32).contiguous().reshape(-1, t)
-    return p2, g2, lead
+    if lengths is None:
+        return p2, g2, lead, None
+    if host is not None:
+        return p2, g2, lead, host.to(p2.device, non_blocking=True)
+    return p2, g2, lead, _device_lengths(lengths, rows, lead, p2.device, what)
 
 
-def si_sdr(preds: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
-    """Scale-invariant SDR in dB per signal: (..., T) -> (...)."""
-    p2, g2, lead = _rows(preds, target, "si_sdr")
+def si_sdr(preds: torch.Tensor, target: torch.Tensor, lengths: Lengths = None) -> torch.Tensor:
+    """Scale-invariant SDR in dB per signal: (..., T) -> (...); with ``lengths``, of ``[..., :lengths[r]]`` per row."""
+    p2, g2, lead, lens = _rows(preds, target, "si_sdr", lengths)
     out = torch.empty(p2.shape[0], dtype=torch.float32, device=p2.device)
-    check(load().eben_si_sdr(ptr(p2), ptr(g2), p2.shape[0], p2.shape[1], ptr(out), stream()), "si_sdr")
+    if lens is None:
+        check(load().eben_si_sdr(ptr(p2), ptr(g2), p2.shape[0], p2.shape[1], ptr(out), stream()), "si_sdr")
+    else:
+        check(load().eben_si_sdr_ragged(ptr(p2), ptr(g2), p2.shape[0], p2.shape[1], lens.data_ptr(), ptr(out), stream()), "si_sdr_ragged")
     return out.reshape(lead)
 
 
@@ -67,9 +119,9 @@ def stoi_resample_table(fs: int) -> Tuple[np.ndarray, int, int]:
 _tables: Dict[Tuple[int, torch.device], torch.Tensor] = {}
 
 
-def stoi(preds: torch.Tensor, target: torch.Tensor, fs: int) -> torch.Tensor:
-    """Classic STOI per signal (target = clean reference): (..., T) -> (...)."""
-    p2, g2, lead = _rows(preds, target, "stoi")
+def stoi(preds: torch.Tensor, target: torch.Tensor, fs: int, lengths: Lengths = None) -> torch.Tensor:
+    """Classic STOI per signal (target = clean reference): (..., T) -> (...); with ``lengths``, of ``[..., :lengths[r]]`` per row."""
+    p2, g2, lead, lens = _rows(preds, target, "stoi", lengths)
     fs = int(fs)
     if fs <= 0:
         raise ValueError(f"stoi: fs must be positive, got {fs}")
@@ -83,10 +135,14 @@ def stoi(preds: torch.Tensor, target: torch.Tensor, fs: int) -> torch.Tensor:
             _tables[key] = torch.from_numpy(stoi_resample_table(fs)[0]).to(torch.float32).to(dev)
         table = _tables[key]
         taps = table.numel()
-    ws_bytes = lib.eben_stoi_workspace(rows, t, fs)
+    ws_bytes = lib.eben_stoi_workspace(rows, t, fs) if lens is None else lib.eben_stoi_ragged_workspace(rows, t, fs)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     out = torch.empty(rows, dtype=torch.float32, device=dev)
-    check(lib.eben_stoi(ptr(g2), ptr(p2), rows, t, fs, ptr(table), taps, ws.data_ptr(), ws_bytes, ptr(out), stream()), "stoi")
+    if lens is None:
+        check(lib.eben_stoi(ptr(g2), ptr(p2), rows, t, fs, ptr(table), taps, ws.data_ptr(), ws_bytes, ptr(out), stream()), "stoi")
+    else:
+        check(lib.eben_stoi_ragged(ptr(g2), ptr(p2), rows, t, lens.data_ptr(), fs, ptr(table), taps, ws.data_ptr(), ws_bytes, ptr(out),
+                                   stream()), "stoi_ragged")
     return out.reshape(lead)
 
 
@@ -98,7 +154,7 @@ class _MeanMetric(torch.nn.Module):
         self._sum: Optional[torch.Tensor] = None
         self._count: Optional[torch.Tensor] = None
 
-    def _values(self, preds: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    def _values(self, preds: torch.Tensor, target: torch.Tensor, lengths: Lengths = None) -> torch.Tensor:
         raise NotImplementedError
 
     def _accumulate(self, values: torch.Tensor) -> None:
@@ -108,8 +164,8 @@ class _MeanMetric(torch.nn.Module):
         self._sum += values.sum(dtype=torch.float64)
         self._count += values.numel()
 
-    def update(self, preds: torch.Tensor, target: torch.Tensor) -> None:
-        self._accumulate(self._values(preds, target))
+    def update(self, preds: torch.Tensor, target: torch.Tensor, lengths: Lengths = None) -> None:
+        self._accumulate(self._values(preds, target, lengths))
 
     def compute(self) -> torch.Tensor:
         if self._sum is None:
@@ -119,9 +175,9 @@ class _MeanMetric(torch.nn.Module):
     def reset(self) -> None:
         self._sum = self._count = None
 
-    def forward(self, preds: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    def forward(self, preds: torch.Tensor, target: torch.Tensor, lengths: Lengths = None) -> torch.Tensor:
         """Batch mean of this call; also accumulated into the running state."""
-        values = self._values(preds, target)
+        values = self._values(preds, target, lengths)
         self._accumulate(values)
         return values.mean()
 
@@ -133,8 +189,8 @@ class ScaleInvariantSignalDistortionRatio(_MeanMetric):
             raise NotImplementedError("only zero_mean=False (torchmetrics' default, the one base_se.py uses) is implemented")
         self.zero_mean = zero_mean
 
-    def _values(self, preds, target):
-        return si_sdr(preds, target)
+    def _values(self, preds, target, lengths=None):
+        return si_sdr(preds, target, lengths)
 
 
 class ShortTimeObjectiveIntelligibility(_MeanMetric):
@@ -145,5 +201,5 @@ class ShortTimeObjectiveIntelligibility(_MeanMetric):
         self.fs = int(fs)
         self.extended = extended
 
-    def _values(self, preds, target):
-        return stoi(preds, target, self.fs)
+    def _values(self, preds, target, lengths=None):
+        return stoi(preds, target, self.fs, lengths)
