@@ -38,6 +38,7 @@ import torch
 
 from . import ops
 from ._lib import check, load, ptr, stream
+from .gen_layers import layers
 
 USE_FUSED_RU = os.environ.get("EBEN_RU_FUSED", "1") != "0"
 USE_FUSED_RU_BWD = os.environ.get("EBEN_RU_FUSED_BWD", "1") != "0"
@@ -134,7 +135,11 @@ class GeneratorEngine:
         self._dw_graphs: List[ops.ReplayedChain] = []
         self._static: Dict[tuple, torch.Tensor] = {}   # (name, shape) -> buffer the graphs read their per-step input from
         self._dwq: Optional[list] = None               # while the input-gradient chain runs in queue mode: its weight-gradient work items
-        self._core_convs = self._core_units = None
+        # the layer table (gen_layers.py): the core entries in launch order, every entry by its path, and the core's units and convs
+        self._core = [la for la in layers(gen) if la.core]
+        self._by_path = {la.path: la for la in layers(gen)}
+        self._core_units = [la.module for la in self._core if la.kind == "unit"]
+        self._core_convs = [m for la in self._core for m in ((la.module.dilated_conv, la.module.pointwise_conv) if la.kind == "unit" else (la.module,))]
 
     # ---- helpers ------------------------------------------------------------------------------------
     def _spec(self, m, in_slope=None, out_slope=None) -> ops.ConvSpec:
@@ -263,12 +268,7 @@ class GeneratorEngine:
     def image_caches(self) -> list:
         """``ops.prepack`` entries of the fused units that hold images."""
         return [(c, lambda slot, ru=ru, c=c: self._ru_rebuild(ru, c, slot))
-                for ru in self._units() if (c := self._ru_images.get(id(ru))) is not None and c.images]
-
-    def _units(self) -> list:
-        if self._core_units is None:
-            self._core_units = [ru for blk in list(self.gen.encoder_blocks) + list(self.gen.decoder_blocks) for ru in blk.residuals]
-        return self._core_units
+                for ru in self._core_units if (c := self._ru_images.get(id(ru))) is not None and c.images]
 
     def _residual_unit(self, ru, x, in_slope, train, recs):
         """y = xin + lrelu(pointwise(dilated(xin))), xin = lrelu(x, in_slope).  Returns y; records (x, h, u) for the backward."""
@@ -319,55 +319,43 @@ class GeneratorEngine:
         return y
 
     # ---- forward -------------------------------------------------------------------------------------
+    def _launch(self, layer, x, train, recs):
+        """Entry ``layer`` of the table on its input: the unit's fused launch, or the conv's."""
+        if layer.kind == "unit":
+            return self._residual_unit(layer.module, x, layer.in_slope, train, recs)
+        return self._conv(layer.module, x, train, in_slope=layer.in_slope if layer.in_slope != 1.0 else None, recs=recs)
+
+    @staticmethod
+    def _records(saved, name, block=None) -> list:
+        """The record list of backward segment (name[, block]) in ``saved``; a block's list is opened by the block's first layer."""
+        recs = saved[name]
+        if block is None:
+            return recs
+        if block == len(recs):
+            recs.append([])
+        return recs[block]
+
     def forward(self, cut_audio: torch.Tensor, train: bool, fill=None):
         """Returns (input of last_conv, first_bands, records for ``backward`` or None).  ``fill(layer path, x)``, inference only: called
         on the input of every layer with taps along time right before its launch (``forward_ragged`` writes the rows' own edges there)."""
         gen = self.gen
         lib = load()
         ops.join_prepack()   # images rebuilt ahead of time on the side stream
-        slope = gen.nl.negative_slope
         first_bands = gen.pqmf(cut_audio, "analysis", bands=gen.p).detach()
-        saved = {"enc": [], "dec": [], "misc": []} if train else None
-        if fill is not None:
-            fill("first_conv", first_bands)
-        a = self._conv(gen.first_conv, first_bands, train, recs=saved["misc"] if train else None)
-        skips = []
-        for i, blk in enumerate(gen.encoder_blocks):
-            recs = [] if train else None
-            cur = a
-            for k, ru in enumerate(blk.residuals):
-                if fill is not None:
-                    fill(f"encoder_blocks.{i}.residuals.{k}", cur)
-                cur = self._residual_unit(ru, cur, slope if k == 0 else 1.0, train, recs)
+        saved = {"enc": [], "dec": [], "misc": [], "latent": []} if train else None
+        x, skips = first_bands, {}
+        for layer in self._core:
+            recs = self._records(saved, *layer.segment) if train else None
+            if layer.add is not None:
+                s = torch.empty_like(x)
+                check(lib.eben_add(ptr(x), ptr(skips[layer.add]), ptr(s), x.numel(), stream()), "add")
+                x = s
             if fill is not None:
-                fill(f"encoder_blocks.{i}.conv", cur)
-            a = self._conv(blk.conv, cur, train, recs=recs)
-            skips.append(a)
-            if train:
-                saved["enc"].append(recs)
-        lat = [] if train else None
-        if fill is not None:
-            fill("latent_conv.1", a)
-        l1 = self._conv(gen.latent_conv[1], a, train, in_slope=slope, recs=lat)
-        if fill is not None:
-            fill("latent_conv.3", l1)
-        cur = self._conv(gen.latent_conv[3], l1, train, recs=lat)
-        if train:
-            saved["latent"] = lat
-        for i, (blk, skip) in enumerate(zip(gen.decoder_blocks, reversed(skips))):
-            recs = [] if train else None
-            s = torch.empty_like(cur)
-            check(lib.eben_add(ptr(cur), ptr(skip), ptr(s), cur.numel(), stream()), "add")
-            if fill is not None:
-                fill(f"decoder_blocks.{i}.conv_trans", s)
-            cur = self._conv(blk.conv_trans, s, train, recs=recs)
-            for k, ru in enumerate(blk.residuals):
-                if fill is not None:
-                    fill(f"decoder_blocks.{i}.residuals.{k}", cur)
-                cur = self._residual_unit(ru, cur, 1.0, train, recs)
-            if train:
-                saved["dec"].append(recs)
-        return cur, first_bands, saved
+                fill(layer.path, x)
+            x = self._launch(layer, x, train, recs)
+            if layer.skip is not None:
+                skips[layer.skip] = x
+        return x, first_bands, saved
 
     # ---- ragged batches: rows of different lengths, inference only (vibravox_amd/ragged.py) ---------------------------------------
     @staticmethod
@@ -423,23 +411,13 @@ class GeneratorEngine:
     def _stream_node(self, name: str, x: torch.Tensor) -> torch.Tensor:
         """Node ``name`` of the stream on its buffer: the launch ``forward(.., train=False)`` makes for that layer."""
         gen = self.gen
-        slope = gen.nl.negative_slope
         if name == "pqmf.analysis":
             return gen.pqmf(x, "analysis", bands=gen.p)
         if name == "pqmf.synthesis":
             return gen.pqmf.synthesis_sum(x)
-        if name == "first_conv":
-            return self._conv(gen.first_conv, x, False)
         if name == "last_conv":
             return gen.last_conv(x)
-        part, *rest = name.split(".")
-        if part == "latent_conv":
-            return self._conv(gen.latent_conv[int(rest[0])], x, False, in_slope=slope if rest[0] == "1" else None)
-        blk = (gen.encoder_blocks if part == "encoder_blocks" else gen.decoder_blocks)[int(rest[0])]
-        if rest[1] == "residuals":
-            first_of_encoder = part == "encoder_blocks" and rest[2] == "0"
-            return self._residual_unit(blk.residuals[int(rest[2])], x, slope if first_of_encoder else 1.0, False, None)
-        return self._conv(getattr(blk, rest[1]), x, False)
+        return self._launch(self._by_path[name], x, False, None)
 
     def _stream_launch(self, state: "StreamState", op, outs: Dict[str, torch.Tensor]) -> torch.Tensor:
         """One ``streaming.Launch`` on every row of ``state``: the node's output."""
@@ -454,16 +432,12 @@ class GeneratorEngine:
             raise RuntimeError(f"stream schedule out of step with the kernels: {op} gave {y.shape[2]} samples")
         return y
 
-    def stream_run(self, state: "StreamState", operations, chunk: Optional[torch.Tensor]) -> Dict[str, torch.Tensor]:
-        """Executes one push's operations (``streaming.Schedule.push``) on ``state``; returns the tensors emitted, by output name.
-        Every input is spliced by ``eben_stream_splice`` and every layer launched as ``forward`` launches it; nothing waits."""
+    def _stream_ops(self, state: "StreamState", operations, chunk, emit_rows: int, splice) -> Dict[str, torch.Tensor]:
+        """The operations of one push on ``state``; returns the tensors emitted (``emit_rows`` rows each), by output name.  Every layer is
+        launched as ``forward`` launches it; ``splice(op, kind, key, dst, total, prev, src, add, channels)`` launches a splice."""
         from .streaming import Splice
 
-        if torch.is_grad_enabled():
-            raise RuntimeError("EBEN generator engine: stream_run has no backward; call it under torch.no_grad()")
-        lib = load()
         ops.join_prepack()
-        rows = state.rows
         outs: Dict[str, torch.Tensor] = {}
         emitted: Dict[str, torch.Tensor] = {}
 
@@ -487,15 +461,28 @@ class GeneratorEngine:
             prev, src, add = operand(op.prev), operand(op.src), operand(op.add)
             channels = (prev if prev is not None else src).shape[1]
             if kind == "emit":
-                dst = emitted[key] = torch.empty((rows, channels, total), dtype=torch.float32, device=state.device)
+                dst = emitted[key] = torch.empty((emit_rows, channels, total), dtype=torch.float32, device=state.device)
             else:
                 dst = state.twin(key, total)
-            pitch = lambda t: 0 if t is None else t.shape[2]
-            check(lib.eben_stream_splice(ptr(dst), total, ptr(prev), pitch(prev), op.prev_off, op.n_carry, ptr(src), pitch(src), op.src_off, op.n_new,
-                                         ptr(add), pitch(add), op.add_off, rows * channels, stream()), "stream_splice")
+            splice(op, kind, key, dst, total, prev, src, add, channels)
             if kind == "tape":
                 state.flip(key, total)
         return emitted
+
+    def stream_run(self, state: "StreamState", operations, chunk: Optional[torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """Executes one push's operations (``streaming.Schedule.push``) on ``state``; returns the tensors emitted, by output name.
+        Every input is spliced by ``eben_stream_splice`` and every layer launched as ``forward`` launches it; nothing waits."""
+        if torch.is_grad_enabled():
+            raise RuntimeError("EBEN generator engine: stream_run has no backward; call it under torch.no_grad()")
+        lib = load()
+        rows = state.rows
+        pitch = lambda t: 0 if t is None else t.shape[2]
+
+        def splice(op, kind, key, dst, total, prev, src, add, channels):
+            check(lib.eben_stream_splice(ptr(dst), total, ptr(prev), pitch(prev), op.prev_off, op.n_carry, ptr(src), pitch(src), op.src_off, op.n_new,
+                                         ptr(add), pitch(add), op.add_off, rows * channels, stream()), "stream_splice")
+
+        return self._stream_ops(state, operations, chunk, rows, splice)
 
     def stream_run_pooled(self, state: "StreamState", steady, chunks: torch.Tensor, mask, n_active: int) -> Dict[str, torch.Tensor]:
         """One steady-state push (``plan.steady``) of the slots whose bit is set in ``mask`` (64-bit words), on the shared ``state`` of a
@@ -503,52 +490,26 @@ class GeneratorEngine:
         slots as in ``stream_run``; every splice is an ``eben_stream_splice_rows``: the analysis tape reads the compact input, every
         tape that holds state carries its idle slots over to the twin buffer, and the emits come back compact, a row per active slot
         in slot order."""
-        from .streaming import Splice
-
         if torch.is_grad_enabled():
             raise RuntimeError("EBEN generator engine: stream_run_pooled has no backward; call it under torch.no_grad()")
         if tuple(chunks.shape[:2]) != (n_active, 1) or n_active != sum(bin(w).count("1") for w in mask) or n_active < 1:
             raise ValueError(f"stream_run_pooled: {tuple(chunks.shape)} chunks for {n_active} active slots of mask {mask}")
         lib = load()
-        ops.join_prepack()
         rows = state.rows
         words = (ctypes.c_uint64 * 4)(*mask)
-        outs: Dict[str, torch.Tensor] = {}
-        emitted: Dict[str, torch.Tensor] = {}
         pitch = lambda t: 0 if t is None else t.shape[2]
 
-        def operand(name):
-            if name is None or name == "input":
-                return chunks if name else None
-            kind, key = name.split(":", 1)
-            return outs[key] if kind == "out" else state.view(key)
-
-        for op in steady:
-            if not isinstance(op, Splice):
-                outs[op.node] = self._stream_launch(state, op, outs)
-                continue
-            total = op.n_carry + op.n_new
-            kind, key = op.dst.split(":", 1)
-            if total == 0:
-                state.length[key] = 0
-                continue
-            prev, src, add = operand(op.prev), operand(op.src), operand(op.add)
-            channels = (prev if prev is not None else src).shape[1]
+        def splice(op, kind, key, dst, total, prev, src, add, channels):
             idle = None
-            if kind == "emit":
-                dst = emitted[key] = torch.empty((n_active, channels, total), dtype=torch.float32, device=state.device)
-            else:
-                dst = state.twin(key, total)
-                if key != "lift.operand":   # rewritten whole from another tape every push: it holds no state
-                    idle = state.view(key)
-                    if idle.shape[2] != total:
-                        raise RuntimeError(f"pool state out of step with the steady list: {op} on a buffer of {idle.shape[2]}")
+            if kind == "tape" and key != "lift.operand":   # the lift's operand is rewritten whole from another tape every push: it holds no state
+                idle = state.view(key)
+                if idle.shape[2] != total:
+                    raise RuntimeError(f"pool state out of step with the steady list: {op} on a buffer of {idle.shape[2]}")
             check(lib.eben_stream_splice_rows(ptr(dst), total, ptr(prev), pitch(prev), op.prev_off, op.n_carry, ptr(src), pitch(src), op.src_off,
                                               op.n_new, ptr(add), pitch(add), op.add_off, ptr(idle), pitch(idle), rows * channels, channels, words,
                                               1 if op.src == "input" else 0, 1 if kind == "emit" else 0, stream()), "stream_splice_rows")
-            if kind == "tape":
-                state.flip(key, total)
-        return emitted
+
+        return self._stream_ops(state, steady, chunks, n_active, splice)
 
     def stream_move(self, pool: "StreamState", slot: int, private: "StreamState", names, into_pool: bool) -> None:
         """A session's steady-state buffers (tensors ``names`` of the plan) between the batch-1 state ``private`` and row ``slot`` of the
@@ -782,14 +743,9 @@ class GeneratorEngine:
     def _fwd_sig(self, buf: torch.Tensor) -> tuple:
         """Everything the captured forward depends on besides values: input buffer, arithmetic, and per layer and fused unit the image
         cache's buffers and whether they are current (a stale image makes the eager path rebuild it -- a replay would not)."""
-        if self._core_convs is None:
-            gen = self.gen
-            from .torch_modules.utils import HipConv1d
-            self._core_convs = [m for part in (gen.first_conv, gen.encoder_blocks, gen.latent_conv, gen.decoder_blocks)
-                                for m in part.modules() if isinstance(m, HipConv1d)]
         parts = [buf.data_ptr(), tuple(buf.shape), ops._backward_math[0], conv_forward_math(), ru_forward_math()]
         parts += [m._packed.state() for m in self._core_convs]
-        parts += [None if (c := self._ru_images.get(id(ru))) is None else c.state() for ru in self._units()]
+        parts += [None if (c := self._ru_images.get(id(ru))) is None else c.state() for ru in self._core_units]
         return tuple(parts)
 
     def forward_train(self, x: torch.Tensor):

@@ -7,14 +7,16 @@ supplied: the mirror ``x[L + j] = x[L - 2 - j]`` for reflect-padded layers, zero
 ordinary kernel then computes the row's outputs ``[0, L_out)`` exactly as the row's own batch-1 forward does; what it writes beyond is
 junk nobody reads, and the next fill overwrites the part that matters.
 
-``plan`` walks the generator's layers in the order ``GeneratorEngine.forward`` launches them and derives, from each layer's
-``ConvSpec``, how many samples past a row's last one the row's last output reads -- the fill count in front of that layer -- and from
-the largest such reach the margin every row needs.  ``compose_batches`` deals a corpus into such batches.
+``plan`` walks the generator's layer table (``gen_layers.layers``: the order ``GeneratorEngine.forward`` launches, a ResidualUnit
+standing as its dilated conv) and derives, from each entry's ``ConvSpec``, how many samples past a row's last one the row's last
+output reads -- the fill count in front of that layer -- and from the largest such reach the margin every row needs.  ``compose_batches`` deals a corpus into such batches.
 """
 from __future__ import annotations
 
 import dataclasses
 from typing import List, Sequence, Tuple
+
+from .gen_layers import layers
 
 MIRROR, ZERO, ZERO_ALL = "mirror", "zero", "zero_all"   # ZERO_ALL: the whole slack (the input and the two outputs); count = what is needed
 
@@ -55,35 +57,20 @@ def reach(spec, l_in: int) -> int:
     return (l_out - 1) * spec.stride - spec.pad_l + (spec.ksize - 1) * spec.dilation - (l_in - 1)
 
 
-def _layers(gen) -> list:
-    """(module path, ConvSpec) of every layer with taps along time, in the order of ``GeneratorEngine.forward``; a ResidualUnit is its
-    dilated conv (the pointwise conv reads one sample, the residual add none)."""
-    out = [("first_conv", gen.first_conv.spec)]
-    for i, blk in enumerate(gen.encoder_blocks):
-        out += [(f"encoder_blocks.{i}.residuals.{k}", ru.dilated_conv.spec) for k, ru in enumerate(blk.residuals)]
-        out.append((f"encoder_blocks.{i}.conv", blk.conv.spec))
-    out += [("latent_conv.1", gen.latent_conv[1].spec), ("latent_conv.3", gen.latent_conv[3].spec)]
-    for i, blk in enumerate(gen.decoder_blocks):
-        out.append((f"decoder_blocks.{i}.conv_trans", blk.conv_trans.spec))
-        out += [(f"decoder_blocks.{i}.residuals.{k}", ru.dilated_conv.spec) for k, ru in enumerate(blk.residuals)]
-    out.append(("last_conv", gen.last_conv.spec))
-    return out
-
-
 def _walk(gen, audio_lengths: Sequence[int], rows: int):
-    """Row lengths per resolution and, per layer, (path, spec, resolution of its input).  The first ``rows`` entries of ``audio_lengths``
-    are clips (checked against the layers' reflect pads), any further ones buffers."""
+    """Row lengths per resolution and, per entry of ``gen_layers.layers``, (layer, resolution of its input).  The first ``rows`` entries
+    of ``audio_lengths`` are clips (checked against the layers' reflect pads), any further ones buffers."""
     m, n = gen.pqmf.decimation, gen.pqmf.kernel_size
     levels = [tuple(audio_lengths), tuple((t + n - 2) // m + 1 for t in audio_lengths)]
     cur, steps = 1, []
-    for path, spec in _layers(gen):
-        lens = levels[cur]
+    for layer in layers(gen):
+        path, spec, lens = layer.path, layer.spec, levels[cur]
         if spec.reflect:
             for r in range(rows):
                 if max(spec.pad_l, spec.pad_r) >= lens[r]:
                     raise ValueError(f"clip {r} ({audio_lengths[r]} samples after cut_to_valid_length) is too short: {path} reflect-pads "
                                      f"{max(spec.pad_l, spec.pad_r)} onto a row of {lens[r]}")
-        steps.append((path, spec, cur))
+        steps.append((layer, cur))
         out = tuple(spec.out_len(l) for l in lens)
         if out != lens:
             if out not in levels:
@@ -111,10 +98,10 @@ def plan(gen, lengths: Sequence[int]) -> RaggedPlan:
     m, n = gen.pqmf.decimation, gen.pqmf.kernel_size
     # the analysis bank (zero pad n - 1, stride m): the row's last band sample reads the audio up to (L0 - 1) m
     fills = [Fill("pqmf.analysis", ZERO_ALL, max((l0 - 1) * m - (t - 1) for t, l0 in zip(cut, levels[1])), 0)]
-    for path, spec, lv in steps:
-        count = max(reach(spec, l) for l in set(levels[lv]))
+    for layer, lv in steps:
+        count = max(reach(layer.spec, l) for l in set(levels[lv]))
         if count > 0:
-            fills.append(Fill(path, MIRROR if spec.reflect else ZERO, count, lv))
+            fills.append(Fill(layer.path, MIRROR if layer.spec.reflect else ZERO, count, lv))
     # The synthesis bank: a row's own samples read no frame past its last one (the transposed form's reach is 0), but the n samples behind
     # its end do; one filter span of zeroed frames, n / m, keeps those the bank's own tail and junk-free.  The bands are an output, so
     # all of their slack is zeroed.

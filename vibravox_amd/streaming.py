@@ -9,13 +9,15 @@ outputs whose taps stay inside the buffer.
 
 Everything here is arithmetic on positions (host only, no GPU needed):
 
+  * ``nodes_of`` makes a stream node of every entry of the generator's layer table (``gen_layers.layers``: order, kind, and which
+    encoder output a layer produces or adds come from there; no module path is parsed here), between the two PQMF banks.
   * ``Schedule`` tracks, per tensor, the stream positions ``[S, F)`` its buffer holds and from where the next push still needs it, and
     turns one push into a list of ``Splice`` / ``Launch`` operations with buffer-relative offsets.  Warm-up (growing buffers with a
     true left edge), the steady state and ``finish`` (a true right edge) are the same rules; in the steady state the list repeats.
   * ``plan`` runs a schedule to its steady state and reads off, per tensor: rate, new samples per push, frontier lag, carry, buffer
     length and capacity; and ``lookahead`` / ``latency``.
-  * ``StreamingEnhancer`` executes the operations on the device through ``GeneratorEngine``; ``tests/stream_oracle.py`` executes the
-    same operations in float64 on poisoned buffers.
+  * ``StreamingEnhancer`` executes the operations on the device through ``GeneratorEngine``, which finds a node's launch in the same
+    table by its path; ``tests/stream_oracle.py`` executes the same operations in float64 on poisoned buffers.
   * ``PoolBook`` keeps independent sessions -- streams that begin, pause and end whenever they like -- in the slots of one shared state:
     the steady-state list is position-free and every position of a ``Schedule`` moves by a constant per steady push
     (``Schedule.advance``), so all sessions that push in a tick share ONE run of ``plan.steady`` with a mask of the slots that advance.
@@ -92,22 +94,17 @@ def _ceil(a: int, b: int) -> int:
 
 
 def nodes_of(gen) -> List[Node]:
-    """The generator as stream nodes: ``ragged``'s layer walk with the two PQMF banks and the tanh lift added."""
+    """The generator as stream nodes: a node per entry of the layer table (``gen_layers.layers``, at the resolutions of ``ragged``'s
+    walk) with the two PQMF banks and the tanh lift added."""
     m, n, p = gen.pqmf.decimation, gen.pqmf.kernel_size, gen.p
-    n_enc = len(gen.encoder_blocks)
     out = [Node("pqmf.analysis", "analysis", 1, p, n, m, 1, n - 1, n - 1, False, 1, feeds=("first_bands",))]
     levels, steps = ragged._walk(gen, (gen.multiple * 64 - n,), 0)
     rate = [1] + [m * (levels[1][0] // lv[0]) for lv in levels[1:]]
-    for path, spec, lv in steps:
-        unit = ".residuals." in path
-        kind = "convT" if spec.transposed else "unit" if unit else "conv"
-        add, feeds = None, ()
-        if path.startswith("encoder_blocks.") and path.endswith(".conv"):
-            feeds = (f"skip.{int(path.split('.')[1])}",)
-        if path.startswith("decoder_blocks.") and path.endswith(".conv_trans"):
-            add = f"skip.{n_enc - 1 - int(path.split('.')[1])}"
-        out.append(Node(path, kind, spec.c_in, spec.c_in if unit else spec.c_out, spec.ksize, spec.stride, spec.dilation, spec.pad_l,
-                        spec.pad_l if spec.transposed else spec.pad_r, bool(spec.reflect), rate[lv], add, feeds))
+    for layer, lv in steps:
+        spec = layer.spec
+        out.append(Node(layer.path, layer.kind, spec.c_in, spec.c_in if layer.kind == "unit" else spec.c_out, spec.ksize, spec.stride,
+                        spec.dilation, spec.pad_l, spec.pad_l if spec.transposed else spec.pad_r, bool(spec.reflect), rate[lv],
+                        None if layer.add is None else f"skip.{layer.add}", () if layer.skip is None else (f"skip.{layer.skip}",)))
     out.append(Node("lift", "lift", m, m, 1, 1, 1, 0, 0, False, m, feeds=("bands",)))
     out.append(Node("pqmf.synthesis", "synthesis", m, 1, n, m, 1, 0, 0, False, m, feeds=("enhanced",)))
     return out
@@ -380,7 +377,8 @@ def plan(gen, chunk_samples: int) -> StreamPlan:
     else:
         raise RuntimeError("the stream schedule did not settle")
     steady = tuple(ops)
-    new = {o.dst[5:]: (o.n_carry, o.n_new) for o in steady if isinstance(o, Splice) and o.dst.startswith("tape:")}
+    dsts = ((o, *o.dst.split(":", 1)) for o in steady if isinstance(o, Splice))
+    new = {key: (o.n_carry, o.n_new) for o, kind, key in dsts if kind == "tape"}
     tensors = []
     for name, t in sch.tapes.items():
         carry, fresh = new[name]
@@ -399,21 +397,18 @@ def plan(gen, chunk_samples: int) -> StreamPlan:
 
 
 # ---- the public driver ----------------------------------------------------------------------------------------------------------------
-class StreamingEnhancer:
-    """``generator`` on audio that is still arriving: ``push`` a ``(streams, 1, chunk_samples)`` float32 device tensor, get the newly
-    final enhanced samples ``(streams, 1, k)`` -- k is 0 during warm-up and exactly ``chunk_samples`` from the first non-empty return on;
-    ``finish()`` (optionally with the last, shorter chunk) returns the rest, up to ``ragged.cut_length(generator, total pushed)``.  The
-    concatenation is what ``generator(cut_to_valid_length(whole clip))`` returns.  Rows advance in lockstep.  ``return_bands``: every
-    call returns ``(enhanced, bands)``, the bands with the same semantics at their rate.  Nothing here waits for the device."""
+class _Driver:
+    """What the two drivers share: the plan, the state's device, the check of a pushed chunk and the tensors a call returns."""
 
-    def __init__(self, generator, chunk_samples: int, streams: int = 1, return_bands: bool = False):
-        if int(streams) < 1:
-            raise ValueError(f"streams must be positive, got {streams}")
-        self.generator, self.streams, self.return_bands = generator, int(streams), bool(return_bands)
+    _who = ""     # the class as its messages name it
+    _per = ""     # ... and whose the chunk is
+    _last = ""    # the call that takes the shorter last chunk
+
+    def __init__(self, generator, chunk_samples: int, return_bands: bool):
+        self.generator, self.return_bands = generator, bool(return_bands)
         self.plan = plan(generator, chunk_samples)
         self.chunk_samples = self.plan.chunk_samples
-        self._schedule = Schedule(generator, chunk_samples)
-        self.state = None   # device buffers: allocated at the first push, on the chunk's device
+        self.state = None   # device buffers: allocated by prepare() or at the first push, on the chunk's device
 
     @property
     def latency(self) -> int:
@@ -423,15 +418,66 @@ class StreamingEnhancer:
     def lookahead(self) -> int:
         return self.plan.lookahead
 
-    def prepare(self, device) -> "StreamingEnhancer":
-        """Allocates the state on ``device`` now instead of at the first push (it is allocated once either way)."""
+    def _allocate(self, device, rows: int) -> bool:
+        """The state of ``rows`` rows on ``device``; True when it was allocated by this call."""
         import torch
 
         from . import gen_engine
 
         device = torch.empty(0, device=device).device   # "cuda" -> cuda:0
-        if self.state is None or self.state.device != device:
-            self.state = gen_engine.engine_of(self.generator).stream_state(self.plan, self.streams, device)
+        if self.state is not None and self.state.device == device:
+            return False
+        self.state = gen_engine.engine_of(self.generator).stream_state(self.plan, rows, device)
+        return True
+
+    def _no_grad(self, what: str) -> None:
+        import torch
+
+        if torch.is_grad_enabled():
+            raise RuntimeError(f"{self._who}: {what} has no backward; call it under torch.no_grad()")
+
+    def _check(self, chunk, rows: int, what: str) -> None:
+        """``chunk``: ``rows`` rows of one chunk, or of fewer samples in the call that ends a stream."""
+        import torch
+
+        last = what == self._last
+        if (not isinstance(chunk, torch.Tensor) or chunk.dim() != 3 or tuple(chunk.shape[:2]) != (rows, 1) or chunk.dtype is not torch.float32
+                or not (chunk.shape[2] < self.chunk_samples if last else chunk.shape[2] == self.chunk_samples)):
+            got = f"{chunk.dtype} {tuple(chunk.shape)}" if isinstance(chunk, torch.Tensor) else type(chunk).__name__
+            raise ValueError(f"{self._who}: {what} expects a float32 ({rows}, 1, {self.chunk_samples}) tensor{self._per}"
+                             f"{' or a shorter last one' if last else ''}, got {got}")
+        if not chunk.is_cuda:
+            from ._lib import EbenError
+
+            raise EbenError(f"{self._who} runs only on an MI355X HIP device (got a tensor on '{chunk.device}'); there is no CPU path")
+
+    def _emitted(self, out: dict, rows: int, device) -> list:
+        """[enhanced] or [enhanced, bands] of a run's emits: ``(rows, c, 0)`` where nothing was emitted."""
+        import torch
+
+        names = (("enhanced", 1), ("bands", self.generator.pqmf.decimation))[: 2 if self.return_bands else 1]
+        return [t if (t := out.get(name)) is not None else torch.empty((rows, c, 0), dtype=torch.float32, device=device) for name, c in names]
+
+
+class StreamingEnhancer(_Driver):
+    """``generator`` on audio that is still arriving: ``push`` a ``(streams, 1, chunk_samples)`` float32 device tensor, get the newly
+    final enhanced samples ``(streams, 1, k)`` -- k is 0 during warm-up and exactly ``chunk_samples`` from the first non-empty return on;
+    ``finish()`` (optionally with the last, shorter chunk) returns the rest, up to ``ragged.cut_length(generator, total pushed)``.  The
+    concatenation is what ``generator(cut_to_valid_length(whole clip))`` returns.  Rows advance in lockstep.  ``return_bands``: every
+    call returns ``(enhanced, bands)``, the bands with the same semantics at their rate.  Nothing here waits for the device."""
+
+    _who, _last = "StreamingEnhancer", "finish"
+
+    def __init__(self, generator, chunk_samples: int, streams: int = 1, return_bands: bool = False):
+        if int(streams) < 1:
+            raise ValueError(f"streams must be positive, got {streams}")
+        self.streams = int(streams)
+        super().__init__(generator, chunk_samples, return_bands)
+        self._schedule = Schedule(generator, chunk_samples)
+
+    def prepare(self, device) -> "StreamingEnhancer":
+        """Allocates the state on ``device`` now instead of at the first push (it is allocated once either way)."""
+        self._allocate(device, self.streams)
         return self
 
     def reset(self) -> None:
@@ -440,56 +486,29 @@ class StreamingEnhancer:
         if self.state is not None:
             self.state.reset()
 
-    def _check(self, chunk, length_ok, what: str):
-        import torch
-
-        if torch.is_grad_enabled():
-            raise RuntimeError(f"StreamingEnhancer: {what} has no backward; call it under torch.no_grad()")
-        if (not isinstance(chunk, torch.Tensor) or chunk.dim() != 3 or tuple(chunk.shape[:2]) != (self.streams, 1) or not length_ok(chunk.shape[2])
-                or chunk.dtype is not torch.float32):
-            got = f"{chunk.dtype} {tuple(chunk.shape)}" if isinstance(chunk, torch.Tensor) else type(chunk).__name__
-            raise ValueError(f"StreamingEnhancer: {what} expects a float32 ({self.streams}, 1, {self.chunk_samples}) tensor"
-                             f"{' or a shorter last one' if what == 'finish' else ''}, got {got}")
-        if not chunk.is_cuda:
-            from ._lib import EbenError
-
-            raise EbenError(f"StreamingEnhancer runs only on an MI355X HIP device (got a tensor on '{chunk.device}'); there is no CPU path")
-
     def _run(self, chunk, n_in: int, final: bool):
         from . import gen_engine
 
         engine = gen_engine.engine_of(self.generator)
         device = chunk.device if chunk is not None else self.state.device if self.state is not None else next(self.generator.parameters()).device
         self.prepare(device)
-        ops = self._schedule.push(n_in, final)
-        out = engine.stream_run(self.state, ops, chunk)
-        import torch
-
-        enhanced = out.get("enhanced")
-        if enhanced is None:
-            enhanced = torch.empty((self.streams, 1, 0), dtype=torch.float32, device=device)
-        if not self.return_bands:
-            return enhanced
-        bands = out.get("bands")
-        if bands is None:
-            bands = torch.empty((self.streams, self.generator.pqmf.decimation, 0), dtype=torch.float32, device=device)
-        return enhanced, bands
+        out = engine.stream_run(self.state, self._schedule.push(n_in, final), chunk)
+        got = self._emitted(out, self.streams, device)
+        return tuple(got) if self.return_bands else got[0]
 
     def push(self, chunk):
-        self._check(chunk, lambda l: l == self.chunk_samples, "push")
+        self._no_grad("push")
+        self._check(chunk, self.streams, "push")
         return self._run(chunk.contiguous(), self.chunk_samples, False)
 
     def finish(self, tail=None):
         """The rest of the stream.  ``tail``: the last ``(streams, 1, r)`` samples, ``r < chunk_samples`` (what did not fill a chunk).
         ``ValueError`` when everything pushed is shorter than the shortest clip the generator accepts."""
-        import torch
-
-        if torch.is_grad_enabled():
-            raise RuntimeError("StreamingEnhancer: finish has no backward; call it under torch.no_grad()")
+        self._no_grad("finish")
         if tail is not None and tail.shape[-1] == 0:
             tail = None
         if tail is not None:
-            self._check(tail, lambda l: l < self.chunk_samples, "finish")
+            self._check(tail, self.streams, "finish")
             tail = tail.contiguous()
         return self._run(tail, 0 if tail is None else tail.shape[2], True)
 
@@ -639,7 +658,7 @@ class PoolBook:
         return entries
 
 
-class StreamPool:
+class StreamPool(_Driver):
     """Independent streams through one ``generator``: ``open()`` a session whenever a stream begins, ``step({session: chunk})`` with the
     ``(1, 1, chunk_samples)`` float32 device chunks of the sessions that have one this tick, ``close(session, tail)`` when it ends.  Per
     session the returns are those of ``StreamingEnhancer.push`` / ``finish`` on a stream of its own.  A session warms up and finishes
@@ -647,33 +666,18 @@ class StreamPool:
     tick is served by ONE run of the steady-state list over all rows, with masked splices (``eben_stream_splice_rows``) that leave the
     rows of the others as they are.  Nothing here waits for the device."""
 
+    _who, _per, _last = "StreamPool", " per session", "close"
+
     def __init__(self, generator, chunk_samples: int, slots: int = 64, return_bands: bool = False):
-        self.generator, self.return_bands = generator, bool(return_bands)
-        self.plan = plan(generator, chunk_samples)
-        self.chunk_samples = self.plan.chunk_samples
+        super().__init__(generator, chunk_samples, return_bands)   # ``state``: the shared one
         self.book = PoolBook(generator, chunk_samples, slots, self.plan)
         self.slots = self.book.slots
-        self.state = None      # the shared state: allocated by prepare() or at the first step
         self.private = {}      # id -> batch-1 StreamState, allocated when the book first hands the id out and kept
-
-    @property
-    def latency(self) -> int:
-        return self.plan.latency
-
-    @property
-    def lookahead(self) -> int:
-        return self.plan.lookahead
 
     def prepare(self, device, private: int = 0) -> "StreamPool":
         """Allocates the shared state on ``device`` now instead of at the first step, and ``private`` batch-1 states for sessions that
         warm up or finish at the same time (further ones are allocated when first needed, and kept)."""
-        import torch
-
-        from . import gen_engine
-
-        device = torch.empty(0, device=device).device
-        if self.state is None or self.state.device != device:
-            self.state = gen_engine.engine_of(self.generator).stream_state(self.plan, self.slots, device)
+        if self._allocate(device, self.slots):
             for t in self.plan.tensors:
                 self.state.length[t.name] = t.length
             self.private = {}
@@ -683,19 +687,6 @@ class StreamPool:
 
     def open(self) -> Session:
         return self.book.open()
-
-    def _check(self, chunk, length_ok, what: str):
-        import torch
-
-        if (not isinstance(chunk, torch.Tensor) or chunk.dim() != 3 or tuple(chunk.shape[:2]) != (1, 1) or not length_ok(chunk.shape[2])
-                or chunk.dtype is not torch.float32):
-            got = f"{chunk.dtype} {tuple(chunk.shape)}" if isinstance(chunk, torch.Tensor) else type(chunk).__name__
-            raise ValueError(f"StreamPool: {what} expects a float32 (1, 1, {self.chunk_samples}) tensor per session"
-                             f"{' or a shorter last one' if what == 'close' else ''}, got {got}")
-        if not chunk.is_cuda:
-            from ._lib import EbenError
-
-            raise EbenError(f"StreamPool runs only on an MI355X HIP device (got a tensor on '{chunk.device}'); there is no CPU path")
 
     def _private_state(self, i: int):
         from . import gen_engine
@@ -707,15 +698,7 @@ class StreamPool:
     def _results(self, out, sessions, results: dict) -> None:
         """The emitted tensors, a row per session, as what each session's call returns (rows are split in one call: a view per session
         built one by one costs more host time at 64 sessions than the mask does)."""
-        import torch
-
-        m = self.generator.pqmf.decimation
-        per_name = []
-        for name, c in (("enhanced", 1), ("bands", m))[: 2 if self.return_bands else 1]:
-            t = out.get(name)
-            if t is None:
-                t = torch.empty((len(sessions), c, 0), dtype=torch.float32, device=self.state.device)
-            per_name.append(t.split(1, dim=0) if len(sessions) > 1 else (t,))
+        per_name = [t.split(1, dim=0) if len(sessions) > 1 else (t,) for t in self._emitted(out, len(sessions), self.state.device)]
         for a, s in enumerate(sessions):
             results[s] = (per_name[0][a], per_name[1][a]) if self.return_bands else per_name[0][a]
 
@@ -741,15 +724,12 @@ class StreamPool:
 
     def step(self, chunks: dict) -> dict:
         """One tick: ``{session: chunk}`` -> ``{session: newly final samples}`` (``(enhanced, bands)`` with ``return_bands``)."""
-        import torch
-
-        if torch.is_grad_enabled():
-            raise RuntimeError("StreamPool: step has no backward; call it under torch.no_grad()")
+        self._no_grad("step")
         if not isinstance(chunks, dict):
             raise ValueError(f"StreamPool: step expects a dict of session -> chunk, got {type(chunks).__name__}")
         self.book.check(chunks)
         for chunk in chunks.values():
-            self._check(chunk, lambda l: l == self.chunk_samples, "step")
+            self._check(chunk, 1, "step")
         if not chunks:
             return {}
         chunks = {s: c.contiguous() for s, c in chunks.items()}
@@ -761,13 +741,12 @@ class StreamPool:
         """The rest of ``session``'s stream, as ``StreamingEnhancer.finish``; its slot is free for the next ``open()``."""
         import torch
 
-        if torch.is_grad_enabled():
-            raise RuntimeError("StreamPool: close has no backward; call it under torch.no_grad()")
+        self._no_grad("close")
         self.book.check([session])
         if tail is not None and isinstance(tail, torch.Tensor) and tail.shape[-1] == 0:
             tail = None
         if tail is not None:
-            self._check(tail, lambda l: l < self.chunk_samples, "close")
+            self._check(tail, 1, "close")
             tail = tail.contiguous()
         self.prepare(tail.device if tail is not None else self.state.device if self.state is not None
                      else next(self.generator.parameters()).device)
