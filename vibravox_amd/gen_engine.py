@@ -8,10 +8,11 @@ encoder blocks, latent convs, decoder blocks: everything up to the input of ``la
 
   * forward: one fused launch per ResidualUnit (``eben_ru_fwd``: x read once; h = dilated(x) and u = lrelu(pointwise(h)) kept
     for the backward), the shared LeakyReLU of the block inputs (:187-189) folded into that launch's tile staging;
-  * backward: per ResidualUnit ``g_h = pointwise^T(g_y * lrelu'(u))`` and ``g_x = (g_y + fold(dilated^T(g_h))) * lrelu'(x) +
-    skip`` -- the residual / skip joins ride in the reflect-fold pass (``eben_conv1d_bwd_dx_res``), no add kernel runs; the
-    weight gradients are launched beside the input-gradient chain (``ops.weight_grads``: side stream, straight into ``.grad``
-    or the data-parallel buckets);
+  * backward: the reverse walk of the layer table (``gen_layers.backward_segments``) over the forward's records, one per core layer
+    -- per step the input gradient, then the weight gradient.  Per ResidualUnit ``g_h = pointwise^T(g_y * lrelu'(u))`` and ``g_x =
+    (g_y + fold(dilated^T(g_h))) * lrelu'(x) + skip`` -- the residual / skip joins ride in the reflect-fold pass
+    (``eben_conv1d_bwd_dx_res``), no add kernel runs; the weight gradients are launched beside the input-gradient chain
+    (``ops.weight_grads``: side stream, straight into ``.grad`` or the data-parallel buckets);
   * ``last_conv`` (the leaf of the loss balancing, eben.py:223), the tanh recomposition and the PQMF synthesis stay in
     autograd: the step differentiates them three extra times with ``retain_graph`` and they are cheap.
 
@@ -31,14 +32,16 @@ from __future__ import annotations
 import ctypes
 import dataclasses
 import contextlib
+import functools
 import os
+import weakref
 from typing import Dict, List, Optional
 
 import torch
 
 from . import ops
 from ._lib import check, load, ptr, stream
-from .gen_layers import layers
+from .gen_layers import backward_segments, layers
 
 USE_FUSED_RU = os.environ.get("EBEN_RU_FUSED", "1") != "0"
 USE_FUSED_RU_BWD = os.environ.get("EBEN_RU_FUSED_BWD", "1") != "0"
@@ -115,12 +118,23 @@ def _params(m):
 
 
 class _ConvRec:
-    """What the backward of one conv launch needs."""
+    """What the backward of one conv launch needs (``layer``: its table entry; None for the two convs inside a ``_UnitRec``)."""
 
-    __slots__ = ("m", "spec", "d", "x", "y", "wp_bwd", "norm", "scale")
+    __slots__ = ("m", "spec", "d", "x", "y", "wp_bwd", "norm", "scale", "layer")
 
-    def __init__(self, m, spec, d, x, y, wp_bwd, norm, scale=None):
-        self.m, self.spec, self.d, self.x, self.y, self.wp_bwd, self.norm, self.scale = m, spec, d, x, y, wp_bwd, norm, scale
+    def __init__(self, m, spec, d, x, y, wp_bwd, norm, scale=None, layer=None):
+        self.m, self.spec, self.d, self.x, self.y, self.wp_bwd, self.norm, self.scale, self.layer = m, spec, d, x, y, wp_bwd, norm, scale, layer
+
+
+class _UnitRec:
+    """What the backward of one ResidualUnit needs: the records of its two convs and, by ``route``, "bl": the backward image ``img`` and
+    the bf16 bundles ``xb`` / ``hb`` + sign bytes ``um`` (csrc/ru_bl.hip); "fused": ``img`` in arithmetic ``math``, x / h / u in the conv
+    records; "layers": nothing more -- gradients conv by conv."""
+
+    __slots__ = ("layer", "route", "dil", "pwc", "img", "math", "xb", "hb", "um")
+
+    def __init__(self, layer, route, dil, pwc, img=None, math=None, xb=None, hb=None, um=None):
+        self.layer, self.route, self.dil, self.pwc, self.img, self.math, self.xb, self.hb, self.um = layer, route, dil, pwc, img, math, xb, hb, um
 
 
 class GeneratorEngine:
@@ -134,9 +148,11 @@ class GeneratorEngine:
         self._dx_graphs: List[ops.ReplayedChain] = []   # per backward segment (decoder block / latent / encoder block)
         self._dw_graphs: List[ops.ReplayedChain] = []
         self._static: Dict[tuple, torch.Tensor] = {}   # (name, shape) -> buffer the graphs read their per-step input from
-        self._dwq: Optional[list] = None               # while the input-gradient chain runs in queue mode: its weight-gradient work items
-        # the layer table (gen_layers.py): the core entries in launch order, every entry by its path, and the core's units and convs
+        self._dwq: Optional[list] = None               # while the input-gradient chain runs in queue mode: its weight-gradient jobs
+        self._serial, self._graph_serial, self._fwd_replayed, self._outstanding = 0, None, False, None   # forward_train's guard
+        # the layer table (gen_layers.py): the core entries in launch order (= their slot in the records), every entry by its path, units, convs
         self._core = [la for la in layers(gen) if la.core]
+        self._bwd = tuple(tuple((st, self._core.index(st.layer)) for st in seg) for seg in backward_segments(gen))   # (step, its record's slot)
         self._by_path = {la.path: la for la in layers(gen)}
         self._core_units = [la.module for la in self._core if la.kind == "unit"]
         self._core_convs = [m for la in self._core for m in ((la.module.dilated_conv, la.module.pointwise_conv) if la.kind == "unit" else (la.module,))]
@@ -193,8 +209,8 @@ class GeneratorEngine:
         return (S2D_MIN_STRIDE > 0 and spec.stride >= S2D_MIN_STRIDE and spec.ksize % spec.stride == 0 and spec.groups == 1
                 and spec.dilation == 1 and math != ops.MATH_F32)
 
-    def _conv(self, m, x, train, in_slope=None, recs=None):
-        """y = conv layer ``m`` on x (its own fused output activation; ``in_slope``: LeakyReLU on load)."""
+    def _conv(self, m, x, train, in_slope=None, recs=None, layer=None):
+        """y = conv layer ``m`` on x (its own fused output activation; ``in_slope``: LeakyReLU on load); ``recs``: gets its record."""
         lib = load()
         spec = self._spec(m, in_slope=in_slope)
         b, _, l_in = x.shape
@@ -213,7 +229,7 @@ class GeneratorEngine:
         else:
             check(lib.eben_conv1d_fwd(ctypes.byref(d), ptr(x), ptr(pw.wp_fwd), ptr(m.bias), None, ptr(y), stream()), "conv1d_fwd")
         if recs is not None:
-            recs.append(_ConvRec(m, spec, d_bwd, x, y if spec.out_slope != 1.0 else None, pw.wp_bwd, pw.norm, pw.scale))
+            recs.append(_ConvRec(m, spec, d_bwd, x, y if spec.out_slope != 1.0 else None, pw.wp_bwd, pw.norm, pw.scale, layer))
         return y
 
     @staticmethod
@@ -270,8 +286,8 @@ class GeneratorEngine:
         return [(c, lambda slot, ru=ru, c=c: self._ru_rebuild(ru, c, slot))
                 for ru in self._core_units if (c := self._ru_images.get(id(ru))) is not None and c.images]
 
-    def _residual_unit(self, ru, x, in_slope, train, recs):
-        """y = xin + lrelu(pointwise(dilated(xin))), xin = lrelu(x, in_slope).  Returns y; records (x, h, u) for the backward."""
+    def _residual_unit(self, ru, x, in_slope, train, recs, layer=None):
+        """y = xin + lrelu(pointwise(dilated(xin))), xin = lrelu(x, in_slope).  Returns y; ``recs`` gets the ``_UnitRec`` of the route."""
         lib = load()
         b, c, l = x.shape
         dil, pwc = ru.dilated_conv, ru.pointwise_conv
@@ -292,8 +308,8 @@ class GeneratorEngine:
             um = torch.empty((b, c // 8, l), dtype=torch.uint8, device=x.device)
             check(lib.eben_rubl_fwd(fwd_math, b, c, l, dil.spec.dilation, ptr(x), float(in_slope), float(pwc.spec.out_slope), ptr(img), ptr(y),
                                     xb.data_ptr(), hb.data_ptr(), um.data_ptr(), stream()), "rubl_fwd")
-            recs.append((("bl", self._ru_image(ru, 1), xb, hb, um), _ConvRec(dil, spec_d, dd_bwd, x if in_slope != 1.0 else None, None, pw_d.wp_bwd, pw_d.norm),
-                         _ConvRec(pwc, pwc.spec, dp_bwd, None, None, pw_p.wp_bwd, pw_p.norm)))
+            recs.append(_UnitRec(layer, "bl", _ConvRec(dil, spec_d, dd_bwd, x if in_slope != 1.0 else None, None, pw_d.wp_bwd, pw_d.norm),
+                                 _ConvRec(pwc, pwc.spec, dp_bwd, None, None, pw_p.wp_bwd, pw_p.norm), self._ru_image(ru, 1), xb=xb, hb=hb, um=um))
             return y
         if USE_FUSED_RU and fusable:
             img = self._ru_image(ru)
@@ -314,45 +330,35 @@ class GeneratorEngine:
         if train:
             bm = self._ru_bwd_math()
             fused = USE_FUSED_RU_BWD and dil.spec.ksize == 3 and dil.spec.reflect and lib.eben_ru_supported(c, dil.spec.dilation, bm) == 1
-            recs.append(((self._ru_image(ru, 1), bm) if fused else None, _ConvRec(dil, spec_d, dd_bwd, x, None, pw_d.wp_bwd, pw_d.norm),
-                         _ConvRec(pwc, pwc.spec, dp_bwd, h, u, pw_p.wp_bwd, pw_p.norm)))
+            dil_rec, pwc_rec = _ConvRec(dil, spec_d, dd_bwd, x, None, pw_d.wp_bwd, pw_d.norm), _ConvRec(pwc, pwc.spec, dp_bwd, h, u, pw_p.wp_bwd, pw_p.norm)
+            recs.append(_UnitRec(layer, "fused", dil_rec, pwc_rec, self._ru_image(ru, 1), bm) if fused else _UnitRec(layer, "layers", dil_rec, pwc_rec))
         return y
 
     # ---- forward -------------------------------------------------------------------------------------
     def _launch(self, layer, x, train, recs):
-        """Entry ``layer`` of the table on its input: the unit's fused launch, or the conv's."""
+        """Entry ``layer`` of the table on its input: the unit's fused launch, or the conv's; ``recs``: gets the layer's record."""
         if layer.kind == "unit":
-            return self._residual_unit(layer.module, x, layer.in_slope, train, recs)
-        return self._conv(layer.module, x, train, in_slope=layer.in_slope if layer.in_slope != 1.0 else None, recs=recs)
-
-    @staticmethod
-    def _records(saved, name, block=None) -> list:
-        """The record list of backward segment (name[, block]) in ``saved``; a block's list is opened by the block's first layer."""
-        recs = saved[name]
-        if block is None:
-            return recs
-        if block == len(recs):
-            recs.append([])
-        return recs[block]
+            return self._residual_unit(layer.module, x, layer.in_slope, train, recs, layer)
+        return self._conv(layer.module, x, train, in_slope=layer.in_slope if layer.in_slope != 1.0 else None, recs=recs, layer=layer)
 
     def forward(self, cut_audio: torch.Tensor, train: bool, fill=None):
-        """Returns (input of last_conv, first_bands, records for ``backward`` or None).  ``fill(layer path, x)``, inference only: called
-        on the input of every layer with taps along time right before its launch (``forward_ragged`` writes the rows' own edges there)."""
+        """Returns (input of last_conv, first_bands, the records for ``backward`` -- one per core layer, in table order -- or None).
+        ``fill(layer path, x)``, inference only: called on the input of every layer with taps along time right before its launch
+        (``forward_ragged`` writes the rows' own edges there)."""
         gen = self.gen
         lib = load()
         ops.join_prepack()   # images rebuilt ahead of time on the side stream
         first_bands = gen.pqmf(cut_audio, "analysis", bands=gen.p).detach()
-        saved = {"enc": [], "dec": [], "misc": [], "latent": []} if train else None
+        saved = [] if train else None
         x, skips = first_bands, {}
         for layer in self._core:
-            recs = self._records(saved, *layer.segment) if train else None
             if layer.add is not None:
                 s = torch.empty_like(x)
                 check(lib.eben_add(ptr(x), ptr(skips[layer.add]), ptr(s), x.numel(), stream()), "add")
                 x = s
             if fill is not None:
                 fill(layer.path, x)
-            x = self._launch(layer, x, train, recs)
+            x = self._launch(layer, x, train, saved)
             if layer.skip is not None:
                 skips[layer.skip] = x
         return x, first_bands, saved
@@ -565,14 +571,29 @@ class GeneratorEngine:
                                          ptr(ws), ws_bytes, stream()), "conv1d_bwd_dx_res")
         return dx
 
-    def _dw(self, rec: _ConvRec, dy):
+    def _emit_dw(self, grads, *operands) -> None:
+        """One record's weight gradients, ``grads(*operands, trainable_only=..) -> [(parameter, gradient)]``: not wanted, queued for
+        ``_dw_body`` while ``backward_train``'s input-gradient chain runs, or accumulated now.  The queue runs only where ``_deferrable()``
+        found every core parameter trainable and routed alike: there ``grads`` launches without looking (``trainable_only=False``) and a
+        bundle-layout unit it cannot serve is that check's bug, an assertion; launch by launch it is the user's pattern, an error."""
         if ops._skip_weight_grads[0]:
             return
+        job = functools.partial(grads, *operands)
         if self._dwq is not None:
-            self._dwq.append(("conv", rec, dy))
-            return
-        if _params(rec.m)[0].requires_grad:
-            self._accumulate(self._conv_grads(rec, dy))
+            self._dwq.append(job)
+        else:
+            self._accumulate(job(trainable_only=True))
+
+    def _conv_dw(self, rec: _ConvRec, dy, trainable_only: bool) -> list:
+        return self._conv_grads(rec, dy) if not trainable_only or _params(rec.m)[0].requires_grad else []
+
+    def _unit_dw_bl(self, dil: _ConvRec, pwc: _ConvRec, gzb, hb, ghb, xb, trainable_only: bool) -> list:
+        res = self._unit_grads_bl(dil, pwc, gzb, hb, ghb, xb)
+        if res is False:
+            assert trainable_only   # launch by launch
+            raise RuntimeError("bundle-layout ResidualUnit: the two convs' weight gradients are routed differently (one of them holds a gradient "
+                               "or a hook the other does not); set EBEN_RU_BL=0 for this pattern")
+        return res
 
     @staticmethod
     def _accumulate(pairs) -> None:
@@ -614,14 +635,6 @@ class GeneratorEngine:
         res = ops.weight_grads_ru_bl(dil.spec.dilation, gzb, hb, ghb, xb, (vp, gp, pwc.norm), (vd, gd, dil.norm))
         return False if res is False else self._unit_pairs(dil, pwc, res)
 
-    def _ru_dw(self, dil: _ConvRec, pwc: _ConvRec, gy, gh, bm: int) -> None:
-        if ops._skip_weight_grads[0]:
-            return
-        if self._dwq is not None:
-            self._dwq.append(("ru", dil, pwc, gy, gh, bm))
-            return
-        self._accumulate(self._unit_grads(dil, pwc, gy, gh, bm, trainable_only=True))
-
     @staticmethod
     def _ru_bl_params_ok(ru, length: int) -> bool:
         """The bundle-layout weight-gradient launch serves weight-normalised, bias-free, trainable convs (every unit of the reference) whose
@@ -636,80 +649,49 @@ class GeneratorEngine:
             keys.append((v.grad is None and g.grad is None, ops._no_grad_hooks(v) and ops._no_grad_hooks(g)))
         return keys[0] == keys[1] and ru.dilated_conv.spec.dilation < length
 
-    def _ru_backward_bl(self, rec, gy, res_post=None):
-        (_, img_b, xb, hb, um), dil, pwc = rec
+    def _ru_backward(self, rec: _UnitRec, gy, res_post=None):
+        dil, pwc, ins = rec.dil, rec.pwc, rec.dil.spec.in_slope
         b, c, l = gy.shape
-        gx = torch.empty_like(gy)
-        gzb, ghb = torch.empty_like(xb), torch.empty_like(xb)
-        ins = dil.spec.in_slope
-        check(load().eben_rubl_bwd(b, c, l, dil.spec.dilation, ptr(gy), um.data_ptr(), float(pwc.spec.out_slope), ptr(dil.x) if ins != 1.0 else None,
-                                   float(ins), ptr(res_post), ptr(img_b), ptr(gx), gzb.data_ptr(), ghb.data_ptr(), stream()), "rubl_bwd")
-        if not ops._skip_weight_grads[0]:
-            if self._dwq is not None:
-                self._dwq.append(("rubl", dil, pwc, gzb, hb, ghb, xb))
-            else:
-                res = self._unit_grads_bl(dil, pwc, gzb, hb, ghb, xb)
-                if res is False:
-                    raise RuntimeError("bundle-layout ResidualUnit: the two convs' weight gradients are routed differently (one of them holds a gradient "
-                                       "or a hook the other does not); set EBEN_RU_BL=0 for this pattern")
-                self._accumulate(res)
-        return gx
-
-    def _ru_backward(self, rec, gy, res_post=None):
-        fused, dil, pwc = rec
-        if fused is not None and fused[0] == "bl":
-            return self._ru_backward_bl(rec, gy, res_post)
-        if fused is not None:   # one launch: g_h and g_x = (g_y + fold(dilated^T g_h)) * lrelu'(x) + skip gradient
-            b, c, l = gy.shape
+        if rec.route == "bl":
+            gx = torch.empty_like(gy)
+            gzb, ghb = torch.empty_like(rec.xb), torch.empty_like(rec.xb)
+            check(load().eben_rubl_bwd(b, c, l, dil.spec.dilation, ptr(gy), rec.um.data_ptr(), float(pwc.spec.out_slope), ptr(dil.x) if ins != 1.0 else None,
+                                       float(ins), ptr(res_post), ptr(rec.img), ptr(gx), gzb.data_ptr(), ghb.data_ptr(), stream()), "rubl_bwd")
+            self._emit_dw(self._unit_dw_bl, dil, pwc, gzb, rec.hb, ghb, rec.xb)
+            return gx
+        if rec.route == "fused":   # one launch: g_h and g_x = (g_y + fold(dilated^T g_h)) * lrelu'(x) + skip gradient
             gx, gh = torch.empty_like(gy), torch.empty_like(gy)
-            ins = dil.spec.in_slope
-            img_b, bm = fused
-            check(load().eben_ru_bwd_ex(bm, b, c, l, dil.spec.dilation, ptr(gy), ptr(pwc.y), float(pwc.spec.out_slope),
-                                        ptr(dil.x) if ins != 1.0 else None, float(ins), ptr(res_post), ptr(img_b), ptr(gx), ptr(gh), stream()), "ru_bwd")
-            self._ru_dw(dil, pwc, gy, gh, bm)
+            check(load().eben_ru_bwd_ex(rec.math, b, c, l, dil.spec.dilation, ptr(gy), ptr(pwc.y), float(pwc.spec.out_slope),
+                                        ptr(dil.x) if ins != 1.0 else None, float(ins), ptr(res_post), ptr(rec.img), ptr(gx), ptr(gh), stream()), "ru_bwd")
+            self._emit_dw(self._unit_grads, dil, pwc, gy, gh, rec.math)
             return gx
         gh = self._dx(pwc, gy)                       # pointwise^T(gy * lrelu'(u))
-        self._dw(pwc, gy)
+        self._emit_dw(self._conv_dw, pwc, gy)
         gx = self._dx(dil, gh, res_pre=gy, res_post=res_post)   # (gy + fold(dilated^T gh)) * lrelu'(x) + skip gradient
-        self._dw(dil, gh)
+        self._emit_dw(self._conv_dw, dil, gh)
         return gx
 
-    def _n_segments(self, saved) -> int:
-        return len(saved["dec"]) + 1 + len(saved["enc"])
+    def _n_segments(self) -> int:
+        return len(self._bwd)
 
-    def _bwd_segment(self, saved, k: int, g: torch.Tensor, skip_grads: list) -> torch.Tensor:
-        """Segment k of the backward -- decoder blocks (last first), the latent convs, encoder blocks (last first; the first block's
-        segment ends with first_conv's weight gradient): takes the gradient at the segment's output, returns the one at its input.
-        ``skip_grads`` collects the decoder segments' results (the gradients that join the encoder outputs)."""
-        n_dec, n_enc = len(saved["dec"]), len(saved["enc"])
-        if k < n_dec:                                 # decoder blocks, last first: [conv_trans, ru, ru, ru]
-            recs = saved["dec"][n_dec - 1 - k]
-            for rec in reversed(recs[1:]):
-                g = self._ru_backward(rec, g)
-            ct = recs[0]
-            gs = self._dx(ct, g)                      # gradient at (x + skip)
-            self._dw(ct, g)
-            skip_grads.append(gs)                     # dec2 -> a1, dec1 -> a2, dec0 -> a3
-            return gs
-        if k == n_dec:
-            c1, c2 = saved["latent"]
-            gl1 = self._dx(c2, g)
-            self._dw(c2, g)
-            g = self._dx(c1, gl1, res_post=skip_grads[-1])   # a3: latent path (masked by lrelu'(a3)) + the decoder's skip
-            self._dw(c1, gl1)
-            return g
-        i = n_enc - 1 - (k - n_dec - 1)               # encoder blocks, last first: [ru, ru, ru, conv]
-        recs = saved["enc"][i]
-        conv = recs[-1]
-        gy = self._dx(conv, g)
-        self._dw(conv, g)
-        for rec in reversed(recs[1:-1]):
-            gy = self._ru_backward(rec, gy)
-        # the block's input a_i is also a decoder block's skip: that gradient joins behind the activation mask
-        post = skip_grads[i - 1] if i >= 1 else None   # skip_grads: [a1 (dec2), a2 (dec1), a3 (dec0)]
-        g = self._ru_backward(recs[0], gy, res_post=post)
-        if i == 0:
-            self._dw(saved["misc"][0], g)             # first_conv: its input is data, only the weight gradient
+    def _bwd_segment(self, saved, k: int, g: torch.Tensor, skip_grads: dict) -> torch.Tensor:
+        """Segment k of the backward plan (``gen_layers.backward_segments``) on the forward's records: takes the gradient at the segment's
+        output, returns the one at its input.  Per step the input gradient, then the weight gradient.  ``skip_grads``: the gradients of
+        the encoder outputs by their index, filed by the step that added one to its input, read by the one that consumed it."""
+        for step, slot in self._bwd[k]:
+            rec = saved[slot]
+            if rec.layer is not step.layer:
+                raise RuntimeError(f"EBEN generator engine: the record of {rec.layer.path} stands where the backward expects {step.layer.path}")
+            post = None if step.joins is None else skip_grads[step.joins]   # joins behind the layer's activation mask
+            if step.layer.kind == "unit":
+                g = self._ru_backward(rec, g, res_post=post)
+            else:
+                dy = g
+                if step.dx:                           # False: its input is data, only the weight gradient
+                    g = self._dx(rec, dy, res_post=post)
+                self._emit_dw(self._conv_dw, rec, dy)
+            if step.yields is not None:
+                skip_grads[step.yields] = g
         return g
 
     @torch.no_grad()
@@ -717,8 +699,8 @@ class GeneratorEngine:
         """Input-gradient chain on the current stream, weight gradients through ``ops.weight_grads`` (inside
         ``ops.weight_grads_on_side_stream()``: beside the chain, joined by the caller)."""
         g = g_pre.contiguous()
-        skip_grads: List[Optional[torch.Tensor]] = []
-        for k in range(self._n_segments(saved)):
+        skip_grads: Dict[int, torch.Tensor] = {}
+        for k in range(self._n_segments()):
             g = self._bwd_segment(saved, k, g, skip_grads)
 
     # ---- the training step's three launch sequences as replayed graphs ----------------------------------------------------------
@@ -757,7 +739,7 @@ class GeneratorEngine:
         fresh tensors, and ``backward_train`` refuses saved state whose serial is no longer the graph's (a second backward with
         ``retain_graph`` after a newer replay) instead of returning gradients of the wrong forward."""
         self._fwd_replayed = False
-        self._serial = getattr(self, "_serial", 0) + 1
+        self._serial += 1
         if not self._graphs_usable() or self._replay_outstanding():
             return self.forward(x, True)
         ops.join_prepack()   # the wait stays outside the graph
@@ -771,7 +753,7 @@ class GeneratorEngine:
 
     def _replay_outstanding(self) -> bool:
         """The graph's buffers hold a forward that an autograd node still alive has not been differentiated through."""
-        ref = getattr(self, "_outstanding", None)
+        ref = self._outstanding
         if ref is None:
             return False
         if ref() is None:
@@ -780,7 +762,6 @@ class GeneratorEngine:
         return True
 
     def _note_ctx(self, ctx) -> None:
-        import weakref
         ctx.serial = self._serial
         self._outstanding = weakref.ref(ctx) if self._fwd_replayed else None
 
@@ -808,15 +789,8 @@ class GeneratorEngine:
         Returns [(parameter, gradient)] (with a data-parallel ``sink``: the gradients are its bucket views)."""
         jobs, assign = [], []
         with ops.collect_wn_jobs(jobs, sink):
-            for kind, *item in queue:
-                if kind == "conv":
-                    assign += self._conv_grads(*item)
-                elif kind == "rubl":
-                    res = self._unit_grads_bl(*item)
-                    assert res is not False
-                    assign += res
-                else:
-                    assign += self._unit_grads(*item, trainable_only=False)   # _deferrable() has checked requires_grad
+            for job in queue:
+                assign += job(trainable_only=False)   # the queued form: see _emit_dw
         ops.wn_bwd_multi(jobs)
         return assign
 
@@ -829,15 +803,15 @@ class GeneratorEngine:
         ``join()``.  ([MI355X] as two graphs -- the whole chain, then all weight gradients -- the step went 12.0 -> 12.5 ms: the chain
         alone fills a fraction of the GPU.)"""
         from_graph = self._fwd_graph.out is not None and saved is self._fwd_graph.out[2]
-        if from_graph and serial is not None and serial != getattr(self, "_graph_serial", None):
+        if from_graph and serial is not None and serial != self._graph_serial:
             raise RuntimeError("EBEN generator engine: this forward's saved activations were rewritten by a later replayed forward (backward "
                                "through an old graph after a new training forward); set EBEN_GEN_GRAPHS=0 for that pattern")
         self._outstanding = None   # differentiated: the next forward may replay over these buffers
-        if not (self._graphs_usable() and getattr(self, "_fwd_replayed", False) and from_graph and self._deferrable()):
+        if not (self._graphs_usable() and self._fwd_replayed and from_graph and self._deferrable()):
             return self.backward(saved, g_pre)
         gbuf = self._static_buf("g", g_pre)
         gbuf.copy_(g_pre)
-        n = self._n_segments(saved)
+        n = self._n_segments()
         # segments per graph: a replay costs ~70 us of host time, a graph per segment (14 replays) 1.35 ms per step against 0.74 for two
         # graphs; three groups keep the weight gradients beside the chain at 0.5 ms
         sizes = [int(t) for t in BWD_GROUPS.split(",")] if BWD_GROUPS else []
@@ -850,22 +824,22 @@ class GeneratorEngine:
         dev = gbuf.device
         main = torch.cuda.current_stream(dev)
         side = ops._side_stream(dev)
-        g, skip_grads = gbuf, []
+        g, skip_grads = gbuf, {}
         for k in range(len(sizes)):
             def dx_body(k=k, g=g):
                 self._dwq = []
-                sk = list(skip_grads)
+                sk = dict(skip_grads)
                 try:
                     out = g
                     for seg in range(bounds[k], bounds[k + 1]):
                         out = self._bwd_segment(saved, seg, out, sk)
                 finally:
                     queue, self._dwq = self._dwq, None
-                return out, sk[len(skip_grads):], queue
+                return out, {j: t for j, t in sk.items() if j not in skip_grads}, queue
 
             # one signature for all segments: they settle, and are captured, in the same step, each on the results of the one before
             g, new_skips, queue = self._dx_graphs[k].run((self._fwd_graph.captures, gbuf.data_ptr(), ops._backward_math[0]), dx_body, None)
-            skip_grads.extend(new_skips)
+            skip_grads.update(new_skips)
             if not queue:
                 continue
             side.wait_stream(main)

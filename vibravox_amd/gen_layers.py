@@ -2,12 +2,14 @@
 only, no GPU needed).
 
 ``GeneratorEngine.forward`` launches the core entries one by one, ``ragged.plan`` derives its edge fills from their ``ConvSpec``s,
-``streaming.nodes_of`` makes a stream node of each, and ``GeneratorEngine._stream_node`` finds a node's launch by its path.  A change
-to the generator's shape -- another block, a different residual stack, a slope somewhere else -- is made here.
+``streaming.nodes_of`` makes a stream node of each, and ``GeneratorEngine._stream_node`` finds a node's launch by its path.  The
+training backward walks ``backward_segments``: the same entries in reverse, with where a skip's gradient leaves and rejoins the chain.
+A change to the generator's shape -- another block, a different residual stack, a slope somewhere else -- is made here, for both.
 """
 from __future__ import annotations
 
 import dataclasses
+import itertools
 from typing import Optional, Tuple
 
 
@@ -19,7 +21,7 @@ class Layer:
     spec: object               # ConvSpec of the conv with taps along time: a unit is its dilated conv (the pointwise conv reads one
                                # sample, the residual add none)
     in_slope: float            # LeakyReLU applied on load (1.0: none)
-    segment: Optional[tuple]   # where the training forward files its backward record: ("misc",), ("enc", i), ("latent",), ("dec", i)
+    segment: Optional[tuple]   # the backward segment it belongs to (a run of equal values): ("misc",), ("enc", i), ("latent",), ("dec", i)
     add: Optional[int]         # index of the encoder output added to its input
     skip: Optional[int]        # its output is encoder output ``skip``
     core: bool                 # run by the engine; False: last_conv, which stays in autograd
@@ -56,3 +58,26 @@ def layers(gen) -> Tuple[Layer, ...]:
         table = _build(gen)
         object.__setattr__(gen, "_layers", table)   # not a submodule / buffer: invisible to state_dict
     return table
+
+
+@dataclasses.dataclass(frozen=True)
+class BackwardStep:
+    layer: Layer
+    dx: bool                   # its input needs a gradient; False: the input is data, only the weight gradient is taken
+    joins: Optional[int]       # the gradient of encoder output ``joins`` (the layer in front made it) joins behind its activation mask: res_post
+    yields: Optional[int]      # its input gradient is also the gradient of encoder output ``yields``, which it added to its input
+
+
+def backward_segments(gen) -> Tuple[Tuple[BackwardStep, ...], ...]:
+    """The backward of ``gen``'s core, built once and kept on it: the runs of equal ``Layer.segment`` last first, each a tuple of steps in
+    launch order (its layers in reverse).  The run of the first layer alone, whose input is data, rides at the end of the last segment."""
+    plan = getattr(gen, "_backward_segments", None)
+    if plan is None:
+        core = [la for la in layers(gen) if la.core]
+        steps = [BackwardStep(la, i > 0, core[i - 1].skip if i else None, la.add) for i, la in enumerate(core)]
+        plan = [tuple(run) for _, run in itertools.groupby(reversed(steps), key=lambda st: st.layer.segment)]
+        if len(plan) > 1 and not any(st.dx for st in plan[-1]):   # nothing to hand on: its weight gradient closes the segment in front
+            plan[-2:] = [plan[-2] + plan[-1]]
+        plan = tuple(plan)
+        object.__setattr__(gen, "_backward_segments", plan)
+    return plan
