@@ -713,6 +713,38 @@ EBEN_API size_t eben_stoi_ragged_workspace(int rows, int t_max, int fs);
 EBEN_API int eben_stoi_ragged(const float* clean, const float* processed, int rows, int t_max, const int32_t* lengths, int fs,
                               const float* resample_table, int taps, void* workspace, size_t ws_bytes, float* out, void* stream);
 
+/* ---- evaluation metrics beyond the two base_se.py logs: zero-mean SI-SDR / SI-SNR, SNR, ESTOI, log-spectral distance ---------------
+ * The conventions of the ragged entries above, with a NULLABLE lengths (null: every row is t_max long): one value per row, fp64
+ * reductions in a fixed order, so out[r] has the bits of the call on row r alone; a lengths[r] outside its valid range makes that row
+ * NaN and touches nothing else; nothing behind a row's end is read; no host synchronisation.
+ * eben_signal_ratio: kind EBEN_RATIO_SI_SDR is torchmetrics scale_invariant_signal_distortion_ratio(preds, target, zero_mean),
+ *   EBEN_RATIO_SNR its signal_noise_ratio(preds, target, zero_mean) = 10 log10((sum t^2 + eps) / (sum (t - p)^2 + eps)), eps the float32
+ *   machine epsilon.  zero_mean = 1 subtracts each signal's fp64 mean over the row's own length first; SI-SNR is SI_SDR with it.
+ * eben_estoi: pystoi stoi(clean, processed, fs, extended=True) -- the front end of eben_stoi (resample, silence removal, third-octave
+ *   envelopes), then per 15 x 30 segment both matrices' rows, then columns, centred and normalised, d = sum x_n y_n / (30 J).  No
+ *   EPS * randn dither; a row or column whose centred norm is exactly 0 contributes 0.  Fewer than 30 frames: 1e-5.  out_classic
+ *   (nullable) also receives what eben_stoi[_ragged] writes, from the same envelopes: one front end, two tails.
+ *   Workspace: eben_estoi_workspace(rows, t_max, fs) bytes (eben_stoi's plus a double per possible segment).
+ * eben_lsd: P(s) = clamp(|torch.stft(s, n_fft, hop, win_length = n_fft, hann_window(n_fft), center = True, "reflect")|^2, min = 1e-8),
+ *   D[f] = sqrt(mean over the band's bins of (log10 P(preds) - log10 P(target))^2), out[band * rows + r] = mean of D over the row's own
+ *   1 + len / hop frames, reflected at the row's own end.  n_fft a power of two in [256, 4096], 1 <= hop <= n_fft, 1 <= nbands <= 4,
+ *   band b the bins [band_lo[b], band_hi[b]) inside [0, n_fft / 2 + 1) (HOST arrays).  A row with len <= n_fft / 2 cannot be
+ *   reflect-padded: NaN.  Workspace: eben_lsd_workspace(rows, t_max, n_fft, hop, nbands) bytes.
+ * EBEN_EINVAL before any launch for a null pointer (other than lengths / out_classic) or an argument outside the ranges above,
+ * EBEN_EWORKSPACE for a short workspace.  Added without a version bump: functions only, and a binding that needs them finds out by
+ * looking the symbols up. */
+#define EBEN_RATIO_SI_SDR 0
+#define EBEN_RATIO_SNR 1
+EBEN_API int eben_signal_ratio(const float* preds, const float* target, int rows, int t_max, const int32_t* lengths, int kind,
+                               int zero_mean, float* out, void* stream);
+EBEN_API size_t eben_estoi_workspace(int rows, int t_max, int fs);
+EBEN_API int eben_estoi(const float* clean, const float* processed, int rows, int t_max, const int32_t* lengths, int fs,
+                        const float* resample_table, int taps, void* workspace, size_t ws_bytes, float* out, float* out_classic,
+                        void* stream);
+EBEN_API size_t eben_lsd_workspace(int rows, int t_max, int n_fft, int hop, int nbands);
+EBEN_API int eben_lsd(const float* preds, const float* target, int rows, int t_max, const int32_t* lengths, int n_fft, int hop,
+                      const int* band_lo, const int* band_hi, int nbands, void* workspace, size_t ws_bytes, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,18 @@
 // grids and buffers are sized for a row of t_max samples, and every kernel derives the row's own shape from its length (stoi_shape_of,
 // shared with the host), so a row runs the loops of the dense call on that row alone, in the same order.  The dense entries pass
 // lengths == nullptr: every row is t_max long.  A length outside [1, t_max] reads nothing and yields NaN.
+//
+// The evaluation set on top of these (eben_signal_ratio / eben_estoi / eben_lsd), same conventions -- a nullable DEVICE table of row
+// lengths, one value per row, fixed-order fp64 reductions, nothing behind a row's end read:
+//   signal_ratio_kernel       SI-SDR or torchmetrics' signal_noise_ratio, optionally after a first pass that forms both fp64 means over
+//                             the row's own length (zero_mean; SI-SNR is SI-SDR with it)
+//   estoi_seg_kernel          pystoi's extended=True tail on the envelopes of stoi_bands_kernel: one wave per 15 x 30 segment, rows
+//   estoi_sum_kernel          then columns centred and normalised in registers, the segment's sum to the workspace; one workgroup
+//                             per row adds the row's segments in index order
+//   lsd_frames_kernel         one workgroup per (STFT frame, row): the frame of both signals, reflected at the ROW's own ends and
+//                             Hann-windowed, as z = preds + i target through one complex radix-2 FFT in LDS (fp64), separated into the
+//                             two spectra, log10 of the clamped powers, and sqrt(mean over each band's bins of the squared difference)
+//   lsd_mean_kernel           one workgroup per (row, band): the mean over the row's own frames in index order
 #include <cmath>
 
 #include "common.h"
@@ -82,6 +94,62 @@ __global__ __launch_bounds__(256) void si_sdr_kernel(const float* __restrict__ p
   double nn = 0.0;
   for (int i = threadIdx.x; i < t; i += 256) {
     const double e = alpha * (double)g[i] - (double)p[i];
+    nn = fma(e, e, nn);
+  }
+  nn = block_sum(nn, red);
+  if (threadIdx.x == 0) out[r] = (float)(10.0 * log10((alpha * alpha * tt + kSdrEps) / (nn + kSdrEps)));
+}
+
+// SI-SDR (kind EBEN_RATIO_SI_SDR) or SNR = 10 log10((sum t^2 + eps) / (sum (t - p)^2 + eps)) (EBEN_RATIO_SNR, torchmetrics
+// signal_noise_ratio) of one row per workgroup.  zero_mean: a first pass forms both fp64 means over the row's own length and every
+// later pass reads p - mean(p), t - mean(t).  (eben_signal_ratio hands plain SI-SDR to si_sdr_kernel itself.)
+__global__ __launch_bounds__(256) void signal_ratio_kernel(const float* __restrict__ preds, const float* __restrict__ target, int t_max,
+                                                           const int* __restrict__ lengths, int kind, int zero_mean,
+                                                           float* __restrict__ out) {
+  __shared__ double red[4];
+  const long long r = blockIdx.x;
+  const int t = row_length(lengths, r, t_max);
+  if (t == 0) {
+    if (threadIdx.x == 0) out[r] = NAN;
+    return;
+  }
+  const float* p = preds + r * t_max;
+  const float* g = target + r * t_max;
+  double mp = 0.0, mt = 0.0;
+  if (zero_mean) {
+    double sp = 0.0, st = 0.0;
+    for (int i = threadIdx.x; i < t; i += 256) {
+      sp += (double)p[i];
+      st += (double)g[i];
+    }
+    mp = block_sum(sp, red) / (double)t;
+    mt = block_sum(st, red) / (double)t;
+  }
+  if (kind == EBEN_RATIO_SNR) {
+    double tt = 0.0, nn = 0.0;
+    for (int i = threadIdx.x; i < t; i += 256) {
+      const double a = (double)p[i] - mp, b = (double)g[i] - mt;
+      const double e = b - a;
+      tt = fma(b, b, tt);
+      nn = fma(e, e, nn);
+    }
+    tt = block_sum(tt, red);
+    nn = block_sum(nn, red);
+    if (threadIdx.x == 0) out[r] = (float)(10.0 * log10((tt + kSdrEps) / (nn + kSdrEps)));
+    return;
+  }
+  double pt = 0.0, tt = 0.0;
+  for (int i = threadIdx.x; i < t; i += 256) {
+    const double a = (double)p[i] - mp, b = (double)g[i] - mt;
+    pt = fma(a, b, pt);
+    tt = fma(b, b, tt);
+  }
+  pt = block_sum(pt, red);
+  tt = block_sum(tt, red);
+  const double alpha = (pt + kSdrEps) / (tt + kSdrEps);
+  double nn = 0.0;
+  for (int i = threadIdx.x; i < t; i += 256) {
+    const double e = alpha * ((double)g[i] - mt) - ((double)p[i] - mp);
     nn = fma(e, e, nn);
   }
   nn = block_sum(nn, red);
@@ -297,6 +365,185 @@ __global__ __launch_bounds__(256) void stoi_corr_kernel(const double* __restrict
   if (threadIdx.x == 0) out[r] = (float)(acc / ((double)J * kBands));
 }
 
+// sum over the 32 lanes of a wave's half (lanes 0-31 / 32-63); every lane of the half gets it
+__device__ __forceinline__ double half_wave_sum(double v) {
+#pragma unroll
+  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// pystoi's row_col_normalize on one 15 x 30 segment held by a wave: lane l has frame l % 32 (live below 30) of the bands 2 i + l / 32,
+// v[i] for i < 8 (band 15 does not exist: that entry and the dead frames stay 0).  Each band's 30 frames are centred and divided by
+// their norm, then each frame's 15 bands; a norm of exactly 0 leaves zeros (no EPS * randn dither, tests/eval_metrics_oracle.py).
+__device__ __forceinline__ void row_col_normalise(double (&v)[8], bool live, int half) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const bool ok = live && 2 * i + half < kBands;
+    const double mean = half_wave_sum(v[i]) / kSeg;
+    const double c = ok ? v[i] - mean : 0.0;
+    const double norm = sqrt(half_wave_sum(c * c));
+    v[i] = norm > 0.0 ? c / norm : 0.0;
+  }
+  double s = 0.0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) s += v[i];
+  s += __shfl_xor(s, 32, 64);
+  const double mean = s / kBands;
+  double q = 0.0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const bool ok = live && 2 * i + half < kBands;
+    v[i] = ok ? v[i] - mean : 0.0;
+    q = fma(v[i], v[i], q);
+  }
+  q += __shfl_xor(q, 32, 64);
+  const double norm = sqrt(q);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) v[i] = norm > 0.0 ? v[i] / norm : 0.0;
+}
+
+// ESTOI (pystoi extended=True), one wave per segment m (4 per workgroup): seg[row, m] = sum over the segment of x_n * y_n, both
+// matrices row- and column-normalised.  No clipping and no c normalisation.
+__global__ __launch_bounds__(256) void estoi_seg_kernel(const double* __restrict__ tob, const int* __restrict__ count, int fmax,
+                                                        double* __restrict__ seg) {
+  const long long r = blockIdx.y;
+  const int frames = count[r] - 1;
+  const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (frames < kSeg || m > frames - kSeg) return;  // uniform over the wave; nothing below synchronises the workgroup
+  const int lane = threadIdx.x & 63, n = lane & 31, half = lane >> 5;
+  const bool live = n < kSeg;
+  double x[8], y[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int b = 2 * i + half;
+    const bool ok = live && b < kBands;
+    x[i] = ok ? tob[((r * 2 + 0) * kBands + b) * (long long)fmax + m + n] : 0.0;
+    y[i] = ok ? tob[((r * 2 + 1) * kBands + b) * (long long)fmax + m + n] : 0.0;
+  }
+  row_col_normalise(x, live, half);
+  row_col_normalise(y, live, half);
+  double acc = 0.0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) acc = fma(x[i], y[i], acc);
+  acc = wave_sum(acc);
+  if (lane == 0) seg[r * fmax + m] = acc;
+}
+
+// one workgroup per row: d = sum over the row's J segments / (30 J), in index order per thread and block_sum's order across threads
+__global__ __launch_bounds__(256) void estoi_sum_kernel(const double* __restrict__ seg, const int* __restrict__ count, int fmax,
+                                                        float* __restrict__ out) {
+  __shared__ double red[4];
+  const long long r = blockIdx.x;
+  const int frames = count[r] - 1;
+  if (frames < kSeg) {  // uniform over the workgroup; count = -1: the row's length was out of range
+    if (threadIdx.x == 0) out[r] = count[r] < 0 ? NAN : 1e-5f;
+    return;
+  }
+  const int J = frames - kSeg + 1;
+  double acc = 0.0;
+  for (int m = threadIdx.x; m < J; m += 256) acc += seg[r * fmax + m];
+  acc = block_sum(acc, red);
+  if (threadIdx.x == 0) out[r] = (float)(acc / ((double)kSeg * J));
+}
+
+// ---- log-spectral distance ------------------------------------------------------------------------------------------------
+constexpr int kLsdMaxBands = 4;
+constexpr double kLsdFloor = 1e-8;  // clamp(|stft|^2, min = 1e-8)
+
+struct LsdBands {
+  int lo[kLsdMaxBands];  // [lo, hi) FFT bins of each band
+  int hi[kLsdMaxBands];
+  int n;
+};
+
+// frames of a row of len samples (torch.stft, center = True): 1 + len / hop, or none when the row cannot be reflect-padded
+__host__ __device__ inline int lsd_frames_of(int len, int n_fft, int hop) { return len > n_fft / 2 ? 1 + len / hop : 0; }
+
+// one workgroup per (frame f, row).  The frame covers [f hop - N/2, f hop + N/2) of the row reflected at 0 and at len - 1 (one
+// reflection each way suffices for len > N/2), under the periodic Hann window.  z = preds + i target goes through one in-place
+// decimation-in-frequency radix-2 FFT in LDS -- fp64 data and twiddles: the bar on LSD is a multiple of what float32 torch.stft loses,
+// which a float32 FFT of another factorisation can only meet by luck -- leaving Z[k] at the bit-reversed index of k.  With
+// X[k] = (Z[k] + conj Z[N-k]) / 2 and Y[k] = (Z[k] - conj Z[N-k]) / 2i: d2[k] = (log10 max(|X|^2, 1e-8) - log10 max(|Y|^2, 1e-8))^2, and
+// dist[band, row, f] = sqrt(sum of d2 over the band's bins / bins), the sum in a fixed order that starts at the band's own first bin
+// (so a band's value does not depend on which other bands the launch carries).  LDS: N double2 of data, N/2 of twiddles (reused for d2),
+// block_sum's four partial sums.
+__global__ __launch_bounds__(256) void lsd_frames_kernel(const float* __restrict__ preds, const float* __restrict__ target, int t_max,
+                                                         const int* __restrict__ lengths, int n_fft, int log2n, int hop, LsdBands bands,
+                                                         int rows, int frames_max, double* __restrict__ dist) {
+  extern __shared__ __align__(16) unsigned char lsd_lds[];  // all of the kernel's LDS (the attribute raises the dynamic limit to the CU's)
+  double2* z = reinterpret_cast<double2*>(lsd_lds);
+  double2* tw = z + n_fft;
+  double* d2 = reinterpret_cast<double*>(tw);
+  double* red = reinterpret_cast<double*>(tw + (n_fft >> 1));
+  const int f = blockIdx.x;
+  const long long r = blockIdx.y;
+  const int len = row_length(lengths, r, t_max);
+  if (f >= lsd_frames_of(len, n_fft, hop)) return;  // uniform over the workgroup
+  const int tid = threadIdx.x, nh = n_fft >> 1;
+  for (int j = tid; j < nh; j += 256) {  // tw[j] = exp(-2 pi i j / N)
+    double sn, cs;
+    sincospi(2.0 * (double)j / (double)n_fft, &sn, &cs);
+    tw[j] = make_double2(cs, -sn);
+  }
+  __syncthreads();
+  const float* p = preds + r * t_max;
+  const float* g = target + r * t_max;
+  const int start = f * hop - nh;
+  for (int n = tid; n < n_fft; n += 256) {
+    long long idx = (long long)start + n;
+    if (idx < 0) idx = -idx;
+    if (idx >= len) idx = 2ll * (len - 1) - idx;
+    const double w = 0.5 - 0.5 * (n < nh ? tw[n].x : -tw[n - nh].x);  // hann_window(N)[n] = 0.5 - 0.5 cos(2 pi n / N)
+    z[n] = make_double2(w * (double)p[idx], w * (double)g[idx]);
+  }
+  for (int half = nh, shift = 0; half >= 1; half >>= 1, ++shift) {
+    __syncthreads();
+    for (int b = tid; b < nh; b += 256) {
+      const int j = b & (half - 1);
+      const int i0 = ((b - j) << 1) + j, i1 = i0 + half;
+      const double2 a = z[i0], c = z[i1], w = tw[j << shift];
+      const double dr = a.x - c.x, di = a.y - c.y;
+      z[i0] = make_double2(a.x + c.x, a.y + c.y);
+      z[i1] = make_double2(dr * w.x - di * w.y, dr * w.y + di * w.x);
+    }
+  }
+  __syncthreads();
+  for (int k = tid; k <= nh; k += 256) {
+    const double2 a = z[__brev((unsigned)k) >> (32 - log2n)];
+    const double2 c = z[__brev((unsigned)((n_fft - k) & (n_fft - 1))) >> (32 - log2n)];
+    const double xr = 0.5 * (a.x + c.x), xi = 0.5 * (a.y - c.y);
+    const double yr = 0.5 * (a.y + c.y), yi = -0.5 * (a.x - c.x);
+    const double d = log10(fmax(xr * xr + xi * xi, kLsdFloor)) - log10(fmax(yr * yr + yi * yi, kLsdFloor));
+    d2[k] = d * d;
+  }
+  __syncthreads();
+  for (int b = 0; b < bands.n; ++b) {
+    double s = 0.0;
+    for (int k = bands.lo[b] + tid; k < bands.hi[b]; k += 256) s += d2[k];
+    s = block_sum(s, red);
+    if (tid == 0) dist[((long long)b * rows + r) * frames_max + f] = sqrt(s / (double)(bands.hi[b] - bands.lo[b]));
+  }
+}
+
+// one workgroup per (row, band): out[band, row] = mean of the row's own frames' distances, NaN for a row that cannot be reflect-padded
+// (len <= N/2) or whose length is out of range
+__global__ __launch_bounds__(256) void lsd_mean_kernel(const double* __restrict__ dist, int t_max, const int* __restrict__ lengths,
+                                                       int n_fft, int hop, int rows, int frames_max, float* __restrict__ out) {
+  __shared__ double red[4];
+  const long long r = blockIdx.x;
+  const int b = blockIdx.y;
+  const int frames = lsd_frames_of(row_length(lengths, r, t_max), n_fft, hop);
+  if (frames == 0) {
+    if (threadIdx.x == 0) out[(long long)b * rows + r] = NAN;
+    return;
+  }
+  const double* d = dist + ((long long)b * rows + r) * frames_max;
+  double acc = 0.0;
+  for (int f = threadIdx.x; f < frames; f += 256) acc += d[f];
+  acc = block_sum(acc, red);
+  if (threadIdx.x == 0) out[(long long)b * rows + r] = (float)(acc / (double)frames);
+}
+
 StoiShape stoi_shape(int t, int fs) {
   int p = 1, q = 1;
   if (fs != kFs) {
@@ -310,10 +557,11 @@ StoiShape stoi_shape(int t, int fs) {
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 struct StoiWs {
-  size_t sig, energy, kept, count, tob, total;
+  size_t sig, energy, kept, count, tob, seg, total;
 };
 
-StoiWs stoi_ws(int rows, const StoiShape& s, int fs) {
+// extended: room behind the classic layout for the per-segment sums of the ESTOI tail
+StoiWs stoi_ws(int rows, const StoiShape& s, int fs, bool extended = false) {
   StoiWs w{};
   size_t off = 0;
   w.sig = off;
@@ -326,6 +574,8 @@ StoiWs stoi_ws(int rows, const StoiShape& s, int fs) {
   off += align256(sizeof(int) * (size_t)rows);
   w.tob = off;
   off += align256(sizeof(double) * (size_t)rows * 2 * kBands * s.fmax);
+  w.seg = off;
+  off += extended ? align256(sizeof(double) * (size_t)rows * s.fmax) : 0;
   w.total = off;
   return w;
 }
@@ -368,11 +618,12 @@ int launch_si_sdr(const float* preds, const float* target, int rows, int t_max, 
   return EBEN_OK;
 }
 
-// the four STOI stages over rows t_max apart; lengths == nullptr: every row is t_max long (the dense entry)
+// the STOI stages over rows t_max apart; lengths == nullptr: every row is t_max long (the dense entry).  out: the classic tail,
+// out_ext: the extended one (either may be null, not both) -- one run of resample / frames / bands serves both.
 int launch_stoi(const float* clean, const float* processed, int rows, int t_max, const int* lengths, int fs, const float* resample_table,
-                int taps, void* workspace, size_t ws_bytes, float* out, void* stream) {
+                int taps, void* workspace, size_t ws_bytes, float* out, float* out_ext, void* stream) {
   const StoiShape s = stoi_shape(t_max, fs);
-  const StoiWs w = stoi_ws(rows, s, fs);
+  const StoiWs w = stoi_ws(rows, s, fs, out_ext != nullptr);
   if (ws_bytes < w.total) return fail(EBEN_EWORKSPACE, "stoi needs %zu workspace bytes", w.total);
   char* ws = static_cast<char*>(workspace);
   const hipStream_t st = as_stream(stream);
@@ -398,10 +649,23 @@ int launch_stoi(const float* clean, const float* processed, int rows, int t_max,
                        tob);
     EBEN_CHECK_LAUNCH("stoi_bands_kernel");
   }
-  hipLaunchKernelGGL(stoi_corr_kernel, dim3(rows), dim3(256), 0, st, tob, count, s.fmax, out);
-  EBEN_CHECK_LAUNCH("stoi_corr_kernel");
+  if (out) {
+    hipLaunchKernelGGL(stoi_corr_kernel, dim3(rows), dim3(256), 0, st, tob, count, s.fmax, out);
+    EBEN_CHECK_LAUNCH("stoi_corr_kernel");
+  }
+  if (out_ext) {
+    double* seg = reinterpret_cast<double*>(ws + w.seg);
+    if (s.fmax >= kSeg) {
+      hipLaunchKernelGGL(estoi_seg_kernel, dim3(ceil_div(s.fmax - kSeg + 1, 4), rows), dim3(256), 0, st, tob, count, s.fmax, seg);
+      EBEN_CHECK_LAUNCH("estoi_seg_kernel");
+    }
+    hipLaunchKernelGGL(estoi_sum_kernel, dim3(rows), dim3(256), 0, st, seg, count, s.fmax, out_ext);
+    EBEN_CHECK_LAUNCH("estoi_sum_kernel");
+  }
   return EBEN_OK;
 }
+
+LdsAttrOnce lsd_lds_once;
 
 }  // namespace
 
@@ -428,7 +692,7 @@ extern "C" size_t eben_stoi_ragged_workspace(int rows, int t_max, int fs) { retu
 extern "C" int eben_stoi(const float* clean, const float* processed, int rows, int t, int fs, const float* resample_table, int taps,
                          void* workspace, size_t ws_bytes, float* out, void* stream) {
   EBEN_REQUIRE(clean && processed && out && workspace && rows > 0 && rows <= 65535 && t > 0 && fs > 0, "bad stoi arguments");
-  return launch_stoi(clean, processed, rows, t, nullptr, fs, resample_table, taps, workspace, ws_bytes, out, stream);
+  return launch_stoi(clean, processed, rows, t, nullptr, fs, resample_table, taps, workspace, ws_bytes, out, nullptr, stream);
 }
 
 extern "C" int eben_stoi_ragged(const float* clean, const float* processed, int rows, int t_max, const int32_t* lengths, int fs,
@@ -436,5 +700,68 @@ extern "C" int eben_stoi_ragged(const float* clean, const float* processed, int 
   EBEN_REQUIRE(clean && processed && lengths && out && workspace, "stoi_ragged: null pointer");
   EBEN_REQUIRE(rows > 0 && rows <= 65535 && t_max > 0 && fs > 0, "stoi_ragged: rows = %d outside [1, 65535], t_max = %d or fs = %d <= 0", rows,
                t_max, fs);
-  return launch_stoi(clean, processed, rows, t_max, lengths, fs, resample_table, taps, workspace, ws_bytes, out, stream);
+  return launch_stoi(clean, processed, rows, t_max, lengths, fs, resample_table, taps, workspace, ws_bytes, out, nullptr, stream);
+}
+
+extern "C" int eben_signal_ratio(const float* preds, const float* target, int rows, int t_max, const int32_t* lengths, int kind,
+                                 int zero_mean, float* out, void* stream) {
+  EBEN_REQUIRE(preds && target && out, "signal_ratio: null pointer");
+  EBEN_REQUIRE(rows > 0 && t_max > 0, "signal_ratio: rows = %d or t_max = %d <= 0", rows, t_max);
+  EBEN_REQUIRE(kind == EBEN_RATIO_SI_SDR || kind == EBEN_RATIO_SNR, "signal_ratio: kind = %d is neither EBEN_RATIO_SI_SDR nor EBEN_RATIO_SNR", kind);
+  EBEN_REQUIRE(zero_mean == 0 || zero_mean == 1, "signal_ratio: zero_mean = %d is neither 0 nor 1", zero_mean);
+  if (kind == EBEN_RATIO_SI_SDR && !zero_mean) return launch_si_sdr(preds, target, rows, t_max, lengths, out, stream);
+  hipLaunchKernelGGL(signal_ratio_kernel, dim3(rows), dim3(256), 0, as_stream(stream), preds, target, t_max, lengths, kind, zero_mean, out);
+  EBEN_CHECK_LAUNCH("signal_ratio_kernel");
+  return EBEN_OK;
+}
+
+extern "C" size_t eben_estoi_workspace(int rows, int t_max, int fs) {
+  if (rows <= 0 || t_max <= 0 || fs <= 0) return 0;
+  return stoi_ws(rows, stoi_shape(t_max, fs), fs, true).total;
+}
+
+extern "C" int eben_estoi(const float* clean, const float* processed, int rows, int t_max, const int32_t* lengths, int fs,
+                          const float* resample_table, int taps, void* workspace, size_t ws_bytes, float* out, float* out_classic,
+                          void* stream) {
+  EBEN_REQUIRE(clean && processed && out && workspace, "estoi: null pointer");
+  EBEN_REQUIRE(rows > 0 && rows <= 65535 && t_max > 0 && fs > 0, "estoi: rows = %d outside [1, 65535], t_max = %d or fs = %d <= 0", rows, t_max, fs);
+  return launch_stoi(clean, processed, rows, t_max, lengths, fs, resample_table, taps, workspace, ws_bytes, out_classic, out, stream);
+}
+
+extern "C" size_t eben_lsd_workspace(int rows, int t_max, int n_fft, int hop, int nbands) {
+  if (rows <= 0 || t_max <= 0 || n_fft <= 0 || hop <= 0 || nbands <= 0) return 0;
+  return align256(sizeof(double) * (size_t)nbands * rows * (1 + t_max / hop));
+}
+
+extern "C" int eben_lsd(const float* preds, const float* target, int rows, int t_max, const int32_t* lengths, int n_fft, int hop,
+                        const int* band_lo, const int* band_hi, int nbands, void* workspace, size_t ws_bytes, float* out, void* stream) {
+  EBEN_REQUIRE(preds && target && band_lo && band_hi && workspace && out, "lsd: null pointer");
+  EBEN_REQUIRE(rows > 0 && rows <= 65535 && t_max > 0, "lsd: rows = %d outside [1, 65535] or t_max = %d <= 0", rows, t_max);
+  EBEN_REQUIRE(n_fft >= 256 && n_fft <= 4096 && (n_fft & (n_fft - 1)) == 0, "lsd: n_fft = %d is not a power of two in [256, 4096]", n_fft);
+  EBEN_REQUIRE(hop >= 1 && hop <= n_fft, "lsd: hop = %d outside [1, n_fft = %d]", hop, n_fft);
+  EBEN_REQUIRE(nbands >= 1 && nbands <= kLsdMaxBands, "lsd: %d bands outside [1, %d]", nbands, kLsdMaxBands);
+  LsdBands bands{};
+  bands.n = nbands;
+  for (int b = 0; b < nbands; ++b) {
+    EBEN_REQUIRE(band_lo[b] >= 0 && band_lo[b] < band_hi[b] && band_hi[b] <= n_fft / 2 + 1, "lsd: band %d = [%d, %d) is empty or outside [0, %d)", b,
+                 band_lo[b], band_hi[b], n_fft / 2 + 1);
+    bands.lo[b] = band_lo[b];
+    bands.hi[b] = band_hi[b];
+  }
+  const size_t need = eben_lsd_workspace(rows, t_max, n_fft, hop, nbands);
+  if (ws_bytes < need) return fail(EBEN_EWORKSPACE, "lsd needs %zu workspace bytes", need);
+  int log2n = 0;
+  while ((1 << log2n) < n_fft) ++log2n;
+  const int frames_max = 1 + t_max / hop;
+  const size_t lds = sizeof(double2) * ((size_t)n_fft + n_fft / 2) + 4 * sizeof(double);
+  const hipError_t e = lds_attr_once(lsd_lds_once, reinterpret_cast<const void*>(lsd_frames_kernel));
+  if (e != hipSuccess) return hip_fail(e, "lsd_frames_kernel: dynamic LDS attribute");
+  double* dist = static_cast<double*>(workspace);
+  const hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL(lsd_frames_kernel, dim3(frames_max, rows), dim3(256), lds, st, preds, target, t_max, lengths, n_fft, log2n, hop, bands, rows,
+                     frames_max, dist);
+  EBEN_CHECK_LAUNCH("lsd_frames_kernel");
+  hipLaunchKernelGGL(lsd_mean_kernel, dim3(rows, nbands), dim3(256), 0, st, dist, t_max, lengths, n_fft, hop, rows, frames_max, out);
+  EBEN_CHECK_LAUNCH("lsd_mean_kernel");
+  return EBEN_OK;
 }

@@ -10,7 +10,7 @@ one): per batch one ragged forward and the SI-SDR / STOI kernels with a length p
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Sequence
+from typing import Dict, List, Optional, Sequence
 
 import torch
 
@@ -18,6 +18,12 @@ from . import ragged
 
 #: the rate ``base_se.py`` evaluates SI-SDR and STOI at
 EVAL_RATE = 16000
+
+#: what ``evaluate_clips`` can score, all at ``EVAL_RATE``: the two ``base_se.py`` logs (the default) and the evaluation set of a
+#: bandwidth-extension model -- "lsd" over the whole band, "lsd_hf" over [lsd_hf_cutoff_hz, EVAL_RATE / 2] (the band being reconstructed)
+EVAL_METRICS = ("si_sdr", "stoi", "estoi", "si_snr", "snr", "lsd", "lsd_hf")
+DEFAULT_EVAL_METRICS = ("si_sdr", "stoi")
+LSD_N_FFT, LSD_HOP = 2048, 512
 
 #: buffer samples (rows x padded length) per batch: 262 s at 16 kHz.  The widest activations (32 channels at 1/4 of the audio rate,
 #: 64 at 1/8) take 32 bytes per audio sample each, 128 MiB a tensor at this budget
@@ -102,15 +108,33 @@ def _check_clip(c, what: str) -> None:
 
 @torch.no_grad()
 def evaluate_clips(generator, corrupted: Sequence[torch.Tensor], reference: Sequence[torch.Tensor], *, sample_rate: int = EVAL_RATE,
-                   max_batch_samples: int = MAX_BATCH_SAMPLES, return_enhanced: bool = False) -> Dict[str, object]:
+                   max_batch_samples: int = MAX_BATCH_SAMPLES, return_enhanced: bool = False,
+                   metrics: Sequence[str] = DEFAULT_EVAL_METRICS, lsd_hf_cutoff_hz: Optional[float] = None) -> Dict[str, object]:
     """Per-clip SI-SDR and STOI of the enhanced ``corrupted[i]`` against ``reference[i]``, at 16 kHz as ``base_se.py`` logs them:
     ``{"si_sdr": (N,) float32, "stoi": (N,) float32}`` on the device, in input order; with ``return_enhanced`` also ``"enhanced"``, the
-    list ``enhance_clips`` returns.  Clips as for ``enhance_clips``; a pair has one length, and both are scored on their first
+    list ``enhance_clips`` returns.  ``metrics`` selects among ``EVAL_METRICS``, one key each, all on the same 16 kHz buffers and lengths;
+    ``"lsd_hf"`` is the LSD over ``[lsd_hf_cutoff_hz, 8000]`` Hz (Nyquist bin excluded) and needs that cutoff -- it depends on the sensor.
+    ``"stoi"`` and ``"estoi"`` together share one resampling / silence-removal / band-envelope run.
+    Clips as for ``enhance_clips``; a pair has one length, and both are scored on their first
     ``cut_to_valid_length`` samples (a reference may carry anything behind them).  Batches as in ``enhance_clips``: per batch one
     ``forward_ragged`` and the metric kernels with ``lengths = plan.cut`` on the padded buffers -- nothing is unpacked unless
     ``return_enhanced`` asks for it, and nothing here waits for the device."""
-    from . import metrics
+    from . import metrics as M
 
+    names = list(metrics)
+    for name in names:
+        if name not in EVAL_METRICS:
+            raise ValueError(f"evaluate_clips: unknown metric {name!r}; known: {', '.join(EVAL_METRICS)}")
+    if len(set(names)) != len(names):
+        raise ValueError(f"evaluate_clips: a metric is named twice in {names}")
+    if not names:
+        raise ValueError("evaluate_clips: no metric requested")
+    if "lsd_hf" in names and lsd_hf_cutoff_hz is None:
+        raise ValueError("evaluate_clips: 'lsd_hf' needs lsd_hf_cutoff_hz, the lower edge of the band being reconstructed (there is no default: "
+                         "it depends on the sensor)")
+    lsd_bands = [None] * ("lsd" in names) + [(lsd_hf_cutoff_hz, EVAL_RATE // 2)] * ("lsd_hf" in names)
+    for band in lsd_bands:
+        M.lsd_band_bins(band, EVAL_RATE, LSD_N_FFT)   # a cutoff that leaves no bin is refused before anything runs
     corrupted, reference = list(corrupted), list(reference)
     if len(corrupted) != len(reference):
         raise ValueError(f"evaluate_clips: {len(corrupted)} corrupted clips and {len(reference)} references")
@@ -124,8 +148,12 @@ def evaluate_clips(generator, corrupted: Sequence[torch.Tensor], reference: Sequ
         raise ValueError(f"evaluate_clips: sample_rate must be positive, got {sample_rate}")
     lengths = [c.shape[-1] for c in corrupted]
     batches, back = ragged.compose_batches(generator, lengths, max_batch_samples)   # refuses a clip that is too short, by index
-    si_sdr: List[torch.Tensor] = []
-    stoi: List[torch.Tensor] = []
+    if lsd_bands:
+        for i, t in enumerate(lengths):
+            t16 = resampled_length(ragged.cut_length(generator, t), sample_rate, EVAL_RATE)   # the cut length itself at 16 kHz
+            if t16 <= LSD_N_FFT // 2:
+                raise ValueError(f"clip {i}: {t16} samples at {EVAL_RATE} Hz cannot be reflect-padded for the LSD ({LSD_N_FFT // 2 + 1} at least)")
+    values: Dict[str, List[torch.Tensor]] = {name: [] for name in names}
     enhanced: List[torch.Tensor] = []
     for idx in batches:
         plan = ragged.plan(generator, [lengths[i] for i in idx])
@@ -147,10 +175,26 @@ def evaluate_clips(generator, corrupted: Sequence[torch.Tensor], reference: Sequ
             enh, ref = resample(enh, sample_rate, EVAL_RATE), resample(ref, sample_rate, EVAL_RATE)
             rows = [resampled_length(t, sample_rate, EVAL_RATE) for t in rows]
         lens = torch.tensor(rows, dtype=torch.int32).to(dev, non_blocking=True)   # 1 <= each <= the buffer's length by construction
-        si_sdr.append(metrics.si_sdr(enh, ref, lens))
-        stoi.append(metrics.stoi(enh, ref, EVAL_RATE, lens))
-    order = torch.tensor(back, dtype=torch.int64).to(si_sdr[0].device, non_blocking=True)
-    out: Dict[str, object] = {"si_sdr": torch.cat(si_sdr).index_select(0, order), "stoi": torch.cat(stoi).index_select(0, order)}
+        if "si_sdr" in values:
+            values["si_sdr"].append(M.si_sdr(enh, ref, lens))
+        if "stoi" in values and "estoi" in values:
+            classic, extended = M.stoi_and_estoi(enh, ref, EVAL_RATE, lens)
+            values["stoi"].append(classic)
+            values["estoi"].append(extended)
+        elif "stoi" in values:
+            values["stoi"].append(M.stoi(enh, ref, EVAL_RATE, lens))
+        elif "estoi" in values:
+            values["estoi"].append(M.stoi(enh, ref, EVAL_RATE, lens, extended=True))
+        if "si_snr" in values:
+            values["si_snr"].append(M.si_snr(enh, ref, lens))
+        if "snr" in values:
+            values["snr"].append(M.snr(enh, ref, lens))
+        if lsd_bands:
+            both = M.lsd(enh, ref, EVAL_RATE, lens, LSD_N_FFT, LSD_HOP, lsd_bands)
+            for name, row in zip([n for n in ("lsd", "lsd_hf") if n in values], both):
+                values[name].append(row)
+    order = torch.tensor(back, dtype=torch.int64).to(values[names[0]][0].device, non_blocking=True)
+    out: Dict[str, object] = {name: torch.cat(values[name]).index_select(0, order) for name in names}
     if return_enhanced:
         out["enhanced"] = [enhanced[p] for p in back]
     return out

@@ -504,21 +504,29 @@ class EBENLightningModule(BaseSELightningModule):
         return self.common_eval_step(batch, batch_idx, "test", dataloader_idx)
 
     @torch.no_grad()
-    def evaluate_clips(self, corrupted, reference, stage: str = "test", dataloader_idx: int = 0, max_batch_samples: Optional[int] = None):
+    def evaluate_clips(self, corrupted, reference, stage: str = "test", dataloader_idx: int = 0, max_batch_samples: Optional[int] = None,
+                       metrics=("si_sdr", "stoi"), lsd_hf_cutoff_hz: Optional[float] = None):
         """A whole split at once: what the reference's batch-1 test loop (one ``test_step`` + ``on_test_batch_end`` per utterance)
         aggregates SI-SDR and STOI to over an epoch, through ``inference.evaluate_clips`` -- ragged batches, metric kernels with a length
         per row.  The per-clip values join the running state of ``self.metrics`` (``compute()`` is the corpus mean) and their means are
         logged as ``{stage}/torchmetrics_si_sdr{suffix}`` / ``{stage}/torchmetrics_stoi{suffix}``.  Returns the per-clip result dict.
-        The atomic losses ``test_step`` logs are not part of this (no ragged discriminators or MRSTFT)."""
+        The atomic losses ``test_step`` logs are not part of this (no ragged discriminators or MRSTFT).  ``metrics`` /
+        ``lsd_hf_cutoff_hz`` as for ``inference.evaluate_clips``: every other metric's corpus mean is logged as ``{stage}/{name}{suffix}``
+        and stays out of ``self.metrics``, which mirrors the reference's collection."""
         from .. import inference
 
         budget = inference.MAX_BATCH_SAMPLES if max_batch_samples is None else max_batch_samples
-        out = inference.evaluate_clips(self.generator, corrupted, reference, sample_rate=int(self.sample_rate), max_batch_samples=budget)
+        out = inference.evaluate_clips(self.generator, corrupted, reference, sample_rate=int(self.sample_rate), max_batch_samples=budget,
+                                       metrics=metrics, lsd_hf_cutoff_hz=lsd_hf_cutoff_hz)
         names = getattr(self, "dataloader_names", None)
         suffix = f"/{names[dataloader_idx]}" if names is not None else ""
-        for key, values in (("torchmetrics_si_sdr", out["si_sdr"]), ("torchmetrics_stoi", out["stoi"])):
-            self.metrics[key]._accumulate(values)
-            self.log(f"{stage}/{key}{suffix}", values.mean(), sync_dist=True, prog_bar=True, add_dataloader_idx=False)
+        for name, values in out.items():
+            if name in ("si_sdr", "stoi"):
+                key = f"torchmetrics_{name}"
+                self.metrics[key]._accumulate(values)
+                self.log(f"{stage}/{key}{suffix}", values.mean(), sync_dist=True, prog_bar=True, add_dataloader_idx=False)
+            else:
+                self.log(f"{stage}/{name}{suffix}", values.mean(), sync_dist=True, add_dataloader_idx=False)
         return out
 
     def compute_atomic_losses(self, network, enhanced_speech, reference_speech, decomposed_enhanced_speech,

@@ -7,7 +7,12 @@
   resampling to 10 kHz, silence removal, third-octave band envelopes, segment correlations.  pystoi is not installed here,
   so its conventions are restated from its published source (parity unpinned, like the auraloss / torchaudio restatements).
 
-Both take ``(..., T)`` float tensors on a HIP device and return ``(...)`` float32 on that device, with torchmetrics' argument
+Beyond those two, for scoring a bandwidth-extension model: ``si_sdr(..., zero_mean=True)`` / ``si_snr`` and ``snr`` (torchmetrics'
+``scale_invariant_signal_noise_ratio`` and ``signal_noise_ratio``; ``eben_signal_ratio``), ``stoi(..., extended=True)`` (ESTOI: pystoi's
+row- and column-normalised tail on the same envelopes, without its ``EPS * randn`` dither; ``eben_estoi``) and ``lsd`` (log-spectral
+distance over the whole band or over ``band_hz`` ranges; ``eben_lsd``).
+
+All take ``(..., T)`` float tensors on a HIP device and return ``(...)`` float32 on that device, with torchmetrics' argument
 order (preds first).  There is no CPU path: a CPU tensor raises ``EbenError`` (the float64 restatement used to check these
 kernels is test code under ``tests/``).
 
@@ -17,9 +22,10 @@ live on the device as plain attributes, not buffers, so a module that holds them
 
 Rows of different lengths: every entry point takes ``lengths``, one value per row of the flattened leading dimensions.  Row ``r`` is
 then the signal ``[..., :lengths[r]]`` -- what lies behind it is never read -- and its value has the bits of the call on that row
-alone (``eben_si_sdr_ragged`` / ``eben_stoi_ragged``: the same kernels with a length per row).  A sequence of ints or a CPU integer
+alone (``eben_si_sdr_ragged`` / ``eben_stoi_ragged``: the same kernels with a length per row; the newer entries take a nullable table).  A sequence of ints or a CPU integer
 tensor is validated (``ValueError`` naming the row) and uploaded; an ``int32`` tensor on the signals' device is used as it is, without
-synchronisation, and a value outside ``[1, T]`` in it makes that row NaN.
+synchronisation, and a value outside ``[1, T]`` in it makes that row NaN (for ``lsd`` also a value ``<= n_fft // 2``: such a row cannot
+be reflect-padded).
 """
 from __future__ import annotations
 
@@ -37,7 +43,7 @@ STOI_FS = 10000
 Lengths = Union[None, Sequence[int], torch.Tensor]
 
 
-def _host_lengths(lengths, rows: int, t: int, what: str) -> Optional[torch.Tensor]:
+def _host_lengths(lengths, rows: int, t: int, what: str, least: int = 1) -> Optional[torch.Tensor]:
     """A host-side ``lengths`` checked and as a CPU int32 tensor; None for a device tensor (``_device_lengths`` takes those)."""
     if torch.is_tensor(lengths):
         if lengths.is_cuda:
@@ -54,8 +60,8 @@ def _host_lengths(lengths, rows: int, t: int, what: str) -> Optional[torch.Tenso
     if len(values) != rows:
         raise ValueError(f"{what}: {len(values)} lengths for {rows} rows")
     for r, v in enumerate(values):
-        if not 1 <= v <= t:
-            raise ValueError(f"{what}: row {r} has length {v}, outside [1, {t}]")
+        if not least <= v <= t:
+            raise ValueError(f"{what}: row {r} has length {v}, outside [{least}, {t}]")
     return torch.tensor(values, dtype=torch.int32)
 
 
@@ -70,7 +76,7 @@ def _device_lengths(lengths: torch.Tensor, rows: int, lead: Tuple[int, ...], dev
     return lengths.contiguous().reshape(-1)
 
 
-def _rows(preds: torch.Tensor, target: torch.Tensor, what: str, lengths: Lengths = None):
+def _rows(preds: torch.Tensor, target: torch.Tensor, what: str, lengths: Lengths = None, least: int = 1):
     """(preds, target) as contiguous float32 (rows, T), the leading shape and ``lengths`` as a device int32 (rows,) tensor or None."""
     if preds.shape != target.shape:
         raise ValueError(f"{what}: preds and target must have the same shape, got {tuple(preds.shape)} and {tuple(target.shape)}")
@@ -79,7 +85,7 @@ def _rows(preds: torch.Tensor, target: torch.Tensor, what: str, lengths: Lengths
     lead = tuple(preds.shape[:-1])
     t = preds.shape[-1]
     rows = math.prod(lead)
-    host = _host_lengths(lengths, rows, t, what) if lengths is not None else None   # refused before anything touches a device
+    host = _host_lengths(lengths, rows, t, what, least) if lengths is not None else None   # refused before anything touches a device
     for x in (preds, target):
         if not x.is_cuda:
             raise EbenError(f"{what} runs only on an MI355X HIP device (got a tensor on '{x.device}'); there is no CPU path")
@@ -92,8 +98,25 @@ def _rows(preds: torch.Tensor, target: torch.Tensor, what: str, lengths: Lengths
     return p2, g2, lead, _device_lengths(lengths, rows, lead, p2.device, what)
 
 
-def si_sdr(preds: torch.Tensor, target: torch.Tensor, lengths: Lengths = None) -> torch.Tensor:
-    """Scale-invariant SDR in dB per signal: (..., T) -> (...); with ``lengths``, of ``[..., :lengths[r]]`` per row."""
+def _lens_ptr(lens: Optional[torch.Tensor]) -> Optional[int]:
+    return None if lens is None else lens.data_ptr()
+
+
+RATIO_SI_SDR, RATIO_SNR = 0, 1   # include/eben_hip.h EBEN_RATIO_*
+
+
+def _signal_ratio(preds, target, lengths, kind: int, zero_mean: bool, what: str) -> torch.Tensor:
+    p2, g2, lead, lens = _rows(preds, target, what, lengths)
+    out = torch.empty(p2.shape[0], dtype=torch.float32, device=p2.device)
+    check(load().eben_signal_ratio(ptr(p2), ptr(g2), p2.shape[0], p2.shape[1], _lens_ptr(lens), kind, int(bool(zero_mean)), ptr(out), stream()), what)
+    return out.reshape(lead)
+
+
+def si_sdr(preds: torch.Tensor, target: torch.Tensor, lengths: Lengths = None, zero_mean: bool = False) -> torch.Tensor:
+    """Scale-invariant SDR in dB per signal: (..., T) -> (...); with ``lengths``, of ``[..., :lengths[r]]`` per row.  ``zero_mean``
+    subtracts each signal's mean over its own length first."""
+    if zero_mean:
+        return _signal_ratio(preds, target, lengths, RATIO_SI_SDR, True, "si_sdr")
     p2, g2, lead, lens = _rows(preds, target, "si_sdr", lengths)
     out = torch.empty(p2.shape[0], dtype=torch.float32, device=p2.device)
     if lens is None:
@@ -101,6 +124,16 @@ def si_sdr(preds: torch.Tensor, target: torch.Tensor, lengths: Lengths = None) -
     else:
         check(load().eben_si_sdr_ragged(ptr(p2), ptr(g2), p2.shape[0], p2.shape[1], lens.data_ptr(), ptr(out), stream()), "si_sdr_ragged")
     return out.reshape(lead)
+
+
+def si_snr(preds: torch.Tensor, target: torch.Tensor, lengths: Lengths = None) -> torch.Tensor:
+    """torchmetrics ``scale_invariant_signal_noise_ratio``: SI-SDR of the zero-mean signals."""
+    return _signal_ratio(preds, target, lengths, RATIO_SI_SDR, True, "si_snr")
+
+
+def snr(preds: torch.Tensor, target: torch.Tensor, lengths: Lengths = None, zero_mean: bool = False) -> torch.Tensor:
+    """torchmetrics ``signal_noise_ratio`` in dB per signal: 10 log10((sum t^2 + eps) / (sum (t - p)^2 + eps))."""
+    return _signal_ratio(preds, target, lengths, RATIO_SNR, zero_mean, "snr")
 
 
 def stoi_resample_table(fs: int) -> Tuple[np.ndarray, int, int]:
@@ -119,8 +152,46 @@ def stoi_resample_table(fs: int) -> Tuple[np.ndarray, int, int]:
 _tables: Dict[Tuple[int, torch.device], torch.Tensor] = {}
 
 
-def stoi(preds: torch.Tensor, target: torch.Tensor, fs: int, lengths: Lengths = None) -> torch.Tensor:
-    """Classic STOI per signal (target = clean reference): (..., T) -> (...); with ``lengths``, of ``[..., :lengths[r]]`` per row."""
+def _stoi_table(fs: int, dev: torch.device):
+    if fs == STOI_FS:
+        return None, 0
+    key = (fs, dev)
+    if key not in _tables:
+        _tables[key] = torch.from_numpy(stoi_resample_table(fs)[0]).to(torch.float32).to(dev)
+    return _tables[key], _tables[key].numel()
+
+
+def _estoi(preds, target, fs: int, lengths: Lengths, with_classic: bool, what: str):
+    """ESTOI per row, and with ``with_classic`` also classic STOI from the same envelopes (one front end, two tails)."""
+    p2, g2, lead, lens = _rows(preds, target, what, lengths)
+    fs = int(fs)
+    if fs <= 0:
+        raise ValueError(f"{what}: fs must be positive, got {fs}")
+    rows, t = p2.shape
+    dev = p2.device
+    lib = load()
+    table, taps = _stoi_table(fs, dev)
+    ws_bytes = lib.eben_estoi_workspace(rows, t, fs)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    out = torch.empty((2 if with_classic else 1, rows), dtype=torch.float32, device=dev)
+    classic = out[1].data_ptr() if with_classic else None
+    check(lib.eben_estoi(ptr(g2), ptr(p2), rows, t, _lens_ptr(lens), fs, ptr(table), taps, ws.data_ptr(), ws_bytes, out[0].data_ptr(), classic,
+                         stream()), what)
+    return (out[0].reshape(lead), out[1].reshape(lead)) if with_classic else out[0].reshape(lead)
+
+
+def stoi_and_estoi(preds: torch.Tensor, target: torch.Tensor, fs: int, lengths: Lengths = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(classic STOI, ESTOI) per signal from one run of the resampling, silence-removal and band-envelope kernels; each has the bits of
+    its own ``stoi`` call."""
+    estoi, classic = _estoi(preds, target, fs, lengths, True, "stoi_and_estoi")
+    return classic, estoi
+
+
+def stoi(preds: torch.Tensor, target: torch.Tensor, fs: int, lengths: Lengths = None, extended: bool = False) -> torch.Tensor:
+    """STOI per signal (target = clean reference): (..., T) -> (...); with ``lengths``, of ``[..., :lengths[r]]`` per row.  ``extended``
+    selects ESTOI."""
+    if extended:
+        return _estoi(preds, target, fs, lengths, False, "estoi")
     p2, g2, lead, lens = _rows(preds, target, "stoi", lengths)
     fs = int(fs)
     if fs <= 0:
@@ -128,13 +199,7 @@ def stoi(preds: torch.Tensor, target: torch.Tensor, fs: int, lengths: Lengths = 
     rows, t = p2.shape
     dev = p2.device
     lib = load()
-    table, taps = None, 0
-    if fs != STOI_FS:
-        key = (fs, dev)
-        if key not in _tables:
-            _tables[key] = torch.from_numpy(stoi_resample_table(fs)[0]).to(torch.float32).to(dev)
-        table = _tables[key]
-        taps = table.numel()
+    table, taps = _stoi_table(fs, dev)
     ws_bytes = lib.eben_stoi_workspace(rows, t, fs) if lens is None else lib.eben_stoi_ragged_workspace(rows, t, fs)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     out = torch.empty(rows, dtype=torch.float32, device=dev)
@@ -144,6 +209,67 @@ def stoi(preds: torch.Tensor, target: torch.Tensor, fs: int, lengths: Lengths = 
         check(lib.eben_stoi_ragged(ptr(g2), ptr(p2), rows, t, lens.data_ptr(), fs, ptr(table), taps, ws.data_ptr(), ws_bytes, ptr(out),
                                    stream()), "stoi_ragged")
     return out.reshape(lead)
+
+
+LSD_MAX_BANDS = 4   # bands per eben_lsd launch
+
+
+def lsd_band_bins(band_hz, fs: int, n_fft: int) -> Tuple[int, int]:
+    """The bin range [k_lo, k_hi) of ``band_hz = (lo, hi)``: the bins k of the n_fft // 2 + 1 with lo <= k fs / n_fft < hi, in exact
+    integer arithmetic for integer edges.  None is the full band, Nyquist bin included (which no finite ``hi <= fs / 2`` reaches)."""
+    nb = n_fft // 2 + 1
+    if band_hz is None:
+        return 0, nb
+    lo, hi = band_hz
+    if not 0 <= lo < hi:
+        raise ValueError(f"lsd: band_hz = ({lo}, {hi}) needs 0 <= lo < hi")
+
+    def first_at_or_above(hz) -> int:   # min k with k * fs >= hz * n_fft
+        if int(hz) == hz:
+            return -(-int(hz) * n_fft // fs)
+        return math.ceil(hz * n_fft / fs)
+
+    k_lo, k_hi = min(first_at_or_above(lo), nb), min(first_at_or_above(hi), nb)
+    if k_lo >= k_hi:
+        raise ValueError(f"lsd: band_hz = ({lo}, {hi}) holds no bin of a {n_fft}-point transform at {fs} Hz")
+    return k_lo, k_hi
+
+
+def _is_band(b) -> bool:
+    return b is None or (len(b) == 2 and not isinstance(b[0], (tuple, list)) and b[0] is not None and not isinstance(b[1], (tuple, list)))
+
+
+def lsd(preds: torch.Tensor, target: torch.Tensor, fs: int, lengths: Lengths = None, n_fft: int = 2048, hop: int = 512,
+        band_hz=None) -> torch.Tensor:
+    """Log-spectral distance per signal: with P(s) = clamp(|stft(s, n_fft, hop, hann, center, reflect)|^2, min=1e-8), the mean over the
+    signal's own 1 + len // hop frames of sqrt(mean over the band's bins of (log10 P(preds) - log10 P(target))^2).  ``band_hz``: None
+    (all n_fft // 2 + 1 bins), ``(lo, hi)`` in Hz, or a list of up to four of either, which returns ``(nbands, ...)``."""
+    fs, n_fft, hop = int(fs), int(n_fft), int(hop)
+    if fs <= 0:
+        raise ValueError(f"lsd: fs must be positive, got {fs}")
+    if n_fft < 256 or n_fft > 4096 or n_fft & (n_fft - 1):
+        raise ValueError(f"lsd: n_fft must be a power of two in [256, 4096], got {n_fft}")
+    if not 1 <= hop <= n_fft:
+        raise ValueError(f"lsd: hop must lie in [1, n_fft = {n_fft}], got {hop}")
+    many = not _is_band(band_hz)
+    bands = list(band_hz) if many else [band_hz]
+    if not 1 <= len(bands) <= LSD_MAX_BANDS:
+        raise ValueError(f"lsd: {len(bands)} bands, one call takes 1 to {LSD_MAX_BANDS}")
+    bins = [lsd_band_bins(b, fs, n_fft) for b in bands]
+    if preds.dim() >= 1 and preds.shape[-1] <= n_fft // 2:
+        raise ValueError(f"lsd: signals of {preds.shape[-1]} samples cannot be reflect-padded by n_fft // 2 = {n_fft // 2}")
+    p2, g2, lead, lens = _rows(preds, target, "lsd", lengths, least=n_fft // 2 + 1)
+    rows, t = p2.shape
+    lib = load()
+    import ctypes
+
+    lo = (ctypes.c_int * len(bins))(*[b[0] for b in bins])
+    hi = (ctypes.c_int * len(bins))(*[b[1] for b in bins])
+    ws_bytes = lib.eben_lsd_workspace(rows, t, n_fft, hop, len(bins))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=p2.device)
+    out = torch.empty((len(bins), rows), dtype=torch.float32, device=p2.device)
+    check(lib.eben_lsd(ptr(p2), ptr(g2), rows, t, _lens_ptr(lens), n_fft, hop, lo, hi, len(bins), ws.data_ptr(), ws_bytes, ptr(out), stream()), "lsd")
+    return out.reshape((len(bins),) + lead) if many else out[0].reshape(lead)
 
 
 class _MeanMetric(torch.nn.Module):
@@ -185,21 +311,45 @@ class _MeanMetric(torch.nn.Module):
 class ScaleInvariantSignalDistortionRatio(_MeanMetric):
     def __init__(self, zero_mean: bool = False):
         super().__init__()
-        if zero_mean:
-            raise NotImplementedError("only zero_mean=False (torchmetrics' default, the one base_se.py uses) is implemented")
-        self.zero_mean = zero_mean
+        self.zero_mean = bool(zero_mean)
 
     def _values(self, preds, target, lengths=None):
-        return si_sdr(preds, target, lengths)
+        return si_sdr(preds, target, lengths, zero_mean=self.zero_mean)
+
+
+class ScaleInvariantSignalNoiseRatio(_MeanMetric):
+    def _values(self, preds, target, lengths=None):
+        return si_snr(preds, target, lengths)
+
+
+class SignalNoiseRatio(_MeanMetric):
+    def __init__(self, zero_mean: bool = False):
+        super().__init__()
+        self.zero_mean = bool(zero_mean)
+
+    def _values(self, preds, target, lengths=None):
+        return snr(preds, target, lengths, zero_mean=self.zero_mean)
 
 
 class ShortTimeObjectiveIntelligibility(_MeanMetric):
     def __init__(self, fs: int, extended: bool = False):
         super().__init__()
-        if extended:
-            raise NotImplementedError("only classic STOI (extended=False, the one base_se.py uses) is implemented")
         self.fs = int(fs)
-        self.extended = extended
+        self.extended = bool(extended)
 
     def _values(self, preds, target, lengths=None):
-        return stoi(preds, target, self.fs, lengths)
+        return stoi(preds, target, self.fs, lengths, extended=self.extended)
+
+
+class LogSpectralDistance(_MeanMetric):
+    """Mean LSD over one band (``band_hz`` None or ``(lo, hi)`` in Hz)."""
+
+    def __init__(self, fs: int, n_fft: int = 2048, hop: int = 512, band_hz=None):
+        super().__init__()
+        if not _is_band(band_hz):
+            raise ValueError("LogSpectralDistance averages one band: band_hz must be None or (lo, hi)")
+        self.fs, self.n_fft, self.hop, self.band_hz = int(fs), int(n_fft), int(hop), band_hz
+        lsd_band_bins(band_hz, self.fs, self.n_fft)   # a band without a bin is refused here
+
+    def _values(self, preds, target, lengths=None):
+        return lsd(preds, target, self.fs, lengths, self.n_fft, self.hop, self.band_hz)
