@@ -138,10 +138,12 @@ EBEN_API int eben_conv1d_kernel_generation(const EbenConv1dDesc* d, int which);
  * which 0: eben_conv1d_fwd / eben_bl_conv1d_fwd; 1: the input gradient -- eben_conv1d_bwd_dx with mask_on_load = 1 (the fused output
  * activation differentiated as the gradient is staged: out_slope != 1), eben_conv1d_bwd_dx_ex / eben_bl_conv1d_bwd_dx with 0.
  * out[0..7] (n >= 8) = generation, then for generations 4 / 6: FM, XRB, IM, NPW, NPX, BL (tap3_kernel's template arguments; XRB = 0
- * off tap3_kernel), EBEN_VARIANT_*; zeros past out[0] otherwise.  EBEN_EUNSUPPORTED where the launch itself would refuse. */
+ * off tap3_kernel), EBEN_VARIANT_*; for generation 5 (which = 0): FORM, RT, CT, NP (gc_kernel's template arguments, read off the plan
+ * the launch dispatches on), 0, 0, EBEN_VARIANT_GC; zeros past out[0] otherwise.  EBEN_EUNSUPPORTED where the launch itself would refuse. */
 #define EBEN_VARIANT_TAP3 1      /* tap3_kernel (tapconv3.hip) */
 #define EBEN_VARIANT_THIN_BL 2   /* thin_bl_kernel (thin_bl.hip) */
 #define EBEN_VARIANT_TAP4 3      /* tap4_kernel (bigtap.hip) */
+#define EBEN_VARIANT_GC 4        /* gc_kernel (gen_conv.hip) */
 EBEN_API int eben_conv1d_variant(const EbenConv1dDesc* d, int which, int mask_on_load, int* out, int n);
 /* pack v (optionally scaled per dim-0 row: weight-norm) into the MFMA-friendly layouts */
 EBEN_API int eben_conv1d_pack(const EbenConv1dDesc* d, const float* v, const float* scale, float* wp_fwd, float* wp_bwd, void* stream);

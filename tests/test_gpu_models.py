@@ -91,6 +91,51 @@ def test_generator_matches_oracle_and_reference_golden(hip, golden, p):
     assert worst < 2e-3, worst
 
 
+# test_generator_forward_in_the_shipped_bf16x3_arithmetic: the x3 forward's measured distance from the float64 oracle ([MI355X], see the
+# docstring); the test holds 4 x these
+X3_MEASURED = {"enhanced": (2.631e-07, 1.954e-15), "bands": (1.137e-07, 4.829e-16)}   # output -> (max_abs, mse)
+
+
+def test_generator_forward_in_the_shipped_bf16x3_arithmetic(hip, golden):
+    """The generator forward as the bf16-mixed train step runs it -- inside gen_engine.forward_math("bf16x3"): hi + lo bf16 operands,
+    three piece products in every conv and ResidualUnit -- against the oracle in float64, next to the default six-product forward.
+    [MI355X] batch 2 x 8160, max |got - oracle| / mean squared error:
+      default (bf16x6)  enhanced 4.458e-08 / 3.839e-17   bands 2.650e-08 / 5.220e-18
+      bf16x3            enhanced 2.631e-07 / 1.954e-15   bands 1.137e-07 / 4.829e-16   (6 x / 51 x and 4 x / 93 x the default's)
+    The bar on the x3 forward is 4 x its measured distance (input-dependent rounding over 30-odd chained layers): ~1e-6, four orders
+    of magnitude under the 2e-2 .. 5e-2 of the whole-step tests that were its only check; and mse < 1e-8, the figure VERDICT.md quotes for
+    the bf16 plan's generator output against the north-star bar of 1e-5."""
+    from vibravox_amd import gen_engine, ops
+
+    gen, osd = build_generator(golden, 2)
+    x = O.cut_to_valid_length(formula_audio("g_in", 2, 8192))
+    with torch.no_grad():
+        o_enh, o_bands = O.generator_forward({k: v.double() for k, v in osd.items()}, x.double(), 2)
+        assert o_enh.dtype == torch.float64 and o_bands.dtype == torch.float64
+        before = (gen_engine.conv_forward_math(), gen_engine.ru_forward_math())
+        assert before == (ops.MATH_BF16X6, ops.MATH_BF16X6)
+        enh6, bands6 = gen(x.to(DEV))
+        with gen_engine.forward_math("bf16x3"):
+            assert gen_engine.conv_forward_math() == ops.MATH_BF16X3 and gen_engine.ru_forward_math() == ops.MATH_BF16X3
+            enh3, bands3 = gen(x.to(DEV))
+            torch.cuda.synchronize()
+        assert (gen_engine.conv_forward_math(), gen_engine.ru_forward_math()) == before
+
+    def figures(got, ref):
+        return max_abs(got, ref), float(((got.detach().cpu().double() - ref) ** 2).mean())
+
+    got = {"x6": {"enhanced": figures(enh6, o_enh), "bands": figures(bands6, o_bands)},
+           "x3": {"enhanced": figures(enh3, o_enh), "bands": figures(bands3, o_bands)}}
+    for m, outs in got.items():
+        for k, (ma, mse) in outs.items():
+            print(f"[gen {m}] {k}: max_abs {ma:.3e} mse {mse:.3e}")
+    assert not torch.equal(enh3, enh6)   # the block did change the arithmetic
+    for k, (ma, mse) in got["x3"].items():
+        assert ma < 4 * X3_MEASURED[k][0] and mse < 4 * X3_MEASURED[k][1], (k, ma, mse)
+        assert mse < 1e-8, (k, mse)
+        assert got["x6"][k][0] < 2e-5 and got["x6"][k][1] < 1e-10, (k, got["x6"][k])   # the default forward's own bars
+
+
 def test_generator_config1_forward(hip, golden):
     """BASELINE config 1: generator-only forward, batch 4 x 16000 -> 15840."""
     gen, _ = build_generator(golden, 2)

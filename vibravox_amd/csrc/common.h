@@ -224,6 +224,8 @@ int tap3_launch(const Canon& c, int dir, const TapIO& io, int reflect, hipStream
 // the generator's strided / transposed / latent convs with the MFMA B operand loaded straight from the fp32 rows (gen_conv.hip): forward
 // launches only (kernel generation 5 of eben_conv1d_kernel_generation)
 int gc_applicable(const Canon& c, int dir);
+// gc_kernel<FORM, RT, CT, NP> of the launch, read off the plan gc_launch dispatches on (eben_conv1d_variant); returns gc_applicable
+int gc_variant(const Canon& c, int dir, int* form, int* rt, int* ct, int* np);
 size_t gc_packed_floats(const Canon& c, int dir);
 int gc_pack(const Canon& c, int dir, const float* w, const float* scale, float* wp, hipStream_t st);
 int gc_launch(const Canon& c, int dir, const TapIO& io, hipStream_t st);

@@ -567,6 +567,14 @@ int gc_applicable(const Canon& c, int dir) {
   return p.ok;
 }
 
+int gc_variant(const Canon& c, int dir, int* form, int* rt, int* ct, int* np) {
+  GcPlan p;
+  gc_plan(c, dir, &p);
+  if (!p.ok) return 0;
+  *form = p.form; *rt = p.RT; *ct = p.CT; *np = p.np;   // the fields gc_launch / gc_launch_shape pick the instantiation by
+  return 1;
+}
+
 size_t gc_packed_floats(const Canon& c, int dir) {
   GcPlan p;
   gc_plan(c, dir, &p);

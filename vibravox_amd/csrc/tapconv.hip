@@ -668,6 +668,10 @@ extern "C" int eben_conv1d_variant(const EbenConv1dDesc* d, int which, int mask_
   if (rc) return rc;
   for (int i = 0; i < 8; ++i) out[i] = 0;
   out[0] = eben_conv1d_kernel_generation(d, which);
+  if (out[0] == 5) {   // gc_kernel<FORM, RT, CT, NP>: forwards only (generation 5 is never reported for which = 1)
+    if (gc_variant(c, d->transposed ? 1 : 0, &out[1], &out[2], &out[3], &out[4])) out[7] = EBEN_VARIANT_GC;
+    return EBEN_OK;
+  }
   if (out[0] != 4 && out[0] != 6) return EBEN_OK;
   // the launch as the entry points build it: the forward's reflect padding is the kernel's; input gradients fold it in a pass of their own
   const int dir = d->transposed ? 1 - which : which;
