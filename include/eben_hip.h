@@ -127,18 +127,25 @@ typedef struct EbenPackJob {
   float* wp_fwd; float* wp_bwd;
 } EbenPackJob;
 EBEN_API int eben_conv1d_pack_multi(const EbenPackJob* jobs, int n, void* stream);
-/* which tap-conv kernel generation serves the forward (which=0) / input-gradient (which=1) pass of
- * this layer: 1 = tapconv.hip (16x16x4 tiles, any shape), 2 = tapconv2.hip (32x32x2 tiles, LDS-DMA
- * weight stream; deep reductions), 3 = thinconv.hip (VALU), 4 = tapconv3.hip (bf16 operands), 5 = gen_conv.hip (forward only: the
- * generator's strided / transposed / latent convs under EBEN_MATH_BF16X6, eben_generator.py:241-312), 6 = bigtap.hip (bundle layout only: the
- * long reductions of melgan_discriminator.py:119-145 / eben_discriminator.py:118-140 as persistent whole-panel blocks).  The packed layouts differ;
- * pack / fwd / bwd_dx agree by construction. */
+/* The kernel family that serves the forward (which = 0) / input-gradient (which = 1) pass of this layer, asked of the host without
+ * launching anything (the dispatch's own decision, which eben_conv1d_packed_floats, eben_conv1d_pack and every launch read too):
+ * returns EBEN_CONV_ROUTE_*.  The packed layouts differ between routes; pack / fwd / bwd_dx agree by construction. */
+#define EBEN_CONV_ROUTE_NONE 0   /* invalid descriptor, or a bundle-layout layer the bf16 tap-conv does not cover */
+#define EBEN_CONV_ROUTE_TAP1 1   /* tapconv.hip: fp32 16x16x4 tiles, any shape */
+#define EBEN_CONV_ROUTE_TAP2 2   /* tapconv2.hip: fp32 32x32x2 tiles, LDS-DMA weight stream; deep reductions */
+#define EBEN_CONV_ROUTE_THIN 3   /* thinconv.hip: VALU, a handful of output channels per group */
+#define EBEN_CONV_ROUTE_TAP3 4   /* tapconv3.hip: bf16 operands */
+#define EBEN_CONV_ROUTE_GC 5     /* gen_conv.hip: forward only -- the generator's strided / transposed / latent convs under EBEN_MATH_BF16X6 /
+                                    EBEN_MATH_BF16X3 (eben_generator.py:241-312) */
+#define EBEN_CONV_ROUTE_TAP4 6   /* bigtap.hip: bundle layout only -- the long reductions of melgan_discriminator.py:119-145 /
+                                    eben_discriminator.py:118-140 as persistent whole-panel blocks; TAP3's image and entry functions */
 EBEN_API int eben_conv1d_kernel_generation(const EbenConv1dDesc* d, int which);
-/* The kernel a launch of generation 4 / 6 runs, asked of the host without launching anything (the dispatch's own decision, for tests).
+/* The kernel a launch on EBEN_CONV_ROUTE_TAP3 / _TAP4 / _GC runs, asked of the host without launching anything (the dispatch's own
+ * decision, for tests).
  * which 0: eben_conv1d_fwd / eben_bl_conv1d_fwd; 1: the input gradient -- eben_conv1d_bwd_dx with mask_on_load = 1 (the fused output
  * activation differentiated as the gradient is staged: out_slope != 1), eben_conv1d_bwd_dx_ex / eben_bl_conv1d_bwd_dx with 0.
- * out[0..7] (n >= 8) = generation, then for generations 4 / 6: FM, XRB, IM, NPW, NPX, BL (tap3_kernel's template arguments; XRB = 0
- * off tap3_kernel), EBEN_VARIANT_*; for generation 5 (which = 0): FORM, RT, CT, NP (gc_kernel's template arguments, read off the plan
+ * out[0..7] (n >= 8) = EBEN_CONV_ROUTE_*, then on TAP3 / TAP4: FM, XRB, IM, NPW, NPX, BL (tap3_kernel's template arguments; XRB = 0
+ * off tap3_kernel), EBEN_VARIANT_*; on GC (which = 0): FORM, RT, CT, NP (gc_kernel's template arguments, read off the plan
  * the launch dispatches on), 0, 0, EBEN_VARIANT_GC; zeros past out[0] otherwise.  EBEN_EUNSUPPORTED where the launch itself would refuse. */
 #define EBEN_VARIANT_TAP3 1      /* tap3_kernel (tapconv3.hip) */
 #define EBEN_VARIANT_THIN_BL 2   /* thin_bl_kernel (thin_bl.hip) */
@@ -180,7 +187,7 @@ EBEN_API int eben_conv1d_bwd_dx_ex(const EbenConv1dDesc* d, const float* g, cons
  *   dx[b] = ( conv^T(g[b]) + (b < fm_rows ? fm_gs * (sgn(mask[b] - ref[b]) / s2 - s1 * sgn(mask[b]) / s2^2) : 0) )
  *           * lrelu'(mask[map(b)], mask_slope),      (s1, s2) = fm_sums[0..1] (device memory, written by eben_fm_sums)
  * ref = the reference rows of the embedding whose enhanced rows are mask rows 0 .. fm_rows-1.  Only the thin and the bf16 tap-conv
- * kernels (eben_conv1d_kernel_generation(d, 1) == 3 or 4) carry this epilogue; EBEN_EUNSUPPORTED otherwise. */
+ * kernels (eben_conv1d_kernel_generation(d, 1) == EBEN_CONV_ROUTE_THIN or _TAP3) carry this epilogue; EBEN_EUNSUPPORTED otherwise. */
 EBEN_API int eben_conv1d_bwd_dx_fm(const EbenConv1dDesc* d, const float* g, const float* wp_bwd, const float* ref, int fm_rows,
                           const float* fm_sums, float fm_gs, const float* mask, float mask_slope, int seg, const int* seg_map,
                           float* dx, void* stream);
@@ -224,7 +231,7 @@ EBEN_API int eben_bl_conv1d_bwd_dx(const EbenConv1dDesc* d, const void* g_hi, co
                           float fm_gs, void* dx_hi, void* dx_lo /* nullable */, void* stream);
 
 /* "Phases as rows": the input gradient of a strided bundle-layout Conv1d (stride 4..8 at dilation 1; stride 2 up to dilation 2) as ONE
- * stride-1 Conv1d from the Cout channels of dy to stride x Cin rows, stored depth-to-space (csrc/tapconv.hip; MelGAN layers 1-4,
+ * stride-1 Conv1d from the Cout channels of dy to stride x Cin rows, stored depth-to-space (csrc/conv1d.hip; MelGAN layers 1-4,
  * vibravox/torch_modules/dnn/melgan_discriminator.py:97-130, and the stride-2 layers of the PQMF-band discriminators,
  * eben_discriminator.py:86-130).  Rows are (phase, channel) or, at strides 4 and 2, (channel bundle, phase, channel in bundle): a 32-row
  * MFMA tile is then whole 16-byte units at consecutive positions, and mask, feature-matching operands and results move 32 contiguous

@@ -121,7 +121,7 @@ def variant(lib, case):
 def gc_tuple(lib, name, case):
     rc, v = variant(lib, case)
     assert rc == 0, (name, lib.eben_last_error())
-    assert v[0] == 5 and v[7] == GC and v[5:7] == (0, 0), (name, v)
+    assert v[0] == ops.CONV_ROUTE_GC and v[7] == GC and v[5:7] == (0, 0), (name, v)
     return v[1:5]
 
 
@@ -129,7 +129,7 @@ def gc_tuple(lib, name, case):
 def test_case_runs_its_gc_instantiation(lib, name):
     case = CASES[name]
     d = case.desc()
-    assert lib.eben_conv1d_kernel_generation(ctypes.byref(d), 0) == 5, name
+    assert lib.eben_conv1d_kernel_generation(ctypes.byref(d), 0) == ops.CONV_ROUTE_GC, name
     got = gc_tuple(lib, name, case)
     assert got == case.expect, f"{name}: runs gc_kernel{got}, the case is written for {case.expect}"
     assert got[3] == (3 if case.math == X6 else 2), name
@@ -171,4 +171,4 @@ def test_variant_query_reports_nothing_for_input_gradients_of_these_layers(lib):
     out = (ctypes.c_int * 8)()
     d = case.desc()
     assert lib.eben_conv1d_variant(ctypes.byref(d), 1, 0, out, 8) == 0
-    assert out[0] != 5 and out[7] != GC
+    assert out[0] != ops.CONV_ROUTE_GC and out[7] != GC

@@ -11,6 +11,7 @@ import torch
 
 from formula import formula_tensor
 from oracle import eben_oracle as O
+from vibravox_amd.ops import CONV_ROUTE_GC, CONV_ROUTE_TAP1, CONV_ROUTE_TAP2, CONV_ROUTE_TAP3, CONV_ROUTE_THIN, CONV_ROUTES_WITH_FM_EPILOGUE
 
 ROOT = __import__("os").path.dirname(__import__("os").path.dirname(__import__("os").path.abspath(__file__)))
 
@@ -115,29 +116,29 @@ def test_kernel_generations_cover_the_eben_layers(hip):
         spec = ops.ConvSpec(**kw)
         return lib.eben_conv1d_kernel_generation(ctypes.byref(ops.conv_desc(spec, batch, length)), which)
 
-    assert gen("melgan_l3_like_chunked", 0) == 2 and gen("melgan_l3_like_chunked", 1) == 2
-    assert gen("pqmf_l6_like_96rows", 0) == 2
-    assert gen("thin_pqmf_l0", 0) == 3 and gen("thin_pqmf_l1", 1) == 3 and gen("thin_melgan_l1", 1) == 3
-    assert gen("logits_m1", 0) == 1 and gen("stft_like", 0) == 1
+    assert gen("melgan_l3_like_chunked", 0) == CONV_ROUTE_TAP2 and gen("melgan_l3_like_chunked", 1) == CONV_ROUTE_TAP2
+    assert gen("pqmf_l6_like_96rows", 0) == CONV_ROUTE_TAP2
+    assert gen("thin_pqmf_l0", 0) == CONV_ROUTE_THIN and gen("thin_pqmf_l1", 1) == CONV_ROUTE_THIN and gen("thin_melgan_l1", 1) == CONV_ROUTE_THIN
+    assert gen("logits_m1", 0) == CONV_ROUTE_TAP1 and gen("stft_like", 0) == CONV_ROUTE_TAP1
     seen = {gen(n, w) for n in CONV_CASES for w in (0, 1)}
-    assert seen == {1, 2, 3}
+    assert seen == {CONV_ROUTE_TAP1, CONV_ROUTE_TAP2, CONV_ROUTE_THIN}
 
 
 BF16_CASES = {
-    # name: (ConvSpec kwargs, length, (generation of the forward, of the input gradient) at math = bf16)
-    "melgan_l3_like_chunked": (CONV_CASES["melgan_l3_like_chunked"][0], 700, (4, 4)),
-    "pqmf_disc_wide": (CONV_CASES["pqmf_disc_wide"][0], 260, (4, 4)),
-    "dense_k5_chunks": (CONV_CASES["dense_k5_chunks"][0], 300, (4, 4)),
-    "pqmf_l6_like_96rows": (CONV_CASES["pqmf_l6_like_96rows"][0], 140, (4, 4)),
-    "melgan_l2_like": (CONV_CASES["melgan_l2_like"][0], 1100, (4, 4)),   # 16 rows per group on the gradient side: half-filled 32-row tiles
-    "melgan_l1_like": (CONV_CASES["melgan_l1_like"][0], 1500, (4, 4)),   # 4 channels / 4 rows per group: block-diagonal over the groups
-    "pqmf_l1_like_6ch": (CONV_CASES["thin_pqmf_l1"][0], 999, (4, 4)),     # 6 channels per group: the four groups as one block-diagonal contraction
+    # name: (ConvSpec kwargs, length, (CONV_ROUTE_* of the forward, of the input gradient) at math = bf16)
+    "melgan_l3_like_chunked": (CONV_CASES["melgan_l3_like_chunked"][0], 700, (CONV_ROUTE_TAP3, CONV_ROUTE_TAP3)),
+    "pqmf_disc_wide": (CONV_CASES["pqmf_disc_wide"][0], 260, (CONV_ROUTE_TAP3, CONV_ROUTE_TAP3)),
+    "dense_k5_chunks": (CONV_CASES["dense_k5_chunks"][0], 300, (CONV_ROUTE_TAP3, CONV_ROUTE_TAP3)),
+    "pqmf_l6_like_96rows": (CONV_CASES["pqmf_l6_like_96rows"][0], 140, (CONV_ROUTE_TAP3, CONV_ROUTE_TAP3)),
+    "melgan_l2_like": (CONV_CASES["melgan_l2_like"][0], 1100, (CONV_ROUTE_TAP3, CONV_ROUTE_TAP3)),   # 16 rows per group on the gradient side: half-filled 32-row tiles
+    "melgan_l1_like": (CONV_CASES["melgan_l1_like"][0], 1500, (CONV_ROUTE_TAP3, CONV_ROUTE_TAP3)),   # 4 channels / 4 rows per group: block-diagonal over the groups
+    "pqmf_l1_like_6ch": (CONV_CASES["thin_pqmf_l1"][0], 999, (CONV_ROUTE_TAP3, CONV_ROUTE_TAP3)),     # 6 channels per group: the four groups as one block-diagonal contraction
     "melgan_l0_k15": (CONV_CASES["melgan_l0_k15"][0], 2014, (None, None)),   # one input channel: direct kernel, bf16 weight gradient
-    "pqmf_mid_24ch": (dict(c_in=96, c_out=192, ksize=7, stride=2, dilation=3, pad_l=3, pad_r=3, groups=4, out_slope=0.2), 1001, (4, 4)),
+    "pqmf_mid_24ch": (dict(c_in=96, c_out=192, ksize=7, stride=2, dilation=3, pad_l=3, pad_r=3, groups=4, out_slope=0.2), 1001, (CONV_ROUTE_TAP3, CONV_ROUTE_TAP3)),
     "pqmf_low_12ch": (dict(c_in=48, c_out=96, ksize=7, stride=2, dilation=1, pad_l=3, pad_r=3, groups=4, out_slope=0.2), 2003, (None, None)),
-    "ru32_dilated": (dict(c_in=32, c_out=32, ksize=3, dilation=9, pad_l=9, pad_r=9, out_slope=0.01), 900, (4, 4)),   # reduction of 96: 1.5 weight chunks
-    "ru64_pointwise": (dict(c_in=64, c_out=64, ksize=1, out_slope=0.01), 517, (4, 4)),                                # reduction of 64: one chunk
-    "melgan_l4_like": (dict(c_in=512, c_out=512, ksize=41, stride=4, pad_l=20, pad_r=20, groups=4, out_slope=0.2), 500, (4, 4)),
+    "ru32_dilated": (dict(c_in=32, c_out=32, ksize=3, dilation=9, pad_l=9, pad_r=9, out_slope=0.01), 900, (CONV_ROUTE_TAP3, CONV_ROUTE_TAP3)),   # reduction of 96: 1.5 weight chunks
+    "ru64_pointwise": (dict(c_in=64, c_out=64, ksize=1, out_slope=0.01), 517, (CONV_ROUTE_TAP3, CONV_ROUTE_TAP3)),                                # reduction of 64: one chunk
+    "melgan_l4_like": (dict(c_in=512, c_out=512, ksize=41, stride=4, pad_l=20, pad_r=20, groups=4, out_slope=0.2), 500, (CONV_ROUTE_TAP3, CONV_ROUTE_TAP3)),
 }
 
 
@@ -173,7 +174,7 @@ def test_bf16_math_forward_and_batched_input_gradient(hip, name):
     d = ops.conv_desc(spec, 2 * S, length, ops.MATH_BF16)
     fgen = lib.eben_conv1d_kernel_generation(ctypes.byref(d), 0)
     assert gens[0] is None or fgen == gens[0]
-    rnd = _bf16 if fgen == 4 else (lambda t: t.double())
+    rnd = _bf16 if fgen == CONV_ROUTE_TAP3 else (lambda t: t.double())
     ref = torch.nn.functional.leaky_relu(O.conv_layer(rnd(x), rnd(w), None, bias.double(), **okw), spec.out_slope)
     wp = torch.empty(lib.eben_conv1d_packed_floats(ctypes.byref(d), 0), dtype=torch.float32, device=dev)
     check(lib.eben_conv1d_pack(ctypes.byref(d), ptr(wd), None, ptr(wp), None, stream()), "pack")
@@ -183,7 +184,7 @@ def test_bf16_math_forward_and_batched_input_gradient(hip, name):
     assert rel_err(y, ref) < 3e-5
     # ... and the rounding itself costs what bf16 should cost (2^-9 per operand, averaged over the reduction)
     exact = torch.nn.functional.leaky_relu(O.conv_layer(x.double(), w.double(), None, bias.double(), **okw), spec.out_slope)
-    assert (1e-4 if fgen == 4 else 0.0) < rel_err(y, exact) < 1e-2
+    assert (1e-4 if fgen == CONV_ROUTE_TAP3 else 0.0) < rel_err(y, exact) < 1e-2
 
     # batched input gradient of the linear conv: dx[b] = (conv^T(bf16(g[b]); bf16(w)) + res[b < S]) * lrelu'(act[map(b)])
     lin = dataclasses.replace(spec, in_slope=1.0, out_slope=1.0)
@@ -194,7 +195,7 @@ def test_bf16_math_forward_and_batched_input_gradient(hip, name):
     g = formula_tensor(f"bf/{name}/g", (4 * S, spec.c_out, l_out))
     act = formula_tensor(f"bf/{name}/act", (2 * S, spec.c_in, length))
     res = formula_tensor(f"bf/{name}/res", (S, spec.c_in, length))
-    rounded = got_gen == 4
+    rounded = got_gen == CONV_ROUTE_TAP3
     xr = torch.zeros(4 * S, spec.c_in, length, dtype=torch.float64, requires_grad=True)
     (O.conv_layer(xr, _bf16(w) if rounded else w.double(), None, None, **okw) * (_bf16(g) if rounded else g.double())).sum().backward()
     ref = xr.grad.clone()
@@ -239,7 +240,7 @@ def test_bf16_math_forward_and_batched_input_gradient(hip, name):
         yb = formula_tensor(f"bf/{name}/yb", (nb, spec.c_out, l_out))
         masked = gb.double() * torch.where(yb.double() > 0, 1.0, spec.out_slope)
         gens_m = (lib.eben_conv1d_kernel_generation(ctypes.byref(d), 1), )
-        rnd = _bf16 if gens_m[0] == 4 else (lambda t: t.double())
+        rnd = _bf16 if gens_m[0] == CONV_ROUTE_TAP3 else (lambda t: t.double())
         xr = torch.zeros(nb, spec.c_in, length, dtype=torch.float64, requires_grad=True)
         (O.conv_layer(xr, rnd(w), None, None, **okw) * rnd(masked)).sum().backward()
         wp = torch.empty(lib.eben_conv1d_packed_floats(ctypes.byref(d), 1), dtype=torch.float32, device=dev)
@@ -305,7 +306,7 @@ def test_generator_direct_operand_convs(hip, name):
         exact = exact + torch.nn.functional.leaky_relu(res.double(), 0.3)
     dev = torch.device("cuda")
     d = ops.conv_desc(spec, batch, length, ops.MATH_BF16X6)
-    assert lib.eben_conv1d_kernel_generation(ctypes.byref(d), 0) == 5
+    assert lib.eben_conv1d_kernel_generation(ctypes.byref(d), 0) == CONV_ROUTE_GC
     vd, gd, xd = v.to(dev), g.to(dev), x.to(dev)
     scale = torch.empty(wshape[0], dtype=torch.float32, device=dev)
     norm = torch.empty_like(scale)
@@ -363,7 +364,7 @@ def test_split_bf16_math_forward_and_batched_input_gradient(hip, name, math_name
 
     exact = torch.nn.functional.leaky_relu(O.conv_layer(x.double(), w.double(), None, bias.double(), **okw), spec.out_slope)
     y, gen = forward(mm)
-    assert gen in (4, 5)   # 5: the dense stride-1 k = 5 case is a latent-conv shape (gen_conv.hip takes it on two or three pieces per operand)
+    assert gen in (CONV_ROUTE_TAP3, CONV_ROUTE_GC)   # GC: the dense stride-1 k = 5 case is a latent-conv shape (gen_conv.hip takes it on two or three pieces per operand)
     assert rel_err(y, exact) < tol
     if mm == ops.MATH_BF16X6:
         y32, _ = forward(ops.MATH_F32)
@@ -393,7 +394,7 @@ def test_split_bf16_math_forward_and_batched_input_gradient(hip, name, math_name
         return dx, gen
 
     dx, gen = input_gradient(mm)
-    assert gen == 4
+    assert gen == CONV_ROUTE_TAP3
     assert rel_err(dx, ref) < tol
     if mm == ops.MATH_BF16X6:
         dx32, _ = input_gradient(ops.MATH_F32)
@@ -758,7 +759,7 @@ def test_bf16x2_math_keeps_the_activation_operand(hip, name):
     wd, bd, xd = w.to(dev), bias.to(dev), x.to(dev)
     d = ops.conv_desc(spec, 4, length, ops.MATH_BF16X2)
     fgen = lib.eben_conv1d_kernel_generation(ctypes.byref(d), 0)
-    rw = _bf16 if fgen == 4 else (lambda t: t.double())
+    rw = _bf16 if fgen == CONV_ROUTE_TAP3 else (lambda t: t.double())
     xin = torch.nn.functional.leaky_relu(x.double(), spec.in_slope)
     ref = torch.nn.functional.leaky_relu(O.conv_layer(xin, rw(w), None, bias.double(), **{**okw}), spec.out_slope) if spec.in_slope == 1.0 else None
     wp = torch.empty(lib.eben_conv1d_packed_floats(ctypes.byref(d), 0), dtype=torch.float32, device=dev)
@@ -771,7 +772,7 @@ def test_bf16x2_math_keeps_the_activation_operand(hip, name):
         # the item-dependent part of the output (differences between items) survives: single bf16 loses it
         diff, rdiff = (y[1] - y[0]).double().cpu(), ref[1] - ref[0]
         assert float((diff - rdiff).norm() / rdiff.norm()) < 2e-3
-        if fgen == 4:
+        if fgen == CONV_ROUTE_TAP3:
             d1 = ops.conv_desc(spec, 4, length, ops.MATH_BF16)
             wp1 = torch.empty(lib.eben_conv1d_packed_floats(ctypes.byref(d1), 0), dtype=torch.float32, device=dev)
             check(lib.eben_conv1d_pack(ctypes.byref(d1), ptr(wd), None, ptr(wp1), None, stream()), "pack")
@@ -892,7 +893,7 @@ def test_batched_input_gradient_with_feature_matching_epilogue(hip, name, mathmo
     check(lib.eben_conv1d_bwd_dx_ex(ctypes.byref(d), ptr(gd), ptr(wp), ptr(da), S, ptr(ad), 0.2, S, seg_map, ptr(two), stream()), "bwd_dx_ex")
     one_pass = torch.empty_like(two)
     rc = lib.eben_conv1d_bwd_dx_fm(ctypes.byref(d), ptr(gd), ptr(wp), ptr(b), S, ptr(sums), gs, ptr(ad), 0.2, S, seg_map, ptr(one_pass), stream())
-    if gen not in (3, 4):
+    if gen not in CONV_ROUTES_WITH_FM_EPILOGUE:
         assert rc == -3   # EBEN_EUNSUPPORTED
         return
     check(rc, "bwd_dx_fm")

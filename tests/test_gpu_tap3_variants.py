@@ -20,6 +20,7 @@ import torch.nn.functional as F
 
 from formula import formula_tensor
 from tests.test_tap3_variants import BF16, BF16X2, BF16X3, BF16X6, BL, CASES, DW_CASES, DX, FWD, TAP3, dw_variant, variant
+from vibravox_amd.ops import CONV_ROUTE_TAP3
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
@@ -59,7 +60,7 @@ def conv(x, w, spec, bias=None):
 def assert_variant(lib, name, case):
     rc, v = variant(lib, case)
     assert rc == 0, (name, lib.eben_last_error())
-    assert v[0] == 4 and v[7] == TAP3, (name, v)
+    assert v[0] == CONV_ROUTE_TAP3 and v[7] == TAP3, (name, v)
     assert v[1:7] == case.expect, f"{name}: runs tap3_kernel{v[1:7]}, the case is written for {case.expect}"
     return v[1:7]
 

@@ -13,6 +13,7 @@ import torch
 
 from formula import formula_tensor
 from oracle import eben_oracle as O
+from vibravox_amd.ops import CONV_ROUTE_GC, CONV_ROUTE_TAP1, CONV_ROUTE_TAP2, CONV_ROUTE_TAP3, CONV_ROUTE_TAP4, CONV_ROUTE_THIN
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -96,30 +97,63 @@ def test_kernel_family_selection_without_gpu(lib):
         return lib.eben_conv1d_kernel_generation(ctypes.byref(desc), which)
 
     melgan_l4 = EbenConv1dDesc(64, 1024, 1024, 500, 125, 41, 4, 1, 4, 20, 20, 0, 0, 1.0, 0.2)
-    assert gen(melgan_l4, 0) == 2 and gen(melgan_l4, 1) == 2            # second-generation MFMA kernel
+    assert gen(melgan_l4, 0) == CONV_ROUTE_TAP2 and gen(melgan_l4, 1) == CONV_ROUTE_TAP2            # second-generation MFMA kernel
     pqmf_l1 = EbenConv1dDesc(64, 24, 48, 8000, 4000, 7, 2, 1, 4, 3, 3, 0, 0, 1.0, 0.2)
-    assert gen(pqmf_l1, 0) == 3 and gen(pqmf_l1, 1) == 3                # direct kernel: 12 / 6 rows per group
+    assert gen(pqmf_l1, 0) == CONV_ROUTE_THIN and gen(pqmf_l1, 1) == CONV_ROUTE_THIN                # direct kernel: 12 / 6 rows per group
     logits = EbenConv1dDesc(64, 1024, 1, 125, 125, 3, 1, 1, 1, 1, 1, 0, 0, 1.0, 1.0)
-    assert gen(logits, 0) == 1                                           # single-output-channel reduction
+    assert gen(logits, 0) == CONV_ROUTE_TAP1                                           # single-output-channel reduction
     ru = EbenConv1dDesc(32, 64, 64, 4000, 4000, 3, 1, 9, 1, 9, 9, 1, 0, 0.01, 1.0)
-    assert gen(ru, 0) == 2 and gen(ru, 1) == 2
-    # the generator's strided / transposed / latent convs under the forward's fp32-grade math: their own kernel (gen_conv.hip, 5) for the
+    assert gen(ru, 0) == CONV_ROUTE_TAP2 and gen(ru, 1) == CONV_ROUTE_TAP2
+    # the generator's strided / transposed / latent convs under the forward's fp32-grade math: their own kernel (gen_conv.hip, CONV_ROUTE_GC) for the
     # forward, the general tap-conv for the input gradient; the image is sized by the same plan
     X6 = 4
     enc3 = EbenConv1dDesc(32, 128, 256, 999, 125, 16, 8, 1, 1, 7, 7, 1, 0, 1.0, 1.0, X6)
     dec2 = EbenConv1dDesc(32, 128, 64, 999, 3996, 8, 4, 1, 1, 2, 0, 0, 1, 1.0, 0.01, X6)
     lat1 = EbenConv1dDesc(32, 256, 64, 125, 125, 7, 1, 1, 1, 3, 3, 1, 0, 0.01, 0.01, X6)
     for dsc in (enc3, dec2, lat1):
-        assert gen(dsc, 0) == 5 and gen(dsc, 1) != 5
+        assert gen(dsc, 0) == CONV_ROUTE_GC and gen(dsc, 1) != CONV_ROUTE_GC
     # [half][32-row tile][k-step, padded to 8][piece][lane] of 16-byte units
     assert lib.eben_conv1d_packed_floats(ctypes.byref(enc3), 0) == 1 * 8 * 128 * 3 * 64 * 4
     assert lib.eben_conv1d_packed_floats(ctypes.byref(dec2), 0) == 2 * 4 * 16 * 3 * 64 * 4
     grouped = EbenConv1dDesc(32, 128, 256, 999, 125, 16, 8, 1, 4, 7, 7, 1, 0, 1.0, 1.0, X6)
-    assert gen(grouped, 0) != 5                                          # groups stay with the tap-conv
+    assert gen(grouped, 0) != CONV_ROUTE_GC                                          # groups stay with the tap-conv
     nslab, rs = ctypes.c_int(0), ctypes.c_int(0)
     assert lib.eben_conv1d_bwd_dw_workspace(ctypes.byref(melgan_l4), ctypes.byref(nslab), ctypes.byref(rs)) > 4 * 1024 * (256 * 41 + 1)
     assert rs.value == 256 * 41 + 1
     assert lib.eben_stft_loss_sums_workspace(32) == 4 * 3 * 32 * 32
+
+
+def test_conv_routes_named_and_consistent_without_gpu(lib):
+    """The one route decision of csrc/conv1d.hip as its three host queries report it, over the case tables of the GPU suites (fp32
+    layers, bf16 layers in both layouts, every tap3 / gen_conv instantiation): every EBEN_CONV_ROUTE_* is reached, eben_conv1d_variant
+    and eben_conv1d_kernel_generation name the same route, the forward-only family is never an input gradient's, and a routed pass has
+    an image size."""
+    from tests import test_gen_conv_variants, test_gpu_ops, test_tap3_variants
+    from vibravox_amd import ops
+
+    descs = {}
+    for name, (kw, batch, length, _, _) in test_gpu_ops.CONV_CASES.items():
+        descs[f"conv/{name}"] = ops.conv_desc(ops.ConvSpec(**kw), batch, length)
+    for name, (kw, length, _) in test_gpu_ops.BF16_CASES.items():
+        descs[f"bf16/{name}"] = ops.conv_desc(ops.ConvSpec(**kw), 4, length, ops.MATH_BF16)
+        descs[f"bf16_bl/{name}"] = ops.conv_desc(ops.ConvSpec(**kw), 4, length, ops.MATH_BF16 | test_tap3_variants.BL)
+    for mod in (test_tap3_variants, test_gen_conv_variants):
+        for name, case in mod.CASES.items():
+            descs[f"{mod.__name__}/{name}"] = case.desc()
+    assert len(descs) > 150
+
+    seen = set()
+    out = (ctypes.c_int * 8)()
+    for name, d in descs.items():
+        for which in (0, 1):
+            route = lib.eben_conv1d_kernel_generation(ctypes.byref(d), which)
+            assert lib.eben_conv1d_variant(ctypes.byref(d), which, 0, out, 8) == 0, (name, which, lib.eben_last_error())
+            assert out[0] == route, (name, which, out[0], route)
+            assert not (which == 1 and route == CONV_ROUTE_GC), name
+            if route != ops.CONV_ROUTE_NONE:
+                assert lib.eben_conv1d_packed_floats(ctypes.byref(d), which) > 0, (name, which, route)
+            seen.add(route)
+    assert seen >= {CONV_ROUTE_TAP1, CONV_ROUTE_TAP2, CONV_ROUTE_THIN, CONV_ROUTE_TAP3, CONV_ROUTE_GC, CONV_ROUTE_TAP4}, seen
 
 
 def test_discriminator_engine_layout():

@@ -222,7 +222,7 @@ def tap3_tuple(lib, case):
 def test_case_runs_its_tap3_instantiation(lib, name):
     case = CASES[name]
     gen, fm, xrb, im, npw, npx, bl, kernel = tap3_tuple(lib, case)
-    assert (gen, kernel) == (4, TAP3), (name, gen, kernel)
+    assert (gen, kernel) == (ops.CONV_ROUTE_TAP3, TAP3), (name, gen, kernel)
     assert (fm, xrb, im, npw, npx, bl) == case.expect, (name, (fm, xrb, im, npw, npx, bl))
     # the bundle-layout input gradient takes one gradient plane: two-piece bundle-layout cases are forwards
     assert not (case.layout == BL and case.math == BF16X3 and case.direction == DX), name
@@ -271,4 +271,4 @@ def test_variant_query_names_the_other_kernels(lib):
     assert tap3_tuple(lib, thin)[7] == THIN_BL
     big = C(dict(c_in=1536, c_out=1536, ksize=5, groups=4, pad_l=2, pad_r=2), 2, 131, BF16, BL, FWD, 0, ())
     v = tap3_tuple(lib, big)
-    assert (v[0], v[7]) == (6, TAP4)
+    assert (v[0], v[7]) == (ops.CONV_ROUTE_TAP4, TAP4)

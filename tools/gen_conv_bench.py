@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Stand-alone launches of the generator's eight non-residual convs (eben_generator.py:241-312) at BASELINE config-2 shapes (32 items),
 forward in EBEN_MATH_BF16X6 (what the training forward computes in): time per launch, the matrix / HBM roofs of the launch
-(six piece products per multiply-accumulate; fp32 tensors read and written once) and which kernel generation serves it.
+(six piece products per multiply-accumulate; fp32 tensors read and written once) and which route (ops.CONV_ROUTE_*) serves it.
 Usage: python tools/gen_conv_bench.py [--iters 20] [--only enc3]"""
 import argparse, ctypes, os, sys
 import torch
@@ -56,7 +56,7 @@ def main():
         flops = 2 * 6 * macs
         nbytes = 4 * (x.numel() + y.numel())
         gen = lib.eben_conv1d_kernel_generation(ctypes.byref(d), 0)
-        print(f"{name}  {us:7.1f} us   x6 MFMA {flops / 1e9:6.1f} GF = {flops / 2.5e15 * 1e6:5.1f} us at peak   {nbytes / 1e6:6.1f} MB = {nbytes / 8e12 * 1e6:5.1f} us at 8 TB/s   generation {gen}")
+        print(f"{name}  {us:7.1f} us   x6 MFMA {flops / 1e9:6.1f} GF = {flops / 2.5e15 * 1e6:5.1f} us at peak   {nbytes / 1e6:6.1f} MB = {nbytes / 8e12 * 1e6:5.1f} us at 8 TB/s   route {gen}")
         tot += us
     print(f"total {tot:7.1f} us")
 

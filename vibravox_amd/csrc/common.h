@@ -138,11 +138,12 @@ struct Canon {
 };
 int canon_from_desc(const EbenConv1dDesc* d, Canon* c);
 
-// operands / fused element-wise stages of one tap-conv launch (either kernel generation)
+// operands / fused element-wise stages of one tap-conv launch (any family)
 struct TapIO {
   const float* x; const float* xmask; int in_mode; float in_slope;
   const float* wp; const float* bias; const float* res; float res_slope;
   const float* emask; float emask_slope; float out_slope; float* y; int accumulate;
+  int conv1d_fwd;   // the launch is a Conv1d's (not a ConvTranspose1d's) forward: what tap1_launch's single-output-channel kernel serves
   // batched right-hand sides (eben_conv1d_bwd_dx_ex): the residual is added only for batch rows
   // b < res_rows (0 = all rows); the epilogue mask is read from batch row
   // em_map[b / em_seg] * em_seg + b % em_seg (em_seg = 0: row b)
@@ -207,6 +208,14 @@ int fir_bank_geom(int bands, int ntaps, int stride, int which, FirBankGeom* g);
 int fir_bank_launch(int which, const float* in, const float* w, float* out, int batch, int lx, int ly, int bands, int ntaps, int stride,
                     int off0, hipStream_t st);
 
+// The conv families of the forward / input-gradient side.  conv_route() in conv1d.hip is the one place that chooses among them (it
+// alone asks *_applicable for that) and kConvFamilies there is the one table of their {packed_floats, pack, launch}; dir 0: the
+// canonical conv (gather-strided), 1: its adjoint (phase-scatter).
+// first-generation tap-conv (tapconv.hip): 16x16x4 fp32 MFMA tiles, any shape -- the universal fallback, hence no tap1_applicable
+size_t tap1_packed_floats(const Canon& c, int dir);
+int tap1_pack(const Canon& c, int dir, const float* w, const float* scale, float* wp, hipStream_t st);
+int tap1_launch(const Canon& c, int dir, const TapIO& io, int reflect, hipStream_t st);
+
 // second-generation tap-conv (tapconv2.hip): 32x32x2 MFMA tiles, LDS-DMA weight stream
 int tap2_applicable(const Canon& c, int dir);
 size_t tap2_packed_floats(const Canon& c, int dir);
@@ -222,7 +231,7 @@ int tap3_pack_multi(const Canon* cs, const int* dirs, const float* const* ws, co
 int tap3_launch(const Canon& c, int dir, const TapIO& io, int reflect, hipStream_t st);
 
 // the generator's strided / transposed / latent convs with the MFMA B operand loaded straight from the fp32 rows (gen_conv.hip): forward
-// launches only (kernel generation 5 of eben_conv1d_kernel_generation)
+// launches only (EBEN_CONV_ROUTE_GC)
 int gc_applicable(const Canon& c, int dir);
 // gc_kernel<FORM, RT, CT, NP> of the launch, read off the plan gc_launch dispatches on (eben_conv1d_variant); returns gc_applicable
 int gc_variant(const Canon& c, int dir, int* form, int* rt, int* ct, int* np);
@@ -235,8 +244,11 @@ int thin_applicable(const Canon& c, int dir);
 size_t thin_packed_floats(const Canon& c, int dir);
 int thin_pack(const Canon& c, int dir, const float* w, const float* scale, float* wp, hipStream_t st);
 int thin_launch(const Canon& c, int dir, const TapIO& io, int reflect, hipStream_t st);
-// which kernel serves (layer, direction): 1 tapconv.hip, 2 tapconv2.hip, 3 thinconv.hip, 4 tapconv3.hip (bf16)
-int tap_generation(const Canon& c, int dir);
+
+// "phases as rows" (bl_dx_pr.hip): whether a strided bundle-layout Conv1d's input gradient has the form (ok), its geometry, and in
+// *primed the stride-1 layer whose FORWARD the launch is (eben_bl_conv1d_bwd_dx_pr in conv1d.hip)
+struct PrGeom { int ok, S, umin, kq, Lq, fold, cbg, order; };   // order 1: rows (channel bundle, phase, channel in bundle) -- tap4_kernel's coalesced depth-to-space epilogue
+PrGeom pr_geometry(const Canon& c, Canon* primed);
 
 // second-generation weight-gradient kernel (conv_dw2.hip): pre-transposed A image + LDS-DMA
 struct Dw2Args {

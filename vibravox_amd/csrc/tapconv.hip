@@ -23,7 +23,6 @@
 //   * LeakyReLU on load, bias / LeakyReLU / residual / activation-derivative mask in the epilogue;
 //   * blockIdx -> tile mapping is XCD-aware (tiles sharing a weight panel stay on one XCD's L2).
 #include "common.h"
-#include "tap3.h"
 
 #include <cstdlib>
 
@@ -315,41 +314,8 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, WAVES_M * WAVES_N == 8 ? 4 
 }
 
 // ---------------------------------------------------------------------------------------
-// host side: canonical conv, plans, launchers
+// host side: plan, weight packing, launchers
 // ---------------------------------------------------------------------------------------
-
-int canon_from_desc(const EbenConv1dDesc* d, Canon* c) {
-  EBEN_REQUIRE(d != nullptr, "null conv descriptor");
-  EBEN_REQUIRE(d->batch > 0 && d->c_in > 0 && d->c_out > 0 && d->l_in > 0 && d->l_out > 0, "non-positive conv dims");
-  EBEN_REQUIRE(d->ksize > 0 && d->stride > 0 && d->dilation > 0 && d->groups > 0, "non-positive conv params");
-  EBEN_REQUIRE(d->c_in % d->groups == 0 && d->c_out % d->groups == 0, "channels not divisible by groups");
-  EBEN_REQUIRE(d->stride <= 1024 && d->pad_l >= 0 && d->pad_r >= 0, "bad stride / padding");
-  c->B = d->batch; c->k = d->ksize; c->s = d->stride; c->d = d->dilation; c->g = d->groups;
-  c->pl = d->pad_l; c->pr = d->pad_r;
-  const int math = d->math & ~EBEN_LAYOUT_BL;
-  EBEN_REQUIRE(math >= EBEN_MATH_F32 && math <= EBEN_MATH_BF16X6, "unknown math mode %d", d->math);
-  c->bl = (d->math & EBEN_LAYOUT_BL) != 0;
-  EBEN_REQUIRE(!c->bl || math == EBEN_MATH_BF16 || math == EBEN_MATH_BF16X3, "the bundle layout carries EBEN_MATH_BF16 / EBEN_MATH_BF16X3 only");
-  c->bf16 = math != EBEN_MATH_F32;
-  c->np = math == EBEN_MATH_BF16X3 ? 2 : (math == EBEN_MATH_BF16X6 ? 3 : 1);
-  c->xsplit_dir = math == EBEN_MATH_BF16X2 ? (d->transposed ? 1 : 0) : -1;
-  if (!d->transposed) {
-    c->Cin = d->c_in; c->Cout = d->c_out; c->Lin = d->l_in; c->Lout = d->l_out;
-    c->reflect = d->pad_mode == EBEN_PAD_REFLECT;
-    const int expect = (d->l_in + d->pad_l + d->pad_r - d->dilation * (d->ksize - 1) - 1) / d->stride + 1;
-    EBEN_REQUIRE(expect == d->l_out, "Conv1d l_out %d does not match the expected %d", d->l_out, expect);
-    if (c->reflect) EBEN_REQUIRE(d->pad_l < d->l_in && d->pad_r < d->l_in, "reflect padding must be smaller than the input");
-  } else {
-    EBEN_REQUIRE(d->pad_mode == EBEN_PAD_ZERO, "ConvTranspose1d only supports zero padding");
-    c->Cin = d->c_out; c->Cout = d->c_in; c->Lin = d->l_out; c->Lout = d->l_in;
-    c->reflect = 0;
-    c->pr = d->pad_l;
-    // l_out = (l_in-1)*s - 2p + d(k-1) + output_padding + 1 with 0 <= output_padding < s
-    const int base = (d->l_in - 1) * d->stride - 2 * d->pad_l + d->dilation * (d->ksize - 1) + 1;
-    EBEN_REQUIRE(d->l_out >= base && d->l_out < base + d->stride, "ConvTranspose1d l_out %d outside [%d,%d)", d->l_out, base, base + d->stride);
-  }
-  return EBEN_OK;
-}
 
 static int gcd_i(int a, int b) { while (b) { int t = a % b; a = b; b = t; } return a; }
 
@@ -599,499 +565,30 @@ __global__ __launch_bounds__(1024) void conv_m1_fwd_kernel(const float* __restri
   }
 }
 
-// reflect-pad fold: dx[u] = D[u+pl] + D[pl-u] (1<=u<=pl) + D[pl+2(L-1)-u] (L-1-pr<=u<=L-2) (+ pre), then mask (+ post)
-__global__ __launch_bounds__(256) void fold_kernel(const float* __restrict__ D, const float* __restrict__ mask, float* __restrict__ dx,
-                                                   long long rows, int L, int pl, int pr, float slope, int accumulate,
-                                                   const float* __restrict__ pre, const float* __restrict__ post) {
-  const int Lp = L + pl + pr;
-  const long long total = rows * L;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-    const long long row = i / L;
-    const int u = (int)(i - row * L);
-    const float* d = D + row * Lp;
-    float v = d[u + pl];
-    if (u >= 1 && u <= pl) v += d[pl - u];
-    if (u >= L - 1 - pr && u <= L - 2) v += d[pl + 2 * (L - 1) - u];
-    if (pre) v += pre[i];
-    if (mask) v *= dlrelu(mask[i], slope);
-    if (post) v += post[i];
-    if (accumulate) v += dx[i];
-    dx[i] = v;
-  }
-}
-
-}  // namespace eben
-
-using namespace eben;
-
-namespace eben {
-int tap_generation(const Canon& c, int dir) {
-  static const int thin_first = getenv("EBEN_THIN_FIRST") ? atoi(getenv("EBEN_THIN_FIRST")) : 0;
-  if (c.bl) return tap3_applicable(c, dir) ? 4 : 0;  // bundle layout: the bf16 tap-conv or nothing (eben_bl_* report EBEN_EUNSUPPORTED)
-  if (c.bf16 && tap3_applicable(c, dir)) return 4;   // layers the bf16 kernel does not cover keep their fp32 kernel
-  const int t2 = tap2_applicable(c, dir), th = thin_applicable(c, dir);
-  if (th && (thin_first || !t2)) return 3;
-  if (t2) return 2;
-  return 1;
-}
-}  // namespace eben
-
-extern "C" size_t eben_conv1d_packed_floats(const EbenConv1dDesc* d, int which) {
-  Canon c;
-  if (canon_from_desc(d, &c) != EBEN_OK) return 0;
+// ---- the family's row of conv1d.hip's table (EBEN_CONV_ROUTE_TAP1) ------------------------------------------------------------
+size_t tap1_packed_floats(const Canon& c, int dir) {
   TapPlan p;
-  // which: 0 = the layer's forward, 1 = the layer's input gradient
-  const int dir = d->transposed ? 1 - which : which;
-  if (which == 0 && gc_applicable(c, dir)) return gc_packed_floats(c, dir);
-  const int gen = tap_generation(c, dir);
-  if (gen == 2) return tap2_packed_floats(c, dir);
-  if (gen == 3) return thin_packed_floats(c, dir);
-  if (gen == 4) return tap3_packed_floats(c, dir);
   make_plan(c, dir, &p);
   return p.packed_floats;
 }
 
-extern "C" int eben_conv1d_kernel_generation(const EbenConv1dDesc* d, int which) {
-  Canon c;
-  if (canon_from_desc(d, &c) != EBEN_OK) return 0;
-  if (which == 0 && gc_applicable(c, d->transposed ? 1 : 0)) return 5;
-  const int dir = d->transposed ? 1 - which : which;
-  const int gen = tap_generation(c, dir);
-  return gen == 4 && tap3_is_big(c, dir) ? 6 : gen;
-}
-
-extern "C" int eben_conv1d_variant(const EbenConv1dDesc* d, int which, int mask_on_load, int* out, int n) {
-  EBEN_REQUIRE(out && n >= 8 && (which == 0 || which == 1), "eben_conv1d_variant: which 0 / 1 and 8 output slots");
-  EBEN_REQUIRE(!mask_on_load || which == 1, "eben_conv1d_variant: the mask is applied on load by input gradients only");
-  Canon c;
-  const int rc = canon_from_desc(d, &c);
-  if (rc) return rc;
-  for (int i = 0; i < 8; ++i) out[i] = 0;
-  out[0] = eben_conv1d_kernel_generation(d, which);
-  if (out[0] == 5) {   // gc_kernel<FORM, RT, CT, NP>: forwards only (generation 5 is never reported for which = 1)
-    if (gc_variant(c, d->transposed ? 1 : 0, &out[1], &out[2], &out[3], &out[4])) out[7] = EBEN_VARIANT_GC;
-    return EBEN_OK;
-  }
-  if (out[0] != 4 && out[0] != 6) return EBEN_OK;
-  // the launch as the entry points build it: the forward's reflect padding is the kernel's; input gradients fold it in a pass of their own
-  const int dir = d->transposed ? 1 - which : which;
-  Tap3Call k{};
-  k.bl = c.bl; k.in_mode = mask_on_load ? 1 : 0; k.reflect = which == 0 && c.reflect && !d->transposed;
-  Tap3Variant v;
-  if (const int e = tap3_plan_variant(c, dir, k, &v)) return e;
-  out[1] = v.FM; out[2] = v.XRB; out[3] = v.IM; out[4] = v.NPW; out[5] = v.NPX; out[6] = v.BL; out[7] = v.kernel;
-  return EBEN_OK;
-}
-
-extern "C" int eben_conv1d_pack(const EbenConv1dDesc* d, const float* v, const float* scale, float* wp_fwd, float* wp_bwd, void* stream) {
-  Canon c;
-  int rc = canon_from_desc(d, &c);
-  if (rc) return rc;
-  EBEN_REQUIRE(v != nullptr, "null weight");
-  for (int which = 0; which < 2; ++which) {
-    float* dst = which == 0 ? wp_fwd : wp_bwd;
-    if (!dst) continue;
-    const int dir = d->transposed ? 1 - which : which;
-    if (which == 0 && gc_applicable(c, dir)) {
-      if ((rc = gc_pack(c, dir, v, scale, dst, as_stream(stream)))) return rc;
-      continue;
-    }
-    const int gen = tap_generation(c, dir);
-    if (gen != 1) {
-      rc = gen == 2 ? tap2_pack(c, dir, v, scale, dst, as_stream(stream))
-         : gen == 4 ? tap3_pack(c, dir, v, scale, dst, as_stream(stream)) : thin_pack(c, dir, v, scale, dst, as_stream(stream));
-      if (rc) return rc;
-      continue;
-    }
-    TapPlan p;
-    make_plan(c, dir, &p);
-    rc = launch_pack(c, p, v, scale, dst, as_stream(stream));
-    if (rc) return rc;
-  }
-  return EBEN_OK;
-}
-
-extern "C" int eben_conv1d_pack_multi(const EbenPackJob* jobs, int n, void* stream) {
-  EBEN_REQUIRE(n >= 0 && (n == 0 || jobs != nullptr), "bad pack job list");
-  // images of the bf16 tap-conv family (most of a step's ~150 pack launches) are gathered into launches of 16 jobs; the other
-  // families keep their own launches
-  constexpr int CAP = 512;
-  static thread_local Canon cs[CAP];
-  static thread_local int dirs[CAP];
-  static thread_local const float* ws[CAP];
-  static thread_local const float* scs[CAP];
-  static thread_local float* wps[CAP];
-  int m = 0;
-  auto flush = [&]() -> int {
-    const int rc = m ? tap3_pack_multi(cs, dirs, ws, scs, wps, m, as_stream(stream)) : EBEN_OK;
-    m = 0;
-    return rc;
-  };
-  for (int i = 0; i < n; ++i) {
-    const EbenPackJob& jb = jobs[i];
-    Canon c;
-    int rc = canon_from_desc(&jb.desc, &c);
-    if (rc) return rc;
-    EBEN_REQUIRE(jb.v != nullptr, "null weight");
-    for (int which = 0; which < 2; ++which) {
-      float* dst = which == 0 ? jb.wp_fwd : jb.wp_bwd;
-      if (!dst) continue;
-      const int dir = jb.desc.transposed ? 1 - which : which;
-      if (!(which == 0 && gc_applicable(c, dir)) && tap_generation(c, dir) == 4) {
-        if (m == CAP && (rc = flush())) return rc;
-        cs[m] = c; dirs[m] = dir; ws[m] = jb.v; scs[m] = jb.scale; wps[m] = dst;
-        ++m;
-      } else {
-        rc = eben_conv1d_pack(&jb.desc, jb.v, jb.scale, which == 0 ? dst : nullptr, which == 1 ? dst : nullptr, stream);
-        if (rc) return rc;
-      }
-    }
-  }
-  return flush();
-}
-
-static int conv1d_fwd_impl(const EbenConv1dDesc* d, const float* x, const float* wp_fwd, const float* bias,
-                           const float* residual, float res_slope, float* y, void* stream) {
-  Canon c;
-  int rc = canon_from_desc(d, &c);
-  if (rc) return rc;
-  EBEN_REQUIRE(x && wp_fwd && y, "null pointer in conv1d_fwd");
+int tap1_pack(const Canon& c, int dir, const float* w, const float* scale, float* wp, hipStream_t st) {
   TapPlan p;
-  make_plan(c, d->transposed ? 1 : 0, &p);
-  if (!d->transposed && c.Cout == 1 && c.g == 1 && c.s == 1 && !c.reflect && d->in_slope == 1.f && !residual && tap_generation(c, 0) == 1) {
-    hipLaunchKernelGGL(conv_m1_fwd_kernel, dim3(ceil_div(c.Lout, 64), c.B), dim3(1024), 0, as_stream(stream), x, wp_fwd, bias, y,
-                       c.Cin, c.Lin, c.Lout, c.k, c.pl, c.d, p.CI_T, p.KCpad, p.Mp, d->out_slope);
+  make_plan(c, dir, &p);
+  return launch_pack(c, p, w, scale, wp, st);
+}
+
+int tap1_launch(const Canon& c, int dir, const TapIO& io, int reflect, hipStream_t st) {
+  TapPlan p;
+  make_plan(c, dir, &p);
+  if (io.conv1d_fwd && c.Cout == 1 && c.g == 1 && c.s == 1 && !c.reflect && io.in_slope == 1.f && !io.res) {
+    hipLaunchKernelGGL(conv_m1_fwd_kernel, dim3(ceil_div(c.Lout, 64), c.B), dim3(1024), 0, st, io.x, io.wp, io.bias, io.y,
+                       c.Cin, c.Lin, c.Lout, c.k, c.pl, c.d, p.CI_T, p.KCpad, p.Mp, io.out_slope);
     EBEN_CHECK_LAUNCH("conv_m1_fwd_kernel");
     return EBEN_OK;
   }
-  TapIO io{};
-  io.x = x; io.in_mode = 0; io.in_slope = d->in_slope; io.wp = wp_fwd; io.bias = bias;
-  io.res = residual; io.res_slope = res_slope; io.emask = nullptr; io.emask_slope = 1.f;
-  io.out_slope = d->out_slope; io.y = y; io.accumulate = 0;
-  if (gc_applicable(c, d->transposed ? 1 : 0)) return gc_launch(c, d->transposed ? 1 : 0, io, as_stream(stream));
-  const int fgen = tap_generation(c, d->transposed ? 1 : 0);
-  if (fgen == 2) return tap2_launch(c, d->transposed ? 1 : 0, io, c.reflect && !d->transposed, as_stream(stream));
-  if (fgen == 3) return thin_launch(c, d->transposed ? 1 : 0, io, c.reflect && !d->transposed, as_stream(stream));
-  if (fgen == 4) return tap3_launch(c, d->transposed ? 1 : 0, io, c.reflect && !d->transposed, as_stream(stream));
-  return launch_tap(c, p, io, c.reflect && !d->transposed, as_stream(stream));
+  return launch_tap(c, p, io, reflect, st);
 }
 
-extern "C" int eben_conv1d_fwd(const EbenConv1dDesc* d, const float* x, const float* wp_fwd, const float* bias,
-                               const float* residual, float* y, void* stream) {
-  return conv1d_fwd_impl(d, x, wp_fwd, bias, residual, 1.f, y, stream);
-}
-
-extern "C" int eben_conv1d_fwd_res(const EbenConv1dDesc* d, const float* x, const float* wp_fwd, const float* bias,
-                                   const float* residual, float res_slope, float* y, void* stream) {
-  EBEN_REQUIRE(residual != nullptr, "conv1d_fwd_res without a residual");
-  return conv1d_fwd_impl(d, x, wp_fwd, bias, residual, res_slope, y, stream);
-}
-
-extern "C" size_t eben_conv1d_bwd_dx_workspace(const EbenConv1dDesc* d) {
-  Canon c;
-  if (canon_from_desc(d, &c) != EBEN_OK) return 0;
-  if (!d->transposed && c.reflect) return sizeof(float) * (size_t)c.B * c.Cin * (c.Lin + c.pl + c.pr);
-  return 0;
-}
-
-static int conv1d_bwd_dx_impl(const EbenConv1dDesc* d, const float* dy, const float* y, const float* wp_bwd, const float* x,
-                              const float* res_pre, const float* res_post, float* dx, int accumulate, void* workspace, size_t ws_bytes,
-                              void* stream) {
-  Canon c;
-  int rc = canon_from_desc(d, &c);
-  if (rc) return rc;
-  EBEN_REQUIRE(dy && wp_bwd && dx, "null pointer in conv1d_bwd_dx");
-  EBEN_REQUIRE(d->out_slope == 1.f || y, "y is required to differentiate the fused output activation");
-  EBEN_REQUIRE(d->in_slope == 1.f || x, "x is required to differentiate the fused input activation");
-  hipStream_t st = as_stream(stream);
-  TapPlan p;
-  const int dir = d->transposed ? 0 : 1;
-  const int gen = tap_generation(c, dir);
-  make_plan(c, dir, &p);
-  TapIO io{};
-  io.x = dy; io.wp = wp_bwd; io.bias = nullptr; io.res = nullptr; io.res_slope = 1.f; io.out_slope = 1.f;
-  if (d->out_slope != 1.f) { io.in_mode = 1; io.xmask = y; io.in_slope = d->out_slope; }
-  else { io.in_mode = 0; io.in_slope = 1.f; }
-  const bool fold = !d->transposed && c.reflect;
-  if (!fold) {
-    if (res_post) return fail(EBEN_EUNSUPPORTED, "bwd_dx: an addend behind the input-activation mask needs the reflect-fold pass");
-    io.res = res_pre;
-    io.emask = d->in_slope != 1.f ? x : nullptr; io.emask_slope = d->in_slope;
-    io.y = dx; io.accumulate = accumulate;
-    return gen == 2 ? tap2_launch(c, dir, io, 0, st) : gen == 3 ? thin_launch(c, dir, io, 0, st)
-         : gen == 4 ? tap3_launch(c, dir, io, 0, st) : launch_tap(c, p, io, 0, st);
-  }
-  const size_t need = eben_conv1d_bwd_dx_workspace(d);
-  if (!workspace || ws_bytes < need) return fail(EBEN_EWORKSPACE, "bwd_dx needs %zu workspace bytes, got %zu", need, ws_bytes);
-  io.emask = nullptr; io.emask_slope = 1.f; io.y = static_cast<float*>(workspace); io.accumulate = 0;
-  rc = gen == 2 ? tap2_launch(c, dir, io, 0, st) : gen == 3 ? thin_launch(c, dir, io, 0, st)
-     : gen == 4 ? tap3_launch(c, dir, io, 0, st) : launch_tap(c, p, io, 0, st);
-  if (rc) return rc;
-  const long long rows = (long long)c.B * c.Cin;
-  long long blocks = (rows * c.Lin + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(fold_kernel, dim3((unsigned)blocks), dim3(256), 0, st, static_cast<const float*>(workspace),
-                     d->in_slope != 1.f ? x : nullptr, dx, rows, c.Lin, c.pl, c.pr, d->in_slope, accumulate, res_pre, res_post);
-  EBEN_CHECK_LAUNCH("fold_kernel");
-  return EBEN_OK;
-}
-
-extern "C" int eben_conv1d_bwd_dx(const EbenConv1dDesc* d, const float* dy, const float* y, const float* wp_bwd,
-                                  const float* x, float* dx, int accumulate, void* workspace, size_t ws_bytes, void* stream) {
-  return conv1d_bwd_dx_impl(d, dy, y, wp_bwd, x, nullptr, nullptr, dx, accumulate, workspace, ws_bytes, stream);
-}
-
-extern "C" int eben_conv1d_bwd_dx_res(const EbenConv1dDesc* d, const float* dy, const float* y, const float* wp_bwd, const float* x,
-                                      const float* res_pre, const float* res_post, float* dx, void* workspace, size_t ws_bytes,
-                                      void* stream) {
-  return conv1d_bwd_dx_impl(d, dy, y, wp_bwd, x, res_pre, res_post, dx, 0, workspace, ws_bytes, stream);
-}
-
-// Batched input gradient for several right-hand sides that share one set of saved activations
-// (the discriminator backward of the fused train step: feature-matching, adversarial, fake and real
-// seeds stacked along the batch axis):
-//   dx[b] = ( conv^T(g[b]) + (b < res_rows ? res[b] : 0) ) * lrelu'(mask[map(b)], mask_slope)
-// g is consumed as is: the producer already applied its activation derivative in ITS epilogue, so no
-// kernel on this path reads a mask on load.
-static int bwd_dx_batched(const EbenConv1dDesc* d, const float* g, const float* wp_bwd, const float* res, int res_rows, const float* fm_sums,
-                          float fm_gs, const float* mask, float mask_slope, int seg, const int* seg_map, float* dx, void* stream);
-extern "C" int eben_conv1d_bwd_dx_ex(const EbenConv1dDesc* d, const float* g, const float* wp_bwd, const float* res, int res_rows,
-                                     const float* mask, float mask_slope, int seg, const int* seg_map, float* dx, void* stream) {
-  return bwd_dx_batched(d, g, wp_bwd, res, res_rows, nullptr, 0.f, mask, mask_slope, seg, seg_map, dx, stream);
-}
-// The same launch with the feature-matching gradient of the embedding formed in the epilogue instead of read from a buffer a separate
-// kernel wrote (feature_loss.py:40-47: d/da [ sum|a - b| / sum|a| ] = sgn(a - b) / s2 - s1 sgn(a) / s2^2):
-//   dx[b] = ( conv^T(g[b]) + (b < fm_rows ? fm_gs (sgn(mask[b] - ref[b]) / s2 - s1 sgn(mask[b]) / s2^2) : 0) ) * lrelu'(mask[map(b)])
-// with (s1, s2) = fm_sums[0..1] read on the device.  Only the thin and the bf16 tap-conv kernels (generations 3 / 4, the ones the
-// discriminators' input gradients run on) carry this epilogue: EBEN_EUNSUPPORTED otherwise (use eben_fm_bwd + bwd_dx_ex).
-extern "C" int eben_conv1d_bwd_dx_fm(const EbenConv1dDesc* d, const float* g, const float* wp_bwd, const float* ref, int fm_rows,
-                                     const float* fm_sums, float fm_gs, const float* mask, float mask_slope, int seg, const int* seg_map,
-                                     float* dx, void* stream) {
-  EBEN_REQUIRE(ref && fm_sums && mask && fm_rows > 0, "bad feature-matching arguments in conv1d_bwd_dx_fm");
-  return bwd_dx_batched(d, g, wp_bwd, ref, fm_rows, fm_sums, fm_gs, mask, mask_slope, seg, seg_map, dx, stream);
-}
-static int bwd_dx_batched(const EbenConv1dDesc* d, const float* g, const float* wp_bwd, const float* res, int res_rows, const float* fm_sums,
-                          float fm_gs, const float* mask, float mask_slope, int seg, const int* seg_map, float* dx, void* stream) {
-  Canon c;
-  int rc = canon_from_desc(d, &c);
-  if (rc) return rc;
-  EBEN_REQUIRE(g && wp_bwd && dx, "null pointer in conv1d_bwd_dx_ex");
-  EBEN_REQUIRE(!(c.reflect && !d->transposed), "bwd_dx_ex does not fold reflect padding (pad explicitly)");
-  EBEN_REQUIRE(seg >= 0 && (seg == 0 || (seg_map && c.B <= 4 * seg)), "bad batch segment map");
-  const int dir = d->transposed ? 0 : 1;
-  TapIO io{};
-  io.x = g; io.in_mode = 0; io.in_slope = 1.f; io.wp = wp_bwd; io.out_slope = 1.f;
-  io.res = res; io.res_slope = 1.f; io.res_rows = res_rows;
-  io.emask = mask; io.emask_slope = mask_slope; io.em_seg = mask ? seg : 0;
-  for (int i = 0; i < 4; ++i) io.em_map[i] = (seg > 0 && seg_map) ? seg_map[i] : i;
-  io.y = dx; io.accumulate = 0;
-  const int gen = tap_generation(c, dir);
-  io.fm_sums = fm_sums; io.fm_gs = fm_gs;
-  if (fm_sums && gen != 3 && gen != 4) return fail(EBEN_EUNSUPPORTED, "conv1d_bwd_dx_fm: kernel generation %d has no feature-matching epilogue", gen);
-  hipStream_t st = as_stream(stream);
-  if (gen == 2) return tap2_launch(c, dir, io, 0, st);
-  if (gen == 3) return thin_launch(c, dir, io, 0, st);
-  if (gen == 4) return tap3_launch(c, dir, io, 0, st);
-  TapPlan p;
-  make_plan(c, dir, &p);
-  return launch_tap(c, p, io, 0, st);
-}
-
-// ---- bundle layout (EBEN_LAYOUT_BL): the discriminator layers between the chain heads and the logits ------------------------------
-// Input gradient of a STRIDED Conv1d as "phases as rows" (melgan_discriminator.py:97-118: k 41, stride 4, 4 groups).  The phase-scatter
-// form (tap3 mode 1) runs one stride-1 sub-convolution per output phase: `stride` blocks stage the same window of dy, each with a
-// quarter of the taps, and a layer with few channels per group (16 -> 64: four input channels per group) fills an eighth of its MFMA
-// rows.  Written for all phases at once,
-//     dx[c, S q + ph] = sum_{co, u} W[co, c, ph + pad - S u] dy[co, q + u],
-// the input gradient IS a stride-1 Conv1d from the Cout channels of dy to S Cin output rows (ph, c) with taps u = umin .. umax (11 for
-// k 41 / S 4) whose result is stored depth-to-space: MelGAN L1 / L2 become grouped 64 -> 64 / 256 -> 256 k 11 convolutions, dy staged
-// once, full row tiles.  The primed weights W'[(ph, c)][co][u] are a gather of the layer's weights (pr_weights_kernel), packed as an
-// ordinary forward image of the primed layer; tap3's bundle epilogue maps logical bundle -> (physical bundle, phase) (Tap3Args.pr_*).
-namespace eben {
-struct PrGeom { int ok, S, umin, kq, Lq, fold, cbg, order; };   // order 1: rows (channel bundle, phase, channel in bundle) -- tap4_kernel's coalesced depth-to-space epilogue
-
-static int pr_floordiv(int a, int b) { int q = a / b; if ((a % b != 0) && ((a < 0) != (b < 0))) --q; return q; }
-
-static PrGeom pr_geometry(const Canon& c, Canon* cp) {
-  PrGeom g{};
-  static const int min_s = getenv("EBEN_PR_MIN_STRIDE") ? atoi(getenv("EBEN_PR_MIN_STRIDE")) : 4;
-  static const int max_d = getenv("EBEN_PR_MAX_DIL") ? atoi(getenv("EBEN_PR_MAX_DIL")) : 1;
-  // stride 2 (the PQMF-band layers) in bundle-major row order on tap3_kernel, up to this dilation (0: off).  [MI355X, 128 rows] the five
-  // stride-2 input gradients of a chain at dilation 1: 0.063 / 0.070 / 0.055 / 0.062 / 0.070 -> 0.053 / 0.052 / 0.045 / 0.046 / 0.064 ms,
-  // at dilation 2 (7 primed taps for 4 + 3): 0.071 / 0.085 / 0.064 / 0.077 / 0.089 -> 0.061 / 0.063 / 0.050 / 0.057 / 0.085; at dilation
-  // 3 (10 primed taps) the extra products cost what the whole-unit epilogue saves: 0.057 / 0.066 / 0.054 / 0.063 / 0.071 -> 0.064 /
-  // 0.069 / 0.054 / 0.065 / 0.070
-  static const int s2_max_d = getenv("EBEN_PR2_S2_MAX_DIL") ? atoi(getenv("EBEN_PR2_S2_MAX_DIL")) : 2;
-  const bool s2 = c.s == 2 && c.d <= s2_max_d;
-  if (!c.bl || c.np != 1 || c.reflect || (c.d > max_d && !s2) || c.s < 2 || (c.s < min_s && !s2) || c.s > 8 || (c.k - 1) * c.d + 1 <= c.s || c.pl > (c.k - 1) * c.d) return g;
-  const int Cg = c.Cin / c.g;
-  if ((c.Cin & 7) || (c.Cout & 7)) return g;
-  g.S = c.s;
-  // dilation d: tap j sits at offset j d, i.e. W' is nonzero where ph + pad - S u is a multiple of d inside [0, (k - 1) d]
-  g.umin = -pr_floordiv((c.k - 1) * c.d - c.pl, c.s);     // ceil((pad - (k - 1) d) / S): phase 0, last tap
-  const int umax = pr_floordiv(c.s - 1 + c.pl, c.s);      // phase S - 1, tap 0
-  g.kq = umax - g.umin + 1;
-  g.Lq = ceil_div(c.Lin, c.s);
-  g.fold = (Cg & 7) != 0;                                  // groups that do not start on bundles: one dense (block-diagonal) contraction
-  g.cbg = g.fold ? c.Cin / 8 : Cg / 8;
-  Canon q = c;
-  q.Cin = c.Cout; q.Cout = c.s * c.Cin; q.Lin = c.Lout; q.Lout = g.Lq;
-  q.k = g.kq; q.s = 1; q.d = 1; q.g = g.fold ? 1 : c.g;
-  q.pl = -g.umin;
-  q.pr = g.Lq - c.Lout + g.kq - 1 - q.pl;
-  if (q.pl < 0 || q.pr < 0) return g;
-  q.reflect = 0; q.xsplit_dir = -1;
-  // [MI355X, 128 rows] MelGAN L1 / L2 (4 / 16 channels per group: 64 primed rows per group) 0.336 / 0.310 -> 0.239 / 0.210 ms; L3 / L4 (64 /
-  // 256 channels per group: 256 / 1024 primed rows, full row tiles in either form) 0.414 / 0.412 -> 0.531 / 0.524: the form is for the layers
-  // whose phases leave row tiles empty
-  static const int max_rows = getenv("EBEN_PR_MAX_ROWS") ? atoi(getenv("EBEN_PR_MAX_ROWS")) : 64;
-  // Wider layers (MelGAN L3 / L4: 256 / 1024 primed rows per group) take the form on tap4_kernel (bigtap.hip) with the rows ordered
-  // (channel bundle, phase, channel in bundle): a 32-row MFMA tile is then ONE bundle at the four phases of a position, i.e. 64
-  // contiguous bytes per column -- the phase-scatter form writes (and reads its mask as) 8-byte pieces 64 bytes apart, which a
-  // block per CU cannot hide ([MI355X] phase-scatter on tap4: 0.416 / 0.402 -> 0.506 / 0.444 ms)
-  static const int big_pr = getenv("EBEN_PR_BIG") ? atoi(getenv("EBEN_PR_BIG")) : 1;
-  // ... and the narrow ones (MelGAN L1 / L2: 64 primed rows per group, tap3_kernel) take the same row order: their mask / feature-matching
-  // operands and results move as whole units too ([MI355X] those loads were 36-43 % of the order-0 launches)
-  static const int small_pr2 = getenv("EBEN_PR2_TAP3") ? atoi(getenv("EBEN_PR2_TAP3")) : 1;
-  g.order = (big_pr && c.s == 4 && c.d == 1 && (tap3_is_big(q, 0) || (small_pr2 && (q.Cout / q.g) % 32 == 0))) ? 1 : 0;
-  if (s2) {   // two bundles per 32-row tile: whole bundles at both phases, tap3_kernel only
-    if (tap3_is_big(q, 0) || (q.Cout / q.g) % 16 != 0) return g;
-    g.order = 1;
-  }
-  if (q.Cout / q.g > max_rows && !g.order) return g;
-  if (!tap3_applicable(q, 0)) return g;
-  if (cp) *cp = q;
-  g.ok = 1;
-  return g;
-}
-
-// W'[(g, ph, c)][co][ui] (groups kept) or [(ph, ci)][co][ui] (folded, zero across groups) = scale[co] v[co][c][ph + pad - S (ui + umin)]
-__global__ __launch_bounds__(256) void pr_weights_kernel(const float* __restrict__ v, const float* __restrict__ scale, float* __restrict__ wq,
-                                                          int Cin, int Cout, int G, int k, int S, int pad, int umin, int kq, int fold, int dil, int order) {
-  const int Cg = Cin / G, Mg = Cout / G;
-  const int cin_q = fold ? Cout : Mg;                      // input channels per group of the primed layer
-  const long long total = (long long)S * Cin * cin_q * kq;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-    const int ui = (int)(i % kq);
-    long long r = i / kq;
-    const int cq = (int)(r % cin_q);
-    const int row = (int)(r / cin_q);
-    int ph, ci, co;
-    if (fold && order) { const int lb = row >> 3, cb = lb / S; ph = lb - cb * S; ci = cb * 8 + (row & 7); co = cq; }
-    else if (fold) { ph = row / Cin; ci = row - ph * Cin; co = cq; }
-    else if (order == 0) { const int g = row / (S * Cg), rr = row - g * S * Cg; ph = rr / Cg; ci = g * Cg + (rr - ph * Cg); co = g * Mg + cq; }
-    else {   // (group, channel bundle, phase, channel in bundle)
-      const int g = row / (S * Cg), rr = row - g * S * Cg, lb = rr >> 3, cb = lb / S;
-      ph = lb - cb * S; ci = g * Cg + cb * 8 + (rr & 7); co = g * Mg + cq;
-    }
-    const int off = ph + pad - S * (ui + umin);              // = j dil for the tap this entry stands for, if any
-    const int j = off / dil;
-    float w = 0.f;
-    if (off >= 0 && j * dil == off && j < k && co / Mg == ci / Cg) w = v[((long long)co * Cg + (ci % Cg)) * k + j] * (scale ? scale[co] : 1.f);
-    wq[i] = w;
-  }
-}
-
-static void pr_desc_from_canon(const EbenConv1dDesc* d, const Canon& q, EbenConv1dDesc* o) {
-  *o = *d;
-  o->c_in = q.Cin; o->c_out = q.Cout; o->l_in = q.Lin; o->l_out = q.Lout; o->ksize = q.k; o->stride = 1; o->dilation = 1; o->groups = q.g;
-  o->pad_l = q.pl; o->pad_r = q.pr; o->pad_mode = EBEN_PAD_ZERO; o->transposed = 0; o->in_slope = 1.f; o->out_slope = 1.f;
-}
 }  // namespace eben
 
-extern "C" int eben_bl_dx_pr_desc(const EbenConv1dDesc* d, EbenConv1dDesc* primed) {
-  Canon c, q;
-  int rc = canon_from_desc(d, &c);
-  if (rc) return rc;
-  if (d->transposed || !pr_geometry(c, &q).ok) return fail(EBEN_EUNSUPPORTED, "eben_bl_dx_pr_desc: the layer's input gradient has no phases-as-rows form");
-  EBEN_REQUIRE(primed != nullptr, "null output descriptor");
-  pr_desc_from_canon(d, q, primed);
-  return EBEN_OK;
-}
-
-extern "C" int eben_bl_dx_pr_weights(const EbenConv1dDesc* d, const float* v, const float* scale, float* w_primed, void* stream) {
-  Canon c, q;
-  int rc = canon_from_desc(d, &c);
-  if (rc) return rc;
-  const PrGeom g = d->transposed ? PrGeom{} : pr_geometry(c, &q);
-  if (!g.ok) return fail(EBEN_EUNSUPPORTED, "eben_bl_dx_pr_weights: the layer's input gradient has no phases-as-rows form");
-  EBEN_REQUIRE(v && w_primed, "null pointer in eben_bl_dx_pr_weights");
-  const long long total = (long long)q.Cout * (q.Cin / q.g) * q.k;
-  long long blocks = (total + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(pr_weights_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), v, scale, w_primed, c.Cin, c.Cout, c.g, c.k, c.s, c.pl,
-                     g.umin, g.kq, g.fold, c.d, g.order);
-  EBEN_CHECK_LAUNCH("pr_weights_kernel");
-  return EBEN_OK;
-}
-
-extern "C" int eben_bl_conv1d_bwd_dx_pr(const EbenConv1dDesc* d, const void* g_hi, const float* wp_primed_fwd, const void* act_hi, const void* act_lo,
-                                        float mask_slope, int seg, const int* seg_map, int fm_rows, int ref_row_offset, const float* fm_sums,
-                                        float fm_gs, void* dx_hi, void* dx_lo, void* stream) {
-  return eben_bl_conv1d_bwd_dx_pr_c(d, g_hi, wp_primed_fwd, act_hi, act_lo, nullptr, mask_slope, seg, seg_map, fm_rows, ref_row_offset, fm_sums, fm_gs, dx_hi,
-                                    dx_lo, stream);
-}
-
-extern "C" int eben_bl_conv1d_bwd_dx_pr_c(const EbenConv1dDesc* d, const void* g_hi, const float* wp_primed_fwd, const void* act_hi, const void* act_lo,
-                                          const void* fm_codes, float mask_slope, int seg, const int* seg_map, int fm_rows, int ref_row_offset,
-                                          const float* fm_sums, float fm_gs, void* dx_hi, void* dx_lo, void* stream) {
-  Canon c, q;
-  int rc = canon_from_desc(d, &c);
-  if (rc) return rc;
-  const PrGeom g = d->transposed ? PrGeom{} : pr_geometry(c, &q);
-  if (!g.ok) return fail(EBEN_EUNSUPPORTED, "eben_bl_conv1d_bwd_dx_pr: the layer's input gradient has no phases-as-rows form");
-  EBEN_REQUIRE(g_hi && wp_primed_fwd && dx_hi, "null pointer in eben_bl_conv1d_bwd_dx_pr");
-  EBEN_REQUIRE(seg >= 0 && (seg == 0 || (seg_map && c.B <= 4 * seg)), "bad batch segment map");
-  EBEN_REQUIRE(fm_rows == 0 || (fm_sums && act_hi && act_lo && fm_rows > 0), "feature-matching rows need the sums and both planes of the embedding");
-  TapIO io{};
-  io.in_slope = 1.f; io.wp = wp_primed_fwd; io.out_slope = 1.f; io.res_slope = 1.f;
-  io.res_rows = fm_rows; io.fm_sums = fm_rows > 0 ? fm_sums : nullptr; io.fm_gs = fm_gs;
-  io.emask_slope = mask_slope; io.em_seg = act_hi ? seg : 0;
-  for (int i = 0; i < 4; ++i) io.em_map[i] = (seg > 0 && seg_map) ? seg_map[i] : i;
-  io.xh = g_hi; io.yh = dx_hi; io.yl = dx_lo; io.eh = act_hi; io.el = act_lo; io.bl_ref_off = ref_row_offset;
-  io.ec = fm_rows > 0 ? fm_codes : nullptr;
-  io.pr_S = g.S; io.pr_cbg = g.cbg; io.pr_Ly = c.Lin; io.pr_CBy = c.Cin / 8; io.pr_order = g.order;
-  return tap3_launch(q, 0, io, 0, as_stream(stream));
-}
-
-extern "C" int eben_bl_conv1d_fwd(const EbenConv1dDesc* d, const void* x_hi, const void* x_lo, const float* wp_fwd, const float* bias,
-                                  void* y_hi, void* y_lo, void* stream) {
-  Canon c;
-  int rc = canon_from_desc(d, &c);
-  if (rc) return rc;
-  EBEN_REQUIRE(c.bl && !d->transposed && d->in_slope == 1.f, "eben_bl_conv1d_fwd: a Conv1d descriptor with EBEN_LAYOUT_BL and no input activation");
-  EBEN_REQUIRE(x_hi && wp_fwd && y_hi, "null pointer in eben_bl_conv1d_fwd");
-  if (tap_generation(c, 0) != 4) return fail(EBEN_EUNSUPPORTED, "eben_bl_conv1d_fwd: layer not covered by the bundle-layout tap-conv");
-  TapIO io{};
-  io.in_slope = 1.f; io.wp = wp_fwd; io.bias = bias; io.res_slope = 1.f; io.emask_slope = 1.f; io.out_slope = d->out_slope;
-  io.xh = x_hi; io.xl = x_lo; io.yh = y_hi; io.yl = y_lo;
-  return tap3_launch(c, 0, io, 0, as_stream(stream));
-}
-
-extern "C" int eben_bl_conv1d_bwd_dx(const EbenConv1dDesc* d, const void* g_hi, const float* wp_bwd, const void* act_hi, const void* act_lo,
-                                     float mask_slope, int seg, const int* seg_map, int fm_rows, int ref_row_offset, const float* fm_sums,
-                                     float fm_gs, void* dx_hi, void* dx_lo, void* stream) {
-  return eben_bl_conv1d_bwd_dx_c(d, g_hi, wp_bwd, act_hi, act_lo, nullptr, mask_slope, seg, seg_map, fm_rows, ref_row_offset, fm_sums, fm_gs, dx_hi, dx_lo,
-                                 stream);
-}
-
-extern "C" int eben_bl_conv1d_bwd_dx_c(const EbenConv1dDesc* d, const void* g_hi, const float* wp_bwd, const void* act_hi, const void* act_lo,
-                                       const void* fm_codes, float mask_slope, int seg, const int* seg_map, int fm_rows, int ref_row_offset,
-                                       const float* fm_sums, float fm_gs, void* dx_hi, void* dx_lo, void* stream) {
-  Canon c;
-  int rc = canon_from_desc(d, &c);
-  if (rc) return rc;
-  EBEN_REQUIRE(c.bl && !d->transposed, "eben_bl_conv1d_bwd_dx: a Conv1d descriptor with EBEN_LAYOUT_BL");
-  EBEN_REQUIRE(g_hi && wp_bwd && dx_hi, "null pointer in eben_bl_conv1d_bwd_dx");
-  EBEN_REQUIRE(seg >= 0 && (seg == 0 || (seg_map && c.B <= 4 * seg)), "bad batch segment map");
-  EBEN_REQUIRE(fm_rows == 0 || (fm_sums && act_hi && act_lo && fm_rows > 0), "feature-matching rows need the sums and both planes of the embedding");
-  if (tap_generation(c, 1) != 4) return fail(EBEN_EUNSUPPORTED, "eben_bl_conv1d_bwd_dx: layer not covered by the bundle-layout tap-conv");
-  TapIO io{};
-  io.in_slope = 1.f; io.wp = wp_bwd; io.out_slope = 1.f; io.res_slope = 1.f;
-  io.res_rows = fm_rows; io.fm_sums = fm_rows > 0 ? fm_sums : nullptr; io.fm_gs = fm_gs;
-  io.emask_slope = mask_slope; io.em_seg = act_hi ? seg : 0;
-  for (int i = 0; i < 4; ++i) io.em_map[i] = (seg > 0 && seg_map) ? seg_map[i] : i;
-  io.xh = g_hi; io.yh = dx_hi; io.yl = dx_lo; io.eh = act_hi; io.el = act_lo; io.bl_ref_off = ref_row_offset;
-  io.ec = fm_rows > 0 ? fm_codes : nullptr;
-  return tap3_launch(c, 1, io, 0, as_stream(stream));
-}

@@ -1415,7 +1415,7 @@ int tap3_applicable(const Canon& c, int dir) {
   return p.ok;
 }
 
-int tap3_is_big(const Canon& c, int dir) {   // served by tap4_kernel (bigtap.hip): kernel generation 6
+int tap3_is_big(const Canon& c, int dir) {   // served by tap4_kernel (bigtap.hip): EBEN_CONV_ROUTE_TAP4
   Tap3Plan p;
   make_plan3(c, dir, &p);
   return p.ok && p.big;

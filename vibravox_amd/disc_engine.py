@@ -203,7 +203,7 @@ class _Chain:
             for i in range(1, len(self.layers)):
                 lay = self.layers[i]
                 d = ops.conv_desc(lay.spec_lin, 4 * half, outs[i - 1].shape[2], lay.math_dx)
-                if self.layers[i - 1].spec.out_slope == 1.0 or lib.eben_conv1d_kernel_generation(ctypes.byref(d), 1) not in (3, 4):
+                if self.layers[i - 1].spec.out_slope == 1.0 or lib.eben_conv1d_kernel_generation(ctypes.byref(d), 1) not in ops.CONV_ROUTES_WITH_FM_EPILOGUE:
                     hit = False
             if len(self._fm_ok) > 64:
                 self._fm_ok.clear()

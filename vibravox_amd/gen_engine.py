@@ -192,7 +192,7 @@ class GeneratorEngine:
             alt = self._spec_cache[(id(m), "s2d", in_slope, out_slope)] = ops.ConvSpec(
                 c_in=c * spec.stride, c_out=rows_out, ksize=kq, in_slope=float(in_slope), out_slope=float(out_slope))
         d = ops.conv_desc(alt, batch, l_q, math)
-        if lib.eben_conv1d_kernel_generation(ctypes.byref(d), 0) != 4:
+        if lib.eben_conv1d_kernel_generation(ctypes.byref(d), 0) != ops.CONV_ROUTE_TAP3:
             return None
         v, g = _params(m)
         key = ops.weights_key((v, g), batch, l_q, math)
@@ -217,7 +217,7 @@ class GeneratorEngine:
         d, d_bwd, pw = self._pack(m, spec, b, l_in, train)
         y = torch.empty((b, spec.c_out, d.l_out), dtype=torch.float32, device=x.device)
         route = None
-        if not spec.transposed and self._s2d_wanted(spec, conv_forward_math()) and lib.eben_conv1d_kernel_generation(ctypes.byref(d), 0) not in (4, 5):
+        if not spec.transposed and self._s2d_wanted(spec, conv_forward_math()) and lib.eben_conv1d_kernel_generation(ctypes.byref(d), 0) not in (ops.CONV_ROUTE_TAP3, ops.CONV_ROUTE_GC):
             kq = spec.ksize // spec.stride
             l_q = d.l_out + kq - 1
             route = self._s2d_route(m, spec, b, l_q, kq, conv_forward_math(), spec.c_in, spec.c_out, spec.in_slope, spec.out_slope, pw.scale)
@@ -548,7 +548,7 @@ class GeneratorEngine:
         d = rec.d
         spec = rec.spec
         if (spec.transposed and res_pre is None and res_post is None and spec.in_slope == 1.0 and spec.output_padding == 0
-                and self._s2d_wanted(spec, d.math) and lib.eben_conv1d_kernel_generation(ctypes.byref(d), 1) != 4):
+                and self._s2d_wanted(spec, d.math) and lib.eben_conv1d_kernel_generation(ctypes.byref(d), 1) != ops.CONV_ROUTE_TAP3):
             # input gradient of ConvTranspose1d = stride-S conv of the (masked) output gradient with the same (in, out, k) weights
             b, c_dy, l_dy = dy.shape
             kq = spec.ksize // spec.stride

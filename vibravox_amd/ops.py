@@ -347,6 +347,9 @@ _desc_cache: Dict[Tuple[ConvSpec, int, int], EbenConv1dDesc] = {}
 
 
 MATH_F32, MATH_BF16, MATH_BF16X2, MATH_BF16X3, MATH_BF16X6 = 0, 1, 2, 3, 4   # EBEN_MATH_* of include/eben_hip.h
+# EBEN_CONV_ROUTE_* of include/eben_hip.h: the answers of eben_conv1d_kernel_generation and out[0] of eben_conv1d_variant
+CONV_ROUTE_NONE, CONV_ROUTE_TAP1, CONV_ROUTE_TAP2, CONV_ROUTE_THIN, CONV_ROUTE_TAP3, CONV_ROUTE_GC, CONV_ROUTE_TAP4 = 0, 1, 2, 3, 4, 5, 6
+CONV_ROUTES_WITH_FM_EPILOGUE = (CONV_ROUTE_THIN, CONV_ROUTE_TAP3)   # the input gradients eben_conv1d_bwd_dx_fm accepts
 
 # Arithmetic of the BACKWARD contractions (input and weight gradients) of `conv_layer`; the forward is always exact fp32.
 # Read when the forward runs (the backward image of the weights is packed then).
