@@ -647,6 +647,36 @@ EBEN_API int eben_resample_adjoint(const float* g, const float* kernels, float* 
 EBEN_API int eben_edge_fill(float* x, const int32_t* lens, int rows, int channels, int l_buf, int mode, int count, void* stream);
 EBEN_API int eben_edge_zero(float* x, const int32_t* lens, int rows, int channels, int l_buf, void* stream);
 
+/* ---- per-row loss sums over ragged buffers (csrc/ragged_losses.hip): every clip's own value of the test-time losses -----------
+ * Tables (pointers, channels, l_bufs, targets) are HOST arrays and travel by value in the kernel arguments; every `lens` /
+ * `frames_of_row` they name is a DEVICE int32 array of `rows` entries the host never reads.  All reductions are two-level with a
+ * fixed order and no atomics: two runs give the same bits.  A lens entry outside [0, l_buf] (a frame count outside [0, frames])
+ * makes that row's results NaN and reads nothing; nothing is ever written outside `sums` / `out` and the workspace.
+ * eben_fm_sums_rows: npairs <= 32 pairs; ptrs = (a_0, b_0, a_1, b_1, ...), a_i and b_i fp32 (rows, channels[i], l_bufs[i]) at any
+ *   4-byte alignment (16-byte loads where a row segment of both allows them, scalar heads and tails elsewhere), lens[i] that pair's
+ *   row lengths.  sums[(i * rows + r) * 2 + {0, 1}] = sum |a - b|, sum |a| over c < channels[i], l < lens[i][r].
+ * eben_hinge_rows: n <= 32 terms; xs[i] fp32 (rows, 1, l_bufs[i]) logits.  out[i * rows + r] = mean_{l < lens[i][r]} max(0, 1 -
+ *   targets[i] x[r, 0, l]) (NaN for an empty row).
+ * eben_stft_loss_sums_rows: eben_stft_loss_sums_ex whose row r runs over its first frames_of_row[r] frames only (`frames`: the
+ *   frames per row of the buffer, which the strides describe); a row with frames_of_row[r] == frames gets eben_stft_loss_sums_ex's bits.
+ * eben_clip_losses: out (5, rows) = per row [MRSTFT, feature matching, adv_loss_gen, real_loss, fake_loss] in one launch:
+ *   MRSTFT = mean over the n_res <= 8 resolutions of sqrt(s0 / s1) + s2 / (bins[i] * frames_of_row[i][r]) from stft_sums[i] (rows, 3);
+ *   feature matching = fm_inv_count * sum over the pairs of s1 / s2 from fm_sums; the three hinge values the means over the chains
+ *   of hinge[(3 * chain + k) * rows + r].  A group whose count is 0 (its pointers may then be NULL) leaves NaN in its rows of out.
+ * Added without a version bump: functions only. */
+EBEN_API size_t eben_fm_sums_rows_workspace(int npairs, int rows);
+EBEN_API int eben_fm_sums_rows(const void* const* ptrs, const int* channels, const int* l_bufs, const int32_t* const* lens, int npairs,
+                               int rows, float* partial_ws, size_t ws_bytes, float* sums, void* stream);
+EBEN_API int eben_hinge_rows(const void* const* xs, const int* l_bufs, const float* targets, const int32_t* const* lens, int n, int rows,
+                             float* out, void* stream);
+EBEN_API size_t eben_stft_loss_sums_rows_workspace(int rows);
+EBEN_API int eben_stft_loss_sums_rows(const float* spec_x, const float* spec_y, int rows, int bins, int frames,
+                                      const int32_t* frames_of_row, long long row_stride, long long bin_stride, long long im_off, float eps,
+                                      float* partial_ws, size_t ws_bytes, float* out, void* stream);
+EBEN_API int eben_clip_losses(const void* const* stft_sums, const int32_t* const* frames_of_row, const int* bins, int n_res,
+                              const float* fm_sums, int npairs, float fm_inv_count, const float* hinge, int nchains, int rows, float* out,
+                              void* stream);
+
 /* ---- streaming inference (csrc/stream.hip): a layer's input for this push from the previous push's buffer and fresh output ------
  * dst[rc, j] = prev[rc, prev_off + j] for j < n_carry; dst[rc, n_carry + j] = src[rc, src_off + j] (+ add[rc, add_off + j]) for
  * j < n_new; rc < rows_channels.  fp32 [row][C][L] tensors, each with its own row pitch (in floats); offsets and counts are

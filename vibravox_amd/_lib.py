@@ -233,6 +233,12 @@ SIGNATURES = {
     "eben_resample_adjoint": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "eben_edge_fill": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "eben_edge_zero": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
+    "eben_fm_sums_rows_workspace": (c_size_t, [c_int, c_int]),
+    "eben_fm_sums_rows": (c_int, [POINTER(c_void_p), POINTER(c_int), POINTER(c_int), POINTER(c_void_p), c_int, c_int, _P, c_size_t, _P, _P]),
+    "eben_hinge_rows": (c_int, [POINTER(c_void_p), POINTER(c_int), POINTER(c_float), POINTER(c_void_p), c_int, c_int, _P, _P]),
+    "eben_stft_loss_sums_rows_workspace": (c_size_t, [c_int]),
+    "eben_stft_loss_sums_rows": (c_int, [_P, _P, c_int, c_int, c_int, _P, c_int64, c_int64, c_int64, c_float, _P, c_size_t, _P, _P]),
+    "eben_clip_losses": (c_int, [POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int), c_int, _P, c_int, c_float, _P, c_int, c_int, _P, _P]),
     "eben_stream_splice": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P]),
     "eben_stream_splice_rows": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P, c_int, c_int, _P, c_int, c_int, c_int,
                                         POINTER(ctypes.c_uint64), c_int, c_int, _P]),

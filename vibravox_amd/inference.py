@@ -9,6 +9,7 @@ one): per batch one ragged forward and the SI-SDR / STOI kernels with a length p
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 from typing import Dict, List, Optional, Sequence
 
@@ -106,10 +107,81 @@ def _check_clip(c, what: str) -> None:
         raise ValueError(f"{what}: expected a float32 tensor of shape (T,), (1, T) or (1, 1, T), got {got}")
 
 
+@dataclasses.dataclass(frozen=True)
+class LossTerms:
+    """The losses ``evaluate_clips`` takes per clip, as ``EBENLightningModule.compute_atomic_losses`` takes them per batch: the
+    module's ``discriminator`` and its four loss functions, any of which may be None (its term is then left out, as there)."""
+    discriminator: object = None
+    freq_loss: object = None          # MultiResolutionSTFTLoss: "generator/reconstructive_loss_freq"
+    time_loss: object = None          # any callable (enhanced, reference) -> scalar, row by row: "generator/reconstructive_loss_temp"
+    feature_loss: object = None       # FeatureLossForDiscriminatorMelganMultiScales: "generator/feature_matching_loss"
+    adversarial_loss: object = None   # HingeLossForDiscriminatorMelganMultiScales: "generator/adv_loss_gen", "discriminator/real_loss", "/fake_loss"
+
+    def __post_init__(self):
+        from .torch_modules.dnn.eben_discriminator import DiscriminatorEBENMultiScales
+        from .torch_modules.losses.feature_loss import FeatureLossForDiscriminatorMelganMultiScales
+        from .torch_modules.losses.hinge_loss import HingeLossForDiscriminatorMelganMultiScales
+        from .torch_modules.losses.mrstft_loss import MultiResolutionSTFTLoss
+
+        for name, kind in (("discriminator", DiscriminatorEBENMultiScales), ("freq_loss", MultiResolutionSTFTLoss),
+                           ("feature_loss", FeatureLossForDiscriminatorMelganMultiScales),
+                           ("adversarial_loss", HingeLossForDiscriminatorMelganMultiScales)):
+            value = getattr(self, name)
+            if value is not None and not isinstance(value, kind):
+                raise ValueError(f"LossTerms: {name} must be this package's {kind.__name__} (or None), got {type(value).__name__}: per-clip values "
+                                 "exist for these classes only")
+        if self.time_loss is not None and not callable(self.time_loss):
+            raise ValueError(f"LossTerms: time_loss must be callable, got {type(self.time_loss).__name__}")
+        if (self.feature_loss is not None or self.adversarial_loss is not None) and self.discriminator is None:
+            raise ValueError("LossTerms: feature_loss and adversarial_loss need the discriminator")
+
+    def keys(self) -> List[str]:
+        """The result keys, in the order ``compute_atomic_losses`` yields the terms: the generator's, then the discriminator's."""
+        out = [f"generator/{name}" for name, fn in (("reconstructive_loss_freq", self.freq_loss), ("reconstructive_loss_temp", self.time_loss),
+                                                    ("feature_matching_loss", self.feature_loss), ("adv_loss_gen", self.adversarial_loss))
+               if fn is not None]
+        return out + (["discriminator/real_loss", "discriminator/fake_loss"] if self.adversarial_loss is not None else [])
+
+
+def _batch_losses(terms: LossTerms, generator, plan, enh: torch.Tensor, bnd: torch.Tensor, ref: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """The terms of one ragged batch, (rows,) each: ``enh`` (rows, 1, l_buf) and ``bnd`` as ``forward_ragged`` returned them, ``ref`` the
+    references packed alike.  The enhanced and the reference branch go through the discriminator stacked as 2 x rows."""
+    from . import ops
+
+    rows, cut = len(plan.cut), list(plan.cut)
+    out: Dict[str, torch.Tensor] = {}
+    stft = fm = hinge = None
+    if terms.freq_loss is not None:
+        stft = terms.freq_loss.ragged_sums(enh, ref, cut)
+    if terms.feature_loss is not None or terms.adversarial_loss is not None:
+        disc = terms.discriminator
+        ref_bands = generator.pqmf.forward(ref, "analysis")   # zero behind a row is the bank's own zero padding
+        band_lengths = list(plan.row_lengths[1])
+        dplan = ragged.disc_plan(disc, cut * 2, band_lengths * 2, plan.l_buf, bnd.shape[2])
+        emb, lens = disc.forward_ragged(torch.cat((bnd, ref_bands), dim=0), torch.cat((enh, ref), dim=0), dplan)
+        if terms.feature_loss is not None:
+            pairs = [(scale[lv][:rows], scale[lv][rows:], ln[lv][:rows]) for scale, ln in zip(emb, lens) for lv in range(1, len(scale) - 1)]
+            fm = (ops.fm_sums_rows(pairs, rows), 1.0 / (len(emb) * len(emb[-1][1:-1])))   # feature_loss.py's own count
+        if terms.adversarial_loss is not None:
+            hinge = ops.hinge_rows([(x, target, ln[-1][:rows]) for scale, ln in zip(emb, lens)
+                                    for x, target in ((scale[-1][:rows], 1.0), (scale[-1][rows:], 1.0), (scale[-1][:rows], -1.0))], rows)
+    if stft is not None or fm is not None or hinge is not None:
+        values = ops.clip_losses(rows, enh.device, stft=stft, fm=fm, hinge=hinge)
+        for k, (key, have) in enumerate((("generator/reconstructive_loss_freq", stft), ("generator/feature_matching_loss", fm),
+                                         ("generator/adv_loss_gen", hinge), ("discriminator/real_loss", hinge), ("discriminator/fake_loss", hinge))):
+            if have is not None:
+                out[key] = values[k]
+    if terms.time_loss is not None:
+        out["generator/reconstructive_loss_temp"] = torch.stack(
+            [terms.time_loss(enh[r : r + 1, :, :t], ref[r : r + 1, :, :t]).reshape(()).to(torch.float32) for r, t in enumerate(cut)])
+    return out
+
+
 @torch.no_grad()
 def evaluate_clips(generator, corrupted: Sequence[torch.Tensor], reference: Sequence[torch.Tensor], *, sample_rate: int = EVAL_RATE,
                    max_batch_samples: int = MAX_BATCH_SAMPLES, return_enhanced: bool = False,
-                   metrics: Sequence[str] = DEFAULT_EVAL_METRICS, lsd_hf_cutoff_hz: Optional[float] = None) -> Dict[str, object]:
+                   metrics: Sequence[str] = DEFAULT_EVAL_METRICS, lsd_hf_cutoff_hz: Optional[float] = None,
+                   loss_terms: Optional[LossTerms] = None) -> Dict[str, object]:
     """Per-clip SI-SDR and STOI of the enhanced ``corrupted[i]`` against ``reference[i]``, at 16 kHz as ``base_se.py`` logs them:
     ``{"si_sdr": (N,) float32, "stoi": (N,) float32}`` on the device, in input order; with ``return_enhanced`` also ``"enhanced"``, the
     list ``enhance_clips`` returns.  ``metrics`` selects among ``EVAL_METRICS``, one key each, all on the same 16 kHz buffers and lengths;
@@ -118,7 +190,13 @@ def evaluate_clips(generator, corrupted: Sequence[torch.Tensor], reference: Sequ
     Clips as for ``enhance_clips``; a pair has one length, and both are scored on their first
     ``cut_to_valid_length`` samples (a reference may carry anything behind them).  Batches as in ``enhance_clips``: per batch one
     ``forward_ragged`` and the metric kernels with ``lengths = plan.cut`` on the padded buffers -- nothing is unpacked unless
-    ``return_enhanced`` asks for it, and nothing here waits for the device."""
+    ``return_enhanced`` asks for it, and nothing here waits for the device.
+
+    With ``loss_terms`` the same batch loop also yields the atomic losses ``test_step`` logs, per clip: keys ``"generator/<name>"`` and
+    ``"discriminator/<name>"`` (``LossTerms.keys()``: the terms ``compute_atomic_losses`` would produce for that configuration), each
+    (N,) float32 on the device in input order, each value what the clip's own batch of one gives.  They are taken at the model's rate
+    on the cut clips.  The batches are then planned with the margin the discriminators and the STFT need behind a row
+    (``ragged.loss_margin``); a clip too short for the discriminator's or the STFT's own call is refused by index before anything runs."""
     from . import metrics as M
 
     names = list(metrics)
@@ -147,7 +225,24 @@ def evaluate_clips(generator, corrupted: Sequence[torch.Tensor], reference: Sequ
     if sample_rate <= 0:
         raise ValueError(f"evaluate_clips: sample_rate must be positive, got {sample_rate}")
     lengths = [c.shape[-1] for c in corrupted]
-    batches, back = ragged.compose_batches(generator, lengths, max_batch_samples)   # refuses a clip that is too short, by index
+    min_margin = 0
+    if loss_terms is not None:
+        if not isinstance(loss_terms, LossTerms):
+            raise ValueError(f"evaluate_clips: loss_terms must be a LossTerms, got {type(loss_terms).__name__}")
+        uses_disc = loss_terms.feature_loss is not None or loss_terms.adversarial_loss is not None
+        # the slack the discriminators' deepest layers and the STFT's reflect padding read behind a row
+        min_margin = ragged.loss_margin(loss_terms.discriminator if uses_disc else None, generator.pqmf.decimation, loss_terms.freq_loss)
+    batches, back = ragged.compose_batches(generator, lengths, max_batch_samples, min_margin)   # refuses a clip that is too short, by index
+    if loss_terms is not None:   # and the clips the discriminator's or the STFT's own batch-1 call would refuse, before anything runs
+        cuts = [ragged.cut_length(generator, t) for t in lengths]
+        if uses_disc:
+            n, m = generator.pqmf.kernel_size, generator.pqmf.decimation
+            ragged.disc_plan(loss_terms.discriminator, cuts, [(t + n - 2) // m + 1 for t in cuts])
+        if loss_terms.freq_loss is not None:
+            pad = ragged.loss_margin(None, 1, loss_terms.freq_loss)
+            for i, t in enumerate(cuts):
+                if t < pad + 1:
+                    raise ValueError(f"clip {i} ({t} samples after cut_to_valid_length) is too short: the STFT reflect-pads {pad} samples")
     if lsd_bands:
         for i, t in enumerate(lengths):
             t16 = resampled_length(ragged.cut_length(generator, t), sample_rate, EVAL_RATE)   # the cut length itself at 16 kHz
@@ -155,15 +250,24 @@ def evaluate_clips(generator, corrupted: Sequence[torch.Tensor], reference: Sequ
                 raise ValueError(f"clip {i}: {t16} samples at {EVAL_RATE} Hz cannot be reflect-padded for the LSD ({LSD_N_FFT // 2 + 1} at least)")
     values: Dict[str, List[torch.Tensor]] = {name: [] for name in names}
     enhanced: List[torch.Tensor] = []
+    losses: Dict[str, List[torch.Tensor]] = {key: [] for key in (loss_terms.keys() if loss_terms is not None else ())}
     for idx in batches:
-        plan = ragged.plan(generator, [lengths[i] for i in idx])
+        plan = ragged.plan(generator, [lengths[i] for i in idx], min_margin)
         dev = corrupted[idx[0]].device
         buf = torch.zeros((len(idx), 1, plan.l_buf), dtype=torch.float32, device=dev)
         ref = torch.zeros((len(idx), plan.l_buf), dtype=torch.float32, device=dev)
         for r, i in enumerate(idx):
             buf[r, 0, : plan.cut[r]].copy_(corrupted[i].reshape(-1)[: plan.cut[r]])
             ref[r, : plan.cut[r]].copy_(reference[i].reshape(-1)[: plan.cut[r]])
-        enh, _ = generator.forward_ragged(buf, [lengths[i] for i in idx])   # zero behind every row, like ref
+        if loss_terms is None:
+            enh, _ = generator.forward_ragged(buf, [lengths[i] for i in idx])   # zero behind every row, like ref
+        else:   # the same forward on this batch's wider plan (forward_ragged would plan the batch with the generator's own margin)
+            from . import gen_engine
+
+            enh, bnd = gen_engine.engine_of(generator).forward_ragged(buf, plan)
+            # the losses at the model's rate on the cut clips, as test_step takes them; resampling is for the metrics
+            for key, row in _batch_losses(loss_terms, generator, plan, enh, bnd, ref.reshape(len(idx), 1, plan.l_buf)).items():
+                losses[key].append(row)
         if return_enhanced:
             for r, i in enumerate(idx):
                 enhanced.append(enh[r, 0, : plan.cut[r]].reshape(corrupted[i].shape[:-1] + (plan.cut[r],)).clone())
@@ -195,6 +299,8 @@ def evaluate_clips(generator, corrupted: Sequence[torch.Tensor], reference: Sequ
                 values[name].append(row)
     order = torch.tensor(back, dtype=torch.int64).to(values[names[0]][0].device, non_blocking=True)
     out: Dict[str, object] = {name: torch.cat(values[name]).index_select(0, order) for name in names}
+    for key, rows_of in losses.items():
+        out[key] = torch.cat(rows_of).index_select(0, order)
     if return_enhanced:
         out["enhanced"] = [enhanced[p] for p in back]
     return out

@@ -505,23 +505,33 @@ class EBENLightningModule(BaseSELightningModule):
 
     @torch.no_grad()
     def evaluate_clips(self, corrupted, reference, stage: str = "test", dataloader_idx: int = 0, max_batch_samples: Optional[int] = None,
-                       metrics=("si_sdr", "stoi"), lsd_hf_cutoff_hz: Optional[float] = None):
+                       metrics=("si_sdr", "stoi"), lsd_hf_cutoff_hz: Optional[float] = None, losses: bool = False):
         """A whole split at once: what the reference's batch-1 test loop (one ``test_step`` + ``on_test_batch_end`` per utterance)
         aggregates SI-SDR and STOI to over an epoch, through ``inference.evaluate_clips`` -- ragged batches, metric kernels with a length
         per row.  The per-clip values join the running state of ``self.metrics`` (``compute()`` is the corpus mean) and their means are
         logged as ``{stage}/torchmetrics_si_sdr{suffix}`` / ``{stage}/torchmetrics_stoi{suffix}``.  Returns the per-clip result dict.
-        The atomic losses ``test_step`` logs are not part of this (no ragged discriminators or MRSTFT).  ``metrics`` /
+        With ``losses=True`` the atomic losses ``test_step`` logs join the same pass (``inference.LossTerms`` from this module's
+        discriminator and loss functions: ragged discriminators, per-row feature-matching, hinge and MRSTFT sums): the result holds
+        ``"generator/<name>"`` / ``"discriminator/<name>"``, (N,) per-clip values each, and each term's mean over the clips is logged as
+        ``{stage}/{network}/{name}{suffix}`` -- the reference's epoch value for batches of one.  ``metrics`` /
         ``lsd_hf_cutoff_hz`` as for ``inference.evaluate_clips``: every other metric's corpus mean is logged as ``{stage}/{name}{suffix}``
         and stays out of ``self.metrics``, which mirrors the reference's collection."""
         from .. import inference
 
         budget = inference.MAX_BATCH_SAMPLES if max_batch_samples is None else max_batch_samples
+        terms = None
+        if losses:
+            terms = inference.LossTerms(discriminator=self.discriminator, freq_loss=self.reconstructive_loss_freq_fn or None,
+                                        time_loss=self.reconstructive_loss_temp_fn or None, feature_loss=self.feature_matching_loss_fn or None,
+                                        adversarial_loss=self.adversarial_loss_fn or None)
         out = inference.evaluate_clips(self.generator, corrupted, reference, sample_rate=int(self.sample_rate), max_batch_samples=budget,
-                                       metrics=metrics, lsd_hf_cutoff_hz=lsd_hf_cutoff_hz)
+                                       metrics=metrics, lsd_hf_cutoff_hz=lsd_hf_cutoff_hz, loss_terms=terms)
         names = getattr(self, "dataloader_names", None)
         suffix = f"/{names[dataloader_idx]}" if names is not None else ""
         for name, values in out.items():
-            if name in ("si_sdr", "stoi"):
+            if terms is not None and name in terms.keys():
+                self.log(f"{stage}/{name}{suffix}", values.mean(), sync_dist=True, add_dataloader_idx=False)
+            elif name in ("si_sdr", "stoi"):
                 key = f"torchmetrics_{name}"
                 self.metrics[key]._accumulate(values)
                 self.log(f"{stage}/{key}{suffix}", values.mean(), sync_dist=True, prog_bar=True, add_dataloader_idx=False)

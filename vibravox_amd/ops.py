@@ -1850,3 +1850,100 @@ def mrstft_terms(x: torch.Tensor, y: torch.Tensor, fir: Optional[torch.Tensor], 
     """MultiResolutionSTFTLoss with weights (w_sc, w_log_mag, w_lin_mag), mag_distance L2 (l2) or L1 and the plans' windows and mel
     projections (eben_stft_terms_*); at least one weight non-zero, at most 16 resolutions."""
     return _MRSTFTTermsFn.apply(x, y.detach(), fir, plans, eps, tuple(weights), l2)
+
+
+# --------------------------------------------------------------------------------------------
+# per-row losses over ragged buffers (csrc/ragged_losses.hip): inference only, nothing here waits for the device
+# --------------------------------------------------------------------------------------------
+FILL_ZERO, FILL_MIRROR = 0, 1   # EBEN_FILL_* of include/eben_hip.h
+
+
+def edge_fill(x: torch.Tensor, lens: torch.Tensor, mode: int, count: int) -> None:
+    """``eben_edge_fill`` on (rows, channels, l_buf) ``x`` in place; ``lens``: (rows,) int32 on the device."""
+    rows, channels, l_buf = x.shape
+    check(load().eben_edge_fill(ptr(x), _iptr(lens), rows, channels, l_buf, mode, count, stream()), "edge_fill")
+
+
+def _void_array(addresses):
+    return (ctypes.c_void_p * len(addresses))(*addresses)
+
+
+def fm_sums_rows(pairs, rows: int) -> torch.Tensor:
+    """(npairs, rows, 2) of (sum |a - b|, sum |a|) over each row's valid extent; ``pairs``: (a, b, lens) with a and b (rows, C, l_buf)
+    and lens (rows,) int32 on the device.  At most 32 pairs."""
+    lib, n = load(), len(pairs)
+    addresses = []
+    for a, b, lens in pairs:
+        if a.shape != b.shape or a.dim() != 3 or a.shape[0] != rows or lens.numel() != rows:
+            raise _lib.EbenError(f"fm_sums_rows: pair of {tuple(a.shape)} and {tuple(b.shape)} with {lens.numel()} lengths for {rows} rows")
+        addresses += [ptr(a), ptr(b)]
+    like = pairs[0][0]
+    ws_bytes = lib.eben_fm_sums_rows_workspace(n, rows)
+    ws = _empty(ws_bytes, like)
+    sums = torch.empty((n, rows, 2), dtype=torch.float32, device=like.device)
+    check(lib.eben_fm_sums_rows(_void_array(addresses), (ctypes.c_int * n)(*[a.shape[1] for a, _, _ in pairs]),
+                                (ctypes.c_int * n)(*[a.shape[2] for a, _, _ in pairs]), _void_array([_iptr(lens) for _, _, lens in pairs]), n, rows,
+                                ptr(ws), ws_bytes, ptr(sums), stream()), "fm_sums_rows")
+    return sums
+
+
+def hinge_rows(terms, rows: int) -> torch.Tensor:
+    """(n, rows) of mean max(0, 1 - target x) over each row's valid extent; ``terms``: (x, target, lens) with x (rows, 1, l_buf) logits."""
+    lib, n = load(), len(terms)
+    for x, _, lens in terms:
+        if x.dim() != 3 or x.shape[:2] != (rows, 1) or lens.numel() != rows:
+            raise _lib.EbenError(f"hinge_rows: logits of {tuple(x.shape)} with {lens.numel()} lengths for {rows} rows")
+    out = torch.empty((n, rows), dtype=torch.float32, device=terms[0][0].device)
+    check(lib.eben_hinge_rows(_void_array([ptr(x) for x, _, _ in terms]), (ctypes.c_int * n)(*[x.shape[2] for x, _, _ in terms]),
+                              (ctypes.c_float * n)(*[float(t) for _, t, _ in terms]), _void_array([_iptr(lens) for _, _, lens in terms]), n, rows,
+                              ptr(out), stream()), "hinge_rows")
+    return out
+
+
+def clip_losses(rows: int, device, stft=None, fm=None, hinge=None) -> torch.Tensor:
+    """(5, rows): per row [MRSTFT, feature matching, adv_loss_gen, real_loss, fake_loss] in one launch.  ``stft``: per resolution
+    (sums (rows, 3), frames_of_row (rows,) int32, bins); ``fm``: (sums (npairs, rows, 2), inv_count); ``hinge``: (3 * chains, rows) with
+    term 3 * chain + k, k = adv_loss_gen / real_loss / fake_loss.  A group left out yields NaN."""
+    stft = list(stft or ())
+    n = len(stft)
+    out = torch.empty((5, rows), dtype=torch.float32, device=device)
+    fm_sums, inv = fm if fm is not None else (None, 0.0)
+    check(load().eben_clip_losses(_void_array([ptr(s) for s, _, _ in stft]) if n else None, _void_array([_iptr(f) for _, f, _ in stft]) if n else None,
+                                  (ctypes.c_int * n)(*[int(b) for _, _, b in stft]) if n else None, n, ptr(fm_sums),
+                                  fm_sums.shape[0] if fm_sums is not None else 0, float(inv), ptr(hinge), hinge.shape[0] // 3 if hinge is not None else 0,
+                                  rows, ptr(out), stream()), "clip_losses")
+    return out
+
+
+#: called with the (2 rows, 1, l_buf) A-weighted signal of ``mrstft_sums_rows`` and its row lengths, in front of the mirror fill (tests
+#: write garbage behind the rows there: nothing of it may reach a result)
+mrstft_rows_probe = None
+
+
+def mrstft_sums_rows(x: torch.Tensor, y: torch.Tensor, lens2: torch.Tensor, frames_of_row, fir: Optional[torch.Tensor], plans: List[StftPlan],
+                     eps: float, fill: int) -> List[torch.Tensor]:
+    """Per plan the (rows, 3) sums of ``_MRSTFTFn.forward`` with every row on its own frames: x and y (rows, 1, l_buf), zero behind each
+    row; ``lens2`` (2 rows,) int32 on the device, the row lengths twice; ``frames_of_row[i]`` (rows,) int32, plan i's frames of each row.
+    The FIR's zero padding finds the zeros behind a row, one mirror fill of ``fill`` samples (the largest reflect pad; 0: rows as long
+    as the buffer) stands for every plan's reflect padding, then framing and contraction run on the whole buffer."""
+    lib, st = load(), stream()
+    rows, _, t = x.shape
+    sig = torch.cat((x.reshape(rows, 1, t), y.reshape(rows, 1, t)), dim=0)
+    if fir is not None:
+        nt = fir.numel()
+        sig = _fir_decimate(sig, fir, t, 1, nt, 1, -(nt // 2))
+    if mrstft_rows_probe is not None:
+        mrstft_rows_probe(sig, lens2)
+    if fill:
+        edge_fill(sig, lens2, FILL_MIRROR, fill)
+    out = []
+    for p, fr in zip(plans, frames_of_row):
+        frames = p.frames(t)
+        cols = 2 * rows * frames
+        spec = _stft_spectrum(p, p.math_for(p.math), sig, t, frames)
+        sums = torch.empty((rows, 3), dtype=torch.float32, device=x.device)
+        ws_bytes = lib.eben_stft_loss_sums_rows_workspace(rows)
+        check(lib.eben_stft_loss_sums_rows(ptr(spec), ptr(spec) + 4 * rows * frames, rows, p.bins, frames, _iptr(fr), frames, cols, p.bins * cols, eps,
+                                           ptr(_empty(ws_bytes, x)), ws_bytes, ptr(sums), st), "stft_loss_sums_rows")
+        out.append(sums)
+    return out

@@ -93,3 +93,43 @@ class DiscriminatorEBENMultiScales(nn.Module, PyTorchModelHubMixin):
             for t in scale[1:]:
                 t.record_stream(main)
         return embeddings
+
+    @torch.no_grad()
+    def forward_ragged(self, bands, audio, plan):
+        """Rows of different lengths in one pass (inference): ``bands`` (rows, m, plan.bands_l_buf) and ``audio`` (rows, 1,
+        plan.audio_l_buf) hold row r on ``[0, plan.band_lengths[r])`` / ``[0, plan.cut[r])`` -- usually the enhanced and the reference
+        branch stacked as 2R rows -- with ``plan = ragged.disc_plan(self, ...)``.  Returns ``(embeddings, lens)``: ``forward``'s
+        lists, every row equal to its own batch-1 forward on ``[0, lens[chain][level, row])`` (device int32, level 0 the input) and
+        junk behind.  In front of each layer the plan's ``eben_edge_fill`` calls run on that layer's input, then the layer's ordinary
+        module; the inputs are copied first, so the caller's ``bands`` and ``audio`` stay as they are."""
+        from ... import ops, ragged
+
+        rows = len(plan.cut)
+        if (bands.dim() != 3 or audio.dim() != 3 or bands.shape[0] != rows or bands.shape[2] != plan.bands_l_buf or bands.shape[1] < self.q
+                or audio.shape != (rows, 1, plan.audio_l_buf)):
+            raise ValueError(f"forward_ragged: expected ({rows}, >= {self.q}, {plan.bands_l_buf}) bands and ({rows}, 1, {plan.audio_l_buf}) audio "
+                             f"for this plan, got {tuple(bands.shape)} and {tuple(audio.shape)}")
+        nets = list(self.pqmf_discriminators) + [self.melgan_discriminator]
+        tables = [plan.lengths(c) for c in range(len(plan.chains))]
+        flat = torch.tensor([row for table in tables for row in table], dtype=torch.int32).to(bands.device, non_blocking=True)   # the one upload
+        lens, at = [], 0
+        for table in tables:
+            lens.append(flat[at : at + len(table)])
+            at += len(table)
+        sub = bands[:, -self.q :, :]
+        if not plan.ragged:   # equal rows need no fill: the batched forward
+            return [net(x) for net, x in zip(nets, (sub, sub, sub, audio))], lens
+        sub, audio = sub.clone(memory_format=torch.contiguous_format), audio.clone(memory_format=torch.contiguous_format)
+        modes = {ragged.ZERO: ops.FILL_ZERO, ragged.MIRROR: ops.FILL_MIRROR}
+        embeddings = []
+        for c, (net, x) in enumerate(zip(nets, (sub, sub, sub, audio))):
+            chain = [x]
+            for level, (layer, module) in enumerate(zip(plan.chains[c], net.discriminator)):
+                if x.shape[2] != layer.in_buffer:
+                    raise RuntimeError(f"ragged plan out of step with the forward: {layer.path} on {tuple(x.shape)}")
+                for mode, count in layer.fills:
+                    ops.edge_fill(x, lens[c][level], modes[mode], count)
+                x = module(x)
+                chain.append(x)
+            embeddings.append(chain)
+        return embeddings, lens

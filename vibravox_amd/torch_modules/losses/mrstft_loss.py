@@ -260,3 +260,49 @@ class MultiResolutionSTFTLoss(torch.nn.Module):
         if self.default_terms:
             return ops.mrstft(x, y, self.fir, self._plans, self.eps)
         return ops.mrstft_terms(x, y, self.fir, self._plans, self.eps, (self.w_sc, self.w_log_mag, self.w_lin_mag), self.mag_distance == "L2")
+
+    def ragged_sums(self, x: torch.Tensor, y: torch.Tensor, lengths: Sequence[int]):
+        """The per-row sums behind ``forward_ragged``: per resolution (sums (rows, 3), frames_of_row (rows,) int32 on the device, bins),
+        what ``ops.clip_losses`` takes.  Checks everything ``forward_ragged`` refuses before anything runs."""
+        if self.stft_math not in ("folded", "dense", "bf16x3", "folded_x3", "folded_x6"):
+            raise ValueError(f"unknown STFT math {self.stft_math!r}")
+        if not (self.w_sc == 1.0 and self.w_log_mag == 1.0 and not self.w_lin_mag and self.mag_distance == "L1" and self.scale is None):
+            raise NotImplementedError(
+                f"forward_ragged is built for the multi_stft.yaml term set (w_sc = w_log_mag = 1, L1, no scale; any window), not for w_sc="
+                f"{self.w_sc}, w_log_mag={self.w_log_mag}, w_lin_mag={self.w_lin_mag}, mag_distance={self.mag_distance!r}, scale={self.scale!r}")
+        if len(self.fft_sizes) > 8:
+            raise NotImplementedError("forward_ragged: at most 8 resolutions")
+        if torch.is_grad_enabled() and (x.requires_grad or y.requires_grad):
+            raise RuntimeError("MultiResolutionSTFTLoss.forward_ragged has no backward; its inputs must not require grad")
+        if x.dim() != 3 or x.shape[1] != 1 or x.shape != y.shape or x.dtype is not torch.float32 or y.dtype is not torch.float32:
+            raise ValueError(f"forward_ragged: expected two float32 (rows, 1, l_buf) buffers, got {tuple(x.shape)} and {tuple(y.shape)}")
+        rows, _, l_buf = x.shape
+        lengths = [int(t) for t in lengths]
+        if len(lengths) != rows:
+            raise ValueError(f"forward_ragged: {len(lengths)} lengths for {rows} rows")
+        if self._plans is None or self._plans[0].basis_f.device != x.device or self._plans[0].basis_f.data_ptr() != self.basis_0.data_ptr():
+            self._plans = self._build_plans()
+        pad = max(p.pad for p in self._plans)
+        for r, t in enumerate(lengths):
+            if t < pad + 1:
+                raise ValueError(f"clip {r} ({t} samples) is too short: the STFT reflect-pads {pad} samples")
+            if t > l_buf or (t < l_buf and t + pad > l_buf):
+                raise ValueError(f"clip {r} ({t} samples) needs {pad} samples of slack behind it in a buffer of {l_buf}, or none at all")
+        for p in self._plans:
+            p.math = self.stft_math
+        with torch.no_grad():
+            host = torch.tensor([lengths + lengths] + [[p.frames(t) for t in lengths] * 2 for p in self._plans], dtype=torch.int32)
+            table = host.to(x.device, non_blocking=True)   # the one upload: row lengths, then every resolution's frames per row
+            frames = [table[1 + i, :rows] for i in range(len(self._plans))]
+            fill = pad if any(t < l_buf for t in lengths) else 0
+            sums = ops.mrstft_sums_rows(x.contiguous(), y.contiguous(), table[0], frames, self.fir, self._plans, self.eps, fill)
+        return [(s, f, p.bins) for s, f, p in zip(sums, frames, self._plans)]
+
+    def forward_ragged(self, x: torch.Tensor, y: torch.Tensor, lengths: Sequence[int]) -> torch.Tensor:
+        """(rows,) float32: row r is ``forward(x[r:r+1, :, :lengths[r]], y[r:r+1, :, :lengths[r]])``, all rows in one pass.  ``x`` and ``y``
+        are (rows, 1, l_buf) and zero behind every row; a row shorter than the buffer needs the largest reflect pad of slack behind it.
+        Inference only: no gradient is returned and inputs that require grad are refused.  Built for the multi_stft.yaml term set (SC +
+        log-magnitude L1, linear scale) at any resolutions and ``perceptual_weighting``; every other term set raises NotImplementedError."""
+        terms = self.ragged_sums(x, y, lengths)
+        with torch.no_grad():
+            return ops.clip_losses(x.shape[0], x.device, stft=terms)[0]
