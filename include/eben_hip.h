@@ -720,6 +720,28 @@ EBEN_API int eben_stream_splice_rows(float* dst, int dst_pitch, const float* pre
                                      int dst_compact, void* stream);
 EBEN_API int eben_copy_segments(const EbenCopySegment* segments, int count, void* stream);
 
+/* ---- input at the recording's rate (csrc/rate.hip): eben_resample's arithmetic on ragged rows and on a stream's tape -----------------
+ * y[q * nw + p] = sum_{j < taps} kernels[p][j] * x[q * orig + j - width], taps = 2 * width + orig, fp32 fmaf in ascending j, every
+ * index outside the signal skipped: a row's or a stream's result is bit for bit eben_resample's on the whole signal alone.
+ * A row's buffer holds the samples [pos0, pos0 + len) of a signal that starts at stream position 0 (pos0 stays with the caller); all
+ * indices handed over are buffer-relative.  Indices below 0 and at or behind len read as zero; len is clamped into [0, row pitch], so
+ * nothing outside a row's buffer is read whatever a length table holds.
+ *   eben_resample_ragged  rows of l_in_buf floats with lens[r] samples each (int32 device table) -> rows of l_out_buf floats: row r gets
+ *     its ceil(nw * len / orig) outputs, exact zeros behind them up to l_out_buf, and that count in out_lens[r] (int32 device table).
+ *   eben_resample_stream  a tape [carry | chunk] of len samples per row (pitch tape_pitch) -> out[r, first_out + n], n < n_out.  Output n
+ *     has phase (p0 + n) % nw and its tap 0 at buffer index base0 + ((p0 + n) / nw) * orig, base0 = q0 * orig - width - pos0.  end != 0:
+ *     the tape's right end is the signal's own (zeros behind it); else every tap of every output must lie inside the tape.
+ *   eben_resample_plan    the tile of a ratio, without launching: out[0..3] (n >= 4) = values of q per block, outputs per block, floats
+ *     of the input window staged in LDS, 1 when the table is staged too (nw * taps floats fit its budget) else 0 (read through L2).
+ * EBEN_EINVAL before any launch for a null or misaligned-to-4 pointer, rows outside 1 ... 65535, a ratio whose taps fit no tile,
+ * l_out_buf below ceil(nw * l_in_buf / orig), a length or a range of outputs past its pitch, a phase outside [0, nw), or n_out reaching
+ * past what the tape can serve.  n_out == 0 returns EBEN_OK without a launch.  Added without a version bump: functions only. */
+EBEN_API int eben_resample_plan(int orig, int nw, int width, int* out, int n);
+EBEN_API int eben_resample_ragged(const float* x, const int32_t* lens, const float* kernels, float* out, int32_t* out_lens, int rows,
+                                  int l_in_buf, int l_out_buf, int orig, int nw, int width, void* stream);
+EBEN_API int eben_resample_stream(const float* tape, const float* kernels, float* out, int rows, int tape_pitch, int len, int out_pitch,
+                                  int first_out, int n_out, int p0, int base0, int end, int orig, int nw, int width, void* stream);
+
 /* ---- misc ------------------------------------------------------------------------------- */
 /* out[0] = sqrt(sum x^2) (torch.norm at eben.py:226); `out` must hold 257 floats (scratch) */
 EBEN_API int eben_l2norm(const float* x, size_t n, float* out, void* stream);

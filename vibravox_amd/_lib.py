@@ -243,6 +243,9 @@ SIGNATURES = {
     "eben_stream_splice_rows": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P, c_int, c_int, _P, c_int, c_int, c_int,
                                         POINTER(ctypes.c_uint64), c_int, c_int, _P]),
     "eben_copy_segments": (c_int, [POINTER(EbenCopySegment), c_int, _P]),
+    "eben_resample_plan": (c_int, [c_int, c_int, c_int, POINTER(c_int), c_int]),
+    "eben_resample_ragged": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "eben_resample_stream": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -1,0 +1,233 @@
+// Input at the recording's rate: windowed-sinc resampling of ragged rows and of a stream's tape, on one kernel family.
+//
+// The arithmetic is eben_resample's (direct.hip), unchanged: with the rates reduced to orig : nw and taps = 2 * width + orig,
+//
+//   y[q * nw + p] = sum_{j < taps} kernels[p][j] * x[q * orig + j - width]        fp32, fmaf, ascending j, indices outside the signal skipped
+//
+// so a row's result is bit for bit what eben_resample gives on that row alone.  (A skipped index and a staged zero are the same thing:
+// the accumulator starts at +0 and is never -0, so fmaf(k, 0, acc) == acc for every finite k.  The staging substitutes the zero by INDEX,
+// never by value: what lies outside a row may be NaN.)
+//
+// Buffer view.  A row's buffer holds the samples [pos0, pos0 + len) of a signal that starts at stream position 0; pos0 itself stays on
+// the host.  The launch gets the phase p0 of its first output and the buffer index base0 of that output's tap 0
+// (q0 * orig - width - pos0); output n of the launch is g = p0 + n in the launch's own phase grid, q = g / nw, p = g % nw, its tap j at
+// buffer index base0 + q * orig + j.  Indices below 0 or at / behind len are zero; every index is a buffer-relative 32-bit value.  len
+// is clamped into [0, l_in_buf] whatever the table holds: nothing outside [0, l_in_buf) of a row is ever read.
+//
+// Kernel shape.  A block owns RATE_TQ(orig, nw, taps) values of q of one row = TQ * nw outputs (at most RATE_TILE_OUT, four per thread),
+// stages their TQ * orig + taps - 1 input samples into LDS once -- 16-byte loads over the part of the window that is aligned in memory
+// and lies inside the row, the LDS copy shifted so that those land on 16-byte LDS slots -- and the table beside them when nw * taps fits
+// RATE_TABLE_FLOATS (48 k -> 16 k: 41 floats; 44.1 k -> 16 k: 160 x 475 floats do not fit and are read through L2).  With nw == 1 the four
+// outputs of a thread share each table value.  eben_resample_plan tells the tile constants without launching anything.
+#include "common.h"
+
+namespace eben {
+namespace {
+
+constexpr int RATE_THREADS = 256;
+constexpr int RATE_PER_THREAD = 4;
+constexpr int RATE_TILE_OUT = RATE_THREADS * RATE_PER_THREAD;   // outputs per block at most
+constexpr int RATE_WINDOW_FLOATS = 4096;                        // LDS budget of the input window ...
+constexpr int RATE_TABLE_FLOATS = 2048;                         // ... and of the table
+constexpr int RATE_MAX_SAMPLES = 0x7fff0000;                    // per row: every index plus a tile stays inside int32
+
+struct RateArgs {
+  const float* x;          // rows of in_pitch floats
+  const float* kernels;    // (nw, taps)
+  float* out;              // rows of out_pitch floats
+  const int* lens;         // per-row length (ragged) or null: `len` for every row
+  int* out_lens;           // ragged: receives ceil(nw * len / orig) per row; else null
+  int len, in_pitch, out_pitch;
+  int orig, nw, taps, tq;
+  int p0, base0;           // phase of output 0 and buffer index of its tap 0
+  int first_out, n_out;    // outputs go to out[first_out + n], n < n_out (ragged: n_out per row from its length)
+  int fill_to;             // exact zeros to out[first_out + n] for n_out <= n < fill_to (0: none)
+};
+
+// TABLE: 0 = table through L2, 1 = table in LDS, 2 = table in LDS and nw == 1 (one value per tap for all outputs of a thread)
+template <int TABLE>
+__global__ __launch_bounds__(RATE_THREADS) void rate_kernel(RateArgs a) {
+  __shared__ __attribute__((aligned(16))) float win_raw[RATE_WINDOW_FLOATS + 4];
+  __shared__ float tab[TABLE ? RATE_TABLE_FLOATS : 1];
+  const int t = threadIdx.x, r = blockIdx.y;
+  const int orig = a.orig, nw = a.nw, taps = a.taps;
+  int len = a.len, n_out = a.n_out;
+  if (a.lens) {
+    len = a.lens[r];
+    len = len < 0 ? 0 : len > a.in_pitch ? a.in_pitch : len;
+    n_out = (int)(((long long)nw * len + orig - 1) / orig);   // <= out_pitch: the entry checked the pitch against in_pitch
+    if (blockIdx.x == 0 && t == 0) a.out_lens[r] = n_out;
+  }
+  const int to = a.tq * nw;              // outputs of a tile
+  const int g0 = blockIdx.x * to;        // the tile's first place in the launch's phase grid
+  float* o = a.out + (long long)r * a.out_pitch + a.first_out;
+  const int n_lo = g0 - a.p0;            // output index of the tile's place 0 (below 0 in the first tile when p0 > 0)
+  if (n_lo >= n_out) {                   // nothing to compute: the slack behind the row
+    for (int i = 0; i < RATE_PER_THREAD; ++i) {
+      const int n = n_lo + t + RATE_THREADS * i;
+      if (t + RATE_THREADS * i < to && n < a.fill_to) o[n] = 0.f;
+    }
+    return;
+  }
+  // ---- stage the window: buffer indices [w0, w0 + wlen), zero outside [0, len) -----------------------------------------------------
+  const float* xr = a.x + (long long)r * a.in_pitch;
+  const int w0 = a.base0 + blockIdx.x * a.tq * orig;
+  const int wlen = a.tq * orig + taps - 1;
+  // floats in front of the first 16-byte boundary of memory; the LDS copy starts (4 - head) & 3 floats in, so that boundary is a slot
+  const int head = (int)((0u - (unsigned)(((unsigned long long)reinterpret_cast<uintptr_t>(xr) >> 2) + (unsigned long long)(long long)w0)) & 3u);
+  float* win = win_raw + ((4 - head) & 3);
+  if (t < head && t < wlen) {
+    const int i = w0 + t;
+    win[t] = (i >= 0 && i < len) ? xr[i] : 0.f;
+  }
+  const int nvec = wlen > head ? (wlen - head) >> 2 : 0;
+  for (int v = t; v < nvec; v += RATE_THREADS) {
+    const int s = head + 4 * v, i = w0 + s;
+    float4 q;
+    if (i >= 0 && i + 3 < len) {
+      q = *reinterpret_cast<const float4*>(xr + i);
+    } else {
+      q.x = (i >= 0 && i < len) ? xr[i] : 0.f;
+      q.y = (i + 1 >= 0 && i + 1 < len) ? xr[i + 1] : 0.f;
+      q.z = (i + 2 >= 0 && i + 2 < len) ? xr[i + 2] : 0.f;
+      q.w = (i + 3 >= 0 && i + 3 < len) ? xr[i + 3] : 0.f;
+    }
+    *reinterpret_cast<float4*>(win + s) = q;
+  }
+  {
+    const int s = head + 4 * nvec + t;   // at most 3 left
+    if (s >= head && s < wlen) {
+      const int i = w0 + s;
+      win[s] = (i >= 0 && i < len) ? xr[i] : 0.f;
+    }
+  }
+  if (TABLE) {
+    const int nt = nw * taps;
+    for (int s = t; s < nt; s += RATE_THREADS) tab[s] = a.kernels[s];
+  }
+  __syncthreads();
+  // ---- four outputs per thread, RATE_THREADS apart: consecutive lanes consecutive outputs -------------------------------------------
+  int xo[RATE_PER_THREAD], ko[RATE_PER_THREAD];
+  bool live[RATE_PER_THREAD];
+#pragma unroll
+  for (int i = 0; i < RATE_PER_THREAD; ++i) {
+    const int place = t + RATE_THREADS * i, n = n_lo + place;
+    live[i] = place < to && n >= 0 && n < n_out;
+    const int ql = live[i] ? place / nw : 0;
+    xo[i] = ql * orig;
+    ko[i] = live[i] ? (place - ql * nw) * taps : 0;
+  }
+  float acc[RATE_PER_THREAD] = {0.f, 0.f, 0.f, 0.f};
+  if (TABLE == 2) {
+    for (int j = 0; j < taps; ++j) {
+      const float k = tab[j];
+#pragma unroll
+      for (int i = 0; i < RATE_PER_THREAD; ++i) acc[i] = fmaf(k, win[xo[i] + j], acc[i]);
+    }
+  } else {
+    const float* kt = TABLE ? tab : a.kernels;
+    for (int j = 0; j < taps; ++j) {
+#pragma unroll
+      for (int i = 0; i < RATE_PER_THREAD; ++i) acc[i] = fmaf(kt[ko[i] + j], win[xo[i] + j], acc[i]);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < RATE_PER_THREAD; ++i) {
+    const int place = t + RATE_THREADS * i, n = n_lo + place;
+    if (live[i])
+      o[n] = acc[i];
+    else if (place < to && n >= n_out && n < a.fill_to)
+      o[n] = 0.f;
+  }
+}
+
+// values of q per tile: as many as RATE_TILE_OUT outputs and the window budget allow; 0 when not even one fits
+inline int rate_tq(int orig, int nw, int taps) {
+  const long long by_out = RATE_TILE_OUT / nw, by_win = ((long long)RATE_WINDOW_FLOATS - (taps - 1)) / orig;
+  const long long tq = by_out < by_win ? by_out : by_win;
+  return tq < 1 ? 0 : (int)tq;
+}
+
+int check_ratio(const char* what, int orig, int nw, int width, int* taps, int* tq) {
+  EBEN_REQUIRE(orig > 0 && nw > 0 && width >= 0, "%s: ratio %d : %d, width %d", what, orig, nw, width);
+  const long long tp = 2LL * width + orig;
+  EBEN_REQUIRE(tp <= RATE_WINDOW_FLOATS && nw <= RATE_TILE_OUT && rate_tq(orig, nw, (int)tp) >= 1,
+               "%s: the ratio %d : %d with %lld taps fits no tile (window of %d floats, %d outputs)", what, orig, nw, tp, RATE_WINDOW_FLOATS, RATE_TILE_OUT);
+  *taps = (int)tp;
+  *tq = rate_tq(orig, nw, (int)tp);
+  return EBEN_OK;
+}
+
+int launch_rate(const RateArgs& a, int rows, long long places, void* stream, const char* what) {
+  const long long tiles = (places + (long long)a.tq * a.nw - 1) / ((long long)a.tq * a.nw);
+  EBEN_REQUIRE(tiles >= 1 && tiles <= 0x7fffffffLL, "%s: grid of %lld tiles", what, tiles);
+  const dim3 grid((unsigned)tiles, (unsigned)rows), block(RATE_THREADS);
+  const bool in_lds = (long long)a.nw * a.taps <= RATE_TABLE_FLOATS;
+  if (!in_lds)
+    hipLaunchKernelGGL(rate_kernel<0>, grid, block, 0, as_stream(stream), a);
+  else if (a.nw == 1)
+    hipLaunchKernelGGL(rate_kernel<2>, grid, block, 0, as_stream(stream), a);
+  else
+    hipLaunchKernelGGL(rate_kernel<1>, grid, block, 0, as_stream(stream), a);
+  EBEN_CHECK_LAUNCH("rate_kernel");
+  return EBEN_OK;
+}
+
+inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
+
+}  // namespace
+}  // namespace eben
+
+using namespace eben;
+
+extern "C" int eben_resample_plan(int orig, int nw, int width, int* out, int n) {
+  EBEN_REQUIRE(out && n >= 4, "resample_plan: needs room for 4 values");
+  int taps = 0, tq = 0;
+  if (int rc = check_ratio("resample_plan", orig, nw, width, &taps, &tq)) return rc;
+  out[0] = tq;
+  out[1] = tq * nw;
+  out[2] = tq * orig + taps - 1;
+  out[3] = (long long)nw * taps <= RATE_TABLE_FLOATS ? 1 : 0;
+  return EBEN_OK;
+}
+
+extern "C" int eben_resample_ragged(const float* x, const int32_t* lens, const float* kernels, float* out, int32_t* out_lens, int rows,
+                                    int l_in_buf, int l_out_buf, int orig, int nw, int width, void* stream) {
+  EBEN_REQUIRE(x && lens && kernels && out && out_lens, "resample_ragged: null pointer");
+  EBEN_REQUIRE(aligned4(x) && aligned4(lens) && aligned4(kernels) && aligned4(out) && aligned4(out_lens), "resample_ragged: misaligned pointer");
+  EBEN_REQUIRE(rows > 0 && rows <= 65535, "resample_ragged: %d rows (1 ... 65535)", rows);
+  int taps = 0, tq = 0;
+  if (int rc = check_ratio("resample_ragged", orig, nw, width, &taps, &tq)) return rc;
+  EBEN_REQUIRE(l_in_buf > 0 && l_in_buf <= RATE_MAX_SAMPLES && l_out_buf > 0 && l_out_buf <= RATE_MAX_SAMPLES,
+               "resample_ragged: rows of %d samples in, %d out (1 ... %d)", l_in_buf, l_out_buf, RATE_MAX_SAMPLES);
+  const long long need = ((long long)nw * l_in_buf + orig - 1) / orig;
+  EBEN_REQUIRE(l_out_buf >= need, "resample_ragged: l_out_buf %d below ceil(%d * %d / %d) = %lld", l_out_buf, nw, l_in_buf, orig, need);
+  RateArgs a{x, kernels, out, lens, out_lens, 0, l_in_buf, l_out_buf, orig, nw, taps, tq, 0, -width, 0, 0, l_out_buf};
+  return launch_rate(a, rows, l_out_buf, stream, "resample_ragged");
+}
+
+extern "C" int eben_resample_stream(const float* tape, const float* kernels, float* out, int rows, int tape_pitch, int len, int out_pitch,
+                                    int first_out, int n_out, int p0, int base0, int end, int orig, int nw, int width, void* stream) {
+  EBEN_REQUIRE(tape && kernels && out, "resample_stream: null pointer");
+  EBEN_REQUIRE(aligned4(tape) && aligned4(kernels) && aligned4(out), "resample_stream: misaligned pointer");
+  EBEN_REQUIRE(rows > 0 && rows <= 65535, "resample_stream: %d rows (1 ... 65535)", rows);
+  int taps = 0, tq = 0;
+  if (int rc = check_ratio("resample_stream", orig, nw, width, &taps, &tq)) return rc;
+  EBEN_REQUIRE(tape_pitch > 0 && tape_pitch <= RATE_MAX_SAMPLES && len >= 0 && len <= tape_pitch, "resample_stream: a tape of %d samples at pitch %d", len,
+               tape_pitch);
+  EBEN_REQUIRE(out_pitch > 0 && out_pitch <= RATE_MAX_SAMPLES && first_out >= 0 && n_out >= 0 && (long long)first_out + n_out <= out_pitch,
+               "resample_stream: outputs [%d, %d + %d) past the pitch %d", first_out, first_out, n_out, out_pitch);
+  EBEN_REQUIRE(p0 >= 0 && p0 < nw, "resample_stream: phase %d of %d", p0, nw);
+  EBEN_REQUIRE(base0 >= -RATE_MAX_SAMPLES && base0 <= RATE_MAX_SAMPLES, "resample_stream: base index %d", base0);
+  if (n_out == 0) return EBEN_OK;
+  const long long g_last = (long long)p0 + n_out - 1, q_last = g_last / nw, p_last = g_last - q_last * nw;
+  const long long base_last = base0 + q_last * orig;
+  EBEN_REQUIRE(base_last + taps <= (long long)RATE_MAX_SAMPLES, "resample_stream: the last output's taps start at %lld", base_last);
+  if (end)   // the right end is the signal's own: output n exists when n * orig < nw * total, in buffer terms
+    EBEN_REQUIRE((base_last + width) * nw + p_last * orig < (long long)nw * len, "resample_stream: %d outputs reach past the signal's %d samples", n_out, len);
+  else       // the signal goes on: every tap of every output lies inside the tape
+    EBEN_REQUIRE(base_last + taps <= len, "resample_stream: %d outputs read up to index %lld of a tape of %d that is not the signal's end", n_out,
+                 base_last + taps - 1, len);
+  RateArgs a{tape, kernels, out, nullptr, nullptr, len, tape_pitch, out_pitch, orig, nw, taps, tq, p0, base0, first_out, n_out, 0};
+  return launch_rate(a, rows, (long long)p0 + n_out, stream, "resample_stream");
+}

@@ -6,6 +6,10 @@ each batch goes through ``EBENGenerator.forward_ragged`` -- every clip's result 
 
 ``evaluate_clips`` scores such a corpus against its references the same way (the reference's ``trainer.test`` does it with batches of
 one): per batch one ragged forward and the SI-SDR / STOI kernels with a length per row, straight from the padded buffers.
+
+Recordings at another rate than the model's (the reference's script resamples 48 kHz to 16 kHz in front of every forward) enter
+through ``input_rate=``: one ``rate.resample_ragged`` launch per batch writes the generator's padded buffer, and ``enhance_stream``
+resamples with carried state.
 """
 from __future__ import annotations
 
@@ -35,22 +39,36 @@ MAX_BATCH_SAMPLES = 1 << 22
 STREAM_CHUNK = 16384
 
 
+def _rated(input_rate, model_rate) -> bool:
+    """Whether clips at ``input_rate`` need resampling to reach the model: not without an ``input_rate``, not at the model's own."""
+    if input_rate is None:
+        return False
+    if int(input_rate) <= 0 or int(model_rate) <= 0:
+        raise ValueError(f"input_rate and model_rate must be positive, got {input_rate} and {model_rate}")
+    return int(input_rate) != int(model_rate)
+
+
 @torch.no_grad()
-def enhance_stream(generator, clip: torch.Tensor, chunk_samples: int = STREAM_CHUNK):
+def enhance_stream(generator, clip: torch.Tensor, chunk_samples: int = STREAM_CHUNK, input_rate: Optional[int] = None, model_rate: int = 16000):
     """One long ``clip`` (rows, 1, T) through a ``streaming.StreamingEnhancer`` in pushes of ``chunk_samples``: the activations alive at
     any time are those of one chunk plus the stream state, not those of the whole recording.  Returns what
     ``generator(generator.cut_to_valid_length(clip))`` returns, (enhanced (rows, 1, T'), bands (rows, m, L)).  Nothing here waits for
-    the device."""
+    the device.  With ``input_rate`` the clip is at that rate and enters in pushes of ``chunk_samples`` model-rate samples' worth
+    (``StreamingEnhancer.input_chunk_samples``); the result is that of ``augment.resample(clip, input_rate, model_rate)``, at the
+    model's rate."""
     from . import streaming
 
     if clip.dim() != 3 or clip.shape[1] != 1 or clip.dtype is not torch.float32:
         raise ValueError(f"enhance_stream: expected a float32 (rows, 1, T) tensor, got {clip.dtype} {tuple(clip.shape)}")
     rows, _, total = clip.shape
     m = generator.pqmf.decimation
-    ragged.plan(generator, [total])   # refuses a clip below the shortest one before anything runs
-    cut = ragged.cut_length(generator, total)
-    enhancer = streaming.StreamingEnhancer(generator, chunk_samples, streams=rows, return_bands=True)
-    chunk = enhancer.chunk_samples
+    rated = _rated(input_rate, model_rate)
+    at_model = resampled_length(total, input_rate, model_rate) if rated else total
+    ragged.plan(generator, [at_model])   # refuses a clip below the shortest one before anything runs
+    cut = ragged.cut_length(generator, at_model)
+    enhancer = streaming.StreamingEnhancer(generator, chunk_samples, streams=rows, return_bands=True, input_rate=input_rate if rated else None,
+                                           model_rate=model_rate)
+    chunk = enhancer.input_chunk_samples
     enhanced = torch.empty((rows, 1, cut), dtype=torch.float32, device=clip.device)
     bands = torch.empty((rows, m, (cut + generator.pqmf.kernel_size) // m), dtype=torch.float32, device=clip.device)
     pos = done_e = done_b = 0
@@ -67,24 +85,51 @@ def enhance_stream(generator, clip: torch.Tensor, chunk_samples: int = STREAM_CH
     return enhanced, bands
 
 
+def _resampled_rows(clips, idx, l_buf: int, input_rate: int, model_rate: int) -> torch.Tensor:
+    """The clips ``idx``, at ``input_rate``, as rows at ``model_rate``: packed raw into one padded buffer and resampled by ONE
+    ``rate.resample_ragged`` launch into a (rows, 1, >= l_buf) buffer -- row r starts with ``augment.resample`` of its clip alone and is
+    zero behind it.  The buffer is ``l_buf`` wide unless the longest clip resamples to more (rows of equal cut lengths: no margin)."""
+    from . import rate
+
+    raw_lengths = [clips[i].shape[-1] for i in idx]
+    device = clips[idx[0]].device
+    raw = torch.empty((len(idx), 1, max(raw_lengths)), dtype=torch.float32, device=device)   # what lies behind a row is never read
+    for r, i in enumerate(idx):
+        raw[r, 0, : raw_lengths[r]].copy_(clips[i].reshape(-1))
+    width = max(l_buf, resampled_length(raw.shape[2], input_rate, model_rate))
+    out = torch.empty((len(idx), 1, width), dtype=torch.float32, device=device)
+    rate.resample_ragged(raw, raw_lengths, input_rate, model_rate, out=out)
+    return out
+
+
 @torch.no_grad()
-def enhance_clips(generator, clips: Sequence[torch.Tensor], *, max_batch_samples: int = MAX_BATCH_SAMPLES, return_bands: bool = False):
+def enhance_clips(generator, clips: Sequence[torch.Tensor], *, max_batch_samples: int = MAX_BATCH_SAMPLES, return_bands: bool = False,
+                  input_rate: Optional[int] = None, model_rate: int = 16000):
     """``clips``: 1-D, (1, T) or (1, 1, T) float32 tensors on the generator's device.  Returns the enhanced clips in input order, each
     ``cut_to_valid_length`` long and of its clip's rank; with ``return_bands`` also the list of their (m, L) enhanced bands.  Nothing
-    here waits for the device: packing and unpacking are copies on the current stream."""
+    here waits for the device: packing and unpacking are copies on the current stream.
+
+    ``input_rate``: the clips are at that rate (the reference's script resamples 48 kHz recordings in front of the model); they are
+    packed raw, the batches are composed on their lengths at ``model_rate``, and one ``rate.resample_ragged`` launch per batch writes
+    the generator's input buffer.  The results are at the model's rate: those of ``enhance_clips`` on ``augment.resample(clip,
+    input_rate, model_rate)``, bit for bit."""
     clips = list(clips)
     for i, c in enumerate(clips):
         if c.dim() not in (1, 2, 3) or c.numel() != c.shape[-1] or c.dtype is not torch.float32:
             raise ValueError(f"clip {i}: expected a float32 tensor of shape (T,), (1, T) or (1, 1, T), got {c.dtype} {tuple(c.shape)}")
-    lengths = [c.shape[-1] for c in clips]
+    rated = _rated(input_rate, model_rate)
+    lengths = [resampled_length(c.shape[-1], input_rate, model_rate) if rated else c.shape[-1] for c in clips]
     batches, back = ragged.compose_batches(generator, lengths, max_batch_samples)
     enhanced: List[torch.Tensor] = []
     bands: List[torch.Tensor] = []
     for idx in batches:
         plan = ragged.plan(generator, [lengths[i] for i in idx])
-        buf = torch.zeros((len(idx), 1, plan.l_buf), dtype=torch.float32, device=clips[idx[0]].device)
-        for r, i in enumerate(idx):
-            buf[r, 0, : plan.cut[r]].copy_(clips[i].reshape(-1)[: plan.cut[r]])
+        if rated:
+            buf = _resampled_rows(clips, idx, plan.l_buf, input_rate, model_rate)
+        else:
+            buf = torch.zeros((len(idx), 1, plan.l_buf), dtype=torch.float32, device=clips[idx[0]].device)
+            for r, i in enumerate(idx):
+                buf[r, 0, : plan.cut[r]].copy_(clips[i].reshape(-1)[: plan.cut[r]])
         enh, bnd = generator.forward_ragged(buf, [lengths[i] for i in idx])
         for r, i in enumerate(idx):
             enhanced.append(enh[r, 0, : plan.cut[r]].reshape(clips[i].shape[:-1] + (plan.cut[r],)).clone())
@@ -99,6 +144,15 @@ def resampled_length(length: int, orig_freq: int, new_freq: int) -> int:
     g = math.gcd(int(orig_freq), int(new_freq))
     orig, new = int(orig_freq) // g, int(new_freq) // g
     return -(-new * int(length) // orig)
+
+
+def _zero_behind(x: torch.Tensor, lengths: Sequence[int]) -> None:
+    """``x`` (rows, l_buf): exact zeros behind ``lengths[r]`` in every row, in place (one launch)."""
+    from ._lib import check, load, ptr, stream
+
+    rows, l_buf = x.shape
+    lens = torch.tensor(list(lengths), dtype=torch.int32).to(x.device, non_blocking=True)
+    check(load().eben_edge_zero(ptr(x), lens.data_ptr(), rows, 1, l_buf, stream()), "edge_zero")
 
 
 def _check_clip(c, what: str) -> None:
@@ -181,7 +235,7 @@ def _batch_losses(terms: LossTerms, generator, plan, enh: torch.Tensor, bnd: tor
 def evaluate_clips(generator, corrupted: Sequence[torch.Tensor], reference: Sequence[torch.Tensor], *, sample_rate: int = EVAL_RATE,
                    max_batch_samples: int = MAX_BATCH_SAMPLES, return_enhanced: bool = False,
                    metrics: Sequence[str] = DEFAULT_EVAL_METRICS, lsd_hf_cutoff_hz: Optional[float] = None,
-                   loss_terms: Optional[LossTerms] = None) -> Dict[str, object]:
+                   loss_terms: Optional[LossTerms] = None, input_rate: Optional[int] = None) -> Dict[str, object]:
     """Per-clip SI-SDR and STOI of the enhanced ``corrupted[i]`` against ``reference[i]``, at 16 kHz as ``base_se.py`` logs them:
     ``{"si_sdr": (N,) float32, "stoi": (N,) float32}`` on the device, in input order; with ``return_enhanced`` also ``"enhanced"``, the
     list ``enhance_clips`` returns.  ``metrics`` selects among ``EVAL_METRICS``, one key each, all on the same 16 kHz buffers and lengths;
@@ -196,7 +250,11 @@ def evaluate_clips(generator, corrupted: Sequence[torch.Tensor], reference: Sequ
     ``"discriminator/<name>"`` (``LossTerms.keys()``: the terms ``compute_atomic_losses`` would produce for that configuration), each
     (N,) float32 on the device in input order, each value what the clip's own batch of one gives.  They are taken at the model's rate
     on the cut clips.  The batches are then planned with the margin the discriminators and the STFT need behind a row
-    (``ragged.loss_margin``); a clip too short for the discriminator's or the STFT's own call is refused by index before anything runs."""
+    (``ragged.loss_margin``); a clip too short for the discriminator's or the STFT's own call is refused by index before anything runs.
+
+    ``input_rate``: both clips of every pair are at that rate, and ``sample_rate`` stays the model's.  Per batch two
+    ``rate.resample_ragged`` launches bring them to ``sample_rate`` in the padded buffers; every value is the one this call gives on
+    the pairs resampled beforehand with ``augment.resample``."""
     from . import metrics as M
 
     names = list(metrics)
@@ -224,7 +282,8 @@ def evaluate_clips(generator, corrupted: Sequence[torch.Tensor], reference: Sequ
     sample_rate = int(sample_rate)
     if sample_rate <= 0:
         raise ValueError(f"evaluate_clips: sample_rate must be positive, got {sample_rate}")
-    lengths = [c.shape[-1] for c in corrupted]
+    rated = _rated(input_rate, sample_rate)
+    lengths = [resampled_length(c.shape[-1], input_rate, sample_rate) if rated else c.shape[-1] for c in corrupted]   # at the model's rate
     min_margin = 0
     if loss_terms is not None:
         if not isinstance(loss_terms, LossTerms):
@@ -254,11 +313,16 @@ def evaluate_clips(generator, corrupted: Sequence[torch.Tensor], reference: Sequ
     for idx in batches:
         plan = ragged.plan(generator, [lengths[i] for i in idx], min_margin)
         dev = corrupted[idx[0]].device
-        buf = torch.zeros((len(idx), 1, plan.l_buf), dtype=torch.float32, device=dev)
-        ref = torch.zeros((len(idx), plan.l_buf), dtype=torch.float32, device=dev)
-        for r, i in enumerate(idx):
-            buf[r, 0, : plan.cut[r]].copy_(corrupted[i].reshape(-1)[: plan.cut[r]])
-            ref[r, : plan.cut[r]].copy_(reference[i].reshape(-1)[: plan.cut[r]])
+        if rated:
+            buf = _resampled_rows(corrupted, idx, plan.l_buf, input_rate, sample_rate)[:, :, : plan.l_buf].contiguous()
+            ref = _resampled_rows(reference, idx, plan.l_buf, input_rate, sample_rate)[:, 0, : plan.l_buf].contiguous()
+            _zero_behind(ref, plan.cut)   # a reference ends at its cut length, like its row of the forward
+        else:
+            buf = torch.zeros((len(idx), 1, plan.l_buf), dtype=torch.float32, device=dev)
+            ref = torch.zeros((len(idx), plan.l_buf), dtype=torch.float32, device=dev)
+            for r, i in enumerate(idx):
+                buf[r, 0, : plan.cut[r]].copy_(corrupted[i].reshape(-1)[: plan.cut[r]])
+                ref[r, : plan.cut[r]].copy_(reference[i].reshape(-1)[: plan.cut[r]])
         if loss_terms is None:
             enh, _ = generator.forward_ragged(buf, [lengths[i] for i in idx])   # zero behind every row, like ref
         else:   # the same forward on this batch's wider plan (forward_ragged would plan the batch with the generator's own margin)

@@ -505,7 +505,8 @@ class EBENLightningModule(BaseSELightningModule):
 
     @torch.no_grad()
     def evaluate_clips(self, corrupted, reference, stage: str = "test", dataloader_idx: int = 0, max_batch_samples: Optional[int] = None,
-                       metrics=("si_sdr", "stoi"), lsd_hf_cutoff_hz: Optional[float] = None, losses: bool = False):
+                       metrics=("si_sdr", "stoi"), lsd_hf_cutoff_hz: Optional[float] = None, losses: bool = False,
+                       input_rate: Optional[int] = None):
         """A whole split at once: what the reference's batch-1 test loop (one ``test_step`` + ``on_test_batch_end`` per utterance)
         aggregates SI-SDR and STOI to over an epoch, through ``inference.evaluate_clips`` -- ragged batches, metric kernels with a length
         per row.  The per-clip values join the running state of ``self.metrics`` (``compute()`` is the corpus mean) and their means are
@@ -515,7 +516,8 @@ class EBENLightningModule(BaseSELightningModule):
         ``"generator/<name>"`` / ``"discriminator/<name>"``, (N,) per-clip values each, and each term's mean over the clips is logged as
         ``{stage}/{network}/{name}{suffix}`` -- the reference's epoch value for batches of one.  ``metrics`` /
         ``lsd_hf_cutoff_hz`` as for ``inference.evaluate_clips``: every other metric's corpus mean is logged as ``{stage}/{name}{suffix}``
-        and stays out of ``self.metrics``, which mirrors the reference's collection."""
+        and stays out of ``self.metrics``, which mirrors the reference's collection.  ``input_rate``: the rate both clips of every
+        pair are recorded at, when it is not this module's ``sample_rate`` (``inference.evaluate_clips`` resamples them on the device)."""
         from .. import inference
 
         budget = inference.MAX_BATCH_SAMPLES if max_batch_samples is None else max_batch_samples
@@ -525,7 +527,7 @@ class EBENLightningModule(BaseSELightningModule):
                                         time_loss=self.reconstructive_loss_temp_fn or None, feature_loss=self.feature_matching_loss_fn or None,
                                         adversarial_loss=self.adversarial_loss_fn or None)
         out = inference.evaluate_clips(self.generator, corrupted, reference, sample_rate=int(self.sample_rate), max_batch_samples=budget,
-                                       metrics=metrics, lsd_hf_cutoff_hz=lsd_hf_cutoff_hz, loss_terms=terms)
+                                       metrics=metrics, lsd_hf_cutoff_hz=lsd_hf_cutoff_hz, loss_terms=terms, input_rate=input_rate)
         names = getattr(self, "dataloader_names", None)
         suffix = f"/{names[dataloader_idx]}" if names is not None else ""
         for name, values in out.items():

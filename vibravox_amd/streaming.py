@@ -23,6 +23,9 @@ Everything here is arithmetic on positions (host only, no GPU needed):
     (``Schedule.advance``), so all sessions that push in a tick share ONE run of ``plan.steady`` with a mask of the slots that advance.
     ``StreamPool`` executes its per-tick lists on the device; ``tests/pool_oracle.py`` executes them in float64.
 
+  * A stream that arrives at the recording's rate (``StreamingEnhancer(input_rate=...)``) passes through ``rate.ChunkFront`` first: a
+    carried-state resampler whose final samples reach the enhancer in whole chunks, one chunk later.  Nothing of the schedule changes.
+
 Audio hold-back: ``cut_to_valid_length`` drops up to ``multiple - 1`` samples from the end of a clip, so a sample pushed now may turn
 out to lie behind the stream's valid length.  The analysis bank therefore treats only ``ragged.cut_length(pushed)`` samples as
 final (for pushes of whole multiples that is ``pushed - n % multiple``): nothing computed ever depends on a sample that is dropped.
@@ -436,15 +439,17 @@ class _Driver:
         if torch.is_grad_enabled():
             raise RuntimeError(f"{self._who}: {what} has no backward; call it under torch.no_grad()")
 
-    def _check(self, chunk, rows: int, what: str) -> None:
-        """``chunk``: ``rows`` rows of one chunk, or of fewer samples in the call that ends a stream."""
+    def _check(self, chunk, rows: int, what: str, samples: Optional[int] = None) -> None:
+        """``chunk``: ``rows`` rows of one chunk, or of fewer samples in the call that ends a stream.  ``samples``: the chunk's length
+        where it is not ``chunk_samples`` (a chunk at the recording's rate)."""
         import torch
 
         last = what == self._last
+        samples = self.chunk_samples if samples is None else samples
         if (not isinstance(chunk, torch.Tensor) or chunk.dim() != 3 or tuple(chunk.shape[:2]) != (rows, 1) or chunk.dtype is not torch.float32
-                or not (chunk.shape[2] < self.chunk_samples if last else chunk.shape[2] == self.chunk_samples)):
+                or not (chunk.shape[2] < samples if last else chunk.shape[2] == samples)):
             got = f"{chunk.dtype} {tuple(chunk.shape)}" if isinstance(chunk, torch.Tensor) else type(chunk).__name__
-            raise ValueError(f"{self._who}: {what} expects a float32 ({rows}, 1, {self.chunk_samples}) tensor{self._per}"
+            raise ValueError(f"{self._who}: {what} expects a float32 ({rows}, 1, {samples}) tensor{self._per}"
                              f"{' or a shorter last one' if last else ''}, got {got}")
         if not chunk.is_cuda:
             from ._lib import EbenError
@@ -464,20 +469,53 @@ class StreamingEnhancer(_Driver):
     final enhanced samples ``(streams, 1, k)`` -- k is 0 during warm-up and exactly ``chunk_samples`` from the first non-empty return on;
     ``finish()`` (optionally with the last, shorter chunk) returns the rest, up to ``ragged.cut_length(generator, total pushed)``.  The
     concatenation is what ``generator(cut_to_valid_length(whole clip))`` returns.  Rows advance in lockstep.  ``return_bands``: every
-    call returns ``(enhanced, bands)``, the bands with the same semantics at their rate.  Nothing here waits for the device."""
+    call returns ``(enhanced, bands)``, the bands with the same semantics at their rate.  Nothing here waits for the device.
+
+    ``input_rate`` (other than ``model_rate``): the stream arrives at the recording's rate, as in the reference's inference script
+    (``Resample(48_000, 16_000)`` in front of the model).  ``push`` then takes ``(streams, 1, input_chunk_samples)`` with
+    ``input_chunk_samples = chunk_samples * orig / new`` over the reduced ratio -- a ``ValueError`` names the smallest ``chunk_samples``
+    for which that is a whole number -- and ``finish`` a shorter tail; the results stay at the model's rate, and their concatenation is
+    ``generator(cut_to_valid_length(augment.resample(whole clip, input_rate, model_rate)))``.  A ``rate.StreamResampler`` in front keeps
+    the final model-rate samples in a device FIFO and hands the enhancer whole chunks; at the end it makes as many pushes as the FIFO
+    holds, then ``finish`` with the rest.  Known cost: the resampler's look-ahead is ``width + orig - 1`` input samples (7 model-rate
+    samples at 3:1), so a push completes one chunk less that lag and the enhancer gets chunk k - 1 at push k: one ``chunk_samples`` of
+    extra latency (16 ms at 256), which ``input_latency`` states in input samples."""
 
     _who, _last = "StreamingEnhancer", "finish"
 
-    def __init__(self, generator, chunk_samples: int, streams: int = 1, return_bands: bool = False):
+    def __init__(self, generator, chunk_samples: int, streams: int = 1, return_bands: bool = False, input_rate: Optional[int] = None,
+                 model_rate: int = 16000):
         if int(streams) < 1:
             raise ValueError(f"streams must be positive, got {streams}")
         self.streams = int(streams)
         super().__init__(generator, chunk_samples, return_bands)
         self._schedule = Schedule(generator, chunk_samples)
+        self._front = None   # rate.ChunkFront: the resampler and its FIFO, when the stream arrives at another rate
+        if input_rate is not None and int(input_rate) != int(model_rate):
+            from . import rate
+
+            self._front = rate.ChunkFront(input_rate, model_rate, self.chunk_samples, self.streams, generator.multiple)
+            self._ratio = rate.ratio(input_rate, model_rate)[:2]
+
+    @property
+    def input_chunk_samples(self) -> int:
+        """Samples per push: ``chunk_samples`` at the rate the stream arrives at."""
+        return self.chunk_samples if self._front is None else self._front.input_chunk_samples
+
+    @property
+    def input_latency(self) -> int:
+        """Input samples pushed minus the input samples the emitted ones correspond to, in the steady state: ``latency`` without
+        ``input_rate``; with it one chunk more (the FIFO in front), at the input's rate."""
+        if self._front is None:
+            return self.plan.latency
+        orig, new = self._ratio
+        return self._front.input_chunk_samples + _ceil(self.plan.latency * orig, new)
 
     def prepare(self, device) -> "StreamingEnhancer":
         """Allocates the state on ``device`` now instead of at the first push (it is allocated once either way)."""
         self._allocate(device, self.streams)
+        if self._front is not None:
+            self._front.prepare(device)
         return self
 
     def reset(self) -> None:
@@ -485,6 +523,8 @@ class StreamingEnhancer(_Driver):
         self._schedule.reset()
         if self.state is not None:
             self.state.reset()
+        if self._front is not None:
+            self._front.reset()
 
     def _run(self, chunk, n_in: int, final: bool):
         from . import gen_engine
@@ -496,20 +536,51 @@ class StreamingEnhancer(_Driver):
         got = self._emitted(out, self.streams, device)
         return tuple(got) if self.return_bands else got[0]
 
+    def _joined(self, results: list, device):
+        """What a call returns for the runs it made: none (empty tensors), one, or several in order."""
+        import torch
+
+        if not results:
+            got = self._emitted({}, self.streams, device)
+            return tuple(got) if self.return_bands else got[0]
+        if len(results) == 1:
+            return results[0]
+        if self.return_bands:
+            return tuple(torch.cat(parts, dim=2) for parts in zip(*results))
+        return torch.cat(results, dim=2)
+
+    def _run_rated(self, chunk, final: bool):
+        """A chunk at the recording's rate: through the resampler into the FIFO, every chunk the FIFO fills through the enhancer."""
+        device = chunk.device if chunk is not None else self.state.device if self.state is not None else next(self.generator.parameters()).device
+        self.prepare(device)
+        if final:   # a stream below the shortest clip is refused in the words of the batch forward, before anything runs
+            orig, new = self._ratio
+            ragged.plan(self.generator, [_ceil(new * (self._front.pushed + (0 if chunk is None else chunk.shape[2])), orig)])
+        results: list = []
+        rest = self._front.feed(chunk, final, lambda full: results.append(self._run(full, self.chunk_samples, False)))
+        if final:
+            results.append(self._run(rest, 0 if rest is None else rest.shape[2], True))
+        return self._joined(results, device)
+
     def push(self, chunk):
         self._no_grad("push")
+        if self._front is not None:
+            self._check(chunk, self.streams, "push", self._front.input_chunk_samples)
+            return self._run_rated(chunk.contiguous(), False)
         self._check(chunk, self.streams, "push")
         return self._run(chunk.contiguous(), self.chunk_samples, False)
 
     def finish(self, tail=None):
-        """The rest of the stream.  ``tail``: the last ``(streams, 1, r)`` samples, ``r < chunk_samples`` (what did not fill a chunk).
-        ``ValueError`` when everything pushed is shorter than the shortest clip the generator accepts."""
+        """The rest of the stream.  ``tail``: the last ``(streams, 1, r)`` samples, ``r < input_chunk_samples`` (what did not fill a
+        chunk).  ``ValueError`` when everything pushed is shorter than the shortest clip the generator accepts."""
         self._no_grad("finish")
         if tail is not None and tail.shape[-1] == 0:
             tail = None
         if tail is not None:
-            self._check(tail, self.streams, "finish")
+            self._check(tail, self.streams, "finish", self.input_chunk_samples)
             tail = tail.contiguous()
+        if self._front is not None:
+            return self._run_rated(tail, True)
         return self._run(tail, 0 if tail is None else tail.shape[2], True)
 
 
