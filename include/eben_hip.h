@@ -152,6 +152,18 @@ EBEN_API int eben_conv1d_kernel_generation(const EbenConv1dDesc* d, int which);
 #define EBEN_VARIANT_TAP4 3      /* tap4_kernel (bigtap.hip) */
 #define EBEN_VARIANT_GC 4        /* gc_kernel (gen_conv.hip) */
 EBEN_API int eben_conv1d_variant(const EbenConv1dDesc* d, int which, int mask_on_load, int* out, int n);
+/* The same question for the exact-fp32 families (for tests): the kernel instantiation a launch on EBEN_CONV_ROUTE_THIN / _TAP2 runs and
+ * the plan decisions its rarely-taken branches hang on, read off the plan the launch dispatches on.  which / mask_on_load as above.
+ * out[0..7] (n >= 8) = EBEN_CONV_ROUTE_*, then
+ *   THIN: MT, BN, NP (thin_kernel's template arguments), id_fast (0: the block id is decomposed by division, the grid being too large
+ *         for multiply-high), pg_n (stride phases whose geometry the host computed; 0: the kernel computes it, more than 8 phases),
+ *         lds_bytes (dynamic LDS of the launch), 0;
+ *   TAP2: FM, XR, H16, IMT (tap2_kernel's template arguments after NW = 4; IMT -1: the mask-on-load switch is a run-time one), ncc
+ *         (channel chunks), nxbuf (input-tile buffers), and 1 where two buffers suffice only because the tiles change on weight-chunk
+ *         boundaries (the aligned hand-over);
+ *   zeros past out[0] on every other route (TAP1 has one kernel per launch form and no plan).
+ * EBEN_EUNSUPPORTED / EBEN_EINVAL where the launch itself would refuse. */
+EBEN_API int eben_conv1d_variant_f32(const EbenConv1dDesc* d, int which, int mask_on_load, int* out, int n);
 /* pack v (optionally scaled per dim-0 row: weight-norm) into the MFMA-friendly layouts */
 EBEN_API int eben_conv1d_pack(const EbenConv1dDesc* d, const float* v, const float* scale, float* wp_fwd, float* wp_bwd, void* stream);
 /* y = lrelu_out( conv(lrelu_in(x)) + bias ) [+ residual] */

@@ -105,6 +105,7 @@ SIGNATURES = {
     "eben_conv1d_packed_floats": (c_size_t, [_D, c_int]),
     "eben_conv1d_kernel_generation": (c_int, [_D, c_int]),
     "eben_conv1d_variant": (c_int, [_D, c_int, c_int, POINTER(c_int), c_int]),
+    "eben_conv1d_variant_f32": (c_int, [_D, c_int, c_int, POINTER(c_int), c_int]),
     "eben_conv1d_pack": (c_int, [_D, _P, _P, _P, _P, _P]),
     "eben_conv1d_pack_multi": (c_int, [POINTER(EbenPackJob), c_int, _P]),
     "eben_conv1d_fwd": (c_int, [_D, _P, _P, _P, _P, _P, _P]),

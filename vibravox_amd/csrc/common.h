@@ -221,6 +221,9 @@ int tap2_applicable(const Canon& c, int dir);
 size_t tap2_packed_floats(const Canon& c, int dir);
 int tap2_pack(const Canon& c, int dir, const float* w, const float* scale, float* wp, hipStream_t st);
 int tap2_launch(const Canon& c, int dir, const TapIO& io, int reflect, hipStream_t st);
+// tap2_kernel<FM, 4, XR, H16, IMT> of the launch with TapIO.in_mode = in_mode, then the channel chunks, the input-tile buffers and whether
+// two buffers are the aligned hand-over, read off the plan tap2_launch dispatches on (eben_conv1d_variant_f32); refuses what it refuses
+int tap2_plan_variant(const Canon& c, int dir, int in_mode, int* out7);
 
 // bf16-operand form of the second generation (tapconv3.hip): 32x32x16 bf16 MFMA, fp32 accumulate / storage
 int tap3_applicable(const Canon& c, int dir);
@@ -244,6 +247,9 @@ int thin_applicable(const Canon& c, int dir);
 size_t thin_packed_floats(const Canon& c, int dir);
 int thin_pack(const Canon& c, int dir, const float* w, const float* scale, float* wp, hipStream_t st);
 int thin_launch(const Canon& c, int dir, const TapIO& io, int reflect, hipStream_t st);
+// thin_kernel<MT, BN, NP> of the launch, then id_fast, pg_n and the dynamic LDS bytes, read off the plan thin_launch dispatches on
+// (eben_conv1d_variant_f32); refuses what it refuses
+int thin_plan_variant(const Canon& c, int dir, int* out6);
 
 // "phases as rows" (bl_dx_pr.hip): whether a strided bundle-layout Conv1d's input gradient has the form (ok), its geometry, and in
 // *primed the stride-1 layer whose FORWARD the launch is (eben_bl_conv1d_bwd_dx_pr in conv1d.hip)

@@ -159,6 +159,20 @@ extern "C" int eben_conv1d_variant(const EbenConv1dDesc* d, int which, int mask_
   return EBEN_OK;
 }
 
+extern "C" int eben_conv1d_variant_f32(const EbenConv1dDesc* d, int which, int mask_on_load, int* out, int n) {
+  EBEN_REQUIRE(out && n >= 8 && (which == 0 || which == 1), "eben_conv1d_variant_f32: which 0 / 1 and 8 output slots");
+  EBEN_REQUIRE(!mask_on_load || which == 1, "eben_conv1d_variant_f32: the mask is applied on load by input gradients only");
+  Canon c;
+  const int rc = canon_from_desc(d, &c);
+  if (rc) return rc;
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  const ConvRoute r = conv_route(c, d->transposed, which);
+  out[0] = r.reported();
+  if (r.family == EBEN_CONV_ROUTE_THIN) return thin_plan_variant(c, r.dir, &out[1]);
+  if (r.family == EBEN_CONV_ROUTE_TAP2) return tap2_plan_variant(c, r.dir, mask_on_load ? 1 : 0, &out[1]);
+  return EBEN_OK;
+}
+
 extern "C" int eben_conv1d_pack(const EbenConv1dDesc* d, const float* v, const float* scale, float* wp_fwd, float* wp_bwd, void* stream) {
   Canon c;
   int rc = canon_from_desc(d, &c);

@@ -401,6 +401,7 @@ struct Tap2Plan {
   int mode, G, Cg, Mg, S, OS, dstep, kstep, nph, J, Lx, Ly, Cx, Cy, off0, nt, ps_pad;
   int FM, NW, BM, BN, FI, WCH, H16, KCH;
   int CI_T, CP, ncc, PLEN, CSTRIDE, nxbuf, XR;
+  int aligned2;   // two input-tile buffers that are enough only because the tiles change on weight-chunk boundaries
   int nmt, ntt, NCH, tab_phase;
   long long w_tile, w_phase, tab_off;
   size_t packed_floats, lds_bytes;
@@ -499,6 +500,7 @@ static void make_plan2(const Canon& c, int dir, Tap2Plan* p) {
   const int KCH = p->KCH;
   const int Cg2 = round_up(p->Cg, KCH);
   p->XR = T2_XR;
+  p->aligned2 = 0;
   if ((long long)Cg2 * p->CSTRIDE * 4 <= xbudget) {
     p->CI_T = Cg2; p->ncc = 1; p->nxbuf = 1;
   } else {
@@ -527,6 +529,7 @@ static void make_plan2(const Canon& c, int dir, Tap2Plan* p) {
         const int kscc = Jmin * (p->CI_T / KCH);
         const bool aligned = Jmin == p->J && kscc >= 16 && kscc % 16 == 0;
         if (p->ncc > 1 && kscc < (nbuf == 2 ? 32 : 16) && !(nbuf == 2 && aligned)) continue;
+        p->aligned2 = p->ncc > 1 && nbuf == 2 && kscc < 32;
         found = true;
         break;
       }
@@ -657,6 +660,27 @@ int tap2_pack(const Canon& c, int dir, const float* w, const float* scale, float
   return EBEN_OK;
 }
 
+// The instantiation tap2_launch runs, read off the plan and the launch's input mode: tap2_launch dispatches on this and
+// eben_conv1d_variant_f32 reports it.  IMT: the mask-on-load switch is compiled in on the 28-element staging forms only (-1: run time).
+struct Tap2Variant { int FM, XR, H16, IMT; };
+static Tap2Variant tap2_variant(const Tap2Plan& p, int in_mode) {
+  Tap2Variant v;
+  v.FM = p.FM; v.XR = p.XR; v.H16 = p.H16 ? 1 : 0;
+  v.IMT = p.XR == T2_XR_BIG ? (in_mode != 0 ? 1 : 0) : -1;
+  return v;
+}
+
+int tap2_plan_variant(const Canon& c, int dir, int in_mode, int* out7) {
+  Tap2Plan p;
+  make_plan2(c, dir, &p);
+  if (!p.ok) return fail(EBEN_EUNSUPPORTED, "tap2_plan_variant on a layer the second-generation kernel does not cover");
+  const long long nb = (long long)p.ntt * c.B * p.nph * p.nmt * p.G;
+  if (nb <= 0 || nb > 0x7fffffffLL) return fail(EBEN_EINVAL, "tap2 grid of %lld blocks", nb);
+  const Tap2Variant v = tap2_variant(p, in_mode);
+  out7[0] = v.FM; out7[1] = v.XR; out7[2] = v.H16; out7[3] = v.IMT; out7[4] = p.ncc; out7[5] = p.nxbuf; out7[6] = p.aligned2;
+  return EBEN_OK;
+}
+
 int tap2_launch(const Canon& c, int dir, const TapIO& io, int reflect, hipStream_t st) {
   Tap2Plan p;
   make_plan2(c, dir, &p);
@@ -677,14 +701,14 @@ int tap2_launch(const Canon& c, int dir, const TapIO& io, int reflect, hipStream
   a.w_tile = p.w_tile; a.w_phase = p.w_phase;
   const long long nb = (long long)p.ntt * c.B * p.nph * p.nmt * p.G;
   if (nb <= 0 || nb > 0x7fffffffLL) return fail(EBEN_EINVAL, "tap2 grid of %lld blocks", nb);
-  const bool im = io.in_mode != 0;
-  if (p.H16) return p.XR == T2_XR_BIG ? (im ? launch2_cfg<1, 4, T2_XR_BIG, true, 1>(a, (int)nb, p.lds_bytes, st)
-                                            : launch2_cfg<1, 4, T2_XR_BIG, true, 0>(a, (int)nb, p.lds_bytes, st))
+  const Tap2Variant v = tap2_variant(p, io.in_mode);
+  if (v.H16) return v.XR == T2_XR_BIG ? (v.IMT == 1 ? launch2_cfg<1, 4, T2_XR_BIG, true, 1>(a, (int)nb, p.lds_bytes, st)
+                                                    : launch2_cfg<1, 4, T2_XR_BIG, true, 0>(a, (int)nb, p.lds_bytes, st))
                                        : launch2_cfg<1, 4, T2_XR, true>(a, (int)nb, p.lds_bytes, st);
-  if (p.XR == T2_XR_BIG) {
-#define EBEN_T2_BIG(FMV) return im ? launch2_cfg<FMV, 4, T2_XR_BIG, false, 1>(a, (int)nb, p.lds_bytes, st) \
-                                   : launch2_cfg<FMV, 4, T2_XR_BIG, false, 0>(a, (int)nb, p.lds_bytes, st)
-    switch (p.FM) {
+  if (v.XR == T2_XR_BIG) {
+#define EBEN_T2_BIG(FMV) return v.IMT == 1 ? launch2_cfg<FMV, 4, T2_XR_BIG, false, 1>(a, (int)nb, p.lds_bytes, st) \
+                                           : launch2_cfg<FMV, 4, T2_XR_BIG, false, 0>(a, (int)nb, p.lds_bytes, st)
+    switch (v.FM) {
       case 1: EBEN_T2_BIG(1);
       case 2: EBEN_T2_BIG(2);
       case 3: EBEN_T2_BIG(3);
@@ -692,7 +716,7 @@ int tap2_launch(const Canon& c, int dir, const TapIO& io, int reflect, hipStream
     }
 #undef EBEN_T2_BIG
   }
-  switch (p.FM) {
+  switch (v.FM) {
     case 1: return launch2_cfg<1, 4, T2_XR>(a, (int)nb, p.lds_bytes, st);
     case 2: return launch2_cfg<2, 4, T2_XR>(a, (int)nb, p.lds_bytes, st);
     case 3: return launch2_cfg<3, 4, T2_XR>(a, (int)nb, p.lds_bytes, st);

@@ -315,6 +315,31 @@ __global__ __launch_bounds__(256) void thin_pack_kernel(const ThinPackArgs P) {
   }
 }
 
+// The instantiation thin_launch runs and the two host decisions its block prologue depends on, read off the plan: thin_launch
+// dispatches on this and eben_conv1d_variant_f32 reports it.
+struct ThinVariant { int MT, BN, NP, id_fast, pg_n; long long nb; };
+static int thin_variant(const ThinPlan& p, int B, ThinVariant* v) {
+  v->MT = p.MT; v->BN = p.BN; v->NP = p.NP;
+  v->nb = (long long)p.ntt * B * p.nph * p.nmt * p.G;
+  if (v->nb <= 0 || v->nb > 0x7fffffffLL) return fail(EBEN_EINVAL, "thin grid of %lld blocks", v->nb);
+  int dmax = p.nph > p.ntt ? p.nph : p.ntt;
+  if (B > dmax) dmax = B;
+  if (p.nmt > dmax) dmax = p.nmt;
+  v->id_fast = v->nb * dmax < 0x100000000LL ? 1 : 0;   // mulhi(n, ceil(2^32 / d)) is exact while n * d < 2^32
+  v->pg_n = p.nph <= 8 ? p.nph : 0;                     // ThinArgs carries the phase geometry of up to 8 phases
+  return EBEN_OK;
+}
+
+int thin_plan_variant(const Canon& c, int dir, int* out6) {
+  ThinPlan p;
+  make_thin_plan(c, dir, &p);
+  if (!p.ok) return fail(EBEN_EUNSUPPORTED, "thin_plan_variant on a layer the direct kernel does not cover");
+  ThinVariant v;
+  if (const int e = thin_variant(p, c.B, &v)) return e;
+  out6[0] = v.MT; out6[1] = v.BN; out6[2] = v.NP; out6[3] = v.id_fast; out6[4] = v.pg_n; out6[5] = (int)p.lds_bytes;
+  return EBEN_OK;
+}
+
 template <int MT, int BN, int NP = 1>
 static int launch_thin_cfg(const ThinArgs& a, int nblocks, size_t lds, hipStream_t st) {
   static LdsAttrOnce attr_once;
@@ -374,16 +399,14 @@ int thin_launch(const Canon& c, int dir, const TapIO& io, int reflect, hipStream
   a.PLEN = p.PLEN; a.CSTRIDE = p.CSTRIDE;
   a.s_magic = p.S > 1 ? (unsigned)((0x100000000ull + p.S - 1) / p.S) : 0u;
   a.ntt = p.ntt; a.nmt = p.nmt; a.w_tile = p.w_tile;
-  const long long nb = (long long)p.ntt * c.B * p.nph * p.nmt * p.G;
-  if (nb <= 0 || nb > 0x7fffffffLL) return fail(EBEN_EINVAL, "thin grid of %lld blocks", nb);
+  ThinVariant v;
+  if (const int e = thin_variant(p, c.B, &v)) return e;
+  const long long nb = v.nb;
   {
     auto magic = [](int d) { return d == 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); };
-    int dmax = p.nph > p.ntt ? p.nph : p.ntt;
-    if (c.B > dmax) dmax = c.B;
-    if (p.nmt > dmax) dmax = p.nmt;
-    a.id_fast = nb * dmax < 0x100000000LL ? 1 : 0;   // mulhi(n, ceil(2^32 / d)) is exact while n * d < 2^32
+    a.id_fast = v.id_fast;
     a.m_ntt = magic(p.ntt); a.m_B = magic(c.B); a.m_nph = magic(p.nph); a.m_nmt = magic(p.nmt);
-    a.pg_n = p.nph <= 8 ? p.nph : 0;
+    a.pg_n = v.pg_n;
     a.tile = p.BN * p.NP;
     const int ad = p.dstep >= 0 ? p.dstep : -p.dstep;
     for (int ph = 0; ph < a.pg_n; ++ph) {
@@ -394,23 +417,23 @@ int thin_launch(const Canon& c, int dir, const TapIO& io, int reflect, hipStream
       a.pg[ph].pad = 0;
     }
   }
-  if (p.BN == 256 && p.NP == 4) {
-    switch (p.MT) {
+  if (v.BN == 256 && v.NP == 4) {
+    switch (v.MT) {
       case 1: return launch_thin_cfg<1, 256, 4>(a, (int)nb, p.lds_bytes, st);
       case 4: return launch_thin_cfg<4, 256, 4>(a, (int)nb, p.lds_bytes, st);
       case 8: return launch_thin_cfg<8, 256, 4>(a, (int)nb, p.lds_bytes, st);
       default: return launch_thin_cfg<16, 256, 4>(a, (int)nb, p.lds_bytes, st);
     }
   }
-  if (p.BN == 256) {
-    switch (p.MT) {
+  if (v.BN == 256) {
+    switch (v.MT) {
       case 1: return launch_thin_cfg<1, 256>(a, (int)nb, p.lds_bytes, st);
       case 4: return launch_thin_cfg<4, 256>(a, (int)nb, p.lds_bytes, st);
       case 8: return launch_thin_cfg<8, 256>(a, (int)nb, p.lds_bytes, st);
       default: return launch_thin_cfg<16, 256>(a, (int)nb, p.lds_bytes, st);
     }
   }
-  switch (p.MT) {
+  switch (v.MT) {
     case 1: return launch_thin_cfg<1, 128>(a, (int)nb, p.lds_bytes, st);
     case 4: return launch_thin_cfg<4, 128>(a, (int)nb, p.lds_bytes, st);
     case 8: return launch_thin_cfg<8, 128>(a, (int)nb, p.lds_bytes, st);
