@@ -83,7 +83,7 @@ EBEN_API const char* eben_last_error(void);
  * that needs it finds out by looking the symbol up.  The same holds for the data front end (eben_clip_powers*, eben_noisy_collate_scaled,
  * eben_biquad*, EbenClip): functions and a new POD type only.
  * eben_version() returns the value the library was built with; bindings compare it with the header they were written against. */
-#define EBEN_ABI_VERSION 5
+#define EBEN_ABI_VERSION 6
 EBEN_API int eben_version(void);
 /* fills name with the device's gcnArchName; returns compute-unit count (or negative) */
 EBEN_API int eben_device_info(char* name, size_t name_bytes);
@@ -492,23 +492,15 @@ EBEN_API int eben_hinge_bwd(const float* x, size_t n, float target, const float*
 EBEN_API int eben_hinge_bwd_stacked(const float* enhanced_logits, const float* reference_logits, size_t per, const float* gout, float scale_adv,
                                     float scale_fake, float scale_real, float* seeds, void* stream);
 /* STFT magnitude losses (auraloss.freq.STFTLoss as configured by multi_stft.yaml; call site
- * vibravox/lightning_modules/eben.py:195-198).  spec_* hold (rows, 2*bins_pad, frames) with re in
- * channels [0,bins) and im in [bins_pad, bins_pad+bins); |.| = sqrt(clamp(re^2+im^2, eps)).
- * per row r: out[3r] = sum (|Y|-|X|)^2, out[3r+1] = sum |Y|^2, out[3r+2] = sum |log|X| - log|Y|| */
-EBEN_API int eben_stft_loss_sums(const float* spec_x, const float* spec_y, int rows, int bins, int bins_pad, int frames,
-                        float eps, float* partial_ws, size_t ws_bytes, float* out, void* stream);
+ * vibravox/lightning_modules/eben.py:195-198), |.| = sqrt(clamp(re^2+im^2, eps)):
+ * eben_stft_loss_sums_ex, per row r: out[3r] = sum (|Y|-|X|)^2, out[3r+1] = sum |Y|^2, out[3r+2] = sum |log|X| - log|Y||;
+ * eben_stft_loss_bwd_ex: dspec_x from d(loss) with loss = mean_rows(sqrt(s0/s1)) + mean(|log X - log Y|); gout device scalar * scale.
+ * eben_overlap_add_ex: adjoint of framing a (reflect-)padded signal: x[b,u] (+)= fold( sum_f buf[b, u+pad-f*hop, f] ).  Used by the
+ * STFT backward: d(frames) = basis^T . d(spec) is a dense pointwise conv (eben_conv1d_fwd, ksize 1), this kernel scatters it back
+ * onto the waveform. */
 EBEN_API size_t eben_stft_loss_sums_workspace(int rows);
-/* dspec_x from d(loss) with loss = mean_rows(sqrt(s0/s1)) + mean(|log X - log Y|); gout device scalar * scale */
-EBEN_API int eben_stft_loss_bwd(const float* spec_x, const float* spec_y, int rows, int bins, int bins_pad, int frames,
-                       float eps, const float* sums, const float* gout, float scale, float* dspec_x, void* stream);
 
-/* adjoint of framing a (reflect-)padded signal: x[b,u] (+)= fold( sum_f buf[b, u+pad-f*hop, f] ) with
- * buf (batch, win, frames).  Used by the STFT backward: d(frames) = basis^T . d(spec) is a dense
- * pointwise conv (eben_conv1d_fwd, ksize 1), this kernel scatters it back onto the waveform. */
-EBEN_API int eben_overlap_add(const float* frames_buf, float* x, int batch, int lx, int win, int frames, int hop, int pad,
-                     int reflect, int accumulate, void* stream);
-
-/* The same three with explicit strides -- element (row r, bin k, frame f) of a spectrum at r*row_stride + k*bin_stride + f
+/* All three take explicit strides -- element (row r, bin k, frame f) of a spectrum at r*row_stride + k*bin_stride + f
  * (imaginary part at + im_off), frame-buffer element (item b, window sample j, frame f) at b*row_stride + j*j_stride + f --
  * so that the windowed DFT of ALL items runs as one dense GEMM over a flat (channels, rows*frames) matrix:
  *   eben_stft_frames: out[j, r*frames + f] = sig[r, reflect(f*hop + j - pad)]   (torch.stft(center=True, pad_mode="reflect") framing)

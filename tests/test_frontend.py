@@ -222,7 +222,7 @@ def test_header_signatures_and_library_agree_on_the_new_names():
     import ctypes
 
     assert ctypes.sizeof(_lib.EbenClip) == 16 and ctypes.sizeof(_lib.EbenCollateItem) == 48   # layouts the by-value tables rely on
-    assert lib.eben_version() == _lib.ABI_VERSION == 5 == int(re.search(r"#define EBEN_ABI_VERSION (\d+)", header).group(1))
+    assert lib.eben_version() == _lib.ABI_VERSION == 6 == int(re.search(r"#define EBEN_ABI_VERSION (\d+)", header).group(1))
     # workspace queries answer without a GPU; the chunk length of vibravox_amd.filters is the library's
     from vibravox_amd.filters import CHUNK
 

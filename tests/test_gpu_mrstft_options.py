@@ -1,4 +1,4 @@
-"""GPU: MultiResolutionSTFTLoss with the options beyond multi_stft.yaml (stft_terms.hip through ops._MRSTFTTermsFn) against the float64
+"""GPU: MultiResolutionSTFTLoss with the options beyond multi_stft.yaml (stft_terms.hip through stft._WeightedTerms) against the float64
 restatement of tests/stft_terms_oracle.py, the default configuration's isolation from the new entry points, and one EBEN training
 step with the reference's mel option.
 

@@ -1370,7 +1370,7 @@ def test_single_band_fir_and_adjoint(hip, ntaps, length, batch):
 @pytest.mark.parametrize("win,hop,n_fft,t,rows", [(240, 50, 512, 31968, 3), (600, 120, 1024, 31968, 2), (1200, 240, 2048, 31968, 2), (240, 50, 512, 1300, 2),
                                                   (600, 120, 1024, 2500, 1), (1200, 240, 2048, 2600, 1)])
 def test_folded_framing_and_overlap_add_tiled_kernels_are_bit_identical(hip, win, hop, n_fft, t, rows):
-    """eben_stft_frames_folded through the LDS transpose and eben_overlap_add_folded from the LDS tile (direct.hip) against the gather kernels
+    """eben_stft_frames_folded through the LDS transpose and eben_overlap_add_folded from the LDS tile (stft.hip) against the gather kernels
     they replace (EBEN_STFT_FRAMES_T=0 / EBEN_OLA_TILED=0 in a second process): the same sums of the same samples, bit for bit -- full-size
     clips and clips a few tiles long (both reflected ends inside one or two blocks)."""
     import os

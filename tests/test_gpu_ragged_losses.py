@@ -117,7 +117,7 @@ def test_row_kernels_give_nan_for_lengths_out_of_range(hip):
 
 @pytest.mark.parametrize("n_fft,hop,win", [(512, 50, 240), (511, 50, 241)])
 def test_stft_loss_sums_rows_against_float64(hip, n_fft, hop, win):
-    from vibravox_amd import ops
+    from vibravox_amd import stft
     from vibravox_amd._lib import check, stream
     from vibravox_amd.torch_modules.losses.mrstft_loss import MultiResolutionSTFTLoss
 
@@ -126,7 +126,7 @@ def test_stft_loss_sums_rows_against_float64(hip, n_fft, hop, win):
     (p,) = loss._build_plans()
     frames = p.frames(t)
     sig = torch.cat([formula_audio(f"sums_rows/{n_fft}/{i}", 1, t) for i in range(2 * rows)]).to(DEV)
-    spec = ops._stft_spectrum(p, p.math_for("folded"), sig, t, frames)   # (1, 2 bins, 2 rows frames): x rows, then y rows
+    spec = stft._stft_spectrum(p, p.math_for("folded"), sig, t, frames)   # (1, 2 bins, 2 rows frames): x rows, then y rows
     of_row = (frames, 1, frames - 1, 17)
     sums = torch.empty((rows, 3), dtype=torch.float32, device=DEV)
     nbytes = hip.eben_stft_loss_sums_rows_workspace(rows)
@@ -167,7 +167,7 @@ def stft_case(weighting):
 @pytest.mark.parametrize("mode", ["folded", "bf16x3"])
 @pytest.mark.parametrize("weighting", [True, False])
 def test_mrstft_forward_ragged_gives_every_row_its_own_loss(hip, weighting, mode):
-    from vibravox_amd import ops
+    from vibravox_amd import stft
     from vibravox_amd.torch_modules.losses.mrstft_loss import MultiResolutionSTFTLoss
 
     x, y, px, py, ref = stft_case(weighting)
@@ -180,11 +180,11 @@ def test_mrstft_forward_ragged_gives_every_row_its_own_loss(hip, weighting, mode
         for r, t in enumerate(CUT + CUT):
             sig[r, :, t:] = float("nan")
 
-    ops.mrstft_rows_probe = garbage
+    stft.mrstft_rows_probe = garbage
     try:
         poisoned = loss.forward_ragged(px, py, CUT)
     finally:
-        ops.mrstft_rows_probe = None
+        stft.mrstft_rows_probe = None
     assert same_bits(poisoned, got)
     with torch.no_grad():
         alone = [float(loss(a.to(DEV), b.to(DEV))) for a, b in zip(x, y)]

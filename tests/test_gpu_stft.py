@@ -1,4 +1,4 @@
-"""GPU: the MRSTFT loss's framing and overlap-add kernels (direct.hip) and MultiResolutionSTFTLoss against float64 restatements.
+"""GPU: the MRSTFT loss's framing and overlap-add kernels (stft.hip) and MultiResolutionSTFTLoss against float64 restatements.
 
 Kernels: eben_stft_frames, eben_stft_frames_folded (split 0 / 1) and eben_overlap_add_ex / eben_overlap_add_folded against an explicit
 index restatement of what they are specified to compute, never against each other; both launches of each (LDS transpose / tile and the
@@ -26,7 +26,7 @@ for _p in (ROOT, os.path.join(ROOT, "tests", "golden")):
 pytestmark = pytest.mark.gpu
 
 U32 = 2.0 ** -24   # unit roundoff of fp32
-OLA_U = 512        # direct.hip: samples per block of overlap_add_folded_t_kernel
+OLA_U = 512        # stft.hip: samples per block of overlap_add_folded_t_kernel
 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # kernels

@@ -74,9 +74,9 @@ def test_multirate_abi_is_declared_bound_and_exported():
 
     header = open(os.path.join(ROOT, "include", "eben_hip.h")).read()
     declared = set(re.findall(r"EBEN_API\s+[\w\s\*]+?\b(eben_\w+)\s*\(", header))
-    assert int(re.search(r"#define EBEN_ABI_VERSION (\d+)", header).group(1)) == _lib.ABI_VERSION == 5
+    assert int(re.search(r"#define EBEN_ABI_VERSION (\d+)", header).group(1)) == _lib.ABI_VERSION == 6
     lib = _lib.load()
-    assert lib.eben_version() == 5
+    assert lib.eben_version() == 6
     for name in NEW_ABI:
         assert name in declared and name in _lib.SIGNATURES and hasattr(lib, name), name
 

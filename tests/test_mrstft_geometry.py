@@ -113,3 +113,40 @@ def test_window_longer_than_fft_is_rejected(n_fft, win):
         MultiResolutionSTFTLoss(fft_sizes=(n_fft,), hop_sizes=(64,), win_lengths=(win,))
     with pytest.raises(RuntimeError):   # torch.stft refuses it too
         torch.stft(torch.zeros(2 * n_fft), n_fft, 64, win, torch.hann_window(win), return_complex=True)
+
+
+# (n_fft, hop, win): bins, pad, (c_in, c_out, ksize, groups) of the dense forward / adjoint convs, frames at t = 4096 / 32000 / 4321, what
+# "folded_x3" resolves to, then the folded and bf16x3 conv pairs -- as the nine-argument StftPlan construction gave them before
+# StftPlan.build derived them: the three resolutions of multi_stft.yaml, one more with win < n_fft, one with odd win (dense only)
+BUILT = {
+    (512, 50, 240): (257, 120, (240, 514, 1, 1), (514, 240, 1, 1), [82, 641, 87], "folded_x3",
+                     ((240, 514, 1, 2), (514, 240, 1, 2)), ((720, 514, 1, 2), (1542, 240, 1, 2))),
+    (1024, 120, 600): (513, 300, (600, 1026, 1, 1), (1026, 600, 1, 1), [35, 267, 37], "folded_x3",
+                       ((600, 1026, 1, 2), (1026, 600, 1, 2)), ((1800, 1026, 1, 2), (3078, 600, 1, 2))),
+    (2048, 240, 1200): (1025, 600, (1200, 2050, 1, 1), (2050, 1200, 1, 1), [18, 134, 19], "folded_x3",
+                        ((1200, 2050, 1, 2), (2050, 1200, 1, 2)), ((3600, 2050, 1, 2), (6150, 1200, 1, 2))),
+    (1024, 100, 400): (513, 200, (400, 1026, 1, 1), (1026, 400, 1, 1), [41, 321, 44], "folded_x3",
+                       ((400, 1026, 1, 2), (1026, 400, 1, 2)), ((1200, 1026, 1, 2), (3078, 400, 1, 2))),
+    (512, 50, 241): (257, 121, (241, 514, 1, 1), (514, 241, 1, 1), [82, 641, 87], "dense", None, None),
+}
+
+
+@pytest.mark.parametrize("geometry", sorted(BUILT))
+def test_build_derives_the_plan_the_hand_written_construction_gave(geometry):
+    from vibravox_amd.ops import ConvSpec
+
+    def shape(c):
+        assert c.spec == ConvSpec(c_in=c.spec.c_in, c_out=c.spec.c_out, ksize=1, groups=c.spec.groups)   # nothing but a pointwise conv
+        assert tuple(c.basis.shape) == c.spec.weight_shape()
+        return c.spec.c_in, c.spec.c_out, c.spec.ksize, c.spec.groups
+
+    bins, pad, fwd, adj, frames, math, folded, bf16x3 = BUILT[geometry]
+    plan = _plan(*geometry)
+    assert (plan.n_fft, plan.hop, plan.win) == geometry and (plan.bins, plan.pad) == (bins, pad)
+    assert tuple(shape(c) for c in plan.parts("dense")) == (fwd, adj)
+    assert plan.parts("dense")[0].basis is plan.basis_f and plan.parts("dense")[1].basis is plan.basis_t
+    assert [plan.frames(t) for t in (4096, 32000, 4321)] == frames
+    assert plan.math_for("folded_x3") == math
+    if folded is not None:
+        for name, want in (("folded", folded), ("bf16x3", bf16x3)):
+            assert tuple(shape(c) for c in plan.parts(name)) == want

@@ -65,7 +65,7 @@ def test_constructor_rejects(kw, exc):
 
 
 def test_default_configuration_is_recognised():
-    """The configurations that stay on the default kernels (ops._MRSTFTFn), whatever spelling of the defaults they use."""
+    """The configurations that stay on the default kernels (stft._YamlTerms), whatever spelling of the defaults they use."""
     assert MultiResolutionSTFTLoss(**REF).default_terms
     assert MultiResolutionSTFTLoss(**REF, window="hann_window", w_sc=1, w_log_mag=1, w_lin_mag=0, w_phs=0, mag_distance="L1",
                                    reduction="mean", output="loss", scale=None).default_terms

@@ -122,7 +122,7 @@ def test_raw_entries_refuse_bad_arguments_before_any_launch():
     from vibravox_amd._lib import load
 
     lib = load()
-    assert lib.eben_version() == 5
+    assert lib.eben_version() == 6
     f = (ctypes.c_float * 4096)()
     i32 = (ctypes.c_int32 * 4)(8, 8, 8, 8)
     addr = lambda a, off=0: ctypes.addressof(a) + off

@@ -25,7 +25,7 @@ def gen():
 def test_library_exports_the_ragged_entries_at_abi_5(lib):
     for name in ("eben_si_sdr_ragged", "eben_stoi_ragged_workspace", "eben_stoi_ragged"):
         assert getattr(lib, name) is not None
-    assert lib.eben_version() == 5
+    assert lib.eben_version() == 6
 
 
 @pytest.mark.parametrize("fs", [16000, 10000, 48000])

@@ -189,10 +189,7 @@ SIGNATURES = {
     "eben_weighted_sum": (c_int, [POINTER(c_void_p), _P, c_int, c_size_t, _P, _P]),
     "eben_hinge_bwd": (c_int, [_P, c_size_t, c_float, _P, c_float, _P, _P]),
     "eben_hinge_bwd_stacked": (c_int, [_P, _P, c_size_t, _P, c_float, c_float, c_float, _P, _P]),
-    "eben_stft_loss_sums": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, _P, c_size_t, _P, _P]),
     "eben_stft_loss_sums_workspace": (c_size_t, [c_int]),
-    "eben_stft_loss_bwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, c_float, _P, _P]),
-    "eben_overlap_add": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "eben_time_mask": (c_int, [_P, c_int64, c_int, c_int, c_int, _P]),
     "eben_phase_vocoder": (c_int, [_P, _P, c_int, c_int, c_int, c_int, ctypes.c_double, c_float, _P]),
     "eben_resample": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
@@ -253,7 +250,7 @@ _lib: Optional[ctypes.CDLL] = None
 
 
 #: include/eben_hip.h EBEN_ABI_VERSION this module's structures and signatures were written against
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 
 def load(path: Optional[str] = None) -> ctypes.CDLL:

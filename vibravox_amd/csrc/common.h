@@ -67,6 +67,13 @@ inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s);
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 inline int round_up(int a, int b) { return ceil_div(a, b) * b; }
 inline size_t ceil_div_z(size_t a, size_t b) { return (a + b - 1) / b; }
+// 256-thread blocks for n elements of a grid-stride kernel, 1 <= blocks <= cap
+inline int grid_for(size_t n, int cap = 4096) {
+  size_t b = (n + 255) / 256;
+  if (b > (size_t)cap) b = cap;
+  if (b < 1) b = 1;
+  return (int)b;
+}
 
 // ---- device helpers ------------------------------------------------------------------
 __device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }

@@ -1,6 +1,6 @@
 // Magnitude terms of auraloss STFTLoss beyond the multi_stft.yaml configuration: the optional mel projection (scale="mel") and the
 // weighted spectral-convergence / log-magnitude / linear-magnitude terms under an L1 or L2 distance.  The default configuration
-// (SC + L1 log, no scale) keeps direct.hip's stft_sums_kernel / stft_bwd_kernel / stft_total_kernel; these run every other one.
+// (SC + L1 log, no scale) keeps stft.hip's stft_sums_kernel / stft_bwd_kernel / stft_total_kernel; these run every other one.
 //
 // The spectrum is the flat (2*bins, cols) windowed-DFT output of StftPlan.dft: bin k of column c at k*cols + c (imaginary part at
 // + bins*cols), cols = 2*rows*frames, x rows in columns [0, rows*frames), y rows after them; column r*frames + f is frame f of row r.

@@ -1543,313 +1543,8 @@ def hinge_mean(x: torch.Tensor, target: float) -> torch.Tensor:
     return _HingeFn.apply(x, target)
 
 
-@dataclass
-class StftPlan:
-    n_fft: int
-    hop: int
-    win: int
-    bins: int
-    pad: int
-    spec_f: ConvSpec  # pointwise conv (win -> 2*bins): the windowed DFT of a frame matrix
-    basis_f: torch.Tensor  # (2*bins, win, 1) windowed DFT rows: [cos ; -sin]
-    spec_t: ConvSpec  # pointwise conv (2*bins -> win) used by the backward
-    basis_t: torch.Tensor  # (win, 2*bins, 1) = basis transposed
-    cache_fwd: PackedWeights
-    cache_bwd: PackedWeights
-    #: "dense": one (2*bins x win) GEMM per resolution; "folded": even / odd parts of the frames, two groups of win/2
-    #: channels (half the products, exact fp32); "bf16x3": the folded form with hi / lo bf16 operand splits on the bf16 MFMA
-    math: str = "folded"
-    folded: Optional[dict] = None   # math -> (spec_f, basis_f, spec_t, basis_t, cache_fwd, cache_bwd), built on first use
-    gemm: Optional[dict] = None     # (math, which) -> (basis address, packed image, basis) for the grouped GEMM kernel
-    #: the window's float32 sample 0 is exactly 0 and w[h + m] == w[h - m] (hann, blackman, bartlett): the folded forms drop sample 0
-    #: and read only the right half of the basis, so hamming or kaiser (w[0] != 0) take "dense"
-    foldable: bool = True
-    #: mel projection of the magnitudes (eben_stft_terms_fwd / _bwd): (n_mels, fb_lo, fb_off, fb_w, bin_m, bin_w), or None
-    mel: Optional[tuple] = None
-
-    def frames(self, t: int) -> int:
-        """Frames of a length-t signal: torch.stft(center=True) pads n_fft // 2 on each side and steps an n_fft window by hop."""
-        return (t + 2 * (self.n_fft // 2) - self.n_fft) // self.hop + 1
-
-    def math_for(self, math: str) -> str:
-        """The arithmetic a plan runs: the folded forms need the window's centre h = win / 2 on the DFT's symmetry point n_fft / 2
-        (win and n_fft even, frames at reflect padding win / 2) and a window they can fold (``foldable``); every other plan takes
-        "dense"."""
-        return math if self.foldable and self.win % 2 == 0 and self.n_fft % 2 == 0 and self.pad == self.win // 2 else "dense"
-
-    def gemm_image(self, math: str, which: int, basis: torch.Tensor) -> torch.Tensor:
-        """Packed basis of the folded contraction for ``eben_gemm_fwd``: which = 0 the forward's (2 groups x bins x win/2), 1 its
-        transpose's (2 groups x win/2 x bins); built once per (math, basis storage) -- the bases are constants."""
-        if self.gemm is None:
-            self.gemm = {}
-        key = (math, which)
-        hit = self.gemm.get(key)
-        if hit is None or hit[0] != basis.data_ptr():
-            lib = load()
-            h, cmath = self.win // 2, _STFT_CONV_MATH[math]
-            m, k = (self.bins, h) if which == 0 else (h, self.bins)
-            wp = torch.empty(lib.eben_gemm_packed_floats(cmath, 2, m, k), dtype=torch.float32, device=basis.device)
-            check(lib.eben_gemm_pack(cmath, 2, m, k, ptr(basis), ptr(wp), stream()), "gemm_pack")
-            hit = self.gemm[key] = (basis.data_ptr(), wp, basis)
-        return hit[1]
-
-    def dft(self, math: str, fr: torch.Tensor, cols: int) -> torch.Tensor:
-        """(1, 2*bins, cols) windowed DFT of a frame matrix: fr is (1, win, cols) from eben_stft_frames for "dense", else the
-        (1, c_in, cols) parts from eben_stft_frames_folded (split for "bf16x3")."""
-        lib, st = load(), stream()
-        if math == "dense":
-            spec_f, basis_f, cache, cmath = self.spec_f, self.basis_f, self.cache_fwd, MATH_F32
-        else:
-            spec_f, basis_f, _, _, cache, _ = self.folded_parts(math)
-            cmath = _STFT_CONV_MATH.get(math, MATH_F32)
-        spec = torch.empty((1, 2 * self.bins, cols), dtype=torch.float32, device=fr.device)
-        if STFT_GEMM and math in ("folded_x3", "folded_x6"):
-            # the folded contraction as what it is, a 2-group GEMM (pw_gemm.hip): no input tile, no staging pass per row tile
-            check(lib.eben_gemm_fwd(cmath, 2, self.bins, self.win // 2, cols, ptr(fr), ptr(self.gemm_image(math, 0, basis_f)), ptr(spec), st),
-                  "stft_fwd")
-        else:
-            d2 = conv_desc(spec_f, 1, cols, cmath)
-            pw = pack_weights(spec_f, d2, basis_f, None, cache, False)
-            check(lib.eben_conv1d_fwd(ctypes.byref(d2), ptr(fr), ptr(pw.wp_fwd), None, None, ptr(spec), st), "stft_fwd")
-        return spec
-
-    def dft_t(self, math: str, dspec: torch.Tensor, cols: int) -> torch.Tensor:
-        """The adjoint of ``dft``: (1, 2*bins, cols) -> (1, win, cols) frame gradients ("dense") or the (1, 2*(win/2), cols) [dE ; dO]
-        parts eben_overlap_add_folded takes."""
-        lib, st = load(), stream()
-        if math == "dense":
-            spec_t, basis_t, cache, cmath = self.spec_t, self.basis_t, self.cache_bwd, MATH_F32
-        else:
-            _, _, spec_t, basis_t, _, cache = self.folded_parts(math)
-            cmath = _STFT_CONV_MATH.get(math, MATH_F32)
-            if math == "bf16x3":
-                dsplit = torch.empty((1, spec_t.c_in, cols), dtype=torch.float32, device=dspec.device)
-                check(lib.eben_split3(ptr(dspec), ptr(dsplit), 2, self.bins, cols, st), "split3")
-                dspec = dsplit
-        dfr = torch.empty((1, spec_t.c_out, cols), dtype=torch.float32, device=dspec.device)
-        if STFT_GEMM and math in ("folded_x3", "folded_x6"):
-            check(lib.eben_gemm_fwd(cmath, 2, self.win // 2, self.bins, cols, ptr(dspec), ptr(self.gemm_image(math, 1, basis_t)), ptr(dfr), st),
-                  "stft_bwd_gemm")
-        else:
-            d1 = conv_desc(spec_t, 1, cols, cmath)
-            pw = pack_weights(spec_t, d1, basis_t, None, cache, False)
-            check(lib.eben_conv1d_fwd(ctypes.byref(d1), ptr(dspec), ptr(pw.wp_fwd), None, None, ptr(dfr), st), "stft_bwd_gemm")
-        return dfr
-
-    def folded_parts(self, math: str):
-        """Weights of the folded pointwise convs (eben_stft_frames_folded): forward, 2 groups x (nsub*h -> bins) with
-        rows basis[:, h:] (x [W_hi, W_hi, W_lo] for bf16x3); backward, 2 groups x (nsub*bins -> h), its transpose."""
-        if self.folded is None:
-            self.folded = {}
-        parts = self.folded.get(math)
-        if parts is None:
-            h, bins = self.win // 2, self.bins
-            w = self.basis_f[:, h:, 0].contiguous()                       # (2*bins, h)
-            wt = w.reshape(2, bins, h).transpose(1, 2).contiguous()       # (2, h, bins): group g, output row m, reduction k
-            if math == "bf16x3":
-                def split(a, dim):
-                    hi = a.to(torch.bfloat16).to(torch.float32)
-                    lo = (a - hi).to(torch.bfloat16).to(torch.float32)
-                    return torch.cat((hi, hi, lo), dim=dim)
-                w, wt, nsub = split(w, 1), split(wt, 2), 3
-            else:
-                nsub = 1
-            parts = (ConvSpec(c_in=2 * nsub * h, c_out=2 * bins, ksize=1, groups=2), w.unsqueeze(-1).contiguous(),
-                     ConvSpec(c_in=2 * nsub * bins, c_out=2 * h, ksize=1, groups=2), wt.reshape(2 * h, nsub * bins, 1).contiguous(),
-                     PackedWeights(), PackedWeights())
-            self.folded[math] = parts
-        return parts
-
-
-#: StftPlan.math -> EBEN_MATH_* of the folded windowed-DFT contractions ("bf16x3": single bf16 operands over the concatenated
-#: [hi ; lo ; hi] x [W_hi ; W_hi ; W_lo] reduction; "folded_x3" / "folded_x6": the tap-conv's own split operands, tapconv3.hip)
-_STFT_CONV_MATH = {"bf16x3": MATH_BF16, "folded_x3": MATH_BF16X3, "folded_x6": MATH_BF16X6}
-
-
 #: loss values from their partial sums by one launch each (eben_stft_loss_total, eben_disc_losses) instead of one-element torch kernels
 FUSED_LOSS_GLUE = os.environ.get("EBEN_FUSED_LOSS_GLUE", "1") != "0"
-#: the folded windowed-DFT contractions on the grouped GEMM kernel (pw_gemm.hip) instead of the pointwise tap-conv
-STFT_GEMM = os.environ.get("EBEN_STFT_GEMM", "1") != "0"
-
-
-def _stft_spectrum(p: StftPlan, math: str, sig: torch.Tensor, t: int, frames: int) -> torch.Tensor:
-    """(1, 2*bins, R*frames) windowed DFT of every row of sig (R, 1, t): eben_stft_frames ("dense") or eben_stft_frames_folded, then
-    the plan's contraction."""
-    lib, st = load(), stream()
-    nrows = sig.shape[0]
-    cols = nrows * frames
-    if math == "dense":
-        fr = torch.empty((1, p.win, cols), dtype=torch.float32, device=sig.device)
-        check(lib.eben_stft_frames(ptr(sig), ptr(fr), nrows, t, p.win, p.hop, p.pad, frames, st), "stft_frames")
-    else:
-        fr = torch.empty((1, p.folded_parts(math)[0].c_in, cols), dtype=torch.float32, device=sig.device)
-        check(lib.eben_stft_frames_folded(ptr(sig), ptr(fr), nrows, t, p.win, p.hop, p.pad, frames, 1 if math == "bf16x3" else 0, st),
-              "stft_frames_folded")
-    return p.dft(math, fr, cols)
-
-
-def _stft_spectrum_adjoint(p: StftPlan, math: str, dspec: torch.Tensor, dsig: torch.Tensor, t: int, frames: int, accumulate: bool) -> None:
-    """dsig (R, 1, t) (+)= the adjoint of ``_stft_spectrum`` applied to dspec (1, 2*bins, R*frames)."""
-    lib, st = load(), stream()
-    rows = dsig.shape[0]
-    xcols = rows * frames
-    # d(frames)[j, (r, f)] = sum_m basis[m, j] dspec[m, (r, f)]: one dense GEMM, then overlap-add
-    dfr = p.dft_t(math, dspec, xcols)
-    if math == "dense":
-        check(lib.eben_overlap_add_ex(ptr(dfr), ptr(dsig), rows, t, p.win, frames, p.hop, p.pad, 1, 1 if accumulate else 0, frames, xcols, st),
-              "overlap_add")
-    else:
-        check(lib.eben_overlap_add_folded(ptr(dfr), ptr(dsig), rows, t, p.win, frames, p.hop, p.pad, 1 if accumulate else 0, frames, xcols, st),
-              "overlap_add_folded")
-
-
-class _MRSTFTFn(torch.autograd.Function):
-    """auraloss MultiResolutionSTFTLoss(x, y) as configured by multi_stft.yaml (see mrstft_loss.py).
-
-    Per resolution: ``eben_stft_frames`` writes the reflect-padded frames of ALL signals (x and y rows) as one
-    (win, R*frames) matrix, the windowed DFT is one dense GEMM over it (pointwise tap-conv, batch 1 -- a strided conv
-    per item would pad every item's 134 / 267 frames to whole 128-column tiles), the loss sums read the flat
-    (2*bins, R*frames) spectrum through strides; backward: d(spec) in the same flat form, d(frames) = basis^T . d(spec)
-    as one GEMM, overlap-add back onto the waveform.  ``plan.math`` "folded" / "bf16x3" (even window lengths): the frames
-    are written as their even and odd parts about the window centre and the GEMMs become 2-group contractions over
-    win/2 channels (``StftPlan.folded_parts``)."""
-
-    @staticmethod
-    def forward(ctx, x, y, fir, plans: List[StftPlan], eps: float):
-        lib = load()
-        st = stream()
-        x, y = x.contiguous(), y.contiguous()
-        b, c, t = x.shape
-        rows = b * c
-        sig = torch.cat((x.reshape(rows, 1, t), y.reshape(rows, 1, t)), dim=0)
-        if fir is not None:
-            nt = fir.numel()
-            sig = _fir_decimate(sig, fir, t, 1, nt, 1, -(nt // 2))
-        total = None
-        saved = []
-        for p in plans:
-            frames = p.frames(t)
-            cols = 2 * rows * frames
-            math = p.math_for(p.math)
-            spec = _stft_spectrum(p, math, sig, t, frames)
-            sums = torch.empty((rows, 3), dtype=torch.float32, device=x.device)
-            # y rows: same strides, column offset rows*frames
-            ws_bytes = lib.eben_stft_loss_sums_workspace(rows)
-            check(lib.eben_stft_loss_sums_ex(ptr(spec), ptr(spec) + 4 * rows * frames, rows, p.bins, frames, frames, cols, p.bins * cols, eps,
-                                             ptr(_empty(ws_bytes, x)), ws_bytes, ptr(sums), st), "stft_loss_sums")
-            saved.append((spec, sums, frames, math))
-        ctx.plans, ctx.eps, ctx.geom, ctx.saved, ctx.fir = plans, eps, (b, c, t, rows), saved, fir
-        n = len(plans)
-        if n <= 8 and FUSED_LOSS_GLUE:   # the value from the per-row sums of all resolutions: one launch instead of ~8 one-element torch kernels per resolution
-            total = torch.empty((), dtype=torch.float32, device=x.device)
-            check(lib.eben_stft_loss_total((ctypes.c_void_p * n)(*[ptr(sv[1]) for sv in saved]),
-                                           (ctypes.c_float * n)(*[1.0 / float(rows * p.bins * sv[2]) for p, sv in zip(plans, saved)]), n, rows,
-                                           ptr(total), st), "stft_loss_total")
-            return total
-        for p, (_, sums, frames, _) in zip(plans, saved):
-            term = torch.sqrt(sums[:, 0] / sums[:, 1]).mean() + sums[:, 2].sum() / float(rows * p.bins * frames)
-            total = term if total is None else total + term
-        return total / n
-
-    @staticmethod
-    def backward(ctx, gout):
-        lib = load()
-        st = stream()
-        b, c, t, rows = ctx.geom
-        gout = gout.contiguous().reshape(1)
-        dsig = torch.empty((rows, 1, t), dtype=torch.float32, device=gout.device)
-        for i, (p, (spec, sums, frames, math)) in enumerate(zip(ctx.plans, ctx.saved)):
-            cols, xcols = 2 * rows * frames, rows * frames
-            dspec = torch.empty((1, 2 * p.bins, xcols), dtype=torch.float32, device=gout.device)
-            check(lib.eben_stft_loss_bwd_ex(ptr(spec), ptr(spec) + 4 * xcols, rows, p.bins, frames, frames, cols, p.bins * cols, ctx.eps,
-                                            ptr(sums), ptr(gout), 1.0 / len(ctx.plans), ptr(dspec), frames, xcols, p.bins * xcols, st),
-                  "stft_loss_bwd")
-            _stft_spectrum_adjoint(p, math, dspec, dsig, t, frames, i > 0)
-        if ctx.fir is not None:
-            nt = ctx.fir.numel()
-            dsig = _fir_interp_sum(dsig, ctx.fir, t, 1, nt, 1, -(nt // 2))
-        return dsig.reshape(b, c, t), None, None, None, None
-
-
-def mrstft(x: torch.Tensor, y: torch.Tensor, fir: Optional[torch.Tensor], plans: List[StftPlan], eps: float = 1e-8) -> torch.Tensor:
-    return _MRSTFTFn.apply(x, y.detach(), fir, plans, eps)
-
-
-#: eben_stft_terms_* term mask bits
-STFT_TERM_SC, STFT_TERM_LOG, STFT_TERM_LIN = 1, 2, 4
-
-
-class _MRSTFTTermsFn(torch.autograd.Function):
-    """auraloss MultiResolutionSTFTLoss(x, y) outside multi_stft.yaml's configuration: any window (through the plans' bases), an
-    optional mel projection per plan (``StftPlan.mel``), the weighted SC / log / lin terms under L1 or L2 (stft_terms.hip).  Framing,
-    windowed DFT, its adjoint, the overlap-add and the FIR are _MRSTFTFn's; only the magnitude terms differ."""
-
-    @staticmethod
-    def forward(ctx, x, y, fir, plans: List[StftPlan], eps: float, weights, l2: bool):
-        lib = load()
-        st = stream()
-        x, y = x.contiguous(), y.contiguous()
-        b, c, t = x.shape
-        rows = b * c
-        w_sc, w_log, w_lin = (float(w) for w in weights)
-        terms = (STFT_TERM_SC if w_sc else 0) | (STFT_TERM_LOG if w_log else 0) | (STFT_TERM_LIN if w_lin else 0)
-        sig = torch.cat((x.reshape(rows, 1, t), y.reshape(rows, 1, t)), dim=0)
-        if fir is not None:
-            nt = fir.numel()
-            sig = _fir_decimate(sig, fir, t, 1, nt, 1, -(nt // 2))
-        saved, inv_counts = [], []
-        ws_bytes = lib.eben_stft_terms_workspace(rows)
-        for p in plans:
-            frames = p.frames(t)
-            math = p.math_for(p.math)
-            spec = _stft_spectrum(p, math, sig, t, frames)
-            sums = torch.empty((rows, 4), dtype=torch.float32, device=x.device)
-            if p.mel is not None:
-                n_out, fb_lo, fb_off, fb_w = p.mel[:4]
-                mags = torch.empty((2, rows, n_out, frames), dtype=torch.float32, device=x.device)
-                mel_ptrs = (_iptr(fb_lo), _iptr(fb_off), ptr(fb_w))
-            else:
-                n_out, mags, mel_ptrs = p.bins, None, (None, None, None)
-            check(lib.eben_stft_terms_fwd(ptr(spec), rows, p.bins, frames, eps, n_out, *mel_ptrs, terms, int(l2), ptr(mags),
-                                          ptr(_empty(ws_bytes, x)), ws_bytes, ptr(sums), st), "stft_terms_fwd")
-            saved.append((spec, sums, frames, math, mags))
-            inv_counts.append(1.0 / float(rows * n_out * frames))
-        ctx.plans, ctx.eps, ctx.geom, ctx.saved, ctx.fir = plans, eps, (b, c, t, rows), saved, fir
-        ctx.terms, ctx.l2, ctx.weights = terms, int(l2), (w_sc, w_log, w_lin)
-        n = len(plans)
-        total = torch.empty((), dtype=torch.float32, device=x.device)
-        check(lib.eben_stft_terms_total((ctypes.c_void_p * n)(*[ptr(sv[1]) for sv in saved]), (ctypes.c_float * n)(*inv_counts), n, rows, terms,
-                                        w_sc, w_log, w_lin, ptr(total), st), "stft_terms_total")
-        return total
-
-    @staticmethod
-    def backward(ctx, gout):
-        lib = load()
-        st = stream()
-        b, c, t, rows = ctx.geom
-        gout = gout.contiguous().reshape(1)
-        dsig = torch.empty((rows, 1, t), dtype=torch.float32, device=gout.device)
-        for i, (p, (spec, sums, frames, math, mags)) in enumerate(zip(ctx.plans, ctx.saved)):
-            dspec = torch.empty((1, 2 * p.bins, rows * frames), dtype=torch.float32, device=gout.device)
-            if p.mel is not None:
-                n_out, bin_m, bin_w = p.mel[0], p.mel[4], p.mel[5]
-                adj = (_iptr(bin_m), ptr(bin_w), ptr(mags))
-            else:
-                n_out, adj = p.bins, (None, None, None)
-            check(lib.eben_stft_terms_bwd(ptr(spec), rows, p.bins, frames, ctx.eps, n_out, *adj, ctx.terms, ctx.l2, *ctx.weights, ptr(sums),
-                                          ptr(gout), 1.0 / len(ctx.plans), ptr(dspec), st), "stft_terms_bwd")
-            _stft_spectrum_adjoint(p, math, dspec, dsig, t, frames, i > 0)
-        if ctx.fir is not None:
-            nt = ctx.fir.numel()
-            dsig = _fir_interp_sum(dsig, ctx.fir, t, 1, nt, 1, -(nt // 2))
-        return dsig.reshape(b, c, t), None, None, None, None, None, None
-
-
-def mrstft_terms(x: torch.Tensor, y: torch.Tensor, fir: Optional[torch.Tensor], plans: List[StftPlan], eps: float, weights: Sequence[float],
-                 l2: bool) -> torch.Tensor:
-    """MultiResolutionSTFTLoss with weights (w_sc, w_log_mag, w_lin_mag), mag_distance L2 (l2) or L1 and the plans' windows and mel
-    projections (eben_stft_terms_*); at least one weight non-zero, at most 16 resolutions."""
-    return _MRSTFTTermsFn.apply(x, y.detach(), fir, plans, eps, tuple(weights), l2)
 
 
 # --------------------------------------------------------------------------------------------
@@ -1912,38 +1607,4 @@ def clip_losses(rows: int, device, stft=None, fm=None, hinge=None) -> torch.Tens
                                   (ctypes.c_int * n)(*[int(b) for _, _, b in stft]) if n else None, n, ptr(fm_sums),
                                   fm_sums.shape[0] if fm_sums is not None else 0, float(inv), ptr(hinge), hinge.shape[0] // 3 if hinge is not None else 0,
                                   rows, ptr(out), stream()), "clip_losses")
-    return out
-
-
-#: called with the (2 rows, 1, l_buf) A-weighted signal of ``mrstft_sums_rows`` and its row lengths, in front of the mirror fill (tests
-#: write garbage behind the rows there: nothing of it may reach a result)
-mrstft_rows_probe = None
-
-
-def mrstft_sums_rows(x: torch.Tensor, y: torch.Tensor, lens2: torch.Tensor, frames_of_row, fir: Optional[torch.Tensor], plans: List[StftPlan],
-                     eps: float, fill: int) -> List[torch.Tensor]:
-    """Per plan the (rows, 3) sums of ``_MRSTFTFn.forward`` with every row on its own frames: x and y (rows, 1, l_buf), zero behind each
-    row; ``lens2`` (2 rows,) int32 on the device, the row lengths twice; ``frames_of_row[i]`` (rows,) int32, plan i's frames of each row.
-    The FIR's zero padding finds the zeros behind a row, one mirror fill of ``fill`` samples (the largest reflect pad; 0: rows as long
-    as the buffer) stands for every plan's reflect padding, then framing and contraction run on the whole buffer."""
-    lib, st = load(), stream()
-    rows, _, t = x.shape
-    sig = torch.cat((x.reshape(rows, 1, t), y.reshape(rows, 1, t)), dim=0)
-    if fir is not None:
-        nt = fir.numel()
-        sig = _fir_decimate(sig, fir, t, 1, nt, 1, -(nt // 2))
-    if mrstft_rows_probe is not None:
-        mrstft_rows_probe(sig, lens2)
-    if fill:
-        edge_fill(sig, lens2, FILL_MIRROR, fill)
-    out = []
-    for p, fr in zip(plans, frames_of_row):
-        frames = p.frames(t)
-        cols = 2 * rows * frames
-        spec = _stft_spectrum(p, p.math_for(p.math), sig, t, frames)
-        sums = torch.empty((rows, 3), dtype=torch.float32, device=x.device)
-        ws_bytes = lib.eben_stft_loss_sums_rows_workspace(rows)
-        check(lib.eben_stft_loss_sums_rows(ptr(spec), ptr(spec) + 4 * rows * frames, rows, p.bins, frames, _iptr(fr), frames, cols, p.bins * cols, eps,
-                                           ptr(_empty(ws_bytes, x)), ws_bytes, ptr(sums), st), "stft_loss_sums_rows")
-        out.append(sums)
     return out

@@ -18,8 +18,8 @@ blackman / bartlett / kaiser), ``w_sc`` / ``w_log_mag`` / ``w_lin_mag`` (a zero 
 L1 / L2, and ``scale="mel"`` with ``n_bins`` -- the magnitudes projected by ``librosa.filters.mel(sr=sample_rate, n_fft=n_fft,
 n_mels=n_bins)`` with its defaults (Slaney scale and norm, fmin 0, fmax sr/2), restated in ``mel_filterbank``.  Per resolution:
 M = sqrt(clamp(re^2 + im^2, eps)) [-> F . M], then w_sc mean_rows ||My - Mx||_F / ||My||_F + w_log_mag dist(log Mx, log My) +
-w_lin_mag dist(Mx, My), the mean over the resolutions.  The multi_stft.yaml configuration keeps its own kernels (ops._MRSTFTFn);
-every other one runs ops._MRSTFTTermsFn (stft_terms.hip).  ``scale="chroma"``, ``w_phs``, ``scale_invariance`` and non-default
+w_lin_mag dist(Mx, My), the mean over the resolutions.  The multi_stft.yaml configuration keeps its own kernels (stft._YamlTerms);
+every other one runs stft._WeightedTerms (stft_terms.hip).  ``scale="chroma"``, ``w_phs``, ``scale_invariance`` and non-default
 ``reduction`` / ``output`` are not built and raise NotImplementedError.
 """
 from __future__ import annotations
@@ -32,7 +32,7 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from ... import ops
+from ... import ops, stft
 
 
 _DATA = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "data")
@@ -205,7 +205,7 @@ class MultiResolutionSTFTLoss(torch.nn.Module):
                 raise ValueError(f"scale='mel' needs 0 < n_bins <= n_fft of every resolution, got n_bins={n_bins}")
         if perceptual_weighting and sample_rate is None:
             raise ValueError("`sample_rate` must be supplied when `perceptual_weighting = True`.")
-        #: the multi_stft.yaml configuration (hann, SC + L1 log-magnitude, no scale) keeps ops._MRSTFTFn; every other runs ops._MRSTFTTermsFn
+        #: the multi_stft.yaml configuration (hann, SC + L1 log-magnitude, no scale) keeps stft._YamlTerms; every other runs stft._WeightedTerms
         self.default_terms = (window == "hann_window" and w_sc == 1.0 and w_log_mag == 1.0 and not w_lin_mag and mag_distance == "L1"
                               and scale is None)
         if not self.default_terms and len(fft_sizes) > 16:
@@ -229,18 +229,11 @@ class MultiResolutionSTFTLoss(torch.nn.Module):
     def _build_plans(self):
         plans = []
         for i, (n_fft, hop, win) in enumerate(zip(self.fft_sizes, self.hop_sizes, self.win_lengths)):
-            bins = n_fft // 2 + 1
             mel = None
             if self.scale == "mel":
                 mel = (self.n_bins,) + tuple(getattr(self, f"mel_{name}_{i}") for name in ("lo", "off", "w", "bin_m", "bin_w"))
-            # the window centred in n_fft (torch.stft puts it (n_fft - win)//2 samples into the frame) + center=True reflect
-            # padding of n_fft//2 == frames of length `win` taken at reflect padding n_fft//2 - (n_fft - win)//2 (the window is
-            # zero outside its `win` samples); win/2 when n_fft and win are both even
-            plans.append(ops.StftPlan(n_fft=n_fft, hop=hop, win=win, bins=bins, pad=n_fft // 2 - (n_fft - win) // 2,
-                                      spec_f=ops.ConvSpec(c_in=win, c_out=2 * bins, ksize=1), basis_f=getattr(self, f"basis_{i}"),
-                                      spec_t=ops.ConvSpec(c_in=2 * bins, c_out=win, ksize=1), basis_t=getattr(self, f"basis_t_{i}"),
-                                      cache_fwd=ops.PackedWeights(), cache_bwd=ops.PackedWeights(),
-                                      foldable=window_foldable(self.window, win), mel=mel))
+            plans.append(stft.StftPlan.build(n_fft, hop, win, getattr(self, f"basis_{i}"), getattr(self, f"basis_t_{i}"),
+                                             foldable=window_foldable(self.window, win), mel=mel))
         return plans
 
     #: arithmetic of the windowed-DFT contractions: "folded" (exact fp32 on the even / odd parts of the frames: half the products
@@ -250,22 +243,26 @@ class MultiResolutionSTFTLoss(torch.nn.Module):
     #: folded forms cannot fold (hamming, kaiser) takes "dense" in every mode.  The mel projection and the terms run in fp32 always.
     stft_math: str = os.environ.get("EBEN_STFT_MATH", "folded")
 
-    def forward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    def _current_plans(self, x: torch.Tensor):
+        """The plans on x's device and the buffers' current storage, set to ``stft_math``."""
         if self.stft_math not in ("folded", "dense", "bf16x3", "folded_x3", "folded_x6"):
             raise ValueError(f"unknown STFT math {self.stft_math!r}")
         if self._plans is None or self._plans[0].basis_f.device != x.device or self._plans[0].basis_f.data_ptr() != self.basis_0.data_ptr():
             self._plans = self._build_plans()
         for p in self._plans:
             p.math = self.stft_math
+        return self._plans
+
+    def forward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        plans = self._current_plans(x)
         if self.default_terms:
-            return ops.mrstft(x, y, self.fir, self._plans, self.eps)
-        return ops.mrstft_terms(x, y, self.fir, self._plans, self.eps, (self.w_sc, self.w_log_mag, self.w_lin_mag), self.mag_distance == "L2")
+            return stft.mrstft(x, y, self.fir, plans, self.eps)
+        return stft.mrstft_terms(x, y, self.fir, plans, self.eps, (self.w_sc, self.w_log_mag, self.w_lin_mag), self.mag_distance == "L2")
 
     def ragged_sums(self, x: torch.Tensor, y: torch.Tensor, lengths: Sequence[int]):
         """The per-row sums behind ``forward_ragged``: per resolution (sums (rows, 3), frames_of_row (rows,) int32 on the device, bins),
         what ``ops.clip_losses`` takes.  Checks everything ``forward_ragged`` refuses before anything runs."""
-        if self.stft_math not in ("folded", "dense", "bf16x3", "folded_x3", "folded_x6"):
-            raise ValueError(f"unknown STFT math {self.stft_math!r}")
+        plans = self._current_plans(x)   # host work only: nothing is launched before the checks below
         if not (self.w_sc == 1.0 and self.w_log_mag == 1.0 and not self.w_lin_mag and self.mag_distance == "L1" and self.scale is None):
             raise NotImplementedError(
                 f"forward_ragged is built for the multi_stft.yaml term set (w_sc = w_log_mag = 1, L1, no scale; any window), not for w_sc="
@@ -280,23 +277,19 @@ class MultiResolutionSTFTLoss(torch.nn.Module):
         lengths = [int(t) for t in lengths]
         if len(lengths) != rows:
             raise ValueError(f"forward_ragged: {len(lengths)} lengths for {rows} rows")
-        if self._plans is None or self._plans[0].basis_f.device != x.device or self._plans[0].basis_f.data_ptr() != self.basis_0.data_ptr():
-            self._plans = self._build_plans()
-        pad = max(p.pad for p in self._plans)
+        pad = max(p.pad for p in plans)
         for r, t in enumerate(lengths):
             if t < pad + 1:
                 raise ValueError(f"clip {r} ({t} samples) is too short: the STFT reflect-pads {pad} samples")
             if t > l_buf or (t < l_buf and t + pad > l_buf):
                 raise ValueError(f"clip {r} ({t} samples) needs {pad} samples of slack behind it in a buffer of {l_buf}, or none at all")
-        for p in self._plans:
-            p.math = self.stft_math
         with torch.no_grad():
-            host = torch.tensor([lengths + lengths] + [[p.frames(t) for t in lengths] * 2 for p in self._plans], dtype=torch.int32)
+            host = torch.tensor([lengths + lengths] + [[p.frames(t) for t in lengths] * 2 for p in plans], dtype=torch.int32)
             table = host.to(x.device, non_blocking=True)   # the one upload: row lengths, then every resolution's frames per row
-            frames = [table[1 + i, :rows] for i in range(len(self._plans))]
+            frames = [table[1 + i, :rows] for i in range(len(plans))]
             fill = pad if any(t < l_buf for t in lengths) else 0
-            sums = ops.mrstft_sums_rows(x.contiguous(), y.contiguous(), table[0], frames, self.fir, self._plans, self.eps, fill)
-        return [(s, f, p.bins) for s, f, p in zip(sums, frames, self._plans)]
+            sums = stft.mrstft_sums_rows(x.contiguous(), y.contiguous(), table[0], frames, self.fir, plans, self.eps, fill)
+        return [(s, f, p.bins) for s, f, p in zip(sums, frames, plans)]
 
     def forward_ragged(self, x: torch.Tensor, y: torch.Tensor, lengths: Sequence[int]) -> torch.Tensor:
         """(rows,) float32: row r is ``forward(x[r:r+1, :, :lengths[r]], y[r:r+1, :, :lengths[r]])``, all rows in one pass.  ``x`` and ``y``
