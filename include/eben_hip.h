@@ -395,6 +395,31 @@ EBEN_API int eben_rubl_bwd(int batch, int channels, int length, int dilation, co
 EBEN_API int eben_rubl_dw_slabs(int batch, int channels, int length);
 EBEN_API int eben_rubl_dw(int batch, int channels, int length, int dilation, const void* gzb, const void* hb, const void* ghb, const void* xb,
                           float* slabs_pw, float* slabs_dil, void* stream);
+/* The kernel instantiation and the launch geometry of a ResidualUnit launch, asked of the host without launching anything (for tests):
+ * the decision the launcher itself dispatches on, the values of its static knobs included (EBEN_RU3_W128; EBEN_RUBL_NW32 / _NW64 / _G128 /
+ * _RT64 / _RT128 / _BKT128 / _SEG32 / _SEG64 / _SEG128; EBEN_RUDW_UNROLL / _SEG -- each read once per process).
+ * op: EBEN_RU_OP_*; math as the entry point takes it (ignored by the three entry points that take none).
+ * out[0 .. EBEN_RU_VARIANT_N - 1] (n >= EBEN_RU_VARIANT_N, else EBEN_EINVAL):
+ *   [0]      EBEN_RU_FAMILY_*
+ *   [1..5]   the template arguments, 0 past the last: F32 <CT>; SPLIT forward <CT, NW, NP, KSC, BL>, input gradient <CT, NW, NP, G>;
+ *            BL_BWD <CT, NW, G>; RU_DW <CT, NP, UN>; RUBL_DW <CT, RT, BKT>
+ *   [6]      positions per block (forwards 128 or 64; input gradients BO = 32 NW - 2 dilation; weight gradients the slab length)
+ *   [7]      tiles per item (weight gradients: slabs per item)       [8]  blocks of the grid       [9]  dynamic LDS bytes
+ *   [10..12] weight gradients: slab length, slabs per item, slabs in all (= eben_ru_dw_slabs / eben_rubl_dw_slabs); 0 otherwise
+ * Returns the code of the launch for what the launch refuses (channels, dilation, length <= dilation, a math mode the op lacks). */
+#define EBEN_RU_OP_FWD 0      /* eben_ru_fwd_ex */
+#define EBEN_RU_OP_BL_FWD 1   /* eben_rubl_fwd */
+#define EBEN_RU_OP_BWD 2      /* eben_ru_bwd_ex */
+#define EBEN_RU_OP_BL_BWD 3   /* eben_rubl_bwd */
+#define EBEN_RU_OP_DW 4       /* eben_ru_dw */
+#define EBEN_RU_OP_BL_DW 5    /* eben_rubl_dw */
+#define EBEN_RU_FAMILY_F32 1      /* ru_fwd_kernel / ru_bwd_kernel (exact_fp32/ru_fused.hip) */
+#define EBEN_RU_FAMILY_SPLIT 2    /* ru3_fwd_kernel / ru3_bwd_kernel (ru_split.hip) */
+#define EBEN_RU_FAMILY_BL_BWD 3   /* rubl_bwd_kernel (ru_bl.hip) */
+#define EBEN_RU_FAMILY_RU_DW 4    /* ru_dw_kernel (ru_dw.hip) */
+#define EBEN_RU_FAMILY_RUBL_DW 5  /* rubl_dw_kernel (ru_bl.hip) */
+#define EBEN_RU_VARIANT_N 13
+EBEN_API int eben_ru_variant(int op, int math, int batch, int channels, int length, int dilation, int* out, int n);
 
 /* ---- PQMF / FIR banks (vibravox/torch_modules/dsp/pqmf.py:17-232, eben_generator.py:209-211; auraloss FIRFilter) ---------- */
 /* Exact fp32 products, fp32 accumulation in a fixed order (bitwise reproducible), any off0 (floor division for negative offsets),

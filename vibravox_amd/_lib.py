@@ -161,6 +161,7 @@ SIGNATURES = {
     "eben_rubl_bwd": (c_int, [c_int, c_int, c_int, c_int, _P, _P, c_float, _P, c_float, _P, _P, _P, _P, _P, _P]),
     "eben_rubl_dw_slabs": (c_int, [c_int, c_int, c_int]),
     "eben_rubl_dw": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "eben_ru_variant": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int), c_int]),
     "eben_fir_decimate": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "eben_fir_interp_sum": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "eben_fir_plan": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int), c_int]),

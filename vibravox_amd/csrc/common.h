@@ -289,4 +289,23 @@ size_t dw3_workspace(const Canon& c, int* nslab, int* row_stride);
 int dw3_launch(const Canon& c, const float* a, const float* amask, float a_slope, const float* x, float x_slope, int has_bias, float* workspace,
                size_t ws_bytes, hipStream_t st);
 
+// ResidualUnit launches (ru_fused.hip, ru_split.hip, ru_bl.hip, ru_dw.hip): the one decision each launcher dispatches on and
+// eben_ru_variant reports -- kernel family, template arguments (the values the static knobs supply included) and launch geometry.
+// A resolver refuses, with the launch's own code, what the launch refuses (the pointers aside).
+struct RuPlan {
+  int family;         // EBEN_RU_FAMILY_*
+  int targ[5];        // the instantiation's template arguments in declaration order, 0 past the last
+  int tile;           // positions per block: forwards BN, input gradients BO = 32 NW - 2 d, weight gradients the slab length
+  int ntile;          // tiles (weight gradients: slabs) per item
+  long long blocks;   // the grid
+  size_t lds;         // dynamic LDS bytes
+  int row;            // fp32 family: floats per staged LDS row (a kernel argument there), else 0
+  int seg;            // weight gradients: slab length (else 0)
+};
+int ru_f32_plan(int which, int batch, int channels, int length, int dilation, RuPlan* p);              // which 0: eben_ru_fwd, 1: eben_ru_bwd
+int ru3_plan(int which, int bl, int math, int batch, int channels, int length, int dilation, RuPlan* p);   // eben_ru_fwd_ex / eben_rubl_fwd (bl) / eben_ru_bwd_ex
+int rubl_bwd_plan(int batch, int channels, int length, int dilation, RuPlan* p);
+int rubl_dw_plan(int batch, int channels, int length, int dilation, RuPlan* p);
+int ru_dw_plan(int math, int batch, int channels, int length, int dilation, RuPlan* p);
+
 }  // namespace eben

@@ -462,6 +462,23 @@ __global__ __launch_bounds__(256) void ru_pack_bwd_kernel(const float* __restric
 
 static int ru_xs(int d) { return round_up(128 + 2 * d + 3, 4); }
 
+// which 0: ru_fwd_kernel<CT> on tiles of 128 positions; 1: ru_bwd_kernel<CT> on windows of 128 columns, BO = 128 - 2 d of them outputs
+int ru_f32_plan(int which, int batch, int channels, int length, int dilation, RuPlan* p) {
+  EBEN_REQUIRE(channels == 32 || channels == 64 || channels == 128, "fused ResidualUnit: 32, 64 or 128 channels (got %d)", channels);
+  EBEN_REQUIRE(batch > 0 && length > 0 && dilation >= 1 && dilation <= 16 && dilation < length, "bad ResidualUnit geometry");
+  *p = RuPlan{};
+  const int CT = channels / 32;
+  p->family = EBEN_RU_FAMILY_F32;
+  p->targ[0] = CT;
+  p->tile = which == 0 ? 128 : 128 - 2 * dilation;
+  p->row = which == 0 ? ru_xs(dilation) : 132;
+  p->ntile = ceil_div(length, p->tile);
+  p->blocks = (long long)batch * p->ntile;
+  p->lds = sizeof(float) * (2 * 16 * 64 * CT + (size_t)32 * CT * p->row);
+  if (p->blocks > 0x7fffffffLL) return fail(EBEN_EINVAL, "ResidualUnit grid too large");
+  return EBEN_OK;
+}
+
 }  // namespace eben
 
 using namespace eben;
@@ -483,10 +500,9 @@ extern "C" int eben_ru_pack(int channels, const float* v_dil, const float* scale
 }
 
 template <int CT>
-static int launch_ru(const RuArgs& a, hipStream_t st) {
+static int launch_ru(const RuArgs& a, size_t lds, hipStream_t st) {
   static LdsAttrOnce attr_once;
   auto kern = ru_fwd_kernel<CT>;
-  const size_t lds = sizeof(float) * (2 * 16 * 64 * CT + (size_t)32 * CT * a.XS);
   {
     const hipError_t e = lds_attr_once(attr_once, reinterpret_cast<const void*>(kern));
     if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(ru_fwd)");
@@ -498,19 +514,18 @@ static int launch_ru(const RuArgs& a, hipStream_t st) {
 
 extern "C" int eben_ru_fwd(int batch, int channels, int length, int dilation, const float* x, float in_slope, float out_slope,
                            const float* wimg, float* y, float* h, float* u, void* stream) {
-  EBEN_REQUIRE(channels == 32 || channels == 64 || channels == 128, "fused ResidualUnit: 32, 64 or 128 channels (got %d)", channels);
-  EBEN_REQUIRE(batch > 0 && length > 0 && dilation >= 1 && dilation <= 16 && dilation < length, "bad ResidualUnit geometry");
+  RuPlan p;
+  if (const int rc = ru_f32_plan(0, batch, channels, length, dilation, &p)) return rc;
   EBEN_REQUIRE(x && wimg && y, "null pointer in ru_fwd");
   RuArgs a;
   a.x = x; a.wimg = wimg; a.y = y; a.h = h; a.u = u;
-  a.B = batch; a.C = channels; a.L = length; a.d = dilation; a.ntt = ceil_div(length, 128); a.XS = ru_xs(dilation);
+  a.B = batch; a.C = channels; a.L = length; a.d = dilation; a.ntt = p.ntile; a.XS = p.row;
   a.in_slope = in_slope; a.out_slope = out_slope;
   a.vec = ((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (length & 3) == 0) ? 1 : 0;
-  if ((long long)a.B * a.ntt > 0x7fffffffLL) return fail(EBEN_EINVAL, "ResidualUnit grid too large");
-  switch (channels / 32) {
-    case 1: return launch_ru<1>(a, as_stream(stream));
-    case 2: return launch_ru<2>(a, as_stream(stream));
-    default: return launch_ru<4>(a, as_stream(stream));
+  switch (p.targ[0]) {
+    case 1: return launch_ru<1>(a, p.lds, as_stream(stream));
+    case 2: return launch_ru<2>(a, p.lds, as_stream(stream));
+    default: return launch_ru<4>(a, p.lds, as_stream(stream));
   }
 }
 
@@ -526,10 +541,9 @@ extern "C" int eben_ru_pack_bwd(int channels, const float* v_dil, const float* s
 }
 
 template <int CT>
-static int launch_ru_bwd(const RuBwdArgs& a, hipStream_t st) {
+static int launch_ru_bwd(const RuBwdArgs& a, size_t lds, hipStream_t st) {
   static LdsAttrOnce attr_once;
   auto kern = ru_bwd_kernel<CT>;
-  const size_t lds = sizeof(float) * (2 * 16 * 64 * CT + (size_t)32 * CT * a.GS);
   {
     const hipError_t e = lds_attr_once(attr_once, reinterpret_cast<const void*>(kern));
     if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(ru_bwd)");
@@ -541,20 +555,19 @@ static int launch_ru_bwd(const RuBwdArgs& a, hipStream_t st) {
 
 extern "C" int eben_ru_bwd(int batch, int channels, int length, int dilation, const float* gy, const float* u, float out_slope,
                            const float* x, float in_slope, const float* post, const float* wimg_bwd, float* gx, float* gh, void* stream) {
-  EBEN_REQUIRE(channels == 32 || channels == 64 || channels == 128, "fused ResidualUnit: 32, 64 or 128 channels (got %d)", channels);
-  EBEN_REQUIRE(batch > 0 && length > 0 && dilation >= 1 && dilation <= 16 && dilation < length, "bad ResidualUnit geometry");
+  RuPlan p;
+  if (const int rc = ru_f32_plan(1, batch, channels, length, dilation, &p)) return rc;
   EBEN_REQUIRE(gy && u && wimg_bwd && gx && gh, "null pointer in ru_bwd");
   EBEN_REQUIRE(in_slope == 1.f || x, "x is required to differentiate the fused input activation");
   RuBwdArgs a;
   a.gy = gy; a.u = u; a.wimg = wimg_bwd; a.xmask = in_slope != 1.f ? x : nullptr; a.post = post; a.gx = gx; a.gh = gh;
   a.B = batch; a.C = channels; a.L = length; a.d = dilation;
-  a.BO = 128 - 2 * dilation; a.ntt = ceil_div(length, a.BO); a.GS = 132;
+  a.BO = p.tile; a.ntt = p.ntile; a.GS = p.row;
   a.out_slope = out_slope; a.in_slope = in_slope;
   a.vec = (((reinterpret_cast<uintptr_t>(gy) | reinterpret_cast<uintptr_t>(u)) & 15) == 0 && (length & 3) == 0) ? 1 : 0;
-  if ((long long)a.B * a.ntt > 0x7fffffffLL) return fail(EBEN_EINVAL, "ResidualUnit grid too large");
-  switch (channels / 32) {
-    case 1: return launch_ru_bwd<1>(a, as_stream(stream));
-    case 2: return launch_ru_bwd<2>(a, as_stream(stream));
-    default: return launch_ru_bwd<4>(a, as_stream(stream));
+  switch (p.targ[0]) {
+    case 1: return launch_ru_bwd<1>(a, p.lds, as_stream(stream));
+    case 2: return launch_ru_bwd<2>(a, p.lds, as_stream(stream));
+    default: return launch_ru_bwd<4>(a, p.lds, as_stream(stream));
   }
 }

@@ -429,11 +429,18 @@ __global__ __launch_bounds__(256, (CT * RT >= 4) ? 2 : 3) void rubl_dw_kernel(co
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
+// dynamic LDS of rubl_bwd_kernel<CT, NW, G> (two weight groups and the window) / of rubl_dw_kernel<CT, RT, BKT> (two chunk buffers)
+static constexpr size_t rubl_bwd_lds(int CT, int NW, int G) { return (size_t)2 * G * 2 * CT * 64 * 16 + (size_t)(4 * CT) * (NW * 32) * 16; }
+static constexpr size_t rubl_dw_lds(int CT, int RT, int BKT) {
+  const int CB = 4 * CT, RB = 4 * RT, TS = BKT + 4, XP = (BKT + 2 * RUBL_DMAX + 63) / 64, RS = XP * 64 + 4;
+  return (size_t)2 * 16 * (2 * RB * TS + CB * TS + CB * RS);
+}
+
 template <int CT, int NW, int G>
 static int launch_rubl_bwd(const RublBwdArgs& a, hipStream_t st) {
   static LdsAttrOnce attr_once;
   auto kern = rubl_bwd_kernel<CT, NW, G>;
-  const size_t lds = (size_t)2 * G * 2 * CT * 64 * 16 + (size_t)(4 * CT) * (NW * 32) * 16;
+  const size_t lds = rubl_bwd_lds(CT, NW, G);
   {
     const hipError_t e = lds_attr_once(attr_once, reinterpret_cast<const void*>(kern));
     if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(rubl_bwd)");
@@ -447,15 +454,12 @@ template <int CT, int RT, int BKT>
 static int launch_rubl_dw(const RublDwArgs& a, hipStream_t st) {
   static LdsAttrOnce attr_once;
   auto kern = rubl_dw_kernel<CT, RT, BKT>;
-  constexpr int CB = 4 * CT, RB = 4 * RT, TS = BKT + 4, XP = (BKT + 2 * RUBL_DMAX + 63) / 64, RS = XP * 64 + 4;
-  const size_t lds = (size_t)2 * 16 * (2 * RB * TS + CB * TS + CB * RS);
+  const size_t lds = rubl_dw_lds(CT, RT, BKT);
   {
     const hipError_t e = lds_attr_once(attr_once, reinterpret_cast<const void*>(kern));
     if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(rubl_dw)");
   }
-  const long long nb = (long long)a.B * a.nseg * (CT / RT);
-  if (nb > 0x7fffffffLL) return fail(EBEN_EINVAL, "rubl_dw grid too large");
-  hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(256), lds, st, a);
+  hipLaunchKernelGGL(kern, dim3((unsigned)((long long)a.B * a.nseg * (CT / RT))), dim3(256), lds, st, a);
   EBEN_CHECK_LAUNCH("rubl_dw_kernel");
   return EBEN_OK;
 }
@@ -476,6 +480,58 @@ static int rubl_seg(int channels, int length) {
   return round_up(ceil_div(length, nseg), 64);
 }
 
+// rubl_bwd_kernel<CT, NW, G>: windows of 32 NW columns (eight waves on request at 32 / 64 channels), BO = 32 NW - 2 d of them outputs;
+// G weight entries per barrier
+int rubl_bwd_plan(int batch, int channels, int length, int dilation, RuPlan* p) {
+  EBEN_REQUIRE(eben_rubl_supported(channels, dilation), "bundle-layout ResidualUnit backward: 32 / 64 / 128 channels, dilation 1..%d (got %d, %d)",
+               RUBL_DMAX, channels, dilation);
+  EBEN_REQUIRE(batch > 0 && length > 0 && dilation < length, "bad ResidualUnit geometry");
+  static const int nw32 = rubl_env("EBEN_RUBL_NW32", 4), nw64 = rubl_env("EBEN_RUBL_NW64", 4);
+  static const int g128 = rubl_env("EBEN_RUBL_G128", 2);
+  *p = RuPlan{};
+  int NW, G;
+  switch (channels / 32) {
+    case 1: NW = nw32 == 8 ? 8 : 4; G = 1; break;
+    case 2: NW = nw64 == 8 ? 8 : 4; G = 2; break;
+    default: NW = 4; G = g128 == 1 ? 1 : 2; break;
+  }
+  p->family = EBEN_RU_FAMILY_BL_BWD;
+  p->targ[0] = channels / 32; p->targ[1] = NW; p->targ[2] = G;
+  p->tile = 32 * NW - 2 * dilation;
+  p->ntile = ceil_div(length, p->tile);
+  p->blocks = (long long)batch * p->ntile;
+  p->lds = rubl_bwd_lds(channels / 32, NW, G);
+  if (p->blocks > 0x7fffffffLL) return fail(EBEN_EINVAL, "ResidualUnit grid too large");
+  return EBEN_OK;
+}
+
+// rubl_dw_kernel<CT, RT, BKT>: RT 32-row tiles per block, K chunks of BKT positions, slabs of rubl_seg positions
+int rubl_dw_plan(int batch, int channels, int length, int dilation, RuPlan* p) {
+  EBEN_REQUIRE(eben_rubl_supported(channels, dilation), "bundle-layout ResidualUnit weight gradient: 32 / 64 / 128 channels, dilation 1..%d (got %d, %d)",
+               RUBL_DMAX, channels, dilation);
+  EBEN_REQUIRE(batch > 0 && length > 0 && dilation < length, "bad ResidualUnit geometry");
+  static const int rt64 = rubl_env("EBEN_RUBL_RT64", 1), bkt128 = rubl_env("EBEN_RUBL_BKT128", 64), rt128 = rubl_env("EBEN_RUBL_RT128", 1);
+  *p = RuPlan{};
+  int RT, BKT;
+  switch (channels / 32) {
+    case 1: RT = 1; BKT = 64; break;
+    case 2: RT = rt64 == 2 ? 2 : 1; BKT = 64; break;
+    default:
+      if (rt128 == 2) { RT = 2; BKT = 32; }
+      else { RT = 1; BKT = bkt128 == 64 ? 64 : 32; }
+  }
+  const int CT = channels / 32;
+  p->family = EBEN_RU_FAMILY_RUBL_DW;
+  p->targ[0] = CT; p->targ[1] = RT; p->targ[2] = BKT;
+  p->seg = rubl_seg(channels, length);
+  p->tile = p->seg;
+  p->ntile = ceil_div(length, p->seg);
+  p->blocks = (long long)batch * p->ntile * (CT / RT);
+  p->lds = rubl_dw_lds(CT, RT, BKT);
+  if (p->blocks > 0x7fffffffLL) return fail(EBEN_EINVAL, "rubl_dw grid too large");
+  return EBEN_OK;
+}
+
 }  // namespace eben
 
 using namespace eben;
@@ -486,28 +542,22 @@ extern "C" int eben_rubl_supported(int channels, int dilation) {
 
 extern "C" int eben_rubl_bwd(int batch, int channels, int length, int dilation, const float* gy, const void* umask, float out_slope, const float* x,
                              float in_slope, const float* post, const float* wimg_bwd, float* gx, void* gzb, void* ghb, void* stream) {
-  EBEN_REQUIRE(eben_rubl_supported(channels, dilation), "bundle-layout ResidualUnit backward: 32 / 64 / 128 channels, dilation 1..%d (got %d, %d)",
-               RUBL_DMAX, channels, dilation);
-  EBEN_REQUIRE(batch > 0 && length > 0 && dilation < length, "bad ResidualUnit geometry");
+  RuPlan p;
+  if (const int rc = rubl_bwd_plan(batch, channels, length, dilation, &p)) return rc;
   EBEN_REQUIRE(gy && umask && wimg_bwd && gx && gzb && ghb, "null pointer in rubl_bwd");
   EBEN_REQUIRE(in_slope == 1.f || x, "x is required to differentiate the fused input activation");
   RublBwdArgs a;
   a.gy = gy; a.um = static_cast<const unsigned char*>(umask); a.wimg = reinterpret_cast<const u32x4*>(wimg_bwd);
   a.xmask = in_slope != 1.f ? x : nullptr; a.post = post; a.gx = gx; a.gzb = static_cast<u32x4*>(gzb); a.ghb = static_cast<u32x4*>(ghb);
   a.B = batch; a.L = length; a.d = dilation;
-  static const int nw32 = rubl_env("EBEN_RUBL_NW32", 4), nw64 = rubl_env("EBEN_RUBL_NW64", 4), nw128 = rubl_env("EBEN_RUBL_NW128", 4);
-  static const int g128 = rubl_env("EBEN_RUBL_G128", 2);
-  const int nw = channels == 32 ? nw32 : channels == 64 ? nw64 : nw128;
-  const int wn = (nw == 8 ? 8 : 4) * 32;
-  a.BO = wn - 2 * dilation; a.ntt = ceil_div(length, a.BO);
+  a.BO = p.tile; a.ntt = p.ntile;
   a.out_slope = out_slope; a.in_slope = in_slope;
-  if ((long long)a.B * a.ntt > 0x7fffffffLL) return fail(EBEN_EINVAL, "ResidualUnit grid too large");
   hipStream_t st = as_stream(stream);
-  switch (channels / 32) {
-    case 1: return nw == 8 ? launch_rubl_bwd<1, 8, 1>(a, st) : launch_rubl_bwd<1, 4, 1>(a, st);
-    case 2: return nw == 8 ? launch_rubl_bwd<2, 8, 2>(a, st) : launch_rubl_bwd<2, 4, 2>(a, st);
-    default: return g128 == 1 ? launch_rubl_bwd<4, 4, 1>(a, st) : launch_rubl_bwd<4, 4, 2>(a, st);
-  }
+#define EBEN_RUBL_BWD(CTV, NWV, GV) \
+  if (p.targ[0] == CTV && p.targ[1] == NWV && p.targ[2] == GV) return launch_rubl_bwd<CTV, NWV, GV>(a, st);
+  EBEN_RUBL_BWD(1, 4, 1) EBEN_RUBL_BWD(1, 8, 1) EBEN_RUBL_BWD(2, 4, 2) EBEN_RUBL_BWD(2, 8, 2) EBEN_RUBL_BWD(4, 4, 2) EBEN_RUBL_BWD(4, 4, 1)
+#undef EBEN_RUBL_BWD
+  return fail(EBEN_EUNSUPPORTED, "rubl_bwd_kernel<%d, %d, %d> is not built", p.targ[0], p.targ[1], p.targ[2]);
 }
 
 extern "C" int eben_rubl_dw_slabs(int batch, int channels, int length) {
@@ -517,22 +567,18 @@ extern "C" int eben_rubl_dw_slabs(int batch, int channels, int length) {
 
 extern "C" int eben_rubl_dw(int batch, int channels, int length, int dilation, const void* gzb, const void* hb, const void* ghb, const void* xb,
                             float* slabs_pw, float* slabs_dil, void* stream) {
-  EBEN_REQUIRE(eben_rubl_supported(channels, dilation), "bundle-layout ResidualUnit weight gradient: 32 / 64 / 128 channels, dilation 1..%d (got %d, %d)",
-               RUBL_DMAX, channels, dilation);
-  EBEN_REQUIRE(batch > 0 && length > 0 && dilation < length, "bad ResidualUnit geometry");
+  RuPlan p;
+  if (const int rc = rubl_dw_plan(batch, channels, length, dilation, &p)) return rc;
   EBEN_REQUIRE(gzb && hb && ghb && xb && slabs_pw && slabs_dil, "null pointer in rubl_dw");
   RublDwArgs a;
   a.gz = static_cast<const u32x4*>(gzb); a.h = static_cast<const u32x4*>(hb); a.gh = static_cast<const u32x4*>(ghb); a.xb = static_cast<const u32x4*>(xb);
   a.slab_p = slabs_pw; a.slab_d = slabs_dil;
   a.B = batch; a.L = length; a.d = dilation;
-  a.seg = rubl_seg(channels, length); a.nseg = ceil_div(length, a.seg);
+  a.seg = p.seg; a.nseg = p.ntile;
   hipStream_t st = as_stream(stream);
-  static const int rt64 = rubl_env("EBEN_RUBL_RT64", 1), bkt128 = rubl_env("EBEN_RUBL_BKT128", 64), rt128 = rubl_env("EBEN_RUBL_RT128", 1);
-  switch (channels / 32) {
-    case 1: return launch_rubl_dw<1, 1, 64>(a, st);
-    case 2: return rt64 == 2 ? launch_rubl_dw<2, 2, 64>(a, st) : launch_rubl_dw<2, 1, 64>(a, st);
-    default:
-      if (rt128 == 2) return launch_rubl_dw<4, 2, 32>(a, st);
-      return bkt128 == 64 ? launch_rubl_dw<4, 1, 64>(a, st) : launch_rubl_dw<4, 1, 32>(a, st);
-  }
+#define EBEN_RUBL_DW(CTV, RTV, BKTV) \
+  if (p.targ[0] == CTV && p.targ[1] == RTV && p.targ[2] == BKTV) return launch_rubl_dw<CTV, RTV, BKTV>(a, st);
+  EBEN_RUBL_DW(1, 1, 64) EBEN_RUBL_DW(2, 1, 64) EBEN_RUBL_DW(2, 2, 64) EBEN_RUBL_DW(4, 1, 64) EBEN_RUBL_DW(4, 1, 32) EBEN_RUBL_DW(4, 2, 32)
+#undef EBEN_RUBL_DW
+  return fail(EBEN_EUNSUPPORTED, "rubl_dw_kernel<%d, %d, %d> is not built", p.targ[0], p.targ[1], p.targ[2]);
 }

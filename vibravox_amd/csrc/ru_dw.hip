@@ -188,6 +188,26 @@ static int rdw_seg(int length) {
   return round_up(ceil_div(length, nseg), 16);
 }
 
+// ru_dw_kernel<CT, NP, UN>: single bf16 operands two k-steps per iteration (one on request), three pieces one; slabs of rdw_seg positions
+int ru_dw_plan(int math, int batch, int channels, int length, int dilation, RuPlan* p) {
+  EBEN_REQUIRE(channels == 32 || channels == 64 || channels == 128, "fused ResidualUnit weight gradient: 32, 64 or 128 channels (got %d)", channels);
+  EBEN_REQUIRE(math == EBEN_MATH_BF16 || math == EBEN_MATH_BF16X6, "ru_dw: EBEN_MATH_BF16 or EBEN_MATH_BF16X6 (got %d)", math);
+  EBEN_REQUIRE(batch > 0 && length > 0 && dilation >= 1 && dilation < length, "bad ResidualUnit geometry");
+  static const int un = getenv("EBEN_RUDW_UNROLL") ? atoi(getenv("EBEN_RUDW_UNROLL")) : 2;
+  *p = RuPlan{};
+  const int CT = channels / 32;
+  p->family = EBEN_RU_FAMILY_RU_DW;
+  p->targ[0] = CT;
+  p->targ[1] = math == EBEN_MATH_BF16 ? 1 : 3;
+  p->targ[2] = (math == EBEN_MATH_BF16 && un >= 2) ? 2 : 1;
+  p->seg = rdw_seg(length);
+  p->tile = p->seg;
+  p->ntile = ceil_div(length, p->seg);
+  p->blocks = (long long)batch * p->ntile * CT;
+  if (p->blocks > 0x7fffffffLL) return fail(EBEN_EINVAL, "ru_dw grid too large");
+  return EBEN_OK;
+}
+
 }  // namespace eben
 
 using namespace eben;
@@ -199,29 +219,27 @@ extern "C" int eben_ru_dw_slabs(int batch, int channels, int length) {
 
 extern "C" int eben_ru_dw(int math, int batch, int channels, int length, int dilation, const float* gy, const float* u, float out_slope,
                           const float* h, const float* gh, const float* x, float in_slope, float* slabs_pw, float* slabs_dil, void* stream) {
-  EBEN_REQUIRE(channels == 32 || channels == 64 || channels == 128, "fused ResidualUnit weight gradient: 32, 64 or 128 channels (got %d)", channels);
-  EBEN_REQUIRE(math == EBEN_MATH_BF16 || math == EBEN_MATH_BF16X6, "ru_dw: EBEN_MATH_BF16 or EBEN_MATH_BF16X6 (got %d)", math);
-  EBEN_REQUIRE(batch > 0 && length > 0 && dilation >= 1 && dilation < length, "bad ResidualUnit geometry");
+  RuPlan p;
+  if (const int rc = ru_dw_plan(math, batch, channels, length, dilation, &p)) return rc;
   EBEN_REQUIRE(gy && u && h && gh && x && slabs_pw && slabs_dil, "null pointer in ru_dw");
   RuDwArgs a;
   a.gy = gy; a.u = u; a.h = h; a.gh = gh; a.x = x; a.slab_p = slabs_pw; a.slab_d = slabs_dil;
   a.B = batch; a.L = length; a.d = dilation;
-  a.seg = rdw_seg(length); a.nseg = ceil_div(length, a.seg);
+  a.seg = p.seg; a.nseg = p.ntile;
   a.out_slope = out_slope; a.in_slope = in_slope;
-  const int CT = channels / 32;
-  const long long nb = (long long)batch * a.nseg * CT;
-  if (nb > 0x7fffffffLL) return fail(EBEN_EINVAL, "ru_dw grid too large");
+  const unsigned nb = (unsigned)p.blocks;
   hipStream_t st = as_stream(stream);
-#define EBEN_RUDW(CTV, NPV, UNV) hipLaunchKernelGGL((ru_dw_kernel<CTV, NPV, UNV>), dim3((unsigned)nb), dim3(256), 0, st, a)
-  static const int un = getenv("EBEN_RUDW_UNROLL") ? atoi(getenv("EBEN_RUDW_UNROLL")) : 2;
-  if (math == EBEN_MATH_BF16 && un >= 2) {
-    switch (CT) { case 1: EBEN_RUDW(1, 1, 2); break; case 2: EBEN_RUDW(2, 1, 2); break; default: EBEN_RUDW(4, 1, 2); }
-  } else if (math == EBEN_MATH_BF16) {
-    switch (CT) { case 1: EBEN_RUDW(1, 1, 1); break; case 2: EBEN_RUDW(2, 1, 1); break; default: EBEN_RUDW(4, 1, 1); }
-  } else {
-    switch (CT) { case 1: EBEN_RUDW(1, 3, 1); break; case 2: EBEN_RUDW(2, 3, 1); break; default: EBEN_RUDW(4, 3, 1); }
+  bool launched = false;
+#define EBEN_RUDW(CTV, NPV, UNV)                                                                     \
+  if (p.targ[0] == CTV && p.targ[1] == NPV && p.targ[2] == UNV) {                                    \
+    hipLaunchKernelGGL((ru_dw_kernel<CTV, NPV, UNV>), dim3(nb), dim3(256), 0, st, a);                \
+    launched = true;                                                                                 \
   }
+  EBEN_RUDW(1, 1, 2) EBEN_RUDW(2, 1, 2) EBEN_RUDW(4, 1, 2)
+  EBEN_RUDW(1, 1, 1) EBEN_RUDW(2, 1, 1) EBEN_RUDW(4, 1, 1)
+  EBEN_RUDW(1, 3, 1) EBEN_RUDW(2, 3, 1) EBEN_RUDW(4, 3, 1)
 #undef EBEN_RUDW
+  if (!launched) return fail(EBEN_EUNSUPPORTED, "ru_dw_kernel<%d, %d, %d> is not built", p.targ[0], p.targ[1], p.targ[2]);
   EBEN_CHECK_LAUNCH("ru_dw_kernel");
   return EBEN_OK;
 }

@@ -670,12 +670,19 @@ static int rs_pieces(int math) {
   }
 }
 
+// dynamic LDS of ru3_fwd_kernel<CT, NW, NP, KSC, .> / ru3_bwd_kernel<CT, NW, NP, G>: two weight chunks and the staged rows
+static constexpr size_t ru3_fwd_lds(int CT, int NW, int NP, int KSC) {
+  return (size_t)2 * KSC * NP * CT * 64 * 16 + sizeof(float) * 32 * CT * (NW * 32 + 2 * RS_DMAX + 6);
+}
+static constexpr size_t ru3_bwd_lds(int CT, int NW, int NP, int G) {
+  return (size_t)2 * G * 2 * NP * CT * 64 * 16 + sizeof(float) * 32 * CT * (NW * 32 + 4);
+}
+
 template <int CT, int NW, int NP, int KSC, bool BL = false>
 static int launch_ru3_fwd(const Ru3Args& a, hipStream_t st) {
   static LdsAttrOnce attr_once;
   auto kern = ru3_fwd_kernel<CT, NW, NP, KSC, BL>;
-  constexpr int XS = NW * 32 + 2 * RS_DMAX + 6;
-  const size_t lds = (size_t)2 * KSC * NP * CT * 64 * 16 + sizeof(float) * 32 * CT * XS;
+  const size_t lds = ru3_fwd_lds(CT, NW, NP, KSC);
   {
     const hipError_t e = lds_attr_once(attr_once, reinterpret_cast<const void*>(kern));
     if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(ru3_fwd)");
@@ -689,8 +696,7 @@ template <int CT, int NW, int NP, int G>
 static int launch_ru3_bwd(const Ru3BwdArgs& a, hipStream_t st) {
   static LdsAttrOnce attr_once;
   auto kern = ru3_bwd_kernel<CT, NW, NP, G>;
-  constexpr int GS = NW * 32 + 4;
-  const size_t lds = (size_t)2 * G * 2 * NP * CT * 64 * 16 + sizeof(float) * 32 * CT * GS;
+  const size_t lds = ru3_bwd_lds(CT, NW, NP, G);
   {
     const hipError_t e = lds_attr_once(attr_once, reinterpret_cast<const void*>(kern));
     if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(ru3_bwd)");
@@ -727,97 +733,108 @@ int ru3_pack(int channels, int math, int which, const float* vd, const float* sd
   return EBEN_OK;
 }
 
-int ru3_fwd(int math, int batch, int channels, int length, int dilation, const float* x, float in_slope, float out_slope, const float* wimg,
+// weight entries streamed per barrier by ru3_bwd_kernel: ~8-16 KB of weights per group
+static int ru3_bwd_group(int channels, int np) {
+  switch (channels / 32) {
+    case 1: return 1;
+    case 2: return np == 3 ? 1 : 2;
+    default: return np == 1 ? 2 : 1;
+  }
+}
+
+// which 0: ru3_fwd_kernel<CT, NW, NP, KSC, BL> on tiles of 32 NW positions (bl: the forward that saves bundle planes -- four waves, two
+// or three pieces); 1: ru3_bwd_kernel<CT, NW, NP, G> on windows of 32 NW columns, BO = 32 NW - 2 d of them outputs
+int ru3_plan(int which, int bl, int math, int batch, int channels, int length, int dilation, RuPlan* p) {
+  EBEN_REQUIRE(ru3_supported(channels, dilation, math), "fused ResidualUnit (split bf16): 32 / 64 / 128 channels, dilation 1..%d (got %d, %d)",
+               RS_DMAX, channels, dilation);
+  EBEN_REQUIRE(batch > 0 && length > 0 && dilation < length, "bad ResidualUnit geometry");
+  const int np = rs_pieces(math);
+  // EBEN_MATH_BF16X6 (fp32-grade: six piece products) or EBEN_MATH_BF16X3 (hi + lo operands, three products: the bf16-mixed plan --
+  // 2^-17 per product, the generator's output stays orders of magnitude inside north_star's 1e-5 MSE; [MI355X] 42 -> 35 us at 64 channels)
+  if (bl && np != 3 && np != 2) return fail(EBEN_EUNSUPPORTED, "eben_rubl_fwd: the forward computes in EBEN_MATH_BF16X6 or EBEN_MATH_BF16X3 (got %d)", math);
+  *p = RuPlan{};
+  const int CT = channels / 32;
+  // (A five-wave, 160-column window for the 128-channel units -- 288 / 320 blocks at d = 3 / 9 are two rounds of one block per CU, 224 / 256
+  // one -- measured 50 -> 41 us per launch in round 3 but needs 2 waves on one SIMD at 256 registers each: 536 bytes of scratch.  Gone;
+  // the bundle-layout backward (ru_bl.hip) halves the LDS per block instead.)
+  const int NW = bl ? 4 : rs_waves(channels);
+  p->family = EBEN_RU_FAMILY_SPLIT;
+  p->targ[0] = CT; p->targ[1] = NW; p->targ[2] = np;
+  if (which == 0) {
+    const int KSC = NW == 4 ? 2 : 1;
+    p->targ[3] = KSC; p->targ[4] = bl ? 1 : 0;
+    p->tile = 32 * NW;
+    p->lds = ru3_fwd_lds(CT, NW, np, KSC);
+  } else {
+    const int G = ru3_bwd_group(channels, np);
+    p->targ[3] = G;
+    p->tile = 32 * NW - 2 * dilation;
+    p->lds = ru3_bwd_lds(CT, NW, np, G);
+  }
+  p->ntile = ceil_div(length, p->tile);
+  p->blocks = (long long)batch * p->ntile;
+  if (p->blocks > 0x7fffffffLL) return fail(EBEN_EINVAL, "ResidualUnit grid too large");
+  return EBEN_OK;
+}
+
+// the instantiation a plan names (every one the resolver can name is listed; anything else is a bug in the resolver)
+static int ru3_fwd_dispatch(const RuPlan& p, const Ru3Args& a, hipStream_t st) {
+#define EBEN_RU3_FWD(CTV, NWV, NPV, KSCV, BLV) \
+  if (p.targ[0] == CTV && p.targ[1] == NWV && p.targ[2] == NPV && p.targ[3] == KSCV && p.targ[4] == (BLV ? 1 : 0)) return launch_ru3_fwd<CTV, NWV, NPV, KSCV, BLV>(a, st);
+#define EBEN_RU3_FWD_NP(NPV)                                                                                                      \
+  EBEN_RU3_FWD(1, 4, NPV, 2, false) EBEN_RU3_FWD(2, 4, NPV, 2, false) EBEN_RU3_FWD(4, 4, NPV, 2, false) EBEN_RU3_FWD(4, 2, NPV, 1, false)
+  EBEN_RU3_FWD_NP(1) EBEN_RU3_FWD_NP(2) EBEN_RU3_FWD_NP(3)
+  EBEN_RU3_FWD(1, 4, 2, 2, true) EBEN_RU3_FWD(2, 4, 2, 2, true) EBEN_RU3_FWD(4, 4, 2, 2, true)
+  EBEN_RU3_FWD(1, 4, 3, 2, true) EBEN_RU3_FWD(2, 4, 3, 2, true) EBEN_RU3_FWD(4, 4, 3, 2, true)
+#undef EBEN_RU3_FWD_NP
+#undef EBEN_RU3_FWD
+  return fail(EBEN_EUNSUPPORTED, "ru3_fwd_kernel<%d, %d, %d, %d, %d> is not built", p.targ[0], p.targ[1], p.targ[2], p.targ[3], p.targ[4]);
+}
+
+static int ru3_bwd_dispatch(const RuPlan& p, const Ru3BwdArgs& a, hipStream_t st) {
+#define EBEN_RU3_BWD(CTV, NWV, NPV, GV) \
+  if (p.targ[0] == CTV && p.targ[1] == NWV && p.targ[2] == NPV && p.targ[3] == GV) return launch_ru3_bwd<CTV, NWV, NPV, GV>(a, st);
+  EBEN_RU3_BWD(1, 4, 1, 1) EBEN_RU3_BWD(2, 4, 1, 2) EBEN_RU3_BWD(4, 4, 1, 2) EBEN_RU3_BWD(4, 2, 1, 2)
+  EBEN_RU3_BWD(1, 4, 2, 1) EBEN_RU3_BWD(2, 4, 2, 2) EBEN_RU3_BWD(4, 4, 2, 1) EBEN_RU3_BWD(4, 2, 2, 1)
+  EBEN_RU3_BWD(1, 4, 3, 1) EBEN_RU3_BWD(2, 4, 3, 1) EBEN_RU3_BWD(4, 4, 3, 1) EBEN_RU3_BWD(4, 2, 3, 1)
+#undef EBEN_RU3_BWD
+  return fail(EBEN_EUNSUPPORTED, "ru3_bwd_kernel<%d, %d, %d, %d> is not built", p.targ[0], p.targ[1], p.targ[2], p.targ[3]);
+}
+
+int ru3_fwd(const RuPlan& p, int batch, int length, int dilation, const float* x, float in_slope, float out_slope, const float* wimg,
             float* y, float* h, float* u, hipStream_t st) {
   Ru3Args a;
   a.x = x; a.wimg = reinterpret_cast<const u32x4*>(wimg); a.y = y; a.h = h; a.u = u;
   a.xb = nullptr; a.hb = nullptr; a.um = nullptr;
   a.B = batch; a.L = length; a.d = dilation;
-  const int bn = rs_waves(channels) * 32;
-  a.ntt = ceil_div(length, bn);
+  a.ntt = p.ntile;
   a.in_slope = in_slope; a.out_slope = out_slope;
   a.vec = ((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (length & 3) == 0) ? 1 : 0;
-  if ((long long)a.B * a.ntt > 0x7fffffffLL) return fail(EBEN_EINVAL, "ResidualUnit grid too large");
-  const int np = rs_pieces(math);
-#define EBEN_RU3_FWD(NPV)                                                 \
-  switch (channels / 32) {                                                \
-    case 1: return launch_ru3_fwd<1, 4, NPV, 2>(a, st);                   \
-    case 2: return launch_ru3_fwd<2, 4, NPV, 2>(a, st);                   \
-    default: return rs_waves(128) == 4 ? launch_ru3_fwd<4, 4, NPV, 2>(a, st) : launch_ru3_fwd<4, 2, NPV, 1>(a, st); \
-  }
-  switch (np) {
-    case 1: EBEN_RU3_FWD(1)
-    case 2: EBEN_RU3_FWD(2)
-    default: EBEN_RU3_FWD(3)
-  }
-#undef EBEN_RU3_FWD
+  return ru3_fwd_dispatch(p, a, st);
 }
 
 // forward that saves for the bundle-layout backward (ru_bl.hip): y fp32, xin / h as bf16 bundles, the sign bits of u
-int ru3_fwd_bl(int math, int batch, int channels, int length, int dilation, const float* x, float in_slope, float out_slope, const float* wimg,
+int ru3_fwd_bl(const RuPlan& p, int batch, int length, int dilation, const float* x, float in_slope, float out_slope, const float* wimg,
                float* y, void* xb, void* hb, void* um, hipStream_t st) {
   Ru3Args a;
   a.x = x; a.wimg = reinterpret_cast<const u32x4*>(wimg); a.y = y; a.h = nullptr; a.u = nullptr;
   a.xb = static_cast<u32x4*>(xb); a.hb = static_cast<u32x4*>(hb); a.um = static_cast<unsigned char*>(um);
   a.B = batch; a.L = length; a.d = dilation;
-  a.ntt = ceil_div(length, 128);
+  a.ntt = p.ntile;
   a.in_slope = in_slope; a.out_slope = out_slope;
   a.vec = ((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (length & 3) == 0) ? 1 : 0;
-  if ((long long)a.B * a.ntt > 0x7fffffffLL) return fail(EBEN_EINVAL, "ResidualUnit grid too large");
-  // EBEN_MATH_BF16X6 (fp32-grade: six piece products) or EBEN_MATH_BF16X3 (hi + lo operands, three products: the bf16-mixed plan --
-  // 2^-17 per product, the generator's output stays orders of magnitude inside north_star's 1e-5 MSE; [MI355X] 42 -> 35 us at 64 channels)
-  const int np = rs_pieces(math);
-  if (np != 3 && np != 2) return fail(EBEN_EUNSUPPORTED, "eben_rubl_fwd: the forward computes in EBEN_MATH_BF16X6 or EBEN_MATH_BF16X3 (got %d)", math);
-  if (np == 2) {
-    switch (channels / 32) {
-      case 1: return launch_ru3_fwd<1, 4, 2, 2, true>(a, st);
-      case 2: return launch_ru3_fwd<2, 4, 2, 2, true>(a, st);
-      default: return launch_ru3_fwd<4, 4, 2, 2, true>(a, st);
-    }
-  }
-  switch (channels / 32) {
-    case 1: return launch_ru3_fwd<1, 4, 3, 2, true>(a, st);
-    case 2: return launch_ru3_fwd<2, 4, 3, 2, true>(a, st);
-    default: return launch_ru3_fwd<4, 4, 3, 2, true>(a, st);
-  }
+  return ru3_fwd_dispatch(p, a, st);
 }
 
-int ru3_bwd(int math, int batch, int channels, int length, int dilation, const float* gy, const float* u, float out_slope, const float* x,
+int ru3_bwd(const RuPlan& p, int batch, int length, int dilation, const float* gy, const float* u, float out_slope, const float* x,
             float in_slope, const float* post, const float* wimg, float* gx, float* gh, hipStream_t st) {
   Ru3BwdArgs a;
   a.gy = gy; a.u = u; a.wimg = reinterpret_cast<const u32x4*>(wimg); a.xmask = in_slope != 1.f ? x : nullptr; a.post = post; a.gx = gx; a.gh = gh;
   a.B = batch; a.L = length; a.d = dilation;
-  // (A five-wave, 160-column window for the 128-channel units -- 288 / 320 blocks at d = 3 / 9 are two rounds of one block per CU, 224 / 256
-  // one -- measured 50 -> 41 us per launch in round 3 but needs 2 waves on one SIMD at 256 registers each: 536 bytes of scratch.  Gone;
-  // the bundle-layout backward (ru_bl.hip) halves the LDS per block instead.)
-  const int nw = rs_waves(channels);
-  const int wn = nw * 32;
-  a.BO = wn - 2 * dilation; a.ntt = ceil_div(length, a.BO);
+  a.BO = p.tile; a.ntt = p.ntile;
   a.out_slope = out_slope; a.in_slope = in_slope;
   a.vec = (((reinterpret_cast<uintptr_t>(gy) | reinterpret_cast<uintptr_t>(u)) & 15) == 0 && (length & 3) == 0) ? 1 : 0;
-  if ((long long)a.B * a.ntt > 0x7fffffffLL) return fail(EBEN_EINVAL, "ResidualUnit grid too large");
-  const int np = rs_pieces(math);
-  // entries per barrier: ~8-16 KB of weights per group
-  switch (np) {
-    case 1:
-      switch (channels / 32) {
-        case 1: return launch_ru3_bwd<1, 4, 1, 1>(a, st);
-        case 2: return launch_ru3_bwd<2, 4, 1, 2>(a, st);
-        default: return nw == 4 ? launch_ru3_bwd<4, 4, 1, 2>(a, st) : launch_ru3_bwd<4, 2, 1, 2>(a, st);
-      }
-    case 2:
-      switch (channels / 32) {
-        case 1: return launch_ru3_bwd<1, 4, 2, 1>(a, st);
-        case 2: return launch_ru3_bwd<2, 4, 2, 2>(a, st);
-        default: return rs_waves(128) == 4 ? launch_ru3_bwd<4, 4, 2, 1>(a, st) : launch_ru3_bwd<4, 2, 2, 1>(a, st);
-      }
-    default:
-      switch (channels / 32) {
-        case 1: return launch_ru3_bwd<1, 4, 3, 1>(a, st);
-        case 2: return launch_ru3_bwd<2, 4, 3, 1>(a, st);
-        default: return rs_waves(128) == 4 ? launch_ru3_bwd<4, 4, 3, 1>(a, st) : launch_ru3_bwd<4, 2, 3, 1>(a, st);
-      }
-  }
+  return ru3_bwd_dispatch(p, a, st);
 }
 
 }  // namespace eben
@@ -870,29 +887,48 @@ extern "C" int eben_ru_pack_multi(const EbenRuPackJob* jobs, int n, void* stream
 extern "C" int eben_ru_fwd_ex(int math, int batch, int channels, int length, int dilation, const float* x, float in_slope, float out_slope,
                               const float* wimg, float* y, float* h, float* u, void* stream) {
   if (math == EBEN_MATH_F32) return eben_ru_fwd(batch, channels, length, dilation, x, in_slope, out_slope, wimg, y, h, u, stream);
-  EBEN_REQUIRE(ru3_supported(channels, dilation, math), "fused ResidualUnit (split bf16): 32 / 64 / 128 channels, dilation 1..%d (got %d, %d)",
-               RS_DMAX, channels, dilation);
-  EBEN_REQUIRE(batch > 0 && length > 0 && dilation < length, "bad ResidualUnit geometry");
+  RuPlan p;
+  if (const int rc = ru3_plan(0, 0, math, batch, channels, length, dilation, &p)) return rc;
   EBEN_REQUIRE(x && wimg && y, "null pointer in ru_fwd_ex");
-  return ru3_fwd(math, batch, channels, length, dilation, x, in_slope, out_slope, wimg, y, h, u, as_stream(stream));
+  return ru3_fwd(p, batch, length, dilation, x, in_slope, out_slope, wimg, y, h, u, as_stream(stream));
 }
 
 extern "C" int eben_ru_bwd_ex(int math, int batch, int channels, int length, int dilation, const float* gy, const float* u, float out_slope,
                               const float* x, float in_slope, const float* post, const float* wimg_bwd, float* gx, float* gh, void* stream) {
   if (math == EBEN_MATH_F32) return eben_ru_bwd(batch, channels, length, dilation, gy, u, out_slope, x, in_slope, post, wimg_bwd, gx, gh, stream);
-  EBEN_REQUIRE(ru3_supported(channels, dilation, math), "fused ResidualUnit (split bf16): 32 / 64 / 128 channels, dilation 1..%d (got %d, %d)",
-               RS_DMAX, channels, dilation);
-  EBEN_REQUIRE(batch > 0 && length > 0 && dilation < length, "bad ResidualUnit geometry");
+  RuPlan p;
+  if (const int rc = ru3_plan(1, 0, math, batch, channels, length, dilation, &p)) return rc;
   EBEN_REQUIRE(gy && u && wimg_bwd && gx && gh, "null pointer in ru_bwd_ex");
   EBEN_REQUIRE(in_slope == 1.f || x, "x is required to differentiate the fused input activation");
-  return ru3_bwd(math, batch, channels, length, dilation, gy, u, out_slope, x, in_slope, post, wimg_bwd, gx, gh, as_stream(stream));
+  return ru3_bwd(p, batch, length, dilation, gy, u, out_slope, x, in_slope, post, wimg_bwd, gx, gh, as_stream(stream));
 }
 
 extern "C" int eben_rubl_fwd(int math, int batch, int channels, int length, int dilation, const float* x, float in_slope, float out_slope,
                              const float* wimg, float* y, void* xb, void* hb, void* umask, void* stream) {
-  EBEN_REQUIRE(ru3_supported(channels, dilation, math), "fused ResidualUnit (split bf16): 32 / 64 / 128 channels, dilation 1..%d (got %d, %d)",
-               RS_DMAX, channels, dilation);
-  EBEN_REQUIRE(batch > 0 && length > 0 && dilation < length, "bad ResidualUnit geometry");
+  RuPlan p;
+  if (const int rc = ru3_plan(0, 1, math, batch, channels, length, dilation, &p)) return rc;
   EBEN_REQUIRE(x && wimg && y && xb && hb && umask, "null pointer in rubl_fwd");
-  return ru3_fwd_bl(math, batch, channels, length, dilation, x, in_slope, out_slope, wimg, y, xb, hb, umask, as_stream(stream));
+  return ru3_fwd_bl(p, batch, length, dilation, x, in_slope, out_slope, wimg, y, xb, hb, umask, as_stream(stream));
+}
+
+extern "C" int eben_ru_variant(int op, int math, int batch, int channels, int length, int dilation, int* out, int n) {
+  EBEN_REQUIRE(out && n >= EBEN_RU_VARIANT_N, "eben_ru_variant: %d output slots", EBEN_RU_VARIANT_N);
+  RuPlan p;
+  int rc;
+  switch (op) {
+    case EBEN_RU_OP_FWD: rc = math == EBEN_MATH_F32 ? ru_f32_plan(0, batch, channels, length, dilation, &p) : ru3_plan(0, 0, math, batch, channels, length, dilation, &p); break;
+    case EBEN_RU_OP_BL_FWD: rc = ru3_plan(0, 1, math, batch, channels, length, dilation, &p); break;
+    case EBEN_RU_OP_BWD: rc = math == EBEN_MATH_F32 ? ru_f32_plan(1, batch, channels, length, dilation, &p) : ru3_plan(1, 0, math, batch, channels, length, dilation, &p); break;
+    case EBEN_RU_OP_BL_BWD: rc = rubl_bwd_plan(batch, channels, length, dilation, &p); break;
+    case EBEN_RU_OP_DW: rc = ru_dw_plan(math, batch, channels, length, dilation, &p); break;
+    case EBEN_RU_OP_BL_DW: rc = rubl_dw_plan(batch, channels, length, dilation, &p); break;
+    default: return fail(EBEN_EINVAL, "eben_ru_variant: op %d is none of EBEN_RU_OP_*", op);
+  }
+  if (rc) return rc;
+  for (int i = 0; i < EBEN_RU_VARIANT_N; ++i) out[i] = 0;
+  out[0] = p.family;
+  for (int i = 0; i < 5; ++i) out[1 + i] = p.targ[i];
+  out[6] = p.tile; out[7] = p.ntile; out[8] = (int)p.blocks; out[9] = (int)p.lds;
+  if (p.seg > 0) { out[10] = p.seg; out[11] = p.ntile; out[12] = batch * p.ntile; }
+  return EBEN_OK;
 }
