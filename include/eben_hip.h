@@ -771,6 +771,46 @@ EBEN_API int eben_resample_ragged(const float* x, const int32_t* lens, const flo
 EBEN_API int eben_resample_stream(const float* tape, const float* kernels, float* out, int rows, int tape_pitch, int len, int out_pitch,
                                   int first_out, int n_out, int p0, int base0, int end, int orig, int nw, int width, void* stream);
 
+/* The same two steps of a stream -- splice, then resample -- for independent sessions in the slots of one state
+ * (streaming.StreamPool with input_rates): every slot has its own counts, phase, ratio and parity.  The state is two tapes and two
+ * FIFO buffers of `slots` rows each (row pitches tape_pitch / fifo_pitch floats); a descriptor names its slot and which of the two it
+ * writes.  Descriptors are read from HOST memory, validated, and passed to the kernel by value (nothing is uploaded; the caller may
+ * reuse its table at once): at most EBEN_RATE_MAX_SPLICES splices or EBEN_RATE_MAX_PIECES pieces (two per splice) per call, one launch.  Slots that no descriptor names are not touched.
+ *   eben_rate_splice_slots  per descriptor, with out = tapes[tape] and in = tapes[1 - tape] (a slot never reads the tape it writes):
+ *     out[slot][0 : n_carry + n_new) = [ in[slot][prev_off : prev_off + n_carry) | src[src_row][0 : n_new) ]; src holds src_rows rows
+ *     of src_pitch floats (NULL when no descriptor has n_new > 0).
+ *   eben_resample_slots     per piece what eben_resample_stream does on one row: the tape tapes[tape][slot] of `len` samples with the
+ *     ratio ratios[ratio] (at most EBEN_RATE_MAX_RATIOS; `kernels` its (nw, 2 * width + orig) device table), p0, base0 and end, the
+ *     n_out outputs to fifos[fifo][slot][first_out + n].  Pieces of different ratios share the launch: the grid is (tiles of the
+ *     largest piece, pieces), each ratio with the tile eben_resample_plan states.  A push whose outputs straddle two FIFO buffers is
+ *     two pieces.  Pieces with n_out == 0 are checked and dropped.
+ * EBEN_EINVAL before any launch, nothing written, for: a null or misaligned-to-4 pointer; slots outside 1 ... EBEN_STREAM_MAX_SLOTS;
+ * a negative count or more descriptors than the call's cap (a null table with count > 0); a slot, src_row, tape, fifo or ratio
+ * index outside its range; per descriptor what eben_stream_splice / eben_resample_stream refuse (negative offsets or counts,
+ * n_carry + n_new == 0 or past tape_pitch, prev_off + n_carry past tape_pitch, n_new past src_pitch, a ratio that fits no tile, len
+ * past tape_pitch, first_out + n_out past fifo_pitch, a phase outside [0, nw), n_out past what the tape serves); two splices on one
+ * slot; two pieces whose outputs overlap on one (fifo, slot); the extents of the two tapes, the two FIFO buffers, src and the ratio
+ * tables in use overlapping where one of them is written.  An empty list returns EBEN_OK without a launch.
+ * Added without a version bump: functions and POD types only. */
+#define EBEN_RATE_MAX_SPLICES 64
+#define EBEN_RATE_MAX_PIECES 128
+#define EBEN_RATE_MAX_RATIOS 8
+typedef struct EbenRateSplice {
+  int slot, src_row, prev_off, n_carry, n_new, tape;
+} EbenRateSplice;
+typedef struct EbenRateRatio {
+  const float* kernels;
+  int orig, nw, width, reserved;
+} EbenRateRatio;
+typedef struct EbenRatePiece {
+  int len, p0, base0, n_out, end, first_out;
+  unsigned char slot, ratio, tape, fifo;   /* 28 bytes: a steady push of every one of 64 slots, two pieces each, is one call */
+} EbenRatePiece;
+EBEN_API int eben_rate_splice_slots(float* tape0, float* tape1, int tape_pitch, int slots, const float* src, int src_pitch, int src_rows,
+                                    const EbenRateSplice* splices, int count, void* stream);
+EBEN_API int eben_resample_slots(const float* tape0, const float* tape1, int tape_pitch, float* fifo0, float* fifo1, int fifo_pitch, int slots,
+                                 const EbenRateRatio* ratios, int n_ratios, const EbenRatePiece* pieces, int count, void* stream);
+
 /* ---- misc ------------------------------------------------------------------------------- */
 /* out[0] = sqrt(sum x^2) (torch.norm at eben.py:226); `out` must hold 257 floats (scratch) */
 EBEN_API int eben_l2norm(const float* x, size_t n, float* out, void* stream);

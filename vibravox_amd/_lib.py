@@ -86,6 +86,21 @@ class EbenCopySegment(ctypes.Structure):
     _fields_ = [("dst", c_void_p), ("src", c_void_p), ("floats", c_int64)]
 
 
+RATE_MAX_SPLICES, RATE_MAX_PIECES, RATE_MAX_RATIOS = 64, 128, 8   # EBEN_RATE_MAX_SPLICES / _PIECES descriptors a call, EBEN_RATE_MAX_RATIOS
+
+
+class EbenRateSplice(ctypes.Structure):
+    _fields_ = [(k, c_int) for k in ("slot", "src_row", "prev_off", "n_carry", "n_new", "tape")]
+
+
+class EbenRateRatio(ctypes.Structure):
+    _fields_ = [("kernels", c_void_p), ("orig", c_int), ("nw", c_int), ("width", c_int), ("reserved", c_int)]
+
+
+class EbenRatePiece(ctypes.Structure):
+    _fields_ = [(k, c_int) for k in ("len", "p0", "base0", "n_out", "end", "first_out")] + [(k, ctypes.c_uint8) for k in ("slot", "ratio", "tape", "fifo")]
+
+
 class EbenClip(ctypes.Structure):
     _fields_ = [("data", c_void_p), ("length", c_int64)]
 
@@ -245,6 +260,8 @@ SIGNATURES = {
     "eben_resample_plan": (c_int, [c_int, c_int, c_int, POINTER(c_int), c_int]),
     "eben_resample_ragged": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "eben_resample_stream": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "eben_rate_splice_slots": (c_int, [_P, _P, c_int, c_int, _P, c_int, c_int, POINTER(EbenRateSplice), c_int, _P]),
+    "eben_resample_slots": (c_int, [_P, _P, c_int, _P, _P, c_int, c_int, POINTER(EbenRateRatio), c_int, POINTER(EbenRatePiece), c_int, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

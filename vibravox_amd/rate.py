@@ -24,14 +24,17 @@ With the rates reduced to ``orig : new`` and ``taps = 2 * width + orig``, output
 ``Schedule`` turns a push into one ``RatePush`` of such buffer-relative numbers; ``StreamResampler`` executes it (``eben_stream_splice``
 into the tape's ping-pong twin -- the carry is never updated by the launch that reads it -- then ``eben_resample_stream``);
 ``tests/rate_oracle.py`` executes it in float64.  ``ChunkFront`` is the resampler in front of a consumer of whole chunks
-(``streaming.StreamingEnhancer(input_rate=...)``).
+(``streaming.StreamingEnhancer(input_rate=...)``).  ``SlotFront`` is the same front for independent sessions in the slots of one state
+(``streaming.StreamPool(input_rates=...)``): a ``Schedule`` and a parity per slot on the host, and two launches for all slots of a tick
+(``eben_rate_splice_slots``, ``eben_resample_slots``: per-slot descriptors by value), executed by ``SlotTapes``.
 """
 from __future__ import annotations
 
 import ctypes
 import dataclasses
 import math
-from typing import Callable, List, Optional, Tuple
+import struct
+from typing import Callable, List, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -361,3 +364,210 @@ class ChunkFront:
         if not final or self.held == 0:
             return None
         return self.fifo[self._cur][:, :, : self.held].contiguous()
+
+
+# ---- independent sessions in the slots of one state (streaming.StreamPool with input_rates) -------------------------------------------
+class SlotSplice(NamedTuple):
+    """Slot ``slot``: tape ``tape`` := ``[the other tape[prev_off : prev_off + n_carry] | row src_row of the compact input, n_new samples]``.
+    The compact input of a tick holds one row per splice of the same ``n_new``, in the order of the list (sessions at different rates
+    push chunks of different lengths: each length is a compact input of its own)."""
+    slot: int
+    src_row: int
+    prev_off: int
+    n_carry: int
+    n_new: int
+    tape: int
+
+
+class SlotPiece(NamedTuple):
+    """``n_out`` outputs of slot ``slot``'s tape ``tape`` (``length`` samples) at ratio ``ratio`` to FIFO buffer ``fifo``, from
+    ``first_out`` on; ``p0``, ``base0``, ``end`` as in ``RatePush``."""
+    slot: int
+    ratio: int
+    tape: int
+    length: int
+    p0: int
+    base0: int
+    n_out: int
+    end: bool
+    fifo: int
+    first_out: int
+
+
+class SlotChunk(NamedTuple):
+    """What a slot's FIFO hands on: the first ``samples`` of its buffer ``fifo`` -- a whole chunk, or the shorter rest at the end."""
+    slot: int
+    fifo: int
+    samples: int
+
+
+@dataclasses.dataclass
+class _Slot:
+    ratio: int
+    schedule: Schedule
+    tape: int = 0      # the current tape of the slot's two
+    fifo: int = 0      # the FIFO buffer being filled ...
+    held: int = 0      # ... and the samples it holds
+    last: Optional[RatePush] = None     # the latest push
+    steady: Optional[RatePush] = None   # the push that repeats, once two in a row were equal past the left edge
+    replay: dict = dataclasses.field(default_factory=dict)   # tape parity -> (splice numbers, pieces, chunks) of a steady push
+    lazy: int = 0      # steady pushes the schedule has not been advanced by yet
+
+
+class SlotFront:
+    """``ChunkFront``'s bookkeeping per slot (host only, no GPU needed): every slot has a ``Schedule`` of its own ratio and its own parity
+    of tapes and FIFO buffers, so a slot that does not push costs nothing.  ``feed`` turns the pushes of a tick into the descriptor
+    lists of ``eben_rate_splice_slots`` and ``eben_resample_slots`` and the chunks each FIFO completed; ``SlotTapes`` executes them on
+    the device, ``tests/pool_rate_oracle.py`` in float64."""
+
+    def __init__(self, chunk_samples: int, slots: int, input_rates, model_rate: int = 16000, multiple: int = 1):
+        from ._lib import RATE_MAX_RATIOS
+
+        self.chunk_samples, self.slots, self.model_rate = int(chunk_samples), int(slots), int(model_rate)
+        self.rates: List[int] = []                 # the declared rates that need resampling; a slot's ``ratio`` indexes these lists
+        self.ratios: List[Tuple[int, int, int]] = []
+        self.input_chunk: List[int] = []
+        for r in input_rates:
+            r = int(r)
+            if r == self.model_rate or r in self.rates:
+                continue
+            n_in = input_chunk_samples(self.chunk_samples, r, self.model_rate, multiple)
+            orig, new, width = ratio(r, self.model_rate)
+            lag = self.chunk_samples - final_outputs(n_in, orig, new, width)
+            if not 0 < lag < self.chunk_samples:
+                raise ValueError(f"chunk_samples = {chunk_samples} does not cover the look-ahead of {width + orig - 1} input samples at {r} Hz")
+            self.rates.append(r)
+            self.ratios.append((orig, new, width))
+            self.input_chunk.append(n_in)
+        if len(self.rates) > RATE_MAX_RATIOS:
+            raise ValueError(f"{len(self.rates)} input rates to resample, at most {RATE_MAX_RATIOS}")
+        self.tape_samples = max((2 * w + o - 1 + n for (o, _, w), n in zip(self.ratios, self.input_chunk)), default=0)
+        self.slot: List[Optional[_Slot]] = [None] * self.slots
+
+    def open(self, slot: int, input_rate: int) -> None:
+        """Slot ``slot`` starts a stream at ``input_rate`` (one of ``rates``): nothing is carried over, the tapes need no clearing."""
+        self.slot[slot] = _Slot(self.rates.index(int(input_rate)), Schedule(input_rate, self.model_rate))
+
+    def release(self, slot: int) -> None:
+        self.slot[slot] = None
+
+    def outputs_after(self, slot: int, n_tail: int) -> int:
+        """Samples at the model's rate of the slot's whole stream if it ended with ``n_tail`` more input samples."""
+        st = self.slot[slot]
+        pushed = st.schedule.pushed + st.lazy * self.input_chunk[st.ratio]
+        return resampled_length(pushed + int(n_tail), st.schedule.orig, st.schedule.new)
+
+    def _apply(self, slot: int, st: _Slot, op: RatePush, final: bool):
+        """Push ``op`` on the slot's tapes and FIFO: (the splice's numbers behind slot and row, or None; its pieces; its chunks)."""
+        c = self.chunk_samples
+        orig, new, _ = self.ratios[st.ratio]
+        splice = None
+        if op.length:
+            st.tape ^= 1
+            splice = (op.prev_off, op.n_carry, op.n_new, st.tape)
+        pieces, out, done = [], [], 0
+        while done < op.n_out:
+            take = min(c - st.held, op.n_out - done)
+            p0, base0 = op.piece(done, orig, new)
+            pieces.append(SlotPiece(slot, st.ratio, st.tape, op.length, p0, base0, take, op.end, st.fifo, st.held))
+            st.held, done = st.held + take, done + take
+            if st.held == c:
+                out.append(SlotChunk(slot, st.fifo, c))
+                st.held, st.fifo = 0, st.fifo ^ 1
+        if final and st.held:
+            out.append(SlotChunk(slot, st.fifo, st.held))
+        return splice, pieces, out
+
+    def feed(self, pushes, final: bool = False):
+        """``pushes``: (slot, samples pushed) per session, each slot once.  Returns ``(splices, pieces, chunks)``: the two descriptor lists
+        and per slot the ``SlotChunk`` its FIFO completed, in order -- none at a stream's first push, one at every later push, and with
+        ``final`` possibly a whole chunk and then the shorter rest.
+
+        Once a slot's carry no longer starts at position 0 its ``RatePush`` repeats (every position moves with the input), and with it
+        the descriptors, up to the parity of tapes and FIFO buffers: a steady push replays them and costs a counter here; the schedule
+        is advanced (``Schedule.advance``) when the stream ends."""
+        splices: List[SlotSplice] = []
+        pieces: List[SlotPiece] = []
+        chunks: dict = {}
+        rows: dict = {}   # pushed length -> rows of that compact input so far
+        for slot, n_in in pushes:
+            st, n_in = self.slot[slot], int(n_in)
+            if slot in chunks or st is None:
+                raise RuntimeError(f"rate front: slot {slot} is {'named twice' if slot in chunks else 'not open'}")
+            whole = self.input_chunk[st.ratio]
+            if not (0 <= n_in < whole if final else n_in == whole):
+                raise ValueError(f"rate front: a push of slot {slot} takes {whole} samples, the final one fewer, got {n_in}")
+            if st.steady is not None and not final:
+                st.lazy += 1
+                parity = st.tape ^ 1   # of the tape this push writes
+                hit = st.replay.get(parity)
+                if hit is None:
+                    hit = st.replay[parity] = self._apply(slot, st, st.steady, False)
+                else:   # what _apply does to the slot in the steady state: both parities flip, the FIFO holds what it held
+                    st.tape, st.fifo = st.tape ^ 1, st.fifo ^ 1
+                splice, mine, out = hit
+            else:
+                if st.lazy:
+                    st.schedule.advance(st.lazy * whole)
+                    st.lazy = 0
+                op = st.schedule.push(n_in, final)
+                s = st.schedule
+                if not final and op == st.last and op.n_out == self.chunk_samples and (s.emitted // s.new) * s.orig >= s.width:
+                    st.steady = op
+                st.last = op
+                splice, mine, out = self._apply(slot, st, op, final)
+            if splice is not None:
+                splices.append(SlotSplice(slot, rows.get(n_in, 0) if n_in else 0, *splice))
+                if n_in:
+                    rows[n_in] = rows.get(n_in, 0) + 1
+            pieces.extend(mine)
+            chunks[slot] = list(out)
+        return splices, pieces, chunks
+
+
+# EbenRateSplice and EbenRatePiece as bytes: a table of 128 descriptors packed this way costs a tenth of 128 ctypes constructors
+_SPLICE_POD, _PIECE_POD = struct.Struct("=6i"), struct.Struct("=6i4B")
+
+
+class SlotTapes:
+    """The device state of a ``SlotFront`` and the executor of its lists: two tapes ``(slots, tape_samples)``, two FIFO buffers
+    ``(slots, 1, chunk_samples)`` and the declared ratios' tables (``augment.resample``'s own), allocated here once."""
+
+    def __init__(self, front: SlotFront, device):
+        from ._lib import EbenRateRatio
+
+        self.front, self.device = front, torch.empty(0, device=device).device
+        self.tapes = [torch.empty((front.slots, front.tape_samples), dtype=torch.float32, device=self.device) for _ in range(2)]
+        self.fifo = [torch.empty((front.slots, 1, front.chunk_samples), dtype=torch.float32, device=self.device) for _ in range(2)]
+        self.tables = [_table(r, front.model_rate, self.device)[0] for r in front.rates]
+        self.ratios = (EbenRateRatio * len(self.tables))(*[EbenRateRatio(t.data_ptr(), o, n, w, 0) for t, (o, n, w) in zip(self.tables, front.ratios)])
+        self._rows = [f.split(1, dim=0) for f in self.fifo]   # a (1, 1, chunk_samples) view per buffer and slot, built once
+
+    def chunk(self, c: SlotChunk) -> torch.Tensor:
+        row = self._rows[c.fifo][c.slot]
+        return row if c.samples == row.shape[2] else row[:, :, : c.samples]
+
+    def run(self, splices, pieces, inputs: dict) -> None:
+        """``inputs``: slot -> the (1, 1, n) chunk it pushes.  One splice launch per pushed length (and ``RATE_MAX_SPLICES`` slots), then one
+        resampling launch per ``RATE_MAX_PIECES`` pieces; nothing waits."""
+        from ._lib import RATE_MAX_PIECES, RATE_MAX_SPLICES, EbenRatePiece, EbenRateSplice, check, load, ptr, stream
+
+        lib, f = load(), self.front
+        by_length: dict = {}
+        for s in splices:
+            by_length.setdefault(s.n_new, []).append(s)
+        for n_new, group in by_length.items():
+            src = None
+            if n_new:
+                src = inputs[group[0].slot] if len(group) == 1 else torch.cat([inputs[s.slot] for s in group], dim=0)
+            for i in range(0, len(group), RATE_MAX_SPLICES):
+                part = group[i : i + RATE_MAX_SPLICES]
+                table = (EbenRateSplice * len(part)).from_buffer_copy(b"".join([_SPLICE_POD.pack(*s) for s in part]))
+                check(lib.eben_rate_splice_slots(ptr(self.tapes[0]), ptr(self.tapes[1]), f.tape_samples, f.slots, ptr(src), n_new, len(group), table,
+                                                 len(part), stream()), "rate_splice_slots")
+        for i in range(0, len(pieces), RATE_MAX_PIECES):
+            part = pieces[i : i + RATE_MAX_PIECES]
+            table = (EbenRatePiece * len(part)).from_buffer_copy(b"".join([_PIECE_POD.pack(p.length, p.p0, p.base0, p.n_out, p.end, p.first_out, p.slot,
+                                                                                           p.ratio, p.tape, p.fifo) for p in part]))
+            check(lib.eben_resample_slots(ptr(self.tapes[0]), ptr(self.tapes[1]), f.tape_samples, ptr(self.fifo[0]), ptr(self.fifo[1]), f.chunk_samples,
+                                          f.slots, self.ratios, len(self.tables), table, len(part), stream()), "resample_slots")

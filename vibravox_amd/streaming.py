@@ -25,6 +25,9 @@ Everything here is arithmetic on positions (host only, no GPU needed):
 
   * A stream that arrives at the recording's rate (``StreamingEnhancer(input_rate=...)``) passes through ``rate.ChunkFront`` first: a
     carried-state resampler whose final samples reach the enhancer in whole chunks, one chunk later.  Nothing of the schedule changes.
+    In a ``StreamPool(input_rates=...)`` every session has a rate of its own: ``rate.SlotFront`` keeps a resampler schedule and a FIFO per
+    slot, one splice launch and one resampling launch serve all slots that push in a tick (``FrontRun``), and the chunk a session's
+    FIFO completes is its push of that tick (``Hand``).
 
 Audio hold-back: ``cut_to_valid_length`` drops up to ``multiple - 1`` samples from the end of a clip, so a sample pushed now may turn
 out to lie behind the stream's valid length.  The analysis bank therefore treats only ``ragged.cut_length(pushed)`` samples as
@@ -612,11 +615,37 @@ class Move:
     into_pool: bool
 
 
-class Session:
-    """Handle of one stream in a ``StreamPool``: ``phase`` is "warming", "pooled" or "closed"."""
+@dataclasses.dataclass(frozen=True)
+class FrontRun:
+    """The resampling front of the sessions that arrive at a recording rate (``rate.SlotFront.feed``): ``splices`` of the chunks that
+    ``order`` pushed into their slots' tapes, then ``pieces`` into their FIFO buffers."""
+    splices: Tuple[object, ...]
+    pieces: Tuple[object, ...]
+    order: Tuple["Session", ...]
 
-    def __init__(self, book: "PoolBook", slot: int, private: int, schedule: Schedule):
+
+@dataclasses.dataclass(frozen=True)
+class Hand:
+    """From here on ``session``'s chunk is what its FIFO completed (``rate.SlotChunk``), at the model's rate; None: it has none."""
+    session: "Session"
+    chunk: object
+
+
+class Session:
+    """Handle of one stream in a ``StreamPool``: ``phase`` is "warming", "pooled" or "closed".  ``input_rate``: the rate its audio arrives
+    at; ``input_chunk_samples``: samples per push at that rate; ``input_latency``: input samples pushed minus those the emitted ones
+    correspond to in the steady state (``StreamingEnhancer``'s properties of the same names)."""
+
+    def __init__(self, book: "PoolBook", slot: int, private: int, schedule: Schedule, input_rate: Optional[int] = None):
         self.book, self.slot, self.schedule = book, slot, schedule
+        self.rated = input_rate is not None   # its chunks pass through the book's rate front first
+        self.input_rate = book.model_rate if input_rate is None else input_rate
+        self.input_chunk_samples, self.input_latency = book.chunk, book.plan.latency
+        if self.rated:
+            front = book.front
+            orig, new, _ = front.ratios[front.rates.index(input_rate)]
+            self.input_chunk_samples = front.input_chunk[front.rates.index(input_rate)]
+            self.input_latency = self.input_chunk_samples + _ceil(book.plan.latency * orig, new)
         self.private = private   # id of the batch-1 state it warms up or finishes on; -1 while it needs none
         self.phase = "warming"
         self.pushes = 0          # private pushes so far
@@ -632,13 +661,20 @@ class PoolBook:
     A session warms up and finishes on a private batch-1 state with its own ``Schedule`` and lives in a slot in between; a pooled push
     costs a counter increment here."""
 
-    def __init__(self, gen, chunk_samples: int, slots: int = 64, stream_plan: Optional[StreamPlan] = None):
+    def __init__(self, gen, chunk_samples: int, slots: int = 64, stream_plan: Optional[StreamPlan] = None, input_rates=(), model_rate: int = 16000):
         slots = int(slots)
         if not 1 <= slots <= 256:
             raise ValueError(f"slots must lie in 1 ... 256, got {slots}")
         self.gen, self.slots = gen, slots
         self.plan = stream_plan if stream_plan is not None else plan(gen, chunk_samples)
         self.chunk = self.plan.chunk_samples
+        self.model_rate = int(model_rate)
+        self.input_rates = tuple(int(r) for r in input_rates)   # the recording rates this pool admits, beside the model's own
+        self.front = None   # rate.SlotFront: a resampler and a FIFO per slot, when a declared rate is not the model's
+        if any(r != self.model_rate for r in self.input_rates):
+            from . import rate
+
+            self.front = rate.SlotFront(self.chunk, slots, self.input_rates, self.model_rate, gen.multiple)
         self.words = (slots + 63) // 64
         self.free_slots = list(range(slots))
         self.free_private: List[int] = []
@@ -656,16 +692,26 @@ class PoolBook:
         self.free_private.append(i)
         self.free_private.sort()
 
-    def open(self) -> Session:
+    def open(self, input_rate: Optional[int] = None) -> Session:
         if not self.free_slots:
             raise RuntimeError(f"StreamPool: all {self.slots} slots hold an open session")
+        if input_rate is not None and int(input_rate) == self.model_rate:
+            input_rate = None
+        if input_rate is not None:
+            input_rate = int(input_rate)
+            if self.front is None or input_rate not in self.front.rates:
+                raise ValueError(f"StreamPool: a session at {input_rate} Hz in a pool that declared input_rates = {self.input_rates} "
+                                 f"(the model's {self.model_rate} Hz needs no declaration)")
         if self.spare:
             schedule = self.spare.pop()
             schedule.reset()
         else:
             schedule = Schedule(self.gen, self.chunk)
             schedule._steady = self.plan.steady
-        return Session(self, self.free_slots.pop(0), -1, schedule)   # a private state is taken at the first push, the slot now
+        session = Session(self, self.free_slots.pop(0), -1, schedule, input_rate)   # a private state is taken at the first push, the slot now
+        if session.rated:
+            self.front.open(session.slot, input_rate)
+        return session
 
     def check(self, sessions) -> None:
         seen = set()
@@ -682,6 +728,18 @@ class PoolBook:
         """The entries of a tick in which exactly ``sessions`` push one chunk each; the others stay where they are."""
         sessions = list(sessions)
         self.check(sessions)
+        rated = sorted((s for s in sessions if s.rated), key=lambda s: s.slot)
+        if not rated:
+            return self._pushes(sessions)
+        # a chunk at a recording rate goes through the front; the chunk its FIFO completes (none at a stream's first push) is the
+        # session's push of this tick
+        splices, pieces, chunks = self.front.feed([(s.slot, s.input_chunk_samples) for s in rated])
+        entries: List[object] = [FrontRun(tuple(splices), tuple(pieces), tuple(rated))]
+        entries.extend(Hand(s, chunks[s.slot][0]) for s in rated if chunks[s.slot])
+        return entries + self._pushes([s for s in sessions if not s.rated or chunks[s.slot]])
+
+    def _pushes(self, sessions) -> List[object]:
+        """The entries of one chunk at the model's rate for each of ``sessions``."""
         entries: List[object] = []
         pooled = sorted((s for s in sessions if s.phase == "pooled"), key=lambda s: s.slot)
         if pooled:
@@ -709,6 +767,24 @@ class PoolBook:
         (a tail of a chunk or more, a stream below the shortest clip) leaves the session open."""
         self.check([session])
         s, entries = session, []
+        if s.rated:
+            # the tail is at the recording's rate: what the FIFO completes with it is first, possibly, one more whole chunk -- an ordinary
+            # push of this session -- and then the rest, which ends the stream
+            if not 0 <= n_tail < s.input_chunk_samples:
+                raise ValueError(f"a push takes {s.input_chunk_samples} samples, the final one fewer, got {n_tail}")
+            ragged.plan(self.gen, [self.front.outputs_after(s.slot, n_tail)])   # refuses a stream below the shortest clip before anything moves
+            splices, pieces, chunks = self.front.feed([(s.slot, n_tail)], final=True)
+            entries.append(FrontRun(tuple(splices), tuple(pieces), (s,)))
+            n_tail = 0
+            for c in chunks[s.slot]:
+                entries.append(Hand(s, c))
+                if c.samples == self.chunk:
+                    entries.extend(self._pushes([s]))
+                else:
+                    n_tail = c.samples
+            if n_tail == 0:
+                entries.append(Hand(s, None))   # the stream ends without a rest
+            self.front.release(s.slot)
         if s.phase == "pooled":
             s.schedule.advance(s.pooled_pushes)
             s.pooled_pushes = 0
@@ -735,29 +811,50 @@ class StreamPool(_Driver):
     session the returns are those of ``StreamingEnhancer.push`` / ``finish`` on a stream of its own.  A session warms up and finishes
     alone on a private batch-1 state; in between it lives in one of ``slots`` rows of a shared state, and every session that pushed in a
     tick is served by ONE run of the steady-state list over all rows, with masked splices (``eben_stream_splice_rows``) that leave the
-    rows of the others as they are.  Nothing here waits for the device."""
+    rows of the others as they are.  Nothing here waits for the device.
+
+    ``input_rates``: the recording rates this pool admits beside ``model_rate``, declared up front so that everything is allocated once
+    (each must give a whole ``rate.input_chunk_samples``; the ``ValueError`` names the smallest ``chunk_samples`` that works).
+    ``open(input_rate=r)`` opens a session whose ``step`` takes ``(1, 1, session.input_chunk_samples)`` at its own rate and whose ``close``
+    takes a shorter tail; per session the returns are those of ``StreamingEnhancer(..., input_rate=r)``: nothing at the first push, one
+    ``chunk_samples`` of extra latency (``session.input_latency``).  All rated sessions of a tick share one splice launch per pushed
+    length and one resampling launch (``eben_rate_splice_slots``, ``eben_resample_slots``).  Without ``input_rates`` the pool is what it
+    was."""
 
     _who, _per, _last = "StreamPool", " per session", "close"
 
-    def __init__(self, generator, chunk_samples: int, slots: int = 64, return_bands: bool = False):
+    def __init__(self, generator, chunk_samples: int, slots: int = 64, return_bands: bool = False, input_rates=(), model_rate: int = 16000):
         super().__init__(generator, chunk_samples, return_bands)   # ``state``: the shared one
-        self.book = PoolBook(generator, chunk_samples, slots, self.plan)
+        self.book = PoolBook(generator, chunk_samples, slots, self.plan, input_rates, model_rate)
         self.slots = self.book.slots
         self.private = {}      # id -> batch-1 StreamState, allocated when the book first hands the id out and kept
+        self.tapes = None      # rate.SlotTapes: the front's tapes, FIFO buffers and tables, when the pool admits recording rates
 
     def prepare(self, device, private: int = 0) -> "StreamPool":
         """Allocates the shared state on ``device`` now instead of at the first step, and ``private`` batch-1 states for sessions that
-        warm up or finish at the same time (further ones are allocated when first needed, and kept)."""
+        warm up or finish at the same time (further ones are allocated when first needed, and kept).  Another device while sessions at a
+        recording rate are open is refused: the front's schedules would go on from tapes that were never written."""
+        before = self.state
         if self._allocate(device, self.slots):
+            if self.tapes is not None and any(st is not None for st in self.book.front.slot):
+                self.state = before
+                raise RuntimeError(f"StreamPool: sessions at a recording rate are open on {self.tapes.device}; their tapes do not move to "
+                                   f"'{device}': close them first")
             for t in self.plan.tensors:
                 self.state.length[t.name] = t.length
             self.private = {}
+        if self.book.front is not None and (self.tapes is None or self.tapes.device != self.state.device):
+            from . import rate
+
+            self.tapes = rate.SlotTapes(self.book.front, self.state.device)
         for i in range(min(int(private), self.slots)):
             self._private_state(i)
         return self
 
-    def open(self) -> Session:
-        return self.book.open()
+    def open(self, input_rate: Optional[int] = None) -> Session:
+        """A session for a stream that begins now.  ``input_rate``: the rate its audio arrives at, one of the declared ``input_rates``
+        (None or ``model_rate``: the model's own); ``ValueError`` for a rate that was not declared."""
+        return self.book.open(input_rate)
 
     def _private_state(self, i: int):
         from . import gen_engine
@@ -769,9 +866,14 @@ class StreamPool(_Driver):
     def _results(self, out, sessions, results: dict) -> None:
         """The emitted tensors, a row per session, as what each session's call returns (rows are split in one call: a view per session
         built one by one costs more host time at 64 sessions than the mask does)."""
+        import torch
+
         per_name = [t.split(1, dim=0) if len(sessions) > 1 else (t,) for t in self._emitted(out, len(sessions), self.state.device)]
         for a, s in enumerate(sessions):
-            results[s] = (per_name[0][a], per_name[1][a]) if self.return_bands else per_name[0][a]
+            got = (per_name[0][a], per_name[1][a]) if self.return_bands else per_name[0][a]
+            if s in results:   # a close at a recording rate whose FIFO completed one more chunk: that push, then the final one
+                got = tuple(torch.cat(pair, dim=2) for pair in zip(results[s], got)) if self.return_bands else torch.cat((results[s], got), dim=2)
+            results[s] = got
 
     def _execute(self, entries, chunks) -> dict:
         import torch
@@ -784,6 +886,12 @@ class StreamPool(_Driver):
             if isinstance(e, PooledRun):
                 compact = chunks[e.order[0]] if len(e.order) == 1 else torch.cat([chunks[s] for s in e.order], dim=0)
                 self._results(engine.stream_run_pooled(self.state, self.plan.steady, compact, e.mask, len(e.order)), e.order, results)
+            elif isinstance(e, FrontRun):
+                self.tapes.run(e.splices, e.pieces, {s.slot: chunks[s] for s in e.order if s in chunks})
+            elif isinstance(e, Hand):
+                chunks.pop(e.session, None)
+                if e.chunk is not None:
+                    chunks[e.session] = self.tapes.chunk(e.chunk)
             elif isinstance(e, PrivatePush):
                 state = self._private_state(e.private)
                 if e.fresh:
@@ -799,13 +907,17 @@ class StreamPool(_Driver):
         if not isinstance(chunks, dict):
             raise ValueError(f"StreamPool: step expects a dict of session -> chunk, got {type(chunks).__name__}")
         self.book.check(chunks)
-        for chunk in chunks.values():
-            self._check(chunk, 1, "step")
+        for s, chunk in chunks.items():
+            self._check(chunk, 1, "step", s.input_chunk_samples)
         if not chunks:
             return {}
         chunks = {s: c.contiguous() for s, c in chunks.items()}
         self.prepare(next(iter(chunks.values())).device)
-        results = self._execute(self.book.tick(chunks), chunks)
+        results = self._execute(self.book.tick(chunks), dict(chunks))
+        if len(results) < len(chunks):   # a stream at a recording rate completes no chunk at its first push
+            got = self._emitted({}, 1, self.state.device)
+            nothing = tuple(got) if self.return_bands else got[0]
+            return {s: results.get(s, nothing) for s in chunks}
         return {s: results[s] for s in chunks}
 
     def close(self, session: Session, tail=None):
@@ -817,7 +929,7 @@ class StreamPool(_Driver):
         if tail is not None and isinstance(tail, torch.Tensor) and tail.shape[-1] == 0:
             tail = None
         if tail is not None:
-            self._check(tail, 1, "close")
+            self._check(tail, 1, "close", session.input_chunk_samples)
             tail = tail.contiguous()
         self.prepare(tail.device if tail is not None else self.state.device if self.state is not None
                      else next(self.generator.parameters()).device)
