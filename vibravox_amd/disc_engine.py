@@ -330,10 +330,7 @@ def inject_grads(params: Sequence[torch.nn.Parameter], grads: Sequence[torch.Ten
     if _DIRECT_INJECT and not (torch.distributed.is_available() and torch.distributed.is_initialized()) and all(
             not getattr(p, "_post_accumulate_grad_hooks", None) and not p._backward_hooks for p in ps):
         for p, g in live:
-            if p.grad is None:
-                p.grad = g
-            else:
-                p.grad.add_(g)
+            ops.accumulate_grad(p, g)
         return
     _InjectGrads.apply(list(gs), *ps).backward()
 

@@ -174,7 +174,7 @@ class GeneratorEngine:
 
     def _pack(self, m, spec, batch, l_in, train):
         d = ops.conv_desc(spec, batch, l_in, conv_forward_math())   # layers the split bf16 tap-conv does not cover run their fp32 kernel
-        d_bwd = ops.conv_desc(spec, batch, l_in, ops._backward_math[0])
+        d_bwd = ops.conv_desc(spec, batch, l_in, ops._mode.math)
         v, g = _params(m)
         pw = ops.pack_weights(m.spec, d, v.detach(), None if g is None else g.detach(), m._packed, train, d_bwd)
         return d, d_bwd, pw
@@ -236,7 +236,7 @@ class GeneratorEngine:
     def _ru_bwd_math() -> int:
         """Math of the fused backward launch: plain bf16 operands next to a bf16 generator backward (``ops.backward_math``), else
         the fp32-grade split."""
-        return ops.MATH_BF16 if ops._backward_math[0] != ops.MATH_F32 else RU_BWD_F32_MATH
+        return ops.MATH_BF16 if ops._mode.math != ops.MATH_F32 else RU_BWD_F32_MATH
 
     def _ru_cache(self, ru) -> ops.PackedWeights:
         c = self._ru_images.get(id(ru))
@@ -576,13 +576,15 @@ class GeneratorEngine:
         ``_dw_body`` while ``backward_train``'s input-gradient chain runs, or accumulated now.  The queue runs only where ``_deferrable()``
         found every core parameter trainable and routed alike: there ``grads`` launches without looking (``trainable_only=False``) and a
         bundle-layout unit it cannot serve is that check's bug, an assertion; launch by launch it is the user's pattern, an error."""
-        if ops._skip_weight_grads[0]:
+        if ops._mode.skip_weight_grads:
             return
         job = functools.partial(grads, *operands)
         if self._dwq is not None:
             self._dwq.append(job)
         else:
-            self._accumulate(job(trainable_only=True))
+            for p, t in job(trainable_only=True):   # not deferred (no side-stream context): accumulate like autograd would
+                if p is not None and t is not None and p.requires_grad:
+                    ops.accumulate_grad(p, t, hooks=True)
 
     def _conv_dw(self, rec: _ConvRec, dy, trainable_only: bool) -> list:
         return self._conv_grads(rec, dy) if not trainable_only or _params(rec.m)[0].requires_grad else []
@@ -594,14 +596,6 @@ class GeneratorEngine:
             raise RuntimeError("bundle-layout ResidualUnit: the two convs' weight gradients are routed differently (one of them holds a gradient "
                                "or a hook the other does not); set EBEN_RU_BL=0 for this pattern")
         return res
-
-    @staticmethod
-    def _accumulate(pairs) -> None:
-        for p, t in pairs:   # not deferred (no side-stream context): accumulate like autograd would
-            if p is not None and t is not None and p.requires_grad:
-                p.grad = t if p.grad is None else p.grad.add_(t)
-                for hook in list((getattr(p, "_post_accumulate_grad_hooks", None) or {}).values()):
-                    hook(p)   # e.g. ddp.GradSync's bucket accounting
 
     @staticmethod
     def _conv_grads(rec: _ConvRec, dy) -> list:
@@ -711,7 +705,7 @@ class GeneratorEngine:
     # which is as long as the step needs it), and the weight images are the ones ops.prepack rebuilds in place.
     @staticmethod
     def _graphs_usable() -> bool:
-        return USE_GRAPHS and ops.ReplayedChain.enabled and not ops.ReplayedPrepack._multi_rank() and not ops._timers_enabled()
+        return USE_GRAPHS and ops.ReplayedChain.enabled and not ops.eager_multi_rank() and not ops._timers_enabled()
 
     def _static_buf(self, name: str, like: torch.Tensor) -> torch.Tensor:
         key = (name, tuple(like.shape), like.dtype, like.device)
@@ -725,7 +719,7 @@ class GeneratorEngine:
     def _fwd_sig(self, buf: torch.Tensor) -> tuple:
         """Everything the captured forward depends on besides values: input buffer, arithmetic, and per layer and fused unit the image
         cache's buffers and whether they are current (a stale image makes the eager path rebuild it -- a replay would not)."""
-        parts = [buf.data_ptr(), tuple(buf.shape), ops._backward_math[0], conv_forward_math(), ru_forward_math()]
+        parts = [buf.data_ptr(), tuple(buf.shape), ops._mode.math, conv_forward_math(), ru_forward_math()]
         parts += [m._packed.state() for m in self._core_convs]
         parts += [None if (c := self._ru_images.get(id(ru))) is None else c.state() for ru in self._core_units]
         return tuple(parts)
@@ -767,22 +761,12 @@ class GeneratorEngine:
 
     def _deferrable(self) -> bool:
         """Weight gradients of the whole core go through ``weight_grads_on_side_stream().join()``'s assignment (no gradient held, no
-        hook, no data-parallel sink)."""
-        if not ops._side["enabled"] or ops._skip_weight_grads[0]:
+        hook) or, data-parallel, straight into the sink's bucket views: the test ``ops._wg_route`` applies layer by layer."""
+        mode = ops._mode
+        if mode.route != ops.ROUTE_SIDE or mode.skip_weight_grads:
             return False
-        sink = ops._side["sink"]
-        for m in self._core_convs:
-            for p in _params(m) + (m.bias,):
-                if p is None:
-                    continue
-                if not p.requires_grad:
-                    return False
-                if sink is not None:
-                    if sink.grad_buffer(p) is None:   # data-parallel: every gradient goes straight into its bucket view
-                        return False
-                elif p.grad is not None or not ops._no_grad_hooks(p):
-                    return False
-        return True
+        params = [p for m in self._core_convs for p in _params(m) + (m.bias,) if p is not None]
+        return all(p.requires_grad for p in params) and ops.bypasses_autograd(params, mode.sink)
 
     def _dw_body(self, queue: list, sink=None) -> list:
         """The queued weight-gradient work on the current stream: every layer's kernel, then ONE slab-sum / weight-norm launch.
@@ -838,29 +822,23 @@ class GeneratorEngine:
                 return out, {j: t for j, t in sk.items() if j not in skip_grads}, queue
 
             # one signature for all segments: they settle, and are captured, in the same step, each on the results of the one before
-            g, new_skips, queue = self._dx_graphs[k].run((self._fwd_graph.captures, gbuf.data_ptr(), ops._backward_math[0]), dx_body, None)
+            g, new_skips, queue = self._dx_graphs[k].run((self._fwd_graph.captures, gbuf.data_ptr(), ops._mode.math), dx_body, None)
             skip_grads.update(new_skips)
             if not queue:
                 continue
             side.wait_stream(main)
-            sink = ops._side["sink"]
+            sink = ops._mode.sink
             with torch.cuda.stream(side):
-                if self._dx_graphs[k].graph is not None:
+                graphed = self._dx_graphs[k].graph is not None
+                if graphed:
                     assign = self._dw_graphs[k].run((self._dx_graphs[k].captures, id(sink)), lambda: self._dw_body(queue, sink), side)
                 else:
                     assign = self._dw_body(queue, sink)
-                    ops._side["keep"].append(queue)   # eager tensors: referenced until join()
-            if sink is None:
-                ops._side["assign"].extend((p, t) for p, t in assign if p.requires_grad)
-            else:
-                # data-parallel: this group's gradients sit in their bucket views once the side stream has run the launches above -- report
-                # them from THAT stream now (GradSync.mark_ready records its event on the current stream), so that a bucket filled by
-                # an early group is exchanged underneath the later groups' input-gradient chain instead of behind join()
-                if DEFER_MARK_READY:
-                    ops._side["sunk"].extend(p for p, _ in assign)   # reported by join(), from the main stream, once it has waited for the side stream
-                else:
-                    with torch.cuda.stream(side):
-                        sink.mark_ready([p for p, _ in assign])
+                # data-parallel: this group's gradients sit in their bucket views once the side stream has run the launches above.  They
+                # are reported by join(), from the main stream, once it has waited for the side stream -- or (early) from THIS stream now
+                # (GradSync.mark_ready records its event on the current stream), so that a bucket filled by an early group is exchanged
+                # underneath the later groups' input-gradient chain instead of behind join().  keep: eager tensors, referenced until join()
+                ops.hand_over(assign, sink, early=not DEFER_MARK_READY, keep=None if graphed else queue)
 
 
 class StreamState:

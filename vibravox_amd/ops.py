@@ -10,6 +10,7 @@ import contextlib
 import ctypes
 import gc
 import os
+import warnings
 import weakref
 from dataclasses import dataclass
 from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
@@ -68,108 +69,176 @@ def conv_params(m):
     return hit[1]
 
 
-# Set (by the train step) while a backward pass only needs input gradients: a Function's
-# ``needs_input_grad`` is fixed at forward time, so without this the weight-gradient GEMMs would
-# run inside torch.autograd.grad(loss, bands) although their results are discarded.
-_skip_weight_grads = [False]
+MATH_F32, MATH_BF16, MATH_BF16X2, MATH_BF16X3, MATH_BF16X6 = 0, 1, 2, 3, 4   # EBEN_MATH_* of include/eben_hip.h
+ROUTE_NOW, ROUTE_SIDE, ROUTE_COLLECT = "now", "side", "collect"
 
 
-# Set while a backward pass only needs WEIGHT gradients (the balancing norms: torch.autograd.grad(bands, last_conv.weight)): the
-# Function cannot know that its input gradient is discarded either.
-_skip_input_grads = [False]
+class BackwardMode(NamedTuple):
+    """What a backward pass has been asked to do: ``_mode``, replaced for the length of a ``_scope``."""
+    # The skips: a Function's ``needs_input_grad`` is fixed at forward time, so without them the weight-gradient GEMMs would run inside
+    # torch.autograd.grad(loss, bands), and the input gradients inside the balancing norms' torch.autograd.grad(bands, last_conv.weight),
+    # although their results are discarded.
+    skip_input_grads: bool = False
+    skip_weight_grads: bool = False
+    # Arithmetic of the BACKWARD contractions (input and weight gradients) of `conv_layer`; the forward is always exact fp32.  Read when
+    # the forward runs (the backward image of the weights is packed then).
+    math: int = MATH_F32
+    # A layer's weight gradient is launched now and returned to the caller (autograd), deferred to the side stream
+    # (``weight_grads_on_side_stream``), or launched now with its slab-sum job appended to ``jobs`` (``collect_wn_jobs``); what that
+    # means for one layer's parameters is ``_wg_route``'s to say.
+    route: str = ROUTE_NOW
+    sink: object = None            # ``ddp.GradSync``: results are written into its gradient-bucket views where it has them
+    jobs: Optional[list] = None    # ROUTE_COLLECT
 
 
-class input_grads_disabled:
+_mode = BackwardMode()
+
+
+class _scope:
+    """Context manager: ``fields`` of the backward mode replaced inside, the record found on entry (``prev``) back on exit."""
+
+    def __init__(self, **fields):
+        self.fields = fields
+
     def __enter__(self):
-        self.prev = _skip_input_grads[0]
-        _skip_input_grads[0] = True
+        global _mode
+        self.prev, _mode = _mode, _mode._replace(**self.fields)
+        return self
 
     def __exit__(self, *exc):
-        _skip_input_grads[0] = self.prev
+        global _mode
+        _mode = self.prev
 
 
-class weight_grads_disabled:
-    def __enter__(self):
-        self.prev = _skip_weight_grads[0]
-        _skip_weight_grads[0] = True
-
-    def __exit__(self, *exc):
-        _skip_weight_grads[0] = self.prev
+def input_grads_disabled():
+    return _scope(skip_input_grads=True)
 
 
-# Weight-gradient work on a side HIP stream.  A layer's backward is a serial chain of launches: input
-# gradient (needed by the next layer) and, independent of it, the weight-gradient GEMM + slab reduction +
-# weight-norm chain rule.  Inside `weight_grads_on_side_stream()` the second group is issued on a side
-# stream, so the input-gradient chain of the whole network is not held up by it (generator backward:
-# ~2.9 ms of dX launches instead of ~8.6 ms of everything in series).  The caller must `join()` before
-# anything on the main stream reads the parameter gradients (the optimiser step); only used while
-# `.grad` is None for the parameters involved and no accumulation hook hangs on them: the deferred gradients never pass through
-# autograd -- backward() returns None for them and `join()` assigns `p.grad` itself once the side stream is done.
-# `keep` holds a reference to every upstream gradient a side-stream kernel reads until `join()`: autograd sums gradients IN PLACE
-# into a buffer it holds the only reference to (a residual add hands the same tensor to both branches), which would rewrite the
-# gradient on the main stream under the kernel reading it.
-_side = {"enabled": False, "stream": None, "keep": [], "prepacked": None, "wn_jobs": [], "sink": None, "sunk": [], "assign": []}
+def weight_grads_disabled():
+    return _scope(skip_weight_grads=True)
+
+
+def backward_math(math: int):
+    """with ops.backward_math(ops.MATH_BF16): forwards run inside record bf16 backward contractions."""
+    return _scope(math=math)
+
+
+def collect_wn_jobs(jobs: list, sink=None):
+    """Inside this context ``weight_grads`` / ``weight_grads_ru`` launch the weight-gradient kernels only, on the current stream (the
+    caller has made the stream the work belongs on current), and append the slab-sum + weight-norm job of each layer to ``jobs``: the
+    caller runs them as ONE ``wn_bwd_multi(jobs)`` (gen_engine's graph-captured weight-gradient body).  sink: results go straight into
+    its gradient buffers (``grad_buffer(param)``)."""
+    return _scope(route=ROUTE_COLLECT, sink=sink, jobs=jobs)
+
+
+def accumulate_grad(p, t, hooks: bool = False) -> None:
+    """``t`` becomes ``p.grad`` or is added to it, as autograd would; hooks: and the post-accumulate hooks fire (``ddp.GradSync``)."""
+    if p.grad is None:
+        p.grad = t
+    else:
+        p.grad.add_(t)
+    if hooks:
+        for hook in list((getattr(p, "_post_accumulate_grad_hooks", None) or {}).values()):
+            hook(p)
 
 
 def _no_grad_hooks(p) -> bool:
     return p is None or (not getattr(p, "_post_accumulate_grad_hooks", None) and not p._backward_hooks)
 
 
-class weight_grads_on_side_stream:
+# Weight-gradient work on a side HIP stream.  A layer's backward is a serial chain of launches: input gradient (needed by the next
+# layer) and, independent of it, the weight-gradient GEMM + slab reduction + weight-norm chain rule.  Inside
+# `weight_grads_on_side_stream()` the second group is issued on a side stream, so the input-gradient chain of the whole network is not
+# held up by it.  The caller must `join()` before anything on the main stream reads the parameter gradients (the optimiser step).  The
+# deferred gradients never pass through autograd -- backward() returns None for them (it may clone what it is given, and the deferred
+# kernels would then fill a tensor nobody reads) -- so without a sink only layers whose parameters hold no `.grad` and carry no
+# accumulation hook are deferred (`_wg_route`): `join()` assigns `p.grad` itself once the side stream is done.
+class _Pending:
+    """What ``join()`` still owes."""
+
+    __slots__ = ("keep", "wn_jobs", "assign", "sunk")
+
+    def __init__(self):
+        # keep: every tensor a side-stream kernel reads, referenced until the join -- autograd sums gradients IN PLACE into a buffer it
+        # holds the only reference to (a residual add hands the same tensor to both branches), which would rewrite the gradient on the
+        # main stream under the kernel reading it.  wn_jobs: the slab sums + weight-norm chain rule of ALL deferred layers, one
+        # multi-tensor call at the join.  assign: (parameter, gradient) for ``.grad``.  sunk: parameters to report to the sink.
+        self.keep, self.wn_jobs, self.assign, self.sunk = [], [], [], []
+
+    def defer(self, keep, jobs) -> None:
+        """A weight-gradient launch on the side stream: what it reads, and the jobs that finish it."""
+        self.keep.append(keep)
+        self.wn_jobs.extend(jobs)
+
+    def hand_over(self, pairs, sink=None, early: bool = False, keep=None) -> None:
+        """(parameter, gradient) pairs of work queued on the side stream, which reads ``keep``: a view of ``sink``'s buckets is reported
+        to it (early: now, from the current stream, else at the join), anything else is assigned at the join."""
+        if keep is not None:
+            self.keep.append(keep)
+        if sink is None:
+            self.assign.extend(pairs)
+        elif early:
+            sink.mark_ready([p for p, _ in pairs])
+        else:
+            self.sunk.extend(p for p, _ in pairs)
+
+    def settle(self, sink) -> None:
+        st = _sides.stream
+        if st is not None:
+            for k in SIDE_STREAMS[1:]:
+                st.wait_stream(aux_stream(k, st.device))
+            if self.wn_jobs:
+                with torch.cuda.stream(st):
+                    wn_bwd_multi(self.wn_jobs)   # two launches
+                self.wn_jobs = []
+            torch.cuda.current_stream(st.device).wait_stream(st)
+        assign, self.assign = self.assign, []
+        for p, t in assign:   # complete on this stream from here on
+            accumulate_grad(p, t)
+        if self.sunk:
+            sunk, self.sunk = self.sunk, []
+            sink.mark_ready(sunk)
+        self.keep.clear()   # the current stream has waited for the side stream: what its kernels read may be reused from here on
+
+    def drop(self) -> None:
+        # a backward that raised half-way leaves jobs pointing at tensors nobody will hand over: wait for what was launched, then
+        # drop everything instead of letting the next join() write through stale pointers
+        st = _sides.stream
+        if st is not None:
+            for k in SIDE_STREAMS:
+                torch.cuda.current_stream(st.device).wait_stream(aux_stream(k, st.device))
+        self.__init__()
+
+
+_pending = _Pending()
+hand_over = _pending.hand_over   # for the engines: what their own side-stream launches produced
+
+
+class weight_grads_on_side_stream(_scope):
     """sink: an object with ``grad_buffer(param) -> tensor | None`` and ``mark_ready(params)`` (``ddp.GradSync``): the
     weight gradients are then written straight into the sink's buffers (data-parallel gradient buckets) and reported at
     ``join()``, instead of being handed to autograd -- which would accumulate them into ``p.grad`` on the main stream
     the moment the layer's backward returns, i.e. force the weight-gradient work back onto the critical path."""
 
     def __init__(self, sink=None):
+        super().__init__(route=ROUTE_SIDE, sink=sink, jobs=None)
         self.sink = sink
 
-    def __enter__(self):
-        self.prev = (_side["enabled"], _side["sink"])
-        _side["enabled"], _side["sink"] = True, self.sink
-        return self
-
     def __exit__(self, exc_type, *exc):
-        _side["enabled"], _side["sink"] = self.prev
+        super().__exit__(exc_type, *exc)
         if exc_type is not None:
-            # a backward that raised half-way leaves jobs pointing at tensors nobody will hand over: wait for what was
-            # launched, then drop everything instead of letting the next join() write through stale pointers
-            st = _side["stream"]
-            if st is not None:
-                for k in SIDE_STREAMS:
-                    torch.cuda.current_stream(st.device).wait_stream(aux_stream(k, st.device))
-            for key in ("wn_jobs", "keep", "sunk", "assign"):
-                _side[key] = []
+            _pending.drop()
 
     def join(self):
-        st = _side["stream"]
-        if st is not None:
-            for k in SIDE_STREAMS[1:]:
-                st.wait_stream(aux_stream(k, st.device))
-            if _side["wn_jobs"]:
-                with torch.cuda.stream(st):
-                    wn_bwd_multi(_side["wn_jobs"])   # slab sums + weight-norm chain rule of every layer: two launches
-                _side["wn_jobs"] = []
-            torch.cuda.current_stream(st.device).wait_stream(st)
-        assign, _side["assign"] = _side["assign"], []
-        for p, t in assign:   # complete on this stream from here on
-            if p.grad is None:
-                p.grad = t
-            else:
-                p.grad.add_(t)
-        if _side["sunk"]:
-            sunk, _side["sunk"] = _side["sunk"], []
-            self.sink.mark_ready(sunk)
-        _side["keep"].clear()   # the current stream has waited for the side stream: what its kernels read may be reused from here on
+        _pending.settle(self.sink)
 
 
-# The HIP runtime multiplexes streams onto FOUR hardware queues (GPU_MAX_HW_QUEUES; 8 measured 50 % slower): a fifth
-# stream shares a queue with another one and its launches are executed in submission order with that one's -- a tiny
-# Adam launch on the main stream then sits behind ~17 ms of weight-gradient kernels of a stream it has nothing to do with
-# (seen as 28 / 33 / 36 ms steps from run to run, depending on which streams happened to collide).  So the step uses the
-# main stream plus exactly THREE auxiliary streams, created once, in this order:
-#   0: MelGAN discriminator chain   1: the three PQMF-band discriminator chains (in series)   2: generator weight
-#   gradients, weight pre-packing
+# The HIP runtime multiplexes a process's streams onto a fixed number of hardware queues, and streams that share a queue execute in
+# submission order with each other (how many queues, and why: _env.py).  So a train step uses the main stream plus exactly THREE
+# auxiliary streams, created together on first use, in this order:
+#   0: MelGAN discriminator chain   1: the three PQMF-band discriminator chains (in series)   2: generator weight gradients and weight
+#   pre-packing (the "side" stream below)
+# A data-parallel rank adds one communication stream of its own (ddp.GradSync).
 _aux = {"device": None, "streams": None}
 #: HIP priorities of the three auxiliary streams (0 = default, -1 = high; torch's range on this device is (0, -1)).  The stream that
 #: carries the generator's weight gradients, the weight pre-packing and (spread backward) one PQMF-band chain gets the high one: the
@@ -194,13 +263,21 @@ def aux_stream(i: int, device=None) -> "torch.cuda.Stream":
 SIDE_STREAMS = tuple(int(t) for t in os.environ.get("EBEN_SIDE_STREAMS", "2").split(",") if t.strip() != "")
 
 
+class _Sides:
+    __slots__ = ("stream", "rr")   # the side stream once it has been used (the joins wait for it); whom the last job was dealt to
+
+
+_sides = _Sides()
+_sides.stream, _sides.rr = None, -1
+
+
 def _side_stream(device, deal: bool = False) -> "torch.cuda.Stream":
     """The side stream (weight pre-packing; joins); ``deal``: the next one of SIDE_STREAMS, for a weight-gradient job."""
-    st = _side["stream"] = aux_stream(SIDE_STREAMS[0], device)
+    st = _sides.stream = aux_stream(SIDE_STREAMS[0], device)
     if not deal or len(SIDE_STREAMS) == 1:
         return st
-    k = _side["rr"] = (_side.get("rr", -1) + 1) % len(SIDE_STREAMS)
-    return aux_stream(SIDE_STREAMS[k], device)
+    _sides.rr = (_sides.rr + 1) % len(SIDE_STREAMS)
+    return aux_stream(SIDE_STREAMS[_sides.rr], device)
 
 
 class WnJob(NamedTuple):
@@ -346,28 +423,9 @@ class ConvSpec:
 _desc_cache: Dict[Tuple[ConvSpec, int, int], EbenConv1dDesc] = {}
 
 
-MATH_F32, MATH_BF16, MATH_BF16X2, MATH_BF16X3, MATH_BF16X6 = 0, 1, 2, 3, 4   # EBEN_MATH_* of include/eben_hip.h
 # EBEN_CONV_ROUTE_* of include/eben_hip.h: the answers of eben_conv1d_kernel_generation and out[0] of eben_conv1d_variant
 CONV_ROUTE_NONE, CONV_ROUTE_TAP1, CONV_ROUTE_TAP2, CONV_ROUTE_THIN, CONV_ROUTE_TAP3, CONV_ROUTE_GC, CONV_ROUTE_TAP4 = 0, 1, 2, 3, 4, 5, 6
 CONV_ROUTES_WITH_FM_EPILOGUE = (CONV_ROUTE_THIN, CONV_ROUTE_TAP3)   # the input gradients eben_conv1d_bwd_dx_fm accepts
-
-# Arithmetic of the BACKWARD contractions (input and weight gradients) of `conv_layer`; the forward is always exact fp32.
-# Read when the forward runs (the backward image of the weights is packed then).
-_backward_math = [MATH_F32]
-
-
-class backward_math:
-    """with ops.backward_math(ops.MATH_BF16): forwards run inside record bf16 backward contractions."""
-
-    def __init__(self, math: int):
-        self.math = math
-
-    def __enter__(self):
-        self.prev = _backward_math[0]
-        _backward_math[0] = self.math
-
-    def __exit__(self, *exc):
-        _backward_math[0] = self.prev
 
 
 def conv_desc(spec: ConvSpec, batch: int, l_in: int, math: int = MATH_F32) -> EbenConv1dDesc:
@@ -532,7 +590,7 @@ def pack_weights(spec: ConvSpec, d: EbenConv1dDesc, v: torch.Tensor, g: Optional
     lib = load()
     d_bwd = d if d_bwd is None else d_bwd
     pw = cache if cache is not None else PackedWeights()
-    if _side["prepacked"] is not None and torch.cuda.current_stream() != _side["stream"]:
+    if _prepacked is not None and torch.cuda.current_stream() != _sides.stream:
         join_prepack()   # images built ahead of time on the side stream: first consumer waits for them
     need_bwd = need_bwd or cache is not None  # a module-level cache serves every later pass
     pw.params = (v, g)
@@ -576,11 +634,17 @@ def graphs_pending() -> int:
     measurement waits until this is 0)."""
     if capture_gate.settled and capture_gate.active():
         return 0   # multi-rank: the gate has closed for good, whatever still runs eagerly stays eager
-    n = 0
-    for r in list(_replayed):
-        if type(r).enabled and r.sig is not None and r.graph is None and not ReplayedPrepack._multi_rank():
-            n += 1
-    return n
+    if eager_multi_rank():
+        return 0
+    return sum(1 for r in list(_replayed) if type(r).enabled and r.sig is not None and r.graph is None)
+
+
+def eager_multi_rank() -> bool:
+    """True when a multi-rank run asked for eager launches (``EBEN_DDP_GRAPHS=0``, see ``DDP_GRAPHS``)."""
+    if DDP_GRAPHS:
+        return False
+    d = torch.distributed
+    return d.is_available() and d.is_initialized() and d.get_world_size() > 1
 
 
 #: Multi-rank runs replay the collective-free launch sequences as graphs like a single-GPU run does (every graph holds the launches of ONE
@@ -700,6 +764,27 @@ def _no_gc():
             gc.enable()
 
 
+# Does ``seq`` capture in this round?  Single rank: once it is at its threshold.  Multi-rank, the gate hears of every eager round: below
+# the threshold the rank is busy, at it the sequence asks (and is held until every rank may capture).
+def _capture_due(seq, what: str, at_threshold: bool) -> bool:
+    if not capture_gate.active():
+        return at_threshold
+    if not at_threshold:
+        capture_gate.counting()
+        return False
+    return capture_gate.may_capture(seq, what)
+
+
+def _try_capture(cls, what: str, fn, stream_):
+    """``cls._capture(fn, stream_)``, or None where it raised (the caller runs ``fn`` itself)."""
+    try:
+        return cls._capture(fn, stream_)
+    except Exception as exc:   # capture is an optimisation: fall back to eager launches for good
+        warnings.warn(f"{what} graph capture failed ({exc!r}): staying with eager launches")
+        cls.enabled = False
+        return None
+
+
 class ReplayedPrepack:
     """Graph replay of a prepack sequence.  Rebuilding the packed weight images after an optimiser step is ~150 tiny launches per
     step (one or two per layer and direction) whose cost is entirely host-side: ~3 ms of Python / launch time per step during which
@@ -718,14 +803,6 @@ class ReplayedPrepack:
         _replayed.add(self)
 
     @staticmethod
-    def _multi_rank() -> bool:
-        """True when a multi-rank run asked for eager launches (``EBEN_DDP_GRAPHS=0``, see ``DDP_GRAPHS``)."""
-        if DDP_GRAPHS:
-            return False
-        d = torch.distributed
-        return d.is_available() and d.is_initialized() and d.get_world_size() > 1
-
-    @staticmethod
     def _capture(body, stream_):
         """``body()`` recorded into a HIP graph on ``stream_`` (tests substitute a recorder)."""
         graph = torch.cuda.CUDAGraph()
@@ -736,7 +813,7 @@ class ReplayedPrepack:
     def run(self, sig, body, stream_) -> bool:
         """Runs (or replays) ``body`` on ``stream_`` (a torch side stream, current on entry); True when it was a replay, in which
         case the caller refreshes its own cache keys (the body's bookkeeping did not run)."""
-        if not self.enabled or self._multi_rank():
+        if not self.enabled or eager_multi_rank():
             body()
             return False
         if sig != self.sig:
@@ -745,22 +822,8 @@ class ReplayedPrepack:
         if self.graph is not None:
             self.graph.replay()
             return True
-        gated = capture_gate.active()
-        if self.rounds < 3:
-            if gated:
-                capture_gate.counting()
-            body()
-            return False
-        if gated and not capture_gate.may_capture(self, "prepack"):
-            body()
-            return False
-        try:
-            graph = self._capture(body, stream_)
-        except Exception as exc:   # capture is an optimisation: fall back to eager launches for good
-            import warnings
-
-            warnings.warn(f"prepack graph capture failed ({exc!r}): staying with eager launches")
-            ReplayedPrepack.enabled = False
+        graph = _try_capture(ReplayedPrepack, "prepack", body, stream_) if _capture_due(self, "prepack", self.rounds >= 3) else None
+        if graph is None:
             body()
             return False
         self.graph = graph
@@ -805,7 +868,7 @@ class ReplayedChain:
         return graph, out
 
     def run(self, sig, fn, stream_):
-        if not self.enabled or ReplayedPrepack._multi_rank() or _timers_enabled():
+        if not self.enabled or eager_multi_rank() or _timers_enabled():
             return fn()
         hit = self._cache.pop(sig, None)
         if hit is not None:
@@ -820,22 +883,14 @@ class ReplayedChain:
         self._seen[sig] = self.rounds
         while len(self._seen) > 4 * max(1, self.KEEP):   # bounded: forget the oldest signatures' counts
             self._seen.pop(next(iter(self._seen)))
-        gated = capture_gate.active()
-        if self.rounds < 2:
-            if gated:
-                capture_gate.counting()
+        if not _capture_due(self, "chain", self.rounds >= 2):
+            if self.rounds >= 2:
+                self._seen[sig] = self.rounds = 1   # held at the threshold: the next sighting asks again
             return fn()
-        if gated and not capture_gate.may_capture(self, "chain"):
-            self._seen[sig] = self.rounds = 1   # held at the threshold: the next sighting asks again
+        captured = _try_capture(ReplayedChain, "chain", fn, stream_)
+        if captured is None:
             return fn()
-        try:
-            graph, out = self._capture(fn, stream_)
-        except Exception as exc:   # capture is an optimisation: fall back to eager launches for good
-            import warnings
-
-            warnings.warn(f"chain graph capture failed ({exc!r}): staying with eager launches")
-            ReplayedChain.enabled = False
-            return fn()
+        graph, out = captured
         ReplayedChain._generation[0] += 1
         self.graph, self.out, self.captures = graph, out, ReplayedChain._generation[0]
         self._cache[sig] = (graph, out, self.captures)
@@ -858,6 +913,7 @@ def prepack(entries, graph: ReplayedPrepack, join: bool = True):
     occupies (conv images as one ``eben_conv1d_pack_multi``, fused-unit images as one ``eben_ru_pack_multi``), replayed by ``graph``
     once the sequence has settled.  Returns the event recorded behind it; ``join``: ``join_prepack`` waits for it (else the caller's
     streams do)."""
+    global _prepacked
     entries = [(c, rebuild) for c, rebuild in entries if c.images or c.scale is not None]
     if not entries:
         return None
@@ -908,15 +964,18 @@ def prepack(entries, graph: ReplayedPrepack, join: bool = True):
         ev = torch.cuda.Event()
         ev.record()
     if join:
-        _side["prepacked"] = ev
+        _prepacked = ev
     return ev
+
+
+_prepacked: Optional["torch.cuda.Event"] = None   # behind the latest ``prepack(join=True)`` until a consumer has waited for it
 
 
 def join_prepack() -> None:
     """The current stream waits for the images `prepack` built (an event: later side-stream work is not waited for)."""
-    ev = _side.get("prepacked")
-    if ev is not None:
-        _side["prepacked"] = None
+    global _prepacked
+    if _prepacked is not None:
+        ev, _prepacked = _prepacked, None
         torch.cuda.current_stream().wait_event(ev)
 
 
@@ -970,26 +1029,6 @@ def weight_grads(d: EbenConv1dDesc, dy: torch.Tensor, y: Optional[torch.Tensor],
     return _wg_finish(use_side, (dy, x, y, norm, slabs) + (premask or ()), [(job, (v, g, bias), sunk)])[0]
 
 
-_wn_collect = [None, None]   # inside collect_wn_jobs(): the list the immediate path appends its slab-sum / weight-norm jobs to, the sink
-
-
-class collect_wn_jobs:
-    """Inside this context the immediate path of ``weight_grads`` / ``weight_grads_ru`` (no side-stream deferral: the caller has made
-    the stream the work belongs on current) launches the weight-gradient kernels only and appends the slab-sum + weight-norm job of
-    each layer to ``jobs``: the caller runs them as ONE ``wn_bwd_multi(jobs)`` (gen_engine's graph-captured weight-gradient body)."""
-
-    def __init__(self, jobs: list, sink=None):
-        self.jobs, self.sink = jobs, sink   # sink: results go straight into its gradient buffers (``grad_buffer(param)``)
-
-    def __enter__(self):
-        self.prev = (_wn_collect[0], _wn_collect[1], _side["enabled"])
-        _wn_collect[0], _wn_collect[1], _side["enabled"] = self.jobs, self.sink, False
-        return self
-
-    def __exit__(self, *exc):
-        _wn_collect[0], _wn_collect[1], _side["enabled"] = self.prev
-
-
 def grad_outputs(v, g, bias, sink=None, whole_layer: bool = False):
     """Where a layer's three weight gradients are written: ((dv, dg, dbias), sunk).  With a data-parallel ``sink`` (``ddp.GradSync``)
     p.grad is a view of a gradient bucket and the results go there directly, a parameter the sink holds no buffer for gets a fresh
@@ -1021,14 +1060,23 @@ def add_logits_branches(params, gf, gr, sink=None):
 
 def _wg_route(v, g, bias):
     """Where a layer's weight gradients go: (issue on the side stream?, the outputs, are they bucket views of a data-parallel sink?)."""
-    is_param = isinstance(v, torch.nn.Parameter)
-    use_side = (_side["enabled"] and is_param and v.grad is None and (g is None or g.grad is None) and (bias is None or bias.grad is None)
-                and _no_grad_hooks(v) and _no_grad_hooks(g) and _no_grad_hooks(bias))
-    sk = _side["sink"] if _side["enabled"] and not use_side else (_wn_collect[1] if _wn_collect[0] is not None else None)
-    outs, sunk = grad_outputs(v, g, bias, sk, whole_layer=True)
-    if sk is not None:
-        use_side = sunk and _wn_collect[0] is None   # collecting: the caller has made the producing stream current
+    # The one place that turns (backward mode, parameter state) into a route.  A side scope defers a layer that may bypass autograd;
+    # one that may not (data-parallel: every ``.grad`` is a bucket view) is deferred all the same where the sink takes all its results.
+    side = _mode.route == ROUTE_SIDE
+    use_side = side and isinstance(v, torch.nn.Parameter) and bypasses_autograd((v, g, bias), None)
+    sink = None if use_side else _mode.sink
+    outs, sunk = grad_outputs(v, g, bias, sink, whole_layer=True)
+    if sink is not None:
+        use_side = sunk and side   # collecting: the caller has made the producing stream current
     return use_side, outs, sunk
+
+
+def bypasses_autograd(params, sink) -> bool:
+    """May the gradients of ``params`` (None allowed) reach them behind autograd's back: each has a bucket view in ``sink``; without
+    one, none holds a gradient that autograd would add to, or a hook that it would fire."""
+    if sink is not None:
+        return all(p is None or sink.grad_buffer(p) is not None for p in params)
+    return all(p is None or (p.grad is None and _no_grad_hooks(p)) for p in params)
 
 
 def _wg_stream(use_side: bool, device) -> int:
@@ -1046,16 +1094,13 @@ def _wg_finish(use_side: bool, keep: tuple, layers) -> list:
     launch reads), collected by ``collect_wn_jobs``, or run here.  Returns (dv, dg, dbias) per layer, Nones where deferred."""
     jobs = [job for job, _, _ in layers]
     if use_side:
-        _side["keep"].append(keep)
-        _side["wn_jobs"].extend(jobs)
+        _pending.defer(keep, jobs)
         for job, params, sunk in layers:
-            if sunk:
-                _side["sunk"].extend(p for p in params if p is not None)
-            else:
-                _side["assign"].extend((p, t) for p, t in zip(params, (job.dv, job.dg, job.dbias)) if p is not None and t is not None)
+            pairs = [(p, t) for p, t in zip(params, (job.dv, job.dg, job.dbias)) if p is not None and t is not None]
+            _pending.hand_over(pairs, _mode.sink if sunk else None)
         return [(None, None, None)] * len(layers)
-    if _wn_collect[0] is not None:
-        _wn_collect[0].extend(jobs)
+    if _mode.route == ROUTE_COLLECT:
+        _mode.jobs.extend(jobs)
     else:
         wn_bwd_multi(jobs)
     return [(job.dv, job.dg, job.dbias) for job in jobs]
@@ -1107,7 +1152,7 @@ class _ConvLayerFn(torch.autograd.Function):
         if c != spec.c_in:
             raise _lib.EbenError(f"conv expects {spec.c_in} input channels, got {c}")
         d = conv_desc(spec, b, l_in)
-        d_bwd = conv_desc(spec, b, l_in, _backward_math[0]) if _backward_math[0] != MATH_F32 else d
+        d_bwd = conv_desc(spec, b, l_in, _mode.math) if _mode.math != MATH_F32 else d
         need_dx = ctx.needs_input_grad[0]
         pw = pack_weights(spec, d, v.detach(), None if g is None else g.detach(), cache, need_dx, d_bwd)
         y = torch.empty((b, spec.c_out, d.l_out), dtype=torch.float32, device=x.device)
@@ -1134,14 +1179,14 @@ class _ConvLayerFn(torch.autograd.Function):
         dy = dy.contiguous()
         st = stream()
         dx = dv = dg = dbias = None
-        if ctx.needs_input_grad[0] and not _skip_input_grads[0]:
+        if ctx.needs_input_grad[0] and not _mode.skip_input_grads:
             ws_bytes = lib.eben_conv1d_bwd_dx_workspace(ctypes.byref(d))
             ws = _empty(ws_bytes, x) if ws_bytes else None
             dx = torch.empty_like(x)
             check(lib.eben_conv1d_bwd_dx(ctypes.byref(d), ptr(dy), ptr(y), ptr(ctx.wp_bwd), ptr(x), ptr(dx), 0, ptr(ws), ws_bytes, st),
                   "conv1d_bwd_dx")
         want_w = ctx.needs_input_grad[1] or (ctx.has_g and ctx.needs_input_grad[2]) or (ctx.has_bias and ctx.needs_input_grad[3])
-        if want_w and not _skip_weight_grads[0]:
+        if want_w and not _mode.skip_weight_grads:
             dv, dg, dbias = weight_grads(d, dy, y, x, ctx.v_param if ctx.v_param is not None else v,
                                          (ctx.g_param if ctx.g_param is not None else g) if ctx.has_g else None,
                                          ctx.bias_param if ctx.has_bias else None, ctx.norm)
