@@ -93,7 +93,8 @@ def test_bucketed_gradient_allreduce_two_ranks():
 
 
 def _engine_sequence_worker(rank, world, port, q):
-    """The data-parallel call sequence of the engine train step (lightning_modules/eben.py::_training_step_engine) on CPU
+    """The data-parallel call sequence of the engine train step (lightning_modules/eben.py: ``_training_step_engine``, whose phases ``_engine_generator_update`` /
+    ``_engine_discriminator_update`` hand ``_grad_sink(optimizer)`` to the backward and end in ``_finish(optimizer)``) on CPU
     tensors: TWO GradSyncs; the generator's gradients partly through autograd's hooks and partly through the sink
     (grad_buffer + mark_ready at the side-stream join); the discriminator's written into the bucket views chain by chain,
     the LAST chain first (disc_engine.backward_finish), each chain reported by its own mark_ready; finish() + the

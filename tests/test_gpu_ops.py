@@ -1005,14 +1005,11 @@ def test_last_conv_gradient_norms_in_one_pass(hip, batch, length, n):
 
 @pytest.mark.parametrize("mode,first", [("ema", True), ("ema", False), ("simple", False)])
 def test_fused_balancing_matches_the_torch_arithmetic_bit_for_bit(hip, mode, first):
-    """eben_balance + eben_weighted_sum == the one-element torch kernels of EBENLightningModule._update_lambdas and the weighted seed
-    (eben.py:229-240): EMA with the first-call quirk, clamp(1 / (ema + 1e-4), 0, 1e4), sum loss_i lambda_i, sum s_i lambda_i."""
-    import ctypes
+    """``LossBalancer.balance``'s two routes: eben_balance + eben_weighted_sum == the one-element torch kernels of the reference's formula
+    (eben.py:229-240; pinned to the reference's recorded lambdas by tests/test_balancing.py) and of the weighted seed: EMA with the
+    first-call quirk, clamp(1 / (ema + 1e-4), 0, 1e4), sum loss_i lambda_i, sum s_i lambda_i."""
+    from vibravox_amd.balancing import LossBalancer
 
-    from vibravox_amd import ops
-    from vibravox_amd._lib import check, load, ptr, stream
-
-    lib = load()
     dev = torch.device("cuda")
     n, beta = 3, 0.9
     norms = [formula_tensor(f"bal/n/{mode}/{i}", (1,), 1.0).abs().reshape(()).to(dev) * (10.0 ** (i - 1)) + 1e-3 for i in range(n)]
@@ -1020,26 +1017,18 @@ def test_fused_balancing_matches_the_torch_arithmetic_bit_for_bit(hip, mode, fir
     losses = [formula_tensor(f"bal/l/{mode}/{i}", (1,), 1.0).reshape(()).to(dev) for i in range(n)]
     old0 = [formula_tensor(f"bal/o/{mode}/{i}", (1,), 1.0).abs().reshape(()).to(dev) + 0.5 for i in range(n)]
     seeds = [formula_tensor(f"bal/s/{mode}/{i}", (2, 4, 1003)).to(dev) for i in range(n)]
-    # torch, as _update_lambdas writes it
-    old = list(norms) if (first or mode == "simple") else list(old0)
-    if mode == "ema":
-        old = [beta * o + (1 - beta) * nv for o, nv in zip(old, norms)]
-    lam = [torch.clamp(1 / (o + 1e-4), min=0.0, max=1e4) for o in old]
-    bp = sum(l * w for l, w in zip(losses, lam))
-    seed = None
-    for s_, w in zip(seeds, lam):
-        seed = s_ * w if seed is None else seed + s_ * w
-    # fused
-    state = torch.stack(old0).contiguous()
-    out = torch.empty(n + 1, dtype=torch.float32, device=dev)
-    check(lib.eben_balance((ctypes.c_void_p * n)(*[ptr(t) for t in norms]), (ctypes.c_void_p * n)(*[ptr(t) for t in losses]), n, ptr(state),
-                           1 if (first or mode == "simple") else 0, 1 if mode == "ema" else 0, beta, 1 - beta, ptr(out), ptr(out[n:]), stream()),
-          "balance")
-    got_seed = ops.weighted_sum(seeds, out[:n])
+    balancers = {fused: LossBalancer() for fused in (False, True)}
+    results = {}
+    for fused, balancer in balancers.items():
+        if not first:
+            balancer.old = [t.clone() for t in old0]
+        results[fused] = balancer.balance(norms, losses, seeds, mode=mode, beta=beta, fused=fused)
     torch.cuda.synchronize()
-    assert torch.equal(state, torch.stack(old))
-    assert torch.equal(out[:n], torch.stack(lam))
-    assert torch.equal(out[n], bp)
+    assert balancers[True]._buf is not None and balancers[False]._buf is None   # the launches on one side, torch on the other
+    (lam, bp, seed), (got_lam, got_bp, got_seed) = results[False], results[True]
+    assert torch.equal(torch.stack(balancers[True].old), torch.stack(balancers[False].old))
+    assert torch.equal(torch.stack(got_lam), torch.stack(lam))
+    assert torch.equal(got_bp, bp)
     assert torch.equal(got_seed, seed)
 
 

@@ -171,6 +171,37 @@ def test_bundle_layout_plan_in_the_other_configurations(hip, golden, vgolden, na
 
 
 @pytest.mark.gpu
+def test_balancing_state_is_one_across_routes_paths_and_an_outside_write(hip, golden):
+    """One "ema" module, plan "f32", four steps: the shipped engine step (balancing as two launches); the same after
+    ``atomic_norms_old`` was assigned doubled clones; the engine step with ``fused_balancing`` off (one-element torch kernels); the
+    autograd step (``use_disc_engine`` off).  After each, ``last_lambdas`` EQUALS the reference's formula (eben.py:229-237) applied on
+    the device, with the same one-element torch operations, to ``last_norms`` and the state this test carries along: every route reads
+    and leaves the one state.  Equality, not a tolerance: test_gpu_ops.test_fused_balancing_matches_the_torch_arithmetic_bit_for_bit."""
+    beta = 0.9
+    mod, _, dev = _make_module(golden, {})
+    mod.disc_math = "f32"
+    assert mod.dynamic_loss_balancing == "ema" and mod.beta_ema == beta and mod.fused_balancing and mod.use_disc_engine
+    torch.manual_seed(3)
+    state = None
+    for i, (bc, air) in enumerate(variant_batches("ratio05", 2) + variant_batches("l1time", 2)):
+        if i == 1:
+            state = [t.clone() * 2 for t in state]
+            mod.atomic_norms_old = [t.clone() for t in state]
+        mod.fused_balancing = i != 2
+        mod.use_disc_engine = i != 3
+        mod.training_step({"audio_body_conducted": bc.to(dev), "audio_airborne": air.to(dev)})
+        norms = [t.detach().clone() for t in mod.last_norms]
+        assert len(norms) == 2 and all(t.is_cuda for t in norms)
+        if state is None:
+            state = norms
+        state = [beta * old + (1 - beta) * new for old, new in zip(state, norms)]
+        expected = torch.stack([torch.clamp(1 / (old + 1e-4), min=0.0, max=1e4) for old in state])
+        assert torch.equal(torch.stack(mod.last_lambdas), expected), (i, torch.stack(mod.last_lambdas), expected)
+        assert torch.equal(torch.stack([torch.as_tensor(t) for t in mod.atomic_norms_old]), torch.stack(state)), i
+    assert mod._disc_engine is not None
+
+
+@pytest.mark.gpu
 def test_grouped_weight_gradients_equal_chain_by_chain(hip, golden):
     """The three PQMF-band chains' weight gradients as one launch sequence (EBEN_DW_GROUP, ``_ChainBL.weight_grads_group``) and the
     two-pass stacked backward (EBEN_SPLIT_BWD) against chain by chain / one 4B-row pass: the discriminator after one step is bit-identical

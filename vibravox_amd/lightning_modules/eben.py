@@ -31,6 +31,7 @@ from typing import Dict, Optional
 import torch
 
 from .. import ops
+from ..balancing import LossBalancer
 from .base_se import BaseSELightningModule
 
 
@@ -82,6 +83,45 @@ _DISCRIMINATOR_TERMS = (("real_loss", "reference", 1), ("fake_loss", "enhanced",
 class EBENLightningModule(BaseSELightningModule):
     exploit_step_redundancy: bool = True
 
+    # -- the step's knobs: class defaults read from the environment once, each one assignable on an instance ----------------
+    #: run the discriminator passes batched and outside autograd (vibravox_amd/disc_engine.py)
+    use_disc_engine: bool = os.environ.get("EBEN_DISC_ENGINE", "1") != "0"
+    #: arithmetic of the discriminator contractions inside the engine: a key of DISC_MATH_PLANS -- "f32" (bit-exact fp32
+    #: products), "bf16" (bf16 MFMA operands, fp32 accumulate, activation operand split -- BASELINE config 2), "bf16_plain" --
+    #: or a plan the engine understands.  The generator's forward computes in fp32-grade split-bf16 products (gen_engine.RU_FWD_MATH /
+    #: CONV_FWD_MATH = EBEN_MATH_BF16X6: every mantissa bit of both fp32 operands, fp32 accumulation) -- except INSIDE the engine
+    #: train step of the bf16-mixed plan (gen_backward_math "bf16" and ``ru_forward_x3``), whose forward takes hi + lo operands
+    #: (EBEN_MATH_BF16X3, ~2^-17 per product); validation / prediction forwards are fp32-grade in every plan.
+    disc_math: str = os.environ.get("EBEN_DISC_MATH", "f32")
+    #: arithmetic of the generator's BACKWARD contractions (input / weight gradients) in the engine step; "bf16" also moves the step's
+    #: forward to hi + lo operands (see ``ru_forward_x3``; "f32": six-piece bf16 products, <= 2^-26 dropped per product: within 2x of
+    #: the fp32 MFMA kernels' own error against fp64, tests/test_gpu_ops.py; EBEN_RU_FWD_MATH=f32 selects those kernels)
+    gen_backward_math: str = os.environ.get("EBEN_GEN_BWD_MATH", "f32")
+    #: arithmetic of the MRSTFT loss's windowed-DFT contractions in the engine step (mrstft_loss.MultiResolutionSTFTLoss.stft_math):
+    #: None leaves the loss module's own setting (exact fp32, folded); "bf16x3" goes with the bf16 step of BASELINE config 2
+    stft_math: Optional[str] = os.environ.get("EBEN_STEP_STFT_MATH") or None
+    #: run the discriminators on the reference half of the batch underneath the generator forward (it does not depend on the generator).
+    #: Round 1 (fp32 discriminators): neutral, 25.8 vs 25.8 ms/step.  Round 4 (bundle-layout plan, generator forward a chain of latency-bound
+    #: launches): [MI355X, same box, interleaved] 10.25 -> 10.05 ms/step -- the generator forward phase lengthens by 0.7 ms (1.47 -> 2.19: its
+    #: launches share the CUs), the discriminator forward phase shortens by 0.8 (2.26 -> 1.49).  On by default.
+    split_discriminator_forward: bool = os.environ.get("EBEN_SPLIT_D_FWD", "1") != "0"
+    _split_forward_forced: bool = os.environ.get("EBEN_SPLIT_D_FWD") == "1"
+    #: bf16-mixed plan: ResidualUnit forwards with three piece products (EBEN_MATH_BF16X3) instead of six; EBEN_RU_FWD_X3=0 keeps six
+    ru_forward_x3: bool = (os.environ.get("EBEN_RU_FWD_X3", "1") != "0" and not os.environ.get("EBEN_RU_FWD_MATH")
+                           and not os.environ.get("EBEN_GEN_CONV_FWD_MATH"))
+    #: rebuild the packed weight images right after each optimiser step, on the side stream (off the critical path)
+    prepack_weights: bool = os.environ.get("EBEN_PREPACK", "1") != "0"
+    #: the engine step's balancing arithmetic (EMA, lambdas, backprop loss, weighted seed) as two launches (`eben_balance`,
+    #: `eben_weighted_sum`) instead of ~35 one-element torch kernels in front of the generator backward; same values bit for bit
+    fused_balancing: bool = os.environ.get("EBEN_FUSED_BALANCING", "1") != "0"
+    #: the balancing norms ||dL_i / d last_conv.weight|| of the engine step from the seeds in one pass (`eben_last_conv_norms`) instead of
+    #: a tanh-backward + weight-gradient + norm chain per loss through autograd; same values up to the order of the fp32 sums
+    fused_norms: bool = os.environ.get("EBEN_FUSED_NORMS", "1") != "0"
+    #: tools/phase_times.py: list that receives (label, event) pairs recorded on the main stream between the phases
+    phase_events = None
+    #: tools/host_times.py: list that receives (label, time.perf_counter()) at the same points -- where the HOST spends the step
+    phase_host = None
+
     def __init__(
         self,
         sample_rate: int,
@@ -110,23 +150,36 @@ class EBENLightningModule(BaseSELightningModule):
         self.adversarial_loss_fn = adversarial_loss_fn
         assert dynamic_loss_balancing in {None, "simple", "ema"}, "dynamic_loss_balancing must be in {None, 'simple', 'ema'}"
         self.dynamic_loss_balancing = dynamic_loss_balancing
-        self.atomic_norms_old = None
         self.beta_ema = beta_ema
         assert 0 <= update_discriminator_ratio <= 1, "update_discriminator_ratio must be in [0, 1]"
         self.update_discriminator_ratio = update_discriminator_ratio
         self.push_to_hub_after_testing = push_to_hub_after_testing
         self.automatic_optimization = False
-        self.last_lambdas = None
-        self.last_norms = None
+        self.balancer = LossBalancer()   # the EMA of the balancing norms, last_norms / last_lambdas (the properties below)
+        self._disc_engine = None         # the engine step's DiscriminatorEngine, built at the first step that takes it
+        self._hip_conv_cache = (None, [])
+        self._loss_stft_math0 = getattr(reconstructive_loss_freq_fn, "stft_math", None)   # the loss module's own arithmetic
         self._prepack_graph = ops.ReplayedPrepack()   # the generator's image rebuild (ops.prepack) as a replayed graph
+
+    #: the balancing state under the reference's name (eben.py:77): one 0-dim tensor per loss, None before the first step; assignable
+    atomic_norms_old = property(lambda self: self.balancer.old, lambda self, value: setattr(self.balancer, "old", value))
+    #: the norms of the last balancing call and the loss weights it returned
+    last_norms = property(lambda self: self.balancer.last_norms)
+    last_lambdas = property(lambda self: self.balancer.last_lambdas)
 
     def configure_optimizers(self):
         return [self.generator_optimizer, self.discriminator_optimizer]
 
     # -- data-parallel hook points (no-ops on one GPU) --------------------------------------
-    def _sync_grads(self, optimizer) -> float:
-        sync = getattr(self, "grad_sync", {}).get(id(optimizer)) if hasattr(self, "grad_sync") else None
-        return sync.finish() if sync is not None else 1.0
+    def _grad_sink(self, optimizer):
+        """The optimizer's gradient exchange (``ddp.GradSync``) or None; ``grad_sync`` is absent under a real Lightning base."""
+        return (getattr(self, "grad_sync", None) or {}).get(id(optimizer))
+
+    def _finish(self, optimizer) -> None:
+        """The end of a network's phase: the ranks' gradients summed, one optimiser step, gradients cleared."""
+        sync = self._grad_sink(optimizer)
+        self._step(optimizer, sync.finish() if sync is not None else 1.0)
+        optimizer.zero_grad()
 
     def _step(self, optimizer, grad_scale: float):
         """optimizer.step() on gradient SUMS over ranks: ``grad_scale`` (1 / world size) is folded into the Adam kernel where
@@ -147,29 +200,9 @@ class EBENLightningModule(BaseSELightningModule):
         else:
             step = self._training_step_literal
         out = step(batch)
-        flush = getattr(self, "flush_logged", None)   # Lightning-free stand-in: the step's sync_dist values as one collective
-        if flush is not None:
-            flush()
+        getattr(self, "flush_logged", lambda: None)()   # Lightning-free stand-in: the step's sync_dist values as one collective
         ops.capture_gate.step_end()   # multi-rank: the ranks' vote on graph captures in the next step (a no-op on one rank / once settled)
         return out
-
-    #: run the discriminator passes batched and outside autograd (vibravox_amd/disc_engine.py)
-    use_disc_engine: bool = os.environ.get("EBEN_DISC_ENGINE", "1") != "0"
-    #: arithmetic of the discriminator contractions inside the engine: a key of DISC_MATH_PLANS -- "f32" (bit-exact fp32
-    #: products), "bf16" (bf16 MFMA operands, fp32 accumulate, activation operand split -- BASELINE config 2), "bf16_plain" --
-    #: or a plan the engine understands.  The generator's forward computes in fp32-grade split-bf16 products (gen_engine.RU_FWD_MATH /
-    #: CONV_FWD_MATH = EBEN_MATH_BF16X6: every mantissa bit of both fp32 operands, fp32 accumulation) -- except INSIDE the engine
-    #: train step of the bf16-mixed plan (gen_backward_math "bf16" and ``ru_forward_x3``), whose forward takes hi + lo operands
-    #: (EBEN_MATH_BF16X3, ~2^-17 per product); validation / prediction forwards are fp32-grade in every plan.
-    disc_math: str = os.environ.get("EBEN_DISC_MATH", "f32")
-    #: arithmetic of the generator's BACKWARD contractions (input / weight gradients) in the engine step; "bf16" also moves the step's
-    #: forward to hi + lo operands (see ``ru_forward_x3``; "f32": six-piece bf16 products, <= 2^-26 dropped per product: within 2x of
-    #: the fp32 MFMA kernels' own error against fp64, tests/test_gpu_ops.py; EBEN_RU_FWD_MATH=f32 selects those kernels)
-    gen_backward_math: str = os.environ.get("EBEN_GEN_BWD_MATH", "f32")
-
-    #: arithmetic of the MRSTFT loss's windowed-DFT contractions in the engine step (mrstft_loss.MultiResolutionSTFTLoss.stft_math):
-    #: None leaves the loss module's own setting (exact fp32, folded); "bf16x3" goes with the bf16 step of BASELINE config 2
-    stft_math: Optional[str] = os.environ.get("EBEN_STEP_STFT_MATH") or None
 
     #: ``trainer.precision`` (vibravox configs/trainer/ddp.yaml:23-25, Lightning's names) -> (disc_math, gen_backward_math, stft_math).
     #: "32-true" is the reference's arithmetic (exact fp32 products), "bf16-mixed" the plan BASELINE config 2 names and bench.py
@@ -199,12 +232,8 @@ class EBENLightningModule(BaseSELightningModule):
         self.disc_math, self.gen_backward_math, stft = self.PRECISION_PLANS[key]
         # "32-true": the loss module's OWN arithmetic again (the step writes stft_math into the module when it is not None: a module that
         # ran a bf16-mixed step must not keep folded_x3 while the step reports the reference's exact fp32)
-        loss = getattr(self, "reconstructive_loss_freq_fn", None)
-        if loss is not None and hasattr(loss, "stft_math"):
-            if not hasattr(self, "_loss_stft_math0"):
-                self._loss_stft_math0 = loss.stft_math
-            if stft is None:
-                loss.stft_math = self._loss_stft_math0
+        if stft is None and hasattr(self.reconstructive_loss_freq_fn, "stft_math"):
+            self.reconstructive_loss_freq_fn.stft_math = self._loss_stft_math0
         self.stft_math = stft
         self.precision = key
         return self
@@ -218,12 +247,6 @@ class EBENLightningModule(BaseSELightningModule):
                 and type(self.feature_matching_loss_fn) is FeatureLossForDiscriminatorMelganMultiScales
                 and type(self.adversarial_loss_fn) is HingeLossForDiscriminatorMelganMultiScales)
 
-    #: tools/phase_times.py: list that receives (label, event) pairs recorded on the main stream between the phases
-    phase_events = None
-
-    #: tools/host_times.py: list that receives (label, time.perf_counter()) at the same points -- where the HOST spends the step
-    phase_host = None
-
     def _mark(self, label: str) -> None:
         if self.phase_host is not None:
             import time
@@ -233,34 +256,60 @@ class EBENLightningModule(BaseSELightningModule):
             ev.record()
             self.phase_events.append((label, ev))
 
+    # -- what the three step paths share ------------------------------------------------------
+    def _cut(self, batch: Dict[str, torch.Tensor]):
+        """The step's two signals at a length the generator takes: (corrupted, reference)."""
+        cut = self.generator.cut_to_valid_length
+        return cut(batch["audio_body_conducted"]), cut(batch["audio_airborne"])
+
+    def _waveform_losses(self, enhanced_speech, reference_speech) -> Dict[str, torch.Tensor]:
+        """The generator terms that do not pass through the discriminators (the reconstructive losses), in the reference's order."""
+        fns = ((name, getattr(self, attr)) for name, attr, operands in _GENERATOR_TERMS if operands == "waveforms")
+        return {name: fn(enhanced_speech, reference_speech) for name, fn in fns if fn}
+
+    def _log_terms(self, network: str, terms: Dict[str, torch.Tensor]) -> None:
+        for name, value in terms.items():
+            self.log(f"train/{network}/{name}", value, sync_dist=True)
+
+    def _log_discriminator(self, real_loss, fake_loss):
+        """The discriminator phase's three log lines; returns its backprop loss."""
+        total = real_loss + fake_loss
+        self._log_terms("discriminator", {"real_loss": real_loss, "fake_loss": fake_loss, "backprop_loss": total})
+        return total
+
+    # -- the engine step: _training_step_fused with the discriminator side run by DiscriminatorEngine ---------------------------
     def _training_step_engine(self, batch: Dict[str, torch.Tensor]):
+        """One batch-2B discriminator forward for both branches and one stacked backward for the four gradient signals (feature matching,
+        adversarial, fake, real): ``_training_step_fused``'s logged values and parameter updates (weight-gradient sums in another fp32 order)."""
+        from .. import gen_engine
+        from ..disc_engine import DiscriminatorEngine
         # bf16-mixed: the generator forward on hi + lo operands (three piece products, 2^-17 each) instead of the fp32-grade six -- the
         # output stays orders of magnitude inside north_star's 1e-5 MSE (tests: < 1e-8 against the oracle at config 2).  Scoped to the
         # step (its forward and the weight-image rebuilds behind the optimiser steps): evaluation forwards keep the default arithmetic.
-        from .. import gen_engine
         with gen_engine.forward_math("bf16x3" if self.gen_backward_math == "bf16" and self.ru_forward_x3 else None):
-            return self._training_step_engine_body(batch)
+            corrupted_speech, reference_speech = self._cut(batch)
+            generator_optimizer, discriminator_optimizer = self.optimizers(use_pl_optimizer=True)
+            math = DISC_MATH_PLANS[self.disc_math] if isinstance(self.disc_math, str) else self.disc_math
+            if self._disc_engine is None or self._disc_engine.disc is not self.discriminator or self._disc_engine.math != math:
+                self._disc_engine = DiscriminatorEngine(self.discriminator, math)
+            engine = self._disc_engine
+            if self.stft_math is not None and hasattr(self.reconstructive_loss_freq_fn, "stft_math"):
+                self.reconstructive_loss_freq_fn.stft_math = self.stft_math
+            enhanced_speech, bands, losses, d_losses = self._engine_losses(engine, corrupted_speech, reference_speech)
+            # the discriminator-phase draw (eben.py:118) is the only CPU RNG use of the step: taking it here
+            # leaves the sequence of draws unchanged and lets the stacked backward skip the weight gradients
+            update_discriminator = bool(torch.rand(1) < self.update_discriminator_ratio)
+            # input gradients now; the discriminator's weight gradients keep running on the engine's streams
+            # underneath the balancing passes and the (launch-bound, GPU-underfilling) generator backward
+            engine.backward_launch(want_param_grads=update_discriminator, sink=self._grad_sink(discriminator_optimizer))
+            seeds, atomic_norms = self._engine_seeds_and_norms(engine, losses, enhanced_speech, bands)
+            self._engine_generator_update(generator_optimizer, losses, seeds, atomic_norms, bands)
+            if update_discriminator:   # the gradients of real_loss + fake_loss are already there
+                self._engine_discriminator_update(engine, discriminator_optimizer, d_losses)
+            return {"corrupted": corrupted_speech, "enhanced": enhanced_speech.detach(), "reference": reference_speech}
 
-    def _training_step_engine_body(self, batch: Dict[str, torch.Tensor]):
-        """``_training_step_fused`` with the discriminator side run by ``DiscriminatorEngine``: one
-        batch-2B forward for the enhanced and reference branches and one stacked backward for the four
-        gradient signals (feature matching, adversarial, fake, real).  Same logged values, same
-        parameter updates (the weight-gradient sums are taken in a different fp32 order)."""
-        from ..disc_engine import DiscriminatorEngine, inject_grads
-
-        corrupted_speech = self.generator.cut_to_valid_length(batch["audio_body_conducted"])
-        reference_speech = self.generator.cut_to_valid_length(batch["audio_airborne"])
-        generator_optimizer, discriminator_optimizer = self.optimizers(use_pl_optimizer=True)
-        g_params = [p for p in ops.parameters_of(self.generator) if p.requires_grad]
-        math = DISC_MATH_PLANS[self.disc_math] if isinstance(self.disc_math, str) else self.disc_math
-        if getattr(self, "_disc_engine", None) is None or self._disc_engine.disc is not self.discriminator or self._disc_engine.math != math:
-            self._disc_engine = DiscriminatorEngine(self.discriminator, math)
-        engine = self._disc_engine
-
-        if self.stft_math is not None and hasattr(self.reconstructive_loss_freq_fn, "stft_math"):
-            self.reconstructive_loss_freq_fn.stft_math = self.stft_math
-
-        # ---- generator phase
+    def _engine_losses(self, engine, corrupted_speech, reference_speech):
+        """Every forward of the step and the generator's atomic losses, logged: (enhanced, bands, losses, the engine's four losses)."""
         ops.join_prepack()
         self._mark("start")
         with torch.no_grad():
@@ -277,123 +326,78 @@ class EBENLightningModule(BaseSELightningModule):
         # the four discriminator chains start on their streams; the reconstructive losses (which do not involve the
         # discriminators) run on this stream underneath them
         engine.forward(bands.detach(), enhanced_speech.detach(), bands_ref, reference_speech, join=False)
-        losses: Dict[str, torch.Tensor] = {}
-        if self.reconstructive_loss_freq_fn:
-            losses["reconstructive_loss_freq"] = self.reconstructive_loss_freq_fn(enhanced_speech, reference_speech)
-        if self.reconstructive_loss_temp_fn:
-            losses["reconstructive_loss_temp"] = self.reconstructive_loss_temp_fn(enhanced_speech, reference_speech)
+        losses = self._waveform_losses(enhanced_speech, reference_speech)
         self._mark("reconstructive losses (discriminator forward beside them)")
         engine.join()
         self._mark("discriminator forward joined")
         d_losses = engine.losses()
         self._mark("fm + hinge losses")
-        losses["feature_matching_loss"] = d_losses["feature_matching_loss"]
-        losses["adv_loss_gen"] = d_losses["adv_loss_gen"]
-        for key, value in losses.items():
-            self.log(f"train/generator/{key}", value, sync_dist=True)
+        losses.update({key: d_losses[key] for key in ("feature_matching_loss", "adv_loss_gen")})
+        self._log_terms("generator", losses)
+        return enhanced_speech, bands, losses, d_losses
 
-        # the discriminator-phase draw (eben.py:118) is the only CPU RNG use of the step: taking it here
-        # leaves the sequence of draws unchanged and lets the stacked backward skip the weight gradients
-        update_discriminator = bool(torch.rand(1) < self.update_discriminator_ratio)
-        # input gradients now; the discriminator's weight gradients keep running on the engine's streams
-        # underneath the balancing passes and the (launch-bound, GPU-underfilling) generator backward
-        syncs = getattr(self, "grad_sync", None) or {}
-        g_sink, d_sink = syncs.get(id(generator_optimizer)), syncs.get(id(discriminator_optimizer))
-        engine.backward_launch(want_param_grads=update_discriminator, sink=d_sink)
-        # balancing (eben.py:222-240) with every gradient taken at `bands`; the seeds of the losses that do not pass
-        # through the discriminators are taken while its input-gradient chains run
-        leaf = self.generator.last_conv.weight
+    def _engine_seeds_and_norms(self, engine, losses, enhanced_speech, bands):
+        """Balancing (eben.py:222-240) with every gradient taken at ``bands``: each loss's seed there and -- with balancing on -- the norm of
+        what it leaves at ``last_conv.weight``.  The seeds that do not pass through the discriminators are taken while its input-gradient chains run."""
         own = {key: torch.autograd.grad(loss, bands, retain_graph=True)[0] for key, loss in losses.items()
                if key not in ("feature_matching_loss", "adv_loss_gen")}
         self._mark("reconstructive seeds (discriminator input gradients beside them)")
         fm_b, fm_a, adv_b, adv_a = engine.backward_finish()
         self._mark("discriminator input gradients joined")
-        seeds = []
-        for key, loss in losses.items():
-            if key == "feature_matching_loss":
-                seeds.append(fm_b + torch.autograd.grad(enhanced_speech, bands, grad_outputs=fm_a, retain_graph=True)[0])
-            elif key == "adv_loss_gen":
-                seeds.append(adv_b + torch.autograd.grad(enhanced_speech, bands, grad_outputs=adv_a, retain_graph=True)[0])
-            else:
-                seeds.append(own[key])
+        through = {"feature_matching_loss": (fm_b, fm_a), "adv_loss_gen": (adv_b, adv_a)}   # d loss / d (bands, audio) from the engine
+        seeds = [own[key] if key in own else
+                 through[key][0] + torch.autograd.grad(enhanced_speech, bands, grad_outputs=through[key][1], retain_graph=True)[0] for key in losses]
+        if self.dynamic_loss_balancing is None:   # eben.py:107-108: no balancing -- no norms, every lambda is 1
+            return seeds, None
         atomic_norms = None
         pre = getattr(self.generator, "_last_pre", None)
-        if self.dynamic_loss_balancing is None:
-            pass   # eben.py:107-108: no balancing -- no norms, every lambda is 1
-        elif self.fused_norms and pre is not None and pre.shape[0] == bands.shape[0] and pre.shape[2] == bands.shape[2]:
+        if self.fused_norms and pre is not None and pre.shape[0] == bands.shape[0] and pre.shape[2] == bands.shape[2]:
             atomic_norms = ops.last_conv_grad_norms(seeds, bands, pre, self.generator.last_conv)   # one pass for the three losses
-        if atomic_norms is None and self.dynamic_loss_balancing is not None:
+        if atomic_norms is None:
+            leaf = self.generator.last_conv.weight
             with ops.input_grads_disabled():   # only last_conv's weight gradient is wanted: its input gradient would be computed and dropped
                 atomic_norms = [torch.norm(torch.autograd.grad(bands, leaf, grad_outputs=s, retain_graph=True)[0]).detach() for s in seeds]
-        if self.dynamic_loss_balancing is None:
-            backprop_loss_generator = sum(loss.detach() for loss in losses.values())
-            seed = seeds[0] if len(seeds) == 1 else ops.weighted_sum(seeds, self._unit_lambdas(len(seeds), seeds[0].device))
-        elif self.fused_balancing and len(seeds) <= 8 and atomic_norms[0].is_cuda:
-            lambdas, backprop_loss_generator = self._update_lambdas_fused(atomic_norms, [loss.detach() for loss in losses.values()])
-            seed = ops.weighted_sum(seeds, self._bal["lam"])
-        else:
-            lambdas = self._update_lambdas(atomic_norms)
-            backprop_loss_generator = sum(loss.detach() * lam for loss, lam in zip(losses.values(), lambdas))
-            seed = None
-            for s, lam in zip(seeds, lambdas):
-                seed = s * lam if seed is None else seed + s * lam
-        self.log("train/generator/backprop_loss", backprop_loss_generator, sync_dist=True)
+        return seeds, atomic_norms
+
+    def _engine_generator_update(self, optimizer, losses, seeds, atomic_norms, bands) -> None:
+        _, backprop_loss, seed = self.balance_losses(atomic_norms, [loss.detach() for loss in losses.values()], seeds)
+        self.log("train/generator/backprop_loss", backprop_loss, sync_dist=True)
         self._mark("balancing (3 seeds + norms)")
-        with ops.weight_grads_on_side_stream(sink=g_sink) as side:   # dX chain on this stream, dW work beside it
+        g_params = [p for p in ops.parameters_of(self.generator) if p.requires_grad]
+        with ops.weight_grads_on_side_stream(sink=self._grad_sink(optimizer)) as side:   # dX chain on this stream, dW work beside it
             torch.autograd.backward(bands, seed, inputs=g_params)
         self._mark("generator backward (dX chain)")
         side.join()
         self._mark("generator weight gradients joined")
-        self._step(generator_optimizer, self._sync_grads(generator_optimizer))
-        generator_optimizer.zero_grad()
+        self._finish(optimizer)
         self._mark("generator Adam")
         if self.prepack_weights:   # next step's generator images -- conv layers and fused units, one sequence -- under the discriminator phase
             g_engine = getattr(self.generator, "_engine", None)
             ops.prepack(ops.conv_images(self._hip_convs(self.generator)) + (g_engine.image_caches() if g_engine is not None else []),
                         self._prepack_graph)
 
-        # ---- discriminator phase: the gradients of real_loss + fake_loss are already there
-        if update_discriminator:
-            real_loss, fake_loss = d_losses["real_loss"], d_losses["fake_loss"]
-            self.log("train/discriminator/real_loss", real_loss, sync_dist=True)
-            self.log("train/discriminator/fake_loss", fake_loss, sync_dist=True)
-            self.log("train/discriminator/backprop_loss", real_loss + fake_loss, sync_dist=True)
-            d_grads = engine.collect_param_grads()   # None when they went straight into the data-parallel buckets
-            if d_grads is not None:
-                inject_grads(ops.parameters_of(self.discriminator), d_grads)
-            self._mark("discriminator weight gradients joined")
-            self._step(discriminator_optimizer, self._sync_grads(discriminator_optimizer))
-            discriminator_optimizer.zero_grad()
-            self._mark("discriminator Adam")
-            if self.prepack_weights:   # next step's discriminator images, under the next generator forward (the chains wait for them)
-                engine.prepack()
-        return {"corrupted": corrupted_speech, "enhanced": enhanced_speech.detach(), "reference": reference_speech}
+    def _engine_discriminator_update(self, engine, optimizer, d_losses) -> None:
+        from ..disc_engine import inject_grads
 
-    #: run the discriminators on the reference half of the batch underneath the generator forward (it does not depend on the generator).
-    #: Round 1 (fp32 discriminators): neutral, 25.8 vs 25.8 ms/step.  Round 4 (bundle-layout plan, generator forward a chain of latency-bound
-    #: launches): [MI355X, same box, interleaved] 10.25 -> 10.05 ms/step -- the generator forward phase lengthens by 0.7 ms (1.47 -> 2.19: its
-    #: launches share the CUs), the discriminator forward phase shortens by 0.8 (2.26 -> 1.49).  On by default.
-    split_discriminator_forward: bool = os.environ.get("EBEN_SPLIT_D_FWD", "1") != "0"
-    _split_forward_forced: bool = os.environ.get("EBEN_SPLIT_D_FWD") == "1"
-
-    #: bf16-mixed plan: ResidualUnit forwards with three piece products (EBEN_MATH_BF16X3) instead of six; EBEN_RU_FWD_X3=0 keeps six
-    ru_forward_x3: bool = (os.environ.get("EBEN_RU_FWD_X3", "1") != "0" and not os.environ.get("EBEN_RU_FWD_MATH")
-                           and not os.environ.get("EBEN_GEN_CONV_FWD_MATH"))
-
-    #: rebuild the packed weight images right after each optimiser step, on the side stream (off the critical path)
-    prepack_weights: bool = os.environ.get("EBEN_PREPACK", "1") != "0"
+        self._log_discriminator(d_losses["real_loss"], d_losses["fake_loss"])
+        d_grads = engine.collect_param_grads()   # None when they went straight into the data-parallel buckets
+        if d_grads is not None:
+            inject_grads(ops.parameters_of(self.discriminator), d_grads)
+        self._mark("discriminator weight gradients joined")
+        self._finish(optimizer)
+        self._mark("discriminator Adam")
+        if self.prepack_weights:   # next step's discriminator images, under the next generator forward (the chains wait for them)
+            engine.prepack()
 
     def _hip_convs(self, net):
-        cached = getattr(self, "_hip_conv_cache", None)
-        if cached is None or cached[0] is not net:
+        if self._hip_conv_cache[0] is not net:
             from ..torch_modules.utils import HipConv1d
-            cached = self._hip_conv_cache = (net, [m for m in net.modules() if isinstance(m, HipConv1d)])
-        return cached[1]
+            self._hip_conv_cache = (net, [m for m in net.modules() if isinstance(m, HipConv1d)])
+        return self._hip_conv_cache[1]
 
     def _training_step_fused(self, batch: Dict[str, torch.Tensor]):
         """Same values as ``_training_step_literal`` with 8 instead of 11 discriminator passes."""
-        corrupted_speech = self.generator.cut_to_valid_length(batch["audio_body_conducted"])
-        reference_speech = self.generator.cut_to_valid_length(batch["audio_airborne"])
+        corrupted_speech, reference_speech = self._cut(batch)
         generator_optimizer, discriminator_optimizer = self.optimizers(use_pl_optimizer=True)
         g_params = [p for p in ops.parameters_of(self.generator) if p.requires_grad]
         d_params = [p for p in ops.parameters_of(self.discriminator) if p.requires_grad]
@@ -401,55 +405,38 @@ class EBENLightningModule(BaseSELightningModule):
         # ---- generator phase: every forward of the step happens here
         enhanced_speech, bands = self.generator(corrupted_speech)
         bands_ref = self.generator.pqmf.forward(reference_speech, "analysis")
-        losses: Dict[str, torch.Tensor] = {}
-        if self.reconstructive_loss_freq_fn:
-            losses["reconstructive_loss_freq"] = self.reconstructive_loss_freq_fn(enhanced_speech, reference_speech)
-        if self.reconstructive_loss_temp_fn:
-            losses["reconstructive_loss_temp"] = self.reconstructive_loss_temp_fn(enhanced_speech, reference_speech)
+        losses = self._waveform_losses(enhanced_speech, reference_speech)
         enhanced_embeddings = self.discriminator(bands=bands, audio=enhanced_speech)
         reference_embeddings = self.discriminator(bands=bands_ref, audio=reference_speech)
         losses["feature_matching_loss"] = self.feature_matching_loss_fn(enhanced_embeddings, reference_embeddings)
         losses["adv_loss_gen"] = self.adversarial_loss_fn(embeddings=enhanced_embeddings, target=1)
-        for key, value in losses.items():
-            self.log(f"train/generator/{key}", value, sync_dist=True)
+        self._log_terms("generator", losses)
 
         # balancing (eben.py:222-240) with the gradients taken at `bands`
-        leaf = self.generator.last_conv.weight
         with ops.weight_grads_disabled():  # only d/d(bands) is wanted from these passes
             seeds = [torch.autograd.grad(loss, bands, retain_graph=True)[0] for loss in losses.values()]
-        if self.dynamic_loss_balancing is None:   # eben.py:107-108: the plain sum
-            lambdas = [1.0] * len(seeds)
-        else:
+        atomic_norms = None
+        if self.dynamic_loss_balancing is not None:   # eben.py:107-108 otherwise: the plain sum
+            leaf = self.generator.last_conv.weight
             atomic_norms = [torch.norm(torch.autograd.grad(bands, leaf, grad_outputs=s, retain_graph=True)[0]).detach() for s in seeds]
-            lambdas = self._update_lambdas(atomic_norms)
-        backprop_loss_generator = sum(loss.detach() * lam for loss, lam in zip(losses.values(), lambdas))
-        self.log("train/generator/backprop_loss", backprop_loss_generator, sync_dist=True)
-        seed = None
-        for s, lam in zip(seeds, lambdas):
-            seed = s * lam if seed is None else seed + s * lam
+        _, backprop_loss, seed = self.balance_losses(atomic_norms, [loss.detach() for loss in losses.values()], seeds)
+        self.log("train/generator/backprop_loss", backprop_loss, sync_dist=True)
         torch.autograd.backward(bands, seed, inputs=g_params, retain_graph=True)
-        self._step(generator_optimizer, self._sync_grads(generator_optimizer))
-        generator_optimizer.zero_grad()
+        self._finish(generator_optimizer)
 
         # ---- discriminator phase on the embeddings already computed (weights untouched since)
         if torch.rand(1) < self.update_discriminator_ratio:
             real_loss = self.adversarial_loss_fn(embeddings=reference_embeddings, target=1)
             fake_loss = self.adversarial_loss_fn(embeddings=enhanced_embeddings, target=-1)
-            self.log("train/discriminator/real_loss", real_loss, sync_dist=True)
-            self.log("train/discriminator/fake_loss", fake_loss, sync_dist=True)
-            backprop_loss_discriminator = real_loss + fake_loss
-            self.log("train/discriminator/backprop_loss", backprop_loss_discriminator, sync_dist=True)
-            backprop_loss_discriminator.backward(inputs=d_params)
-            self._step(discriminator_optimizer, self._sync_grads(discriminator_optimizer))
-            discriminator_optimizer.zero_grad()
+            self._log_discriminator(real_loss, fake_loss).backward(inputs=d_params)
+            self._finish(discriminator_optimizer)
         return {"corrupted": corrupted_speech, "enhanced": enhanced_speech.detach(), "reference": reference_speech}
 
     def _training_step_literal(self, batch: Dict[str, torch.Tensor]):
         """The reference's as-executed order (eben.py:82-130): each network's phase evaluates its own atomic losses from
         scratch -- 4 discriminator forwards, 3 balancing backward passes + the final one."""
         generator_optimizer, discriminator_optimizer = self.optimizers(use_pl_optimizer=True)
-        corrupted = self.generator.cut_to_valid_length(batch["audio_body_conducted"])
-        reference = self.generator.cut_to_valid_length(batch["audio_airborne"])
+        corrupted, reference = self._cut(batch)
 
         def phase(network, optimizer, signals, gate):
             # one network's turn: freeze the other one, losses -> log -> (balance) -> backward -> Adam -> unfreeze.  `gate`
@@ -457,15 +444,13 @@ class EBENLightningModule(BaseSELightningModule):
             self.toggle_optimizer(optimizer)
             terms = self.compute_atomic_losses(network, *signals)
             if gate(terms):
-                for name, value in terms.items():
-                    self.log(f"train/{network}/{name}", value, sync_dist=True)
+                self._log_terms(network, terms)
                 if network == "generator" and self.dynamic_loss_balancing is not None:
                     terms = self.dynamically_balance_losses(terms)
                 total = sum(terms.values())
                 self.log(f"train/{network}/backprop_loss", total, sync_dist=True)
                 self.manual_backward(total)
-                self._step(optimizer, self._sync_grads(optimizer))
-                optimizer.zero_grad()
+                self._finish(optimizer)
             self.untoggle_optimizer(optimizer)
 
         enhanced, bands = self.generator(corrupted)   # no discriminator parameter involved: same graph inside or outside the toggle
@@ -564,13 +549,12 @@ class EBENLightningModule(BaseSELightningModule):
         if network == "generator":
             if self.feature_matching_loss_fn or self.adversarial_loss_fn:
                 embeddings("enhanced")   # the reference runs the enhanced branch first (eben.py:204)
+            out = self._waveform_losses(enhanced_speech, reference_speech)
             for name, attr, operands in _GENERATOR_TERMS:
                 fn = getattr(self, attr)
-                if not fn:
+                if not fn or operands == "waveforms":
                     continue
-                if operands == "waveforms":
-                    out[name] = fn(enhanced_speech, reference_speech)
-                elif operands == "both embeddings":
+                if operands == "both embeddings":
                     out[name] = fn(embeddings("enhanced"), embeddings("reference"))
                 else:
                     out[name] = fn(embeddings=embeddings("enhanced"), target=1)
@@ -580,67 +564,16 @@ class EBENLightningModule(BaseSELightningModule):
                 out[name] = self.adversarial_loss_fn(embeddings=embeddings(branch), target=target)
         return out
 
-    def _unit_lambdas(self, n: int, device) -> torch.Tensor:
-        """n ones on the device (the weighted seed sum of a step without balancing)."""
-        ones = getattr(self, "_ones", None)
-        if ones is None or ones.numel() != n or ones.device != device:
-            ones = self._ones = torch.ones(n, dtype=torch.float32, device=device)
-        return ones
-
-    def _update_lambdas(self, atomic_norms):
-        """Loss weights from the gradient norms at ``generator.last_conv.weight`` (eben.py:229-237): the state is initialised
-        with the first norms and -- quirk kept -- the EMA update is applied on that same call; rank-local like the reference's."""
-        if self.atomic_norms_old is None or self.dynamic_loss_balancing == "simple":
-            self.atomic_norms_old = atomic_norms
-        if self.dynamic_loss_balancing == "ema":
-            self.atomic_norms_old = [self.beta_ema * old + (1 - self.beta_ema) * new for old, new in zip(self.atomic_norms_old, atomic_norms)]
-        lambdas = [torch.clamp(1 / (norm + 1e-4), min=0.0, max=1e4) for norm in self.atomic_norms_old]
-        self.last_norms, self.last_lambdas = atomic_norms, lambdas
-        return lambdas
-
-    #: the engine step's balancing arithmetic (EMA, lambdas, backprop loss, weighted seed) as two launches (`eben_balance`,
-    #: `eben_weighted_sum`) instead of ~35 one-element torch kernels in front of the generator backward; same values bit for bit
-    fused_balancing: bool = os.environ.get("EBEN_FUSED_BALANCING", "1") != "0"
-
-    #: the balancing norms ||dL_i / d last_conv.weight|| of the engine step from the seeds in one pass (`eben_last_conv_norms`) instead of
-    #: a tanh-backward + weight-gradient + norm chain per loss through autograd; same values up to the order of the fp32 sums
-    fused_norms: bool = os.environ.get("EBEN_FUSED_NORMS", "1") != "0"
-
-    def _update_lambdas_fused(self, atomic_norms, losses):
-        """``_update_lambdas`` + the backprop loss on the device in one launch; the state stays readable as ``atomic_norms_old``."""
-        import ctypes
-
-        from .._lib import check, load, ptr, stream
-
-        n = len(atomic_norms)
-        dev = atomic_norms[0].device
-        bal = getattr(self, "_bal", None)
-        if bal is None or bal["n"] != n or bal["old"].device != dev:
-            bal = self._bal = {"n": n, "old": torch.zeros(n, dtype=torch.float32, device=dev), "lam": None}
-        old = self.atomic_norms_old
-        if old is not None and len(old) == n and any(
-                not torch.is_tensor(t) or t.device != dev or t.data_ptr() != bal["old"].data_ptr() + 4 * i for i, t in enumerate(old)):
-            # the state was written by someone else since the last call (another step path, a restore, the user): `atomic_norms_old`
-            # is the one state -- the device buffer follows it
-            bal["old"].copy_(torch.stack([torch.as_tensor(t, dtype=torch.float32).to(dev).reshape(()) for t in old]))
-        init = self.atomic_norms_old is None or self.dynamic_loss_balancing == "simple"
-        out = torch.empty(n + 1, dtype=torch.float32, device=dev)   # fresh per step: last_lambdas of earlier steps stay what they were
-        norms = [t.contiguous() for t in atomic_norms]
-        ls = [t.to(torch.float32).contiguous() for t in losses]
-        check(load().eben_balance((ctypes.c_void_p * n)(*[ptr(t) for t in norms]), (ctypes.c_void_p * n)(*[ptr(t) for t in ls]), n,
-                                  ptr(bal["old"]), 1 if init else 0, 1 if self.dynamic_loss_balancing == "ema" else 0, float(self.beta_ema),
-                                  float(1 - self.beta_ema), ptr(out), ptr(out[n:]), stream()), "balance")
-        bal["lam"] = out[:n]
-        self.atomic_norms_old = [bal["old"][i] for i in range(n)]
-        lambdas = [out[i] for i in range(n)]
-        self.last_norms, self.last_lambdas = atomic_norms, lambdas
-        return lambdas, out[n]
+    def balance_losses(self, norms, losses, seeds=None):
+        """``LossBalancer.balance`` under this module's settings as they are now: (lambdas, backprop loss, weighted seed or None)."""
+        return self.balancer.balance(norms, losses, seeds, mode=self.dynamic_loss_balancing, beta=self.beta_ema, fused=self.fused_balancing)
 
     def dynamically_balance_losses(self, atomic_losses: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-        """eben.py:222-240: one partial backward per loss down to the last generator layer, then ``_update_lambdas``."""
+        """eben.py:222-240: one partial backward per loss down to the last generator layer, then the balancer's lambdas."""
         leaf = self.generator.last_conv.weight
         norms = [torch.norm(torch.autograd.grad(loss, leaf, retain_graph=True)[0]).detach() for loss in atomic_losses.values()]
-        return {name: loss * lam for (name, loss), lam in zip(atomic_losses.items(), self._update_lambdas(norms))}
+        lambdas = self.balancer.lambdas(norms, self.dynamic_loss_balancing, self.beta_ema)
+        return {name: loss * lam for (name, loss), lam in zip(atomic_losses.items(), lambdas)}
 
     def on_test_end(self) -> None:
         """eben.py:176-181: upload the generator when asked to (needs Lightning's trainer / datamodule and network access)."""
