@@ -811,6 +811,45 @@ EBEN_API int eben_rate_splice_slots(float* tape0, float* tape1, int tape_pitch, 
 EBEN_API int eben_resample_slots(const float* tape0, const float* tape1, int tape_pitch, float* fifo0, float* fifo1, int fifo_pitch, int slots,
                                  const EbenRateRatio* ratios, int n_ratios, const EbenRatePiece* pieces, int count, void* stream);
 
+/* ---- recordings to resident clips (csrc/corpus.hip): the `data` chunks of WAVE files, as they lie on disk, to rows of float32 -----------
+ * `data` is one DEVICE byte buffer of data_bytes bytes (16-byte aligned) holding many files' interleaved frames; row r is one channel of
+ * one file, described by an EbenPcmRow: its frames start at data + byte_offset (a multiple of 16), `frames` of them, `channels` samples
+ * each, of which sample `channel` is taken.  Conversions, each exact: EBEN_PCM_S16 x / 2^15, EBEN_PCM_S24 (packed 3-byte little-endian,
+ * sign-extended) x / 2^23, EBEN_PCM_S32 float(x) * 2^-31 with float(x) rounded to nearest once, EBEN_PCM_F32 a copy.
+ * The table is handed over twice: rows_host (HOST memory, validated here before anything is launched) and rows_dev (its upload, what
+ * the kernel reads; typically both travel with the bytes in one copy).  A row of rows_dev whose numbers would reach outside the byte
+ * buffer or the output is treated as empty.  Two output forms:
+ *   padded  out_offsets_host == out_offsets_dev == NULL: out is (rows, out_extent) floats, row r gets its samples, exact zeros behind
+ *           them up to the pitch out_extent, and their count in out_lens[r] (int32 DEVICE table, required) -- the buffers
+ *           eben_resample_ragged takes and writes.
+ *   flat    out_offsets_* (HOST and DEVICE copies of `rows` int64 offsets in floats): row r's samples go to out[out_offsets[r] + n] and
+ *           nothing else is written; out_extent is the size of the whole store in floats; the rows' ranges must ascend without overlap.
+ *           out_lens is optional.
+ *   eben_pcm_decode_ragged    row r = its `frames` converted samples.
+ *   eben_pcm_resample_ragged  row r = its ceil(nw * frames / orig) resampled samples: eben_resample_ragged's kernel with its staging
+ *     replaced by the converting, channel-strided load -- the tile of eben_resample_plan, the same ascending-j fmaf order -- so the
+ *     outputs are bit for bit those of eben_resample_ragged on the decoded row.  `kernels`: the (nw, 2 * width + orig) device table.
+ * Mono EBEN_PCM_S16 rows take 16-byte loads per lane; other rows are read sample by sample.
+ * EBEN_EINVAL before any launch, nothing written, for: a null or misaligned pointer (data to 16 bytes, tables to 8, out / out_lens /
+ * kernels to 4); only one of the two offset tables; rows outside 1 ... 65535; an unknown format; channels outside 1 ... 65535;
+ * channel >= channels; negative frames or more than 0x7fff0000 samples a row; a byte_offset that is negative or no multiple of 16; a
+ * row reaching past data_bytes; a pitch too small for its row; a flat range past out_extent or not behind the previous row's; a
+ * ratio whose taps fit no tile.  Added without a version bump: functions and a POD type only. */
+#define EBEN_PCM_S16 0
+#define EBEN_PCM_S24 1
+#define EBEN_PCM_S32 2
+#define EBEN_PCM_F32 3
+typedef struct EbenPcmRow {
+  long long byte_offset;
+  int frames, channels, channel, format;   /* 24 bytes */
+} EbenPcmRow;
+EBEN_API int eben_pcm_decode_ragged(const void* data, long long data_bytes, const EbenPcmRow* rows_host, const EbenPcmRow* rows_dev,
+                                    const long long* out_offsets_host, const long long* out_offsets_dev, float* out, int32_t* out_lens, int rows,
+                                    long long out_extent, void* stream);
+EBEN_API int eben_pcm_resample_ragged(const void* data, long long data_bytes, const EbenPcmRow* rows_host, const EbenPcmRow* rows_dev,
+                                      const float* kernels, const long long* out_offsets_host, const long long* out_offsets_dev, float* out,
+                                      int32_t* out_lens, int rows, long long out_extent, int orig, int nw, int width, void* stream);
+
 /* ---- misc ------------------------------------------------------------------------------- */
 /* out[0] = sqrt(sum x^2) (torch.norm at eben.py:226); `out` must hold 257 floats (scratch) */
 EBEN_API int eben_l2norm(const float* x, size_t n, float* out, void* stream);

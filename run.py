@@ -117,6 +117,35 @@ def instantiate(node: Any) -> Any:
     return node
 
 
+def _with_rank(node: Dict[str, Any]) -> Dict[str, Any]:
+    """The datamodule's node with this process's ``rank`` / ``world_size`` (torchrun's RANK / WORLD_SIZE) where its constructor takes
+    them and the config does not say."""
+    import inspect
+
+    mod, _, name = node["_target_"].rpartition(".")
+    params = inspect.signature(getattr(importlib.import_module(mod), name)).parameters
+    node = dict(node)
+    for key, env in (("rank", "RANK"), ("world_size", "WORLD_SIZE")):
+        if key in params and key not in node:
+            node[key] = int(os.environ.get(env, 1 if key == "world_size" else 0))
+    return node
+
+
+def _batches(loader):
+    """Batch after batch for as long as the training loop asks: a generator that never ends (the synthetic module's) as it is, a
+    re-iterable loader epoch after epoch."""
+    if hasattr(loader, "__next__"):
+        yield from loader
+        return
+    while True:
+        n = 0
+        for batch in loader:
+            n += 1
+            yield batch
+        if n == 0:
+            raise RuntimeError("the train loader has no batch: fewer items than ranks, or than one batch with drop_last")
+
+
 def main(argv: List[str]) -> int:
     from vibravox_amd._env import configure_hw_queues
     configure_hw_queues()   # data-parallel ranks: before the first HIP call
@@ -126,12 +155,14 @@ def main(argv: List[str]) -> int:
     torch.manual_seed(42)  # run.py:74 seed_everything(42)
     assert torch.cuda.is_available(), "the EBEN HIP path needs an MI355X (there is no CPU fallback)"
     device = torch.device("cuda", 0)
-    datamodule = instantiate(cfg["lightning_datamodule"])
+    datamodule = instantiate(_with_rank(cfg["lightning_datamodule"]))
     module = instantiate(cfg["lightning_module"]).to(device)
     trainer = cfg.get("trainer", {})
     if trainer.get("precision") is not None:   # vibravox configs/trainer/ddp.yaml:23-25: the trainer's precision selects the arithmetic plan
         module.set_precision(trainer["precision"])
-    loader = datamodule.train_dataloader()
+    if hasattr(datamodule, "setup"):
+        datamodule.setup("fit")
+    loader = _batches(datamodule.train_dataloader())
     import gc
     for step in range(int(trainer.get("max_steps", 10))):
         if step == 3:   # set-up and warm-up objects are long-lived: keep the cyclic GC from re-walking them (~100 ms stalls)

@@ -101,6 +101,13 @@ class EbenRatePiece(ctypes.Structure):
     _fields_ = [(k, c_int) for k in ("len", "p0", "base0", "n_out", "end", "first_out")] + [(k, ctypes.c_uint8) for k in ("slot", "ratio", "tape", "fifo")]
 
 
+PCM_S16, PCM_S24, PCM_S32, PCM_F32 = 0, 1, 2, 3   # EBEN_PCM_*
+
+
+class EbenPcmRow(ctypes.Structure):
+    _fields_ = [("byte_offset", c_int64), ("frames", c_int32), ("channels", c_int32), ("channel", c_int32), ("format", c_int32)]
+
+
 class EbenClip(ctypes.Structure):
     _fields_ = [("data", c_void_p), ("length", c_int64)]
 
@@ -262,6 +269,8 @@ SIGNATURES = {
     "eben_resample_stream": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "eben_rate_splice_slots": (c_int, [_P, _P, c_int, c_int, _P, c_int, c_int, POINTER(EbenRateSplice), c_int, _P]),
     "eben_resample_slots": (c_int, [_P, _P, c_int, _P, _P, c_int, c_int, POINTER(EbenRateRatio), c_int, POINTER(EbenRatePiece), c_int, _P]),
+    "eben_pcm_decode_ragged": (c_int, [_P, c_int64, _P, _P, _P, _P, _P, _P, c_int, c_int64, _P]),
+    "eben_pcm_resample_ragged": (c_int, [_P, c_int64, _P, _P, _P, _P, _P, _P, _P, c_int, c_int64, c_int, c_int, c_int, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None
