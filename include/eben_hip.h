@@ -218,6 +218,17 @@ EBEN_API int eben_conv1d_bwd_dw(const EbenConv1dDesc* d, const float* dy, const 
 #define EBEN_DW_ROUTE_DW2 3        /* conv_dw2.hip: fp32, pre-transposed A image */
 #define EBEN_DW_ROUTE_FALLBACK 4   /* conv_dw_kernel (conv_dw.hip) */
 EBEN_API int eben_conv1d_bwd_dw_variant(const EbenConv1dDesc* d, int* out, int n);
+/* The same question for the exact-fp32 routes, read off the decision their launches dispatch on (for tests).  out[0] (n >= 14) =
+ * EBEN_DW_ROUTE_*; then, zero where a route has no such number:
+ *   out[1..4]   FM, FN, WAVES_M, XR of conv_dw2_kernel (DW2; the pre-pass is dw_pack_a_kernel<FM, WAVES_M>)
+ *   out[5..6]   bk (time steps per chunk: 128 / 64 / 32) of conv_dw_kernel<1, 8, 1, 2> and xfits (1: nch_max * span <= the register
+ *               prefetch's capacity; 0: the X tile is staged directly) (FALLBACK)
+ *   out[7]      nsplit: the slab count (TINY / ONE_ROW: one slab per batch item)
+ *   out[8..12]  nchunks ((batch item, time chunk) pairs: block z owns chunks z, z + nsplit, ...), nnt / nmt (column / row tiles),
+ *               nct (time chunks per row), nch_max (input channels per X tile) (DW2, FALLBACK)
+ *   out[13]     the slab row stride (columns + 1)
+ * On the conv_dw3 route out[0] alone: eben_conv1d_bwd_dw_variant is the authority there. */
+EBEN_API int eben_conv1d_bwd_dw_f32_variant(const EbenConv1dDesc* d, int* out, int n);
 
 /* ---- bf16 BUNDLE LAYOUT of the discriminator engine ------------------------------------------------------------------------
  * A (batch, channels, length) tensor, channels a multiple of 8, at rest as bf16 [batch][channels / 8][length][8]: one 16-byte UNIT =

@@ -140,6 +140,7 @@ SIGNATURES = {
     "eben_conv1d_bwd_dx_fm": (c_int, [_D, _P, _P, _P, c_int, _P, c_float, _P, c_float, c_int, POINTER(c_int), _P, _P]),
     "eben_conv1d_bwd_dw": (c_int, [_D, _P, _P, _P, c_int, _P, c_size_t, _P]),
     "eben_conv1d_bwd_dw_variant": (c_int, [_D, POINTER(c_int), c_int]),
+    "eben_conv1d_bwd_dw_f32_variant": (c_int, [_D, POINTER(c_int), c_int]),
     "eben_bl_from_f32": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P]),
     "eben_bl_to_f32": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P]),
     "eben_bl_conv1d_fwd": (c_int, [_D, _P, _P, _P, _P, _P, _P, _P]),

@@ -276,6 +276,9 @@ struct Dw2Args {
 };
 
 int dw2_applicable(const Canon& c);
+// the instantiations a covered layer runs -- conv_dw2_kernel<FM, FN, WAVES_M, XR>, dw_pack_a_kernel<FM, WAVES_M> -- and its plan
+struct Dw2Variant { int FM, FN, WAVES_M, XR, nsplit, nchunks, nnt, nmt, nct, nch_max; };
+int dw2_variant(const Canon& c, Dw2Variant* v);   // 0: not covered (v untouched)
 size_t dw2_workspace(const Canon& c, int* nslab, int* row_stride);
 int dw2_launch(const Canon& c, Dw2Args a, float* workspace, size_t ws_bytes, hipStream_t st);
 

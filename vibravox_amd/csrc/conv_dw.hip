@@ -450,6 +450,14 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restric
   }
 }
 
+// dv element of a weight-normed row, c1 s - c2 v with one rounding per operation in EVERY form.  Left to the compiler, the
+// expression is contracted into an FMA in wn_bwd_kernel's unrolled loop body (rows of more than 768 columns) and nowhere else: the
+// single-tensor form then differed from the multi-tensor form, and from its own remainder loop, in the last bit.
+__device__ __forceinline__ float wn_dv(float c1, float s, float c2, float v) {
+#pragma clang fp contract(off)
+  return c1 * s - c2 * v;
+}
+
 // per weight row: dw row (already summed, row stride `row_stride`) -> dg, dv (+ dbias from column `cols`)
 __global__ __launch_bounds__(256) void wn_bwd_kernel(const float* __restrict__ dw, int cols, int row_stride,
                                                      const float* __restrict__ g, const float* __restrict__ v,
@@ -472,7 +480,7 @@ __global__ __launch_bounds__(256) void wn_bwd_kernel(const float* __restrict__ d
   const float dgr = dot / n;
   if (threadIdx.x == 0) dg[r] = dgr;
   const float c1 = gr / n, c2 = gr * dgr / (n * n);
-  for (int i = threadIdx.x; i < cols; i += 256) orow[i] = c1 * srow[i] - c2 * vrow[i];
+  for (int i = threadIdx.x; i < cols; i += 256) orow[i] = wn_dv(c1, srow[i], c2, vrow[i]);
 }
 
 // ---- multi-tensor forms: one launch for every layer of a network (the per-layer launches are ~5 us kernels whose
@@ -590,7 +598,7 @@ __global__ __launch_bounds__(256) void wn_bwd_multi_kernel(const WnBwdTable T) {
     const float dgr = dot / n;
     if (threadIdx.x == 0) e.dg[r] = dgr;
     const float c1 = gr / n, c2 = gr * dgr / (n * n);
-    walk([&](int sc, int i) { orow[i] = c1 * srow[sc] - c2 * vrow[i]; });
+    walk([&](int sc, int i) { orow[i] = wn_dv(c1, srow[sc], c2, vrow[i]); });
     return;
   }
   if (!e.g) {
@@ -604,7 +612,7 @@ __global__ __launch_bounds__(256) void wn_bwd_multi_kernel(const WnBwdTable T) {
   const float dgr = dot / n;
   if (threadIdx.x == 0) e.dg[r] = dgr;
   const float c1 = gr / n, c2 = gr * dgr / (n * n);
-  for (int i = threadIdx.x; i < cols; i += 256) orow[i] = c1 * srow[i] - c2 * vrow[i];
+  for (int i = threadIdx.x; i < cols; i += 256) orow[i] = wn_dv(c1, srow[i], c2, vrow[i]);
 }
 
 }  // namespace eben
@@ -713,6 +721,36 @@ extern "C" int eben_conv1d_bwd_dw_variant(const EbenConv1dDesc* d, int* out, int
     if (!dw3_variant(c, &v)) return fail(EBEN_EUNSUPPORTED, "eben_conv1d_bwd_dw_variant: no conv_dw3 plan for a layer routed there");
     const int f[12] = {v.FM, v.FN, v.WAVES_M, v.XRB, v.SP, v.MT, v.BKT, v.nsplit, v.nchunks, v.nnt, v.nmt, v.nbg};
     for (int i = 0; i < 12; ++i) out[1 + i] = f[i];
+  }
+  return EBEN_OK;
+}
+
+extern "C" int eben_conv1d_bwd_dw_f32_variant(const EbenConv1dDesc* d, int* out, int n) {
+  EBEN_REQUIRE(out && n >= 14, "eben_conv1d_bwd_dw_f32_variant: 14 output slots");
+  Canon c;
+  const int rc = canon_from_desc(d, &c);
+  if (rc) return rc;
+  for (int i = 0; i < 14; ++i) out[i] = 0;
+  const int route = out[0] = dw_route(c, d);
+  if (route == EBEN_DW_ROUTE_TINY || route == EBEN_DW_ROUTE_ONE_ROW) {   // one slab per batch item
+    out[7] = c.B;
+    out[13] = (c.Cin / c.g) * c.k + 1;
+  } else if (route == EBEN_DW_ROUTE_DW2) {
+    Dw2Variant v;
+    if (!dw2_variant(c, &v)) return fail(EBEN_EUNSUPPORTED, "eben_conv1d_bwd_dw_f32_variant: no conv_dw2 plan for a layer routed there");
+    const int f[4] = {v.FM, v.FN, v.WAVES_M, v.XR};
+    for (int i = 0; i < 4; ++i) out[1 + i] = f[i];
+    const int g[6] = {v.nsplit, v.nchunks, v.nnt, v.nmt, v.nct, v.nch_max};
+    for (int i = 0; i < 6; ++i) out[7 + i] = g[i];
+    out[13] = (c.Cin / c.g) * c.k + 1;
+  } else if (route == EBEN_DW_ROUTE_FALLBACK) {
+    DwPlan p;
+    make_dw_plan(c, &p);
+    out[5] = p.bk;
+    out[6] = (long long)p.nch_max * ((p.bk - 1) * c.s + (c.k - 1) * c.d + 1) <= DW_XCAP ? 1 : 0;
+    const int g[6] = {p.nsplit, p.nchunks, p.nnt, p.nmt, p.nct, p.nch_max};
+    for (int i = 0; i < 6; ++i) out[7 + i] = g[i];
+    out[13] = p.row_stride;
   }
   return EBEN_OK;
 }

@@ -300,8 +300,21 @@ static void make_dw2_plan(const Canon& c, Dw2Plan* p) {
   p->ok = 1;
 }
 
+// The kernels a plan runs: conv_dw2_kernel<FM, FN, WAVES_M, XR> behind dw_pack_a_kernel<FM, WAVES_M>.  THE decision: the launch and the
+// query (eben_conv1d_bwd_dw_f32_variant) read it.  Row configuration = the plan's row-tile height (128 / 96 / 64 / 32 rows); a wide X
+// tile takes 20 register slots per thread on the 128- / 96-row tiles and 32 on the others, a small one 12.
+static Dw2Variant dw2_variant_of(const Dw2Plan& p) {
+  static const int rows[4][3] = {{2, 2, 2}, {3, 1, 1}, {2, 1, 1}, {1, 1, 1}};   // FM, FN, WAVES_M of cfg 0..3
+  Dw2Variant v;
+  v.FM = rows[p.cfg][0]; v.FN = rows[p.cfg][1]; v.WAVES_M = rows[p.cfg][2];
+  v.XR = !p.big_x ? DW2_XR : p.cfg <= 1 ? DW2_XR_MID : DW2_XR_BIG;
+  v.nsplit = p.nsplit; v.nchunks = p.nchunks; v.nnt = p.nnt; v.nmt = p.nmt; v.nct = p.nct; v.nch_max = p.nch_max;
+  return v;
+}
+
 template <int FM, int FN, int WAVES_M, int XR>
-static int launch_dw2(const Dw2Args& a, const Dw2Plan& p, hipStream_t st) {
+static int launch_dw2(const Dw2Variant& v, const Dw2Args& a, const Dw2Plan& p, hipStream_t st) {
+  EBEN_REQUIRE(v.FM == FM && v.FN == FN && v.WAVES_M == WAVES_M && v.XR == XR, "conv_dw2: launch and variant disagree");
   static LdsAttrOnce attr_once;
   auto kern = conv_dw2_kernel<FM, FN, WAVES_M, XR>;
   {
@@ -317,9 +330,31 @@ static int launch_dw2(const Dw2Args& a, const Dw2Plan& p, hipStream_t st) {
   return EBEN_OK;
 }
 
+template <int XR, int XR_WIDE_ROWS>   // XR_WIDE_ROWS: the 128- / 96-row tiles' slots at this X-tile size
+static int launch_dw2_rows(const Dw2Variant& v, const Dw2Args& a, const Dw2Plan& p, hipStream_t st) {
+  switch (v.FM * v.WAVES_M) {
+    case 4: return launch_dw2<2, 2, 2, XR_WIDE_ROWS>(v, a, p, st);
+    case 3: return launch_dw2<3, 1, 1, XR_WIDE_ROWS>(v, a, p, st);
+    case 2: return launch_dw2<2, 1, 1, XR>(v, a, p, st);
+    default: return launch_dw2<1, 1, 1, XR>(v, a, p, st);
+  }
+}
+
+static int launch_dw2_variant(const Dw2Variant& v, const Dw2Args& a, const Dw2Plan& p, hipStream_t st) {
+  if (v.XR == DW2_XR) return launch_dw2_rows<DW2_XR, DW2_XR>(v, a, p, st);
+  return launch_dw2_rows<DW2_XR_BIG, DW2_XR_MID>(v, a, p, st);
+}
+
 int dw2_applicable(const Canon& c) {
   Dw2Plan p;
   make_dw2_plan(c, &p);
+  return p.ok;
+}
+
+int dw2_variant(const Canon& c, Dw2Variant* v) {
+  Dw2Plan p;
+  make_dw2_plan(c, &p);
+  if (p.ok) *v = dw2_variant_of(p);
   return p.ok;
 }
 
@@ -344,20 +379,7 @@ int dw2_launch(const Canon& c, Dw2Args a, float* workspace, size_t ws_bytes, hip
   a.S = c.s; a.d = c.d; a.off0 = -c.pl; a.J = c.k; a.Ng = p.Ng; a.row_stride = p.row_stride; a.reflect = c.reflect;
   a.nsplit = p.nsplit; a.nct = p.nct; a.nchunks = p.nchunks; a.nnt = p.nnt; a.nmt = p.nmt; a.XSTR = p.XSTR; a.nch_max = p.nch_max;
   a.slab_stride = p.slab_stride;
-  if (p.big_x) {
-    switch (p.cfg) {
-      case 0: return launch_dw2<2, 2, 2, DW2_XR_MID>(a, p, st);
-      case 1: return launch_dw2<3, 1, 1, DW2_XR_MID>(a, p, st);
-      case 2: return launch_dw2<2, 1, 1, DW2_XR_BIG>(a, p, st);
-      default: return launch_dw2<1, 1, 1, DW2_XR_BIG>(a, p, st);
-    }
-  }
-  switch (p.cfg) {
-    case 0: return launch_dw2<2, 2, 2, DW2_XR>(a, p, st);
-    case 1: return launch_dw2<3, 1, 1, DW2_XR>(a, p, st);
-    case 2: return launch_dw2<2, 1, 1, DW2_XR>(a, p, st);
-    default: return launch_dw2<1, 1, 1, DW2_XR>(a, p, st);
-  }
+  return launch_dw2_variant(dw2_variant_of(p), a, p, st);
 }
 
 }  // namespace eben
