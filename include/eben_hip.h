@@ -861,6 +861,33 @@ EBEN_API int eben_pcm_resample_ragged(const void* data, long long data_bytes, co
                                       const float* kernels, const long long* out_offsets_host, const long long* out_offsets_dev, float* out,
                                       int32_t* out_lens, int rows, long long out_extent, int orig, int nw, int width, void* stream);
 
+/* ---- rows of float32 to the bytes of WAVE files (csrc/pcm_encode.hip): the decoder's way back ---------------------------------------------
+ * `src` is one DEVICE buffer of src_floats floats; row r, described by an EbenPcmEncRow, is the `samples` floats from src + src_offset
+ * (any offset: a row of a padded buffer at r * pitch and a clip inside a flat store are the same case).  Its mono little-endian samples
+ * go to image + byte_offset (a multiple of 16) of a flat DEVICE byte image of image_bytes bytes (16-byte aligned): `samples` * 2 / 3
+ * (packed) / 4 / 4 bytes and not one more -- headers, the gaps between rows and everything else in the image stay as they are.
+ * Conversions, deterministic, no dither, each the inverse of the decoder's: with b the bit depth and v = rint(x * 2^(b-1)), half to
+ * even in float32 (the product is exact), EBEN_PCM_S16 / S24 / S32 store v clamped to [-2^(b-1), 2^(b-1) - 1] and 0 for a NaN;
+ * EBEN_PCM_F32 stores the bits of x.  clipped[r] (int32 DEVICE table, required; set to zero by a memset on `stream` in front of the
+ * launch) receives the number of samples of row r with v >= 2^(b-1), v < -2^(b-1) or x a NaN -- an integer sum, the same on every run;
+ * EBEN_PCM_F32 never clips.
+ * The table is handed over twice, as for the decoder: rows_host is validated here before anything is launched, the kernel reads
+ * rows_dev and treats a row whose numbers would reach outside src or the image as empty.  EBEN_PCM_S16 rows convert into LDS and
+ * store 16 bytes (8 samples) per lane, whatever the alignment of the source row, the last partial vector sample by sample; the other
+ * formats store sample by sample.  A block owns eben_pcm_encode_plan's out[0] consecutive samples of one row (n >= 1; no launch).
+ * EBEN_EINVAL before any launch, nothing written, for: a null or misaligned pointer (image to 16 bytes, tables to 8, src and clipped
+ * to 4); rows outside 1 ... 65535; an unknown format; negative samples or more than 0x7fff0000 a row; a negative src_offset or a row
+ * reaching past src_floats; a byte_offset that is negative or no multiple of 16; a row reaching past image_bytes; two rows whose byte
+ * ranges overlap (in any order).  Added without a version bump: functions and a POD type only. */
+typedef struct EbenPcmEncRow {
+  long long src_offset;    /* of the row's sample 0 in src, in floats */
+  long long byte_offset;   /* of its first byte in the image */
+  int samples, format;     /* 24 bytes */
+} EbenPcmEncRow;
+EBEN_API int eben_pcm_encode_plan(int* out, int n);
+EBEN_API int eben_pcm_encode_ragged(const float* src, long long src_floats, const EbenPcmEncRow* rows_host, const EbenPcmEncRow* rows_dev, void* image,
+                                    long long image_bytes, int32_t* clipped, int rows, void* stream);
+
 /* ---- misc ------------------------------------------------------------------------------- */
 /* out[0] = sqrt(sum x^2) (torch.norm at eben.py:226); `out` must hold 257 floats (scratch) */
 EBEN_API int eben_l2norm(const float* x, size_t n, float* out, void* stream);

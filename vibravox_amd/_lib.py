@@ -108,6 +108,10 @@ class EbenPcmRow(ctypes.Structure):
     _fields_ = [("byte_offset", c_int64), ("frames", c_int32), ("channels", c_int32), ("channel", c_int32), ("format", c_int32)]
 
 
+class EbenPcmEncRow(ctypes.Structure):
+    _fields_ = [("src_offset", c_int64), ("byte_offset", c_int64), ("samples", c_int32), ("format", c_int32)]
+
+
 class EbenClip(ctypes.Structure):
     _fields_ = [("data", c_void_p), ("length", c_int64)]
 
@@ -272,6 +276,8 @@ SIGNATURES = {
     "eben_resample_slots": (c_int, [_P, _P, c_int, _P, _P, c_int, c_int, POINTER(EbenRateRatio), c_int, POINTER(EbenRatePiece), c_int, _P]),
     "eben_pcm_decode_ragged": (c_int, [_P, c_int64, _P, _P, _P, _P, _P, _P, c_int, c_int64, _P]),
     "eben_pcm_resample_ragged": (c_int, [_P, c_int64, _P, _P, _P, _P, _P, _P, _P, c_int, c_int64, c_int, c_int, c_int, _P]),
+    "eben_pcm_encode_plan": (c_int, [POINTER(c_int), c_int]),
+    "eben_pcm_encode_ragged": (c_int, [_P, c_int64, _P, _P, _P, c_int64, _P, c_int, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None
@@ -310,6 +316,13 @@ def check(rc: int, what: str = "") -> None:
     if rc != 0:
         msg = load().eben_last_error()
         raise EbenError(f"{what or 'libeben_hip'} failed (code {rc}): {msg.decode() if msg else '?'}")
+
+
+def pcm_encode_tile() -> int:
+    """Samples of one row that a block of ``eben_pcm_encode_ragged`` owns (``eben_pcm_encode_plan``; no GPU needed)."""
+    out = (c_int * 1)()
+    check(load().eben_pcm_encode_plan(out, 1), "pcm_encode_plan")
+    return int(out[0])
 
 
 def ptr(t: Optional[torch.Tensor]) -> Optional[int]:

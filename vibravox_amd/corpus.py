@@ -15,6 +15,10 @@ Device side: ``ResidentCorpus.load`` reads the files' ``data`` chunks as they li
 descriptor tables in one copy per group, and converts them in one launch per (group, sensor, rate): ``eben_pcm_decode_ragged`` for
 files already at the model's rate, ``eben_pcm_resample_ragged`` -- the conversion fused into ``rate.resample_ragged``'s kernel -- for the
 others (``csrc/corpus.hip``).  Every clip is bit for bit ``augment.resample`` of the numpy-decoded file.
+
+The way out (``export.enhance_corpus``, ``inference.enhance_to_pcm``) is the mirror image: ``wav_header`` writes the canonical mono
+header, ``plan_image`` places files in group images with every data start on a 16-byte boundary, and ``rows_to_pcm``
+(``eben_pcm_encode_ragged``, ``csrc/pcm_encode.hip``) converts rows of float32, where they lie, into the files' bytes in one launch.
 """
 from __future__ import annotations
 
@@ -37,6 +41,7 @@ ALIGN = 16                                                # every chunk and tabl
 
 _PCM_GUID_TAIL = bytes.fromhex("000000001000800000aa00389b71")   # KSDATAFORMAT_SUBTYPE_*: the format tag, then these 14 bytes
 ROW_DTYPE = np.dtype([("byte_offset", "<i8"), ("frames", "<i4"), ("channels", "<i4"), ("channel", "<i4"), ("format", "<i4")])   # EbenPcmRow
+ENC_ROW_DTYPE = np.dtype([("src_offset", "<i8"), ("byte_offset", "<i8"), ("samples", "<i4"), ("format", "<i4")])   # EbenPcmEncRow
 
 
 class WavInfo(NamedTuple):
@@ -105,6 +110,63 @@ def wav_info(path: str) -> WavInfo:
         raise ValueError(f"{path}: a truncated file: the data chunk says {nbytes} bytes, {avail} are there")
     frames = nbytes // frame
     return WavInfo(rate, channels, frames, name, body, frames * frame)
+
+
+HEADER_BYTES = 44   # of the canonical header ``wav_header`` writes
+
+
+def wav_header(rate: int, frames: int, format: str) -> bytes:
+    """The canonical 44-byte RIFF/WAVE header of a mono file of ``frames`` samples: a ``fmt`` chunk of 16 bytes (tag 1 for the PCM
+    formats, 3 for FLOAT32) and the ``data`` chunk's 8 bytes; the samples follow.  ``wav_info`` of header + data returns
+    ``(rate, 1, frames, format, 44, frames * bytes)``.  ``ValueError`` for a data chunk whose size does not fit 32 bits (no RF64, as in
+    the reader)."""
+    rate, frames = int(rate), int(frames)
+    if format not in BYTES_PER_SAMPLE:
+        raise ValueError(f"wav_header: format must be one of {', '.join(FORMATS)}, got {format!r}")
+    if not 1 <= rate <= 0xFFFFFFFF // 4 or frames < 0:
+        raise ValueError(f"wav_header: {frames} frames at {rate} Hz")
+    width = BYTES_PER_SAMPLE[format]
+    nbytes = frames * width
+    if 36 + nbytes > 0xFFFFFFFF:
+        raise ValueError(f"wav_header: {frames} frames of {format} are {nbytes} bytes of data, too many for the 32-bit sizes of a RIFF file (no RF64)")
+    return (b"RIFF" + struct.pack("<I", 36 + nbytes) + b"WAVEfmt " + struct.pack("<IHHIIHH", 16, 3 if format == "FLOAT32" else 1, 1, rate, rate * width,
+                                                                                 width, 8 * width) + b"data" + struct.pack("<I", nbytes))
+
+
+class ImageGroup(NamedTuple):
+    lo: int               # files [lo, hi) travel in this image
+    hi: int
+    starts: List[int]     # of each file (its header) in the image; its data starts HEADER_BYTES behind, on a 16-byte boundary
+    nbytes: int           # of the image, a multiple of 16
+
+
+def plan_image(sample_counts: Sequence[int], format: str, max_bytes: int) -> List[ImageGroup]:
+    """The counterpart of ``plan_groups`` on the way out: consecutive runs of mono files of ``sample_counts`` samples whose spans fit
+    ``max_bytes`` together, at most 65535 files a run.  A file is one contiguous slice ``[start, start + 44 + samples * bytes)`` of its
+    group's image, placed so that its data starts on a 16-byte boundary (where ``eben_pcm_encode_ragged`` writes it); the header goes into
+    the 44 bytes in front.  ``ValueError`` for a file that does not fit alone."""
+    if format not in BYTES_PER_SAMPLE:
+        raise ValueError(f"plan_image: format must be one of {', '.join(FORMATS)}, got {format!r}")
+    width = BYTES_PER_SAMPLE[format]
+    groups: List[ImageGroup] = []
+    lo, starts, end = 0, [], 0
+    for k, n in enumerate(sample_counts):
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"file {k} has {n} samples")
+        body = n * width
+        alone = _up(_up(HEADER_BYTES) + body)
+        if alone > max_bytes:
+            raise ValueError(f"file {k} needs {alone} bytes of staging, max_stage_bytes allows {max_bytes}")
+        data = _up(end + HEADER_BYTES)
+        if starts and (_up(data + body) > max_bytes or len(starts) >= 65535):
+            groups.append(ImageGroup(lo, k, starts, _up(end)))
+            lo, starts, data = k, [], _up(HEADER_BYTES)
+        starts.append(data - HEADER_BYTES)
+        end = data + body
+    if starts:
+        groups.append(ImageGroup(lo, len(sample_counts), starts, _up(end)))
+    return groups
 
 
 class Scan(NamedTuple):
@@ -263,6 +325,28 @@ def pcm_to_rows(data: torch.Tensor, rows: np.ndarray, *, rates: Optional[Tuple[i
         check(lib.eben_pcm_resample_ragged(data.data_ptr(), data.numel(), rows.ctypes.data, rows_dev.data_ptr(), ptr(table), off_host, off_dev, ptr(out),
                                            lens_ptr, n, extent, orig, new, width, stream()), "pcm_resample_ragged")
     return out, out_lens
+
+
+def rows_to_pcm(src: torch.Tensor, rows: np.ndarray, image: torch.Tensor, clipped: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``csrc/pcm_encode.hip`` on buffers that are on the device: the way back of ``pcm_to_rows``.  ``src``: a contiguous float32 device
+    tensor of any shape, addressed flat; ``rows``: an ``ENC_ROW_DTYPE`` array, one descriptor per row (``src_offset`` in floats,
+    ``byte_offset`` a multiple of 16, ``samples``, ``format`` an index of ``FORMATS``), uploaded here; ``image``: a contiguous uint8
+    device tensor (its storage 16-byte aligned) that receives the rows' bytes and nothing else.  Returns ``clipped``, an int32 device
+    tensor with the clipped-sample count of every row (allocated here unless given).  One launch, nothing waits."""
+    from ._lib import check, load, ptr, stream
+
+    rows = np.ascontiguousarray(rows, dtype=ENC_ROW_DTYPE)
+    n = len(rows)
+    if image.dtype is not torch.uint8 or not image.is_cuda or not image.is_contiguous():
+        raise ValueError(f"rows_to_pcm: image must be a contiguous uint8 device tensor, got {image.dtype} on {image.device}")
+    if clipped is None:
+        clipped = torch.empty(n, dtype=torch.int32, device=image.device)
+    elif clipped.dtype is not torch.int32 or tuple(clipped.shape) != (n,) or clipped.device != image.device or not clipped.is_contiguous():
+        raise ValueError(f"rows_to_pcm: clipped must be a contiguous int32 ({n},) tensor on {image.device}, got {clipped.dtype} {tuple(clipped.shape)}")
+    rows_dev = torch.from_numpy(rows.view(np.uint8).reshape(-1)).to(image.device, non_blocking=True)
+    check(load().eben_pcm_encode_ragged(ptr(src), src.numel(), rows.ctypes.data, rows_dev.data_ptr(), image.data_ptr(), image.numel(), clipped.data_ptr(), n,
+                                        stream()), "pcm_encode_ragged")
+    return clipped
 
 
 class ResidentCorpus:

@@ -10,6 +10,10 @@ one): per batch one ragged forward and the SI-SDR / STOI kernels with a length p
 Recordings at another rate than the model's (the reference's script resamples 48 kHz to 16 kHz in front of every forward) enter
 through ``input_rate=``: one ``rate.resample_ragged`` launch per batch writes the generator's padded buffer, and ``enhance_stream``
 resamples with carried state.
+
+``enhance_to_pcm`` is ``enhance_clips`` whose results leave the device as the bytes of WAVE files (the reference's script stores every
+enhanced recording): one ``eben_pcm_encode_ragged`` launch per batch on the rows of the output buffer, one copy per group to pinned
+memory; ``export.enhance_corpus`` runs it from a directory to a directory.
 """
 from __future__ import annotations
 
@@ -113,15 +117,33 @@ def enhance_clips(generator, clips: Sequence[torch.Tensor], *, max_batch_samples
     packed raw, the batches are composed on their lengths at ``model_rate``, and one ``rate.resample_ragged`` launch per batch writes
     the generator's input buffer.  The results are at the model's rate: those of ``enhance_clips`` on ``augment.resample(clip,
     input_rate, model_rate)``, bit for bit."""
+    clips, rated, lengths = _clips_and_lengths(clips, input_rate, model_rate)
+    batches, back = ragged.compose_batches(generator, lengths, max_batch_samples)
+    enhanced: List[torch.Tensor] = []
+    bands: List[torch.Tensor] = []
+    for idx, plan, enh, bnd in _batch_forwards(generator, clips, lengths, batches, rated, input_rate, model_rate):
+        for r, i in enumerate(idx):
+            enhanced.append(enh[r, 0, : plan.cut[r]].reshape(clips[i].shape[:-1] + (plan.cut[r],)).clone())
+            if return_bands:
+                bands.append(bnd[r, :, : plan.row_lengths[1][r]].clone())
+    enhanced = [enhanced[p] for p in back]
+    return (enhanced, [bands[p] for p in back]) if return_bands else enhanced
+
+
+def _clips_and_lengths(clips, input_rate, model_rate):
+    """``(clips as a list, whether they need resampling, their lengths at the model's rate)``; refuses anything that is no mono clip."""
     clips = list(clips)
     for i, c in enumerate(clips):
         if c.dim() not in (1, 2, 3) or c.numel() != c.shape[-1] or c.dtype is not torch.float32:
             raise ValueError(f"clip {i}: expected a float32 tensor of shape (T,), (1, T) or (1, 1, T), got {c.dtype} {tuple(c.shape)}")
     rated = _rated(input_rate, model_rate)
-    lengths = [resampled_length(c.shape[-1], input_rate, model_rate) if rated else c.shape[-1] for c in clips]
-    batches, back = ragged.compose_batches(generator, lengths, max_batch_samples)
-    enhanced: List[torch.Tensor] = []
-    bands: List[torch.Tensor] = []
+    return clips, rated, [resampled_length(c.shape[-1], input_rate, model_rate) if rated else c.shape[-1] for c in clips]
+
+
+def _batch_forwards(generator, clips, lengths, batches, rated: bool, input_rate, model_rate):
+    """What ``enhance_clips`` and ``enhance_to_pcm`` share: per batch of ``ragged.compose_batches`` the clips packed (or resampled) into
+    the padded buffer and one ``forward_ragged``.  Yields ``(idx, plan, enhanced (rows, 1, l_buf), bands)``; row r belongs to clip
+    ``idx[r]`` and holds ``plan.cut[r]`` samples.  Runs in the caller's grad mode (``forward_ragged`` wants ``torch.no_grad()``)."""
     for idx in batches:
         plan = ragged.plan(generator, [lengths[i] for i in idx])
         if rated:
@@ -131,12 +153,117 @@ def enhance_clips(generator, clips: Sequence[torch.Tensor], *, max_batch_samples
             for r, i in enumerate(idx):
                 buf[r, 0, : plan.cut[r]].copy_(clips[i].reshape(-1)[: plan.cut[r]])
         enh, bnd = generator.forward_ragged(buf, [lengths[i] for i in idx])
-        for r, i in enumerate(idx):
-            enhanced.append(enh[r, 0, : plan.cut[r]].reshape(clips[i].shape[:-1] + (plan.cut[r],)).clone())
-            if return_bands:
-                bands.append(bnd[r, :, : plan.row_lengths[1][r]].clone())
-    enhanced = [enhanced[p] for p in back]
-    return (enhanced, [bands[p] for p in back]) if return_bands else enhanced
+        yield idx, plan, enh, bnd
+
+
+def _encode_group(generator, clips, lengths, counts, group, fmt: int, rated: bool, input_rate, model_rate: int, out_rate: int, max_batch_samples: int,
+                  dev_image: torch.Tensor, host_half: torch.Tensor):
+    """Queues one group of ``enhance_to_pcm``: its clips' batches through the generator, per batch one encode launch from the output
+    buffer's rows into the device image (behind one ``rate.resample_ragged`` launch when the files are at another rate), then one
+    asynchronous copy of image and clipped counts into ``host_half``.  Returns ``(order, event)``: the group's clips in the order of
+    their counts, and the event behind the copy.  Nothing waits."""
+    import numpy as np
+
+    from . import corpus as C
+    from . import rate
+
+    lo, hi = group.lo, group.hi
+    n = hi - lo
+    sub_clips, sub_lengths = clips[lo:hi], lengths[lo:hi]
+    counts_at = group.nbytes
+    total = counts_at + 4 * n
+    image = dev_image[:counts_at]
+    clipped = dev_image[counts_at:total].view(torch.int32)
+    order: List[int] = []
+    with torch.no_grad(), torch.cuda.device(dev_image.device):
+        batches, _ = ragged.compose_batches(generator, sub_lengths, max_batch_samples)
+        for idx, plan, enh, _ in _batch_forwards(generator, sub_clips, sub_lengths, batches, rated, input_rate, model_rate):
+            src = enh if out_rate == model_rate else rate.resample_ragged(enh, list(plan.cut), model_rate, out_rate)[0]
+            src = src.contiguous()
+            pitch = src.shape[-1]
+            table = np.zeros(len(idx), dtype=C.ENC_ROW_DTYPE)
+            for r, i in enumerate(idx):   # the batches are not in clip order: every row carries its own place in the image
+                table[r] = (r * pitch, group.starts[i] + C.HEADER_BYTES, counts[lo + i], fmt)
+            C.rows_to_pcm(src, table, image, clipped[len(order):len(order) + len(idx)])
+            order.extend(idx)
+        host_half[:total].copy_(dev_image[:total], non_blocking=True)
+        event = torch.cuda.Event()
+        event.record()
+    return order, event
+
+
+def enhance_to_pcm(generator, clips: Sequence[torch.Tensor], *, format: str = "PCM16", input_rate: Optional[int] = None,
+                   output_rate: Optional[int] = None, model_rate: int = 16000, max_batch_samples: int = MAX_BATCH_SAMPLES,
+                   max_stage_bytes: int = 1 << 30):
+    """``enhance_clips`` whose results leave the device as the bytes of WAVE files: a generator that yields, group by group,
+    ``(indices, image, spans, clipped)``.  ``indices``: the clips of the group, a run of consecutive input positions; ``image``: a pinned
+    uint8 host tensor; ``spans[k]``: the ``(start, stop)`` of clip ``indices[k]``'s complete mono file in it (``corpus.wav_header`` and
+    the data, ``image[start:stop]`` is what goes to disk); ``clipped[k]``: how many of its samples left the format's range (or were NaN).
+    The image is one of two pinned halves: it is valid until the generator is advanced again.
+
+    A file holds what ``enhance_clips`` returns for its clip (``cut_to_valid_length`` long, at ``model_rate``), or, with ``output_rate``
+    other than ``model_rate``, ``augment.resample`` of it -- converted as ``eben_pcm_encode_ragged`` states: ``rint(x * 2^(b-1))`` clamped
+    for the PCM formats, the bits for FLOAT32, no dither.  Clips, ``input_rate`` and the forwards are ``enhance_clips``'s; each group is
+    dealt into ragged batches of its own.  Behind ``forward_ragged`` nothing is unpacked: one encode launch per batch reads the rows of
+    the output buffer where they lie (one ``rate.resample_ragged`` launch in front of it when the rate changes) and writes at the clips'
+    places of the group's image (``corpus.plan_image``: groups of at most ``max_stage_bytes``, halved when there are several, plus 4
+    bytes a file for the counts); one asynchronous copy per group brings image and counts to the host, and the next group's launches are
+    queued before the previous copy's event is waited for -- the only wait.  The host writes the headers once the copy has arrived."""
+    import numpy as np
+
+    from . import corpus as C
+
+    clips, rated, lengths = _clips_and_lengths(clips, input_rate, model_rate)
+    if format not in C.FORMATS:
+        raise ValueError(f"enhance_to_pcm: format must be one of {', '.join(C.FORMATS)}, got {format!r}")
+    model_rate = int(model_rate)
+    out_rate = model_rate if output_rate is None else int(output_rate)
+    if out_rate <= 0 or model_rate <= 0:
+        raise ValueError(f"enhance_to_pcm: output_rate and model_rate must be positive, got {output_rate} and {model_rate}")
+    if not clips:
+        return
+    ragged.plan(generator, lengths)   # refuses a clip that is too short, by index, before anything runs
+    counts = [ragged.cut_length(generator, t) for t in lengths]
+    if out_rate != model_rate:
+        counts = [resampled_length(t, model_rate, out_rate) for t in counts]
+    for i, t in enumerate(counts):
+        C.wav_header(out_rate, t, format)   # a file too large for a RIFF header is refused before anything runs
+    groups = C.plan_image(counts, format, max_stage_bytes)
+    if len(groups) > 1:
+        groups = C.plan_image(counts, format, max_stage_bytes // 2)
+    n_halves = 2 if len(groups) > 1 else 1
+    half = max(g.nbytes + C._up(4 * (g.hi - g.lo)) for g in groups)
+    device = clips[0].device
+    with torch.cuda.device(device):
+        dev_image = torch.empty(half, dtype=torch.uint8, device=device)   # one: a group's launches follow the previous copy in stream order
+        host = torch.empty(n_halves * half, dtype=torch.uint8, pin_memory=True)
+    fmt = C.FORMATS.index(format)
+
+    def arrived(group, h, order, event):
+        event.synchronize()   # the copy that filled this half has finished (a copy's event, never a kernel's)
+        n = group.hi - group.lo
+        image = host[h * half:h * half + group.nbytes]
+        view = image.numpy()
+        spans = []
+        for k, start in enumerate(group.starts):
+            t = counts[group.lo + k]
+            view[start:start + C.HEADER_BYTES] = np.frombuffer(C.wav_header(out_rate, t, format), dtype=np.uint8)
+            spans.append((start, start + C.HEADER_BYTES + t * C.BYTES_PER_SAMPLE[format]))
+        got = host[h * half + group.nbytes:h * half + group.nbytes + 4 * n].numpy().view("<i4")
+        clipped = [0] * n
+        for pos, i in enumerate(order):
+            clipped[i] = int(got[pos])
+        return list(range(group.lo, group.hi)), image, spans, clipped
+
+    pending = None
+    for g, group in enumerate(groups):
+        h = g % n_halves
+        order, event = _encode_group(generator, clips, lengths, counts, group, fmt, rated, input_rate, model_rate, out_rate, max_batch_samples,
+                                     dev_image, host[h * half:(h + 1) * half])
+        if pending is not None:
+            yield arrived(*pending)
+        pending = (group, h, order, event)
+    yield arrived(*pending)
 
 
 def resampled_length(length: int, orig_freq: int, new_freq: int) -> int:
