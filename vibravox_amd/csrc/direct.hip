@@ -1260,14 +1260,16 @@ extern "C" int eben_adam_step(const EbenAdamTensor* table, int ntensors, int64_t
   EBEN_REQUIRE(table && ntensors > 0 && step > 0, "bad adam arguments");
   const double bc1 = 1.0 - pow((double)beta1, step);
   const double bc2 = 1.0 - pow((double)beta2, step);
+  // the whole table is checked before the first launch: a bad entry in a later chunk must not leave the earlier chunks stepped
+  for (int i = 0; i < ntensors; ++i)
+    if (!table[i].param || !table[i].grad || !table[i].exp_avg || !table[i].exp_avg_sq || table[i].numel <= 0)
+      return fail(EBEN_EINVAL, "adam tensor %d is null or empty", i);
   for (int p0 = 0; p0 < ntensors; p0 += ADAM_CHUNK) {
     const int cnt = ntensors - p0 < ADAM_CHUNK ? ntensors - p0 : ADAM_CHUNK;
     AdamTable T;
     long long blocks = 0;
     for (int i = 0; i < cnt; ++i) {
       T.t[i] = table[p0 + i];
-      if (!T.t[i].param || !T.t[i].grad || !T.t[i].exp_avg || !T.t[i].exp_avg_sq || T.t[i].numel <= 0)
-        return fail(EBEN_EINVAL, "adam tensor %d is null or empty", p0 + i);
       blocks += (T.t[i].numel + ADAM_BLOCK_ELEMS - 1) / ADAM_BLOCK_ELEMS;
       if (blocks > 0x7fffffffLL) return fail(EBEN_EINVAL, "adam launch too large");
       T.bend[i] = (int)blocks;
