@@ -888,6 +888,35 @@ EBEN_API int eben_pcm_encode_plan(int* out, int n);
 EBEN_API int eben_pcm_encode_ragged(const float* src, long long src_floats, const EbenPcmEncRow* rows_host, const EbenPcmEncRow* rows_dev, void* image,
                                     long long image_bytes, int32_t* clipped, int rows, void* stream);
 
+/* ---- many tensors to one byte image and back (csrc/snapshot.hip): the device half of a checkpoint ------------------------------------
+ * Entry i is the nbytes bytes at the DEVICE pointer `tensor` (any alignment for kind 0; kind 1 is float32: pointer and nbytes multiples
+ * of 4) and the bytes [image_offset, image_offset + nbytes) of a flat DEVICE image of image_bytes bytes (pointer and size multiples of
+ * 16).  Every offset is a multiple of 16; nbytes 0 is legal and copies nothing.  The copies move bits (NaN payloads, -0.0 and denormals
+ * survive): a block owns eben_pack_plan's *block_bytes consecutive bytes of one entry; one that lies wholly inside its tensor with the
+ * tensor on the 16-byte grid moves 16-byte vectors, all loads before the first store, every other block goes byte by byte.
+ *   eben_pack_tensors    tensors -> image.  The table is in the image's order (offsets ascending, no overlap).  The padding in front of
+ *                        the first entry, between one entry's end and the next one's offset and behind the last up to image_bytes is
+ *                        written as zeros, so every byte of the image is written.  nonfinite[i] (n counters, zeroed here on the stream;
+ *                        may be null without a kind-1 entry) receives the number of infinities and NaNs of entry i when it is kind 1:
+ *                        integer sums, one atomicAdd per block that found any.  `reserved` is ignored.
+ *   eben_unpack_tensors  image -> tensors, the entries in any order (no overlap in the image).  Only the entries' own bytes are written.
+ *   eben_pack_plan       no launch: *blocks = the blocks eben_pack_tensors launches for the table (the last entry counted up to the
+ *                        next multiple of 16), *block_bytes = a block's bytes.  Either output may be null, and so may the table with n 0.
+ * The whole table is checked before the first launch: EBEN_EINVAL, nothing launched or written, for a null table, tensor or image,
+ * n < 1, a kind other than 0 / 1, negative nbytes, a float32 entry off the 4-byte grid, a misaligned or negative offset, an entry
+ * reaching past image_bytes, overlapping entries, and -- pack -- offsets that do not ascend or float32 entries without counters.
+ * Added without a version bump: functions and a POD type only. */
+typedef struct EbenPackEntry {
+  void* tensor;
+  long long image_offset;
+  long long nbytes;
+  int kind;       /* 0 bytes, 1 float32 */
+  int reserved;   /* 32 bytes */
+} EbenPackEntry;
+EBEN_API int eben_pack_tensors(const EbenPackEntry* table, int n, void* image, long long image_bytes, unsigned* nonfinite, void* stream);
+EBEN_API int eben_unpack_tensors(const EbenPackEntry* table, int n, const void* image, long long image_bytes, void* stream);
+EBEN_API int eben_pack_plan(const EbenPackEntry* table, int n, long long* blocks, int* block_bytes);
+
 /* ---- misc ------------------------------------------------------------------------------- */
 /* out[0] = sqrt(sum x^2) (torch.norm at eben.py:226); `out` must hold 257 floats (scratch) */
 EBEN_API int eben_l2norm(const float* x, size_t n, float* out, void* stream);

@@ -7,6 +7,10 @@ neither is available in this image, so this entry point carries a small resolver
 Hydra the EBEN configs use -- ``defaults`` lists with ``group@package: option``, ``_target_`` /
 ``_partial_`` instantiation, ``${key}`` interpolation and ``a.b=c`` / ``+a.b=c`` / ``++a.b=c`` overrides --
 and a plain training loop calling ``EBENLightningModule.training_step``.
+
+``+callbacks=bwe_checkpoint``, ``+logging=csv``, ``+ckpt_path=FILE`` or one of ``trainer.max_epochs``, ``trainer.check_val_every_n_epoch``,
+``trainer.limit_train_batches``, ``trainer.limit_val_batches`` selects the fit loop of ``vibravox_amd/fit.py`` instead: epochs with
+validation, checkpoints, resume, then the test split scored from ``last.ckpt``.
 """
 from __future__ import annotations
 
@@ -81,8 +85,13 @@ def _resolve(node: Any, root: Dict[str, Any]) -> Any:
     return node
 
 
+#: what the fit loop (vibravox_amd/fit.py) reads from the trainer node beyond configs/trainer/ddp.yaml's keys: Trainer arguments left
+#: at their defaults there, so `trainer.max_epochs=2` sets one without Hydra's "+"
+FIT_TRAINER_KEYS = ("max_epochs", "check_val_every_n_epoch", "limit_train_batches", "limit_val_batches")
+
+
 def compose(overrides: List[str]) -> Dict[str, Any]:
-    group_choice, value_overrides = {}, []
+    group_choice, value_overrides, added_groups = {}, [], {}
     for ov in overrides:
         key, _, val = ov.partition("=")
         bare = key.lstrip("+")
@@ -93,12 +102,18 @@ def compose(overrides: List[str]) -> Dict[str, Any]:
         is_group = os.path.isdir(os.path.join(CONFIG_DIR, *bare.split("."))) or bare in ("lightning_module", "lightning_datamodule", "trainer")
         if is_group and os.path.exists(os.path.join(CONFIG_DIR, *bare.split("."), val + ".yaml")):
             group_choice[bare] = val
+            if key.startswith("+"):   # Hydra's +group=option: a group the defaults list may not name (callbacks, logging)
+                added_groups[bare] = val
         else:
             value_overrides.append((key, yaml.safe_load(val)))
     cfg = _compose("", "run", group_choice)
+    for group, option in added_groups.items():
+        if group not in cfg:
+            cfg[group] = _compose(group, option, group_choice)
     for key, val in value_overrides:
-        create = key.startswith("+")
-        _set(cfg, key.lstrip("+"), val, create)
+        bare = key.lstrip("+")
+        create = key.startswith("+") or (bare.startswith("trainer.") and bare[len("trainer."):] in FIT_TRAINER_KEYS)
+        _set(cfg, bare, val, create)
     return _resolve(cfg, cfg)
 
 
@@ -146,6 +161,33 @@ def _batches(loader):
             raise RuntimeError("the train loader has no batch: fewer items than ranks, or than one batch with drop_last")
 
 
+def fit_requested(cfg: Dict[str, Any]) -> bool:
+    """Whether the invocation asks for the fit loop: a callbacks or logging group, a checkpoint to resume from, or one of the
+    trainer keys only that loop reads.  Without any of them ``main`` is the plain loop over ``trainer.max_steps`` steps."""
+    return any(k in cfg for k in ("callbacks", "logging", "ckpt_path")) or any(k in cfg.get("trainer", {}) for k in FIT_TRAINER_KEYS)
+
+
+def _fit(cfg: Dict[str, Any], argv: List[str], module, datamodule) -> int:
+    """``trainer.fit`` then ``trainer.test(ckpt_path="last")`` (vibravox run.py:76-80) on ``vibravox_amd.fit.Trainer``."""
+    from vibravox_amd.fit import Trainer
+
+    node, logging = cfg.get("trainer", {}), cfg.get("logging", {})
+    # configs/trainer/ddp.yaml's max_steps of 10 bounds the plain loop; a run given in epochs is bounded by it only when it says so
+    steps_given = any(a.lstrip("+").startswith("trainer.max_steps=") for a in argv)
+    trainer = Trainer(max_epochs=node.get("max_epochs"), max_steps=node.get("max_steps", -1) if steps_given or "max_epochs" not in node else -1,
+                      check_val_every_n_epoch=node.get("check_val_every_n_epoch", 1), limit_train_batches=node.get("limit_train_batches"),
+                      limit_val_batches=node.get("limit_val_batches"), log_every_n_steps=logging.get("log_every_n_steps", node.get("log_every_n_steps", 1)),
+                      callbacks=list(instantiate(cfg.get("callbacks", {})).values()), logger=instantiate(logging.get("logger")), freeze_gc=True)
+    trainer.fit(module, datamodule, ckpt_path=cfg.get("ckpt_path"))
+    print(f"fit: {trainer.global_step} steps, {trainer.current_epoch} epochs; validation: "
+          + " ".join(f"{k}={v:.4f}" for k, v in trainer.callback_metrics.items()), flush=True)
+    checkpoint = trainer.checkpoint_callback
+    if checkpoint is not None and checkpoint.save_last and hasattr(datamodule, "test_clips"):
+        for name, value in trainer.test(module, datamodule, ckpt_path="last").items():
+            print(f"{name}={value:.4f}", flush=True)
+    return 0
+
+
 def main(argv: List[str]) -> int:
     from vibravox_amd._env import configure_hw_queues
     configure_hw_queues()   # data-parallel ranks: before the first HIP call
@@ -162,6 +204,8 @@ def main(argv: List[str]) -> int:
         module.set_precision(trainer["precision"])
     if hasattr(datamodule, "setup"):
         datamodule.setup("fit")
+    if fit_requested(cfg):
+        return _fit(cfg, argv, module, datamodule)
     loader = _batches(datamodule.train_dataloader())
     import gc
     for step in range(int(trainer.get("max_steps", 10))):

@@ -112,6 +112,10 @@ class EbenPcmEncRow(ctypes.Structure):
     _fields_ = [("src_offset", c_int64), ("byte_offset", c_int64), ("samples", c_int32), ("format", c_int32)]
 
 
+class EbenPackEntry(ctypes.Structure):
+    _fields_ = [("tensor", c_void_p), ("image_offset", c_int64), ("nbytes", c_int64), ("kind", c_int32), ("reserved", c_int32)]
+
+
 class EbenClip(ctypes.Structure):
     _fields_ = [("data", c_void_p), ("length", c_int64)]
 
@@ -278,6 +282,9 @@ SIGNATURES = {
     "eben_pcm_resample_ragged": (c_int, [_P, c_int64, _P, _P, _P, _P, _P, _P, _P, c_int, c_int64, c_int, c_int, c_int, _P]),
     "eben_pcm_encode_plan": (c_int, [POINTER(c_int), c_int]),
     "eben_pcm_encode_ragged": (c_int, [_P, c_int64, _P, _P, _P, c_int64, _P, c_int, _P]),
+    "eben_pack_tensors": (c_int, [POINTER(EbenPackEntry), c_int, _P, c_int64, _P, _P]),
+    "eben_unpack_tensors": (c_int, [POINTER(EbenPackEntry), c_int, _P, c_int64, _P]),
+    "eben_pack_plan": (c_int, [POINTER(EbenPackEntry), c_int, POINTER(c_int64), POINTER(c_int)]),
 }
 
 _lib: Optional[ctypes.CDLL] = None
@@ -323,6 +330,13 @@ def pcm_encode_tile() -> int:
     out = (c_int * 1)()
     check(load().eben_pcm_encode_plan(out, 1), "pcm_encode_plan")
     return int(out[0])
+
+
+def pack_block_bytes() -> int:
+    """Bytes of one entry that a block of ``eben_pack_tensors`` / ``eben_unpack_tensors`` owns (``eben_pack_plan``; no GPU needed)."""
+    out = c_int(0)
+    check(load().eben_pack_plan(None, 0, None, ctypes.byref(out)), "pack_plan")
+    return int(out.value)
 
 
 def ptr(t: Optional[torch.Tensor]) -> Optional[int]:
