@@ -888,6 +888,66 @@ EBEN_API int eben_pcm_encode_plan(int* out, int n);
 EBEN_API int eben_pcm_encode_ragged(const float* src, long long src_floats, const EbenPcmEncRow* rows_host, const EbenPcmEncRow* rows_dev, void* image,
                                     long long image_bytes, int32_t* clipped, int rows, void* stream);
 
+/* ---- live sessions in and out as PCM at the caller's rate (csrc/stream_pcm.hip): the pool's front and back end, one launch each ----------
+ * eben_stream_pcm_out: the back end of all sessions of one run -- what eben_rate_splice_slots, eben_resample_slots and
+ * eben_pcm_encode_ragged do one after the other, per slot, without the float FIFO between them.  The state is two tapes of `slots` rows
+ * (row pitch tape_pitch floats) as in eben_rate_splice_slots; `src` holds src_rows rows of src_pitch floats (the model-rate samples a run
+ * emitted, one row per session); `image` is a flat DEVICE byte image of image_bytes < 2^31 bytes (16-byte aligned).  Pieces are read from
+ * HOST memory, validated, and passed to the kernel by value: at most EBEN_STREAM_PCM_MAX_PIECES per call, one launch.  Per piece:
+ *   tape     with out = tapes[tape] and in = tapes[1 - tape]: out[slot][0 : n_carry + n_new) = [ in[slot][prev_off : prev_off + n_carry) |
+ *            src[src_row][0 : n_new) ], exactly what eben_rate_splice_slots leaves behind -- also when n_out == 0 (a push below the
+ *            look-ahead completes no output);
+ *   outputs  output n < n_out is what eben_resample_stream computes on that tape (len = n_carry + n_new) with ratios[ratio] (`kernels` its
+ *            (nw, 2 * width + orig) device table), p0, base0 and end: acc = 0, acc = fmaf(k[j], x[j], acc) in ascending j over all taps,
+ *            taps outside [0, len) reading zero -- bit for bit the outputs of eben_resample_slots;
+ *   store    each output converted by the rules of eben_pcm_encode_ragged (rint(x * 2^(b-1)) half to even, clamped, a NaN as 0;
+ *            EBEN_PCM_F32 the bits) to image + byte_offset + n * bytes per sample, byte_offset a multiple of 16; clipped[slot] (int32
+ *            DEVICE table of `slots` entries, accumulated and never cleared here) grows by the count eben_pcm_encode_ragged would report.
+ *   ratio == -1 (the session leaves at the model's rate): output n = src[src_row][n], n_out == n_new, n_carry == 0; no tape is touched
+ *            (both tapes may be NULL when no piece resamples).
+ * The blocks of a piece read only tapes[1 - tape] and src and write only tapes[tape] and the image: no launch reads what it writes.
+ * The grid is (tiles of the largest piece, pieces), 256 threads, consecutive lanes consecutive outputs; the window is staged in LDS from
+ * its two sources, the table beside it when it fits (else read through L2); stores go out sample by sample.
+ *   eben_stream_pcm_plan  the tile of a ratio, without a launch: out[0..2] (n >= 3) = outputs per block, floats of the input window staged
+ *     in LDS, the table's route (0 through L2, 1 in LDS, 2 in LDS with one value per tap for every output).  orig == nw == 1 with width 0
+ *     states the tile of ratio == -1.
+ * EBEN_EINVAL before any launch, nothing written, for: a null or misaligned pointer (image to 16 bytes, the others to 4); slots outside
+ * 1 ... EBEN_STREAM_MAX_SLOTS; a negative count or more than EBEN_STREAM_PCM_MAX_PIECES pieces; image_bytes negative or not below 2^31;
+ * a slot, src_row, tape, ratio, format or end outside its range; per piece what eben_rate_splice_slots, eben_resample_slots and
+ * eben_pcm_encode_ragged refuse (negative offsets or counts, n_carry + n_new == 0 or past tape_pitch, prev_off + n_carry past tape_pitch,
+ * n_new past src_pitch, a ratio that fits no tile, a phase outside [0, nw), n_out past what the tape serves, a byte_offset that is
+ * negative or no multiple of 16, bytes past image_bytes); ratio == -1 with n_carry != 0 or n_out != n_new; two pieces on one slot; two
+ * pieces whose byte ranges overlap; the extents of the tapes, src, the image, clipped and the tables in use overlapping where one of
+ * them is written.  An empty list returns EBEN_OK without a launch.
+ *
+ * eben_pcm_chunks_in: the front of all sessions of a tick.  Chunk i is `n` mono samples of `format` at the DEVICE pointer `bytes` (any
+ * alignment: a frame inside a network buffer), converted exactly as eben_pcm_decode_ragged converts them, to dst[dst_row][0 : n) of a
+ * (rows, pitch) float32 buffer; nothing else is written.  Descriptors are read from HOST memory, validated and passed by value: at most
+ * EBEN_PCM_MAX_CHUNKS per call, one launch; a block owns EBEN_PCM_CHUNK_TILE consecutive samples of one chunk.  EBEN_EINVAL before any
+ * launch, nothing written, for: a null table, a null or misaligned-to-4 dst, a negative count or more than EBEN_PCM_MAX_CHUNKS chunks,
+ * rows or pitch below 1, null bytes with n > 0, negative n or n past the pitch, an unknown format, a dst_row outside [0, rows), two
+ * chunks on one row, a chunk's bytes overlapping dst's extent.  Chunks of 0 samples are legal; nothing to convert returns EBEN_OK
+ * without a launch.  Added without a version bump: functions and POD types only. */
+#define EBEN_STREAM_PCM_MAX_PIECES 64
+#define EBEN_PCM_MAX_CHUNKS 64
+#define EBEN_PCM_CHUNK_TILE 1024
+typedef struct EbenStreamPcmPiece {
+  int prev_off, n_carry, n_new, p0, base0, n_out, byte_offset;
+  unsigned short src_row;
+  unsigned char slot, tape;
+  signed char ratio;                     /* -1: no resampling */
+  unsigned char format, end, reserved;   /* 36 bytes: 64 pieces and the ratios stay below eben_resample_slots' piece table */
+} EbenStreamPcmPiece;
+typedef struct EbenPcmChunk {
+  const void* bytes;
+  int n, format, dst_row;   /* 24 bytes with the tail padding */
+} EbenPcmChunk;
+EBEN_API int eben_stream_pcm_plan(int orig, int nw, int width, int* out, int n);
+EBEN_API int eben_stream_pcm_out(float* tape0, float* tape1, int tape_pitch, int slots, const float* src, int src_pitch, int src_rows,
+                                 const EbenRateRatio* ratios, int n_ratios, void* image, long long image_bytes, int32_t* clipped,
+                                 const EbenStreamPcmPiece* pieces, int count, void* stream);
+EBEN_API int eben_pcm_chunks_in(const EbenPcmChunk* chunks, int count, float* dst, int rows, int pitch, void* stream);
+
 /* ---- many tensors to one byte image and back (csrc/snapshot.hip): the device half of a checkpoint ------------------------------------
  * Entry i is the nbytes bytes at the DEVICE pointer `tensor` (any alignment for kind 0; kind 1 is float32: pointer and nbytes multiples
  * of 4) and the bytes [image_offset, image_offset + nbytes) of a flat DEVICE image of image_bytes bytes (pointer and size multiples of

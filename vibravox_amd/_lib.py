@@ -112,6 +112,18 @@ class EbenPcmEncRow(ctypes.Structure):
     _fields_ = [("src_offset", c_int64), ("byte_offset", c_int64), ("samples", c_int32), ("format", c_int32)]
 
 
+STREAM_PCM_MAX_PIECES, PCM_MAX_CHUNKS, PCM_CHUNK_TILE = 64, 64, 1024   # EBEN_STREAM_PCM_MAX_PIECES, EBEN_PCM_MAX_CHUNKS, EBEN_PCM_CHUNK_TILE
+
+
+class EbenStreamPcmPiece(ctypes.Structure):
+    _fields_ = ([(k, c_int) for k in ("prev_off", "n_carry", "n_new", "p0", "base0", "n_out", "byte_offset")] + [("src_row", ctypes.c_uint16)]
+                + [(k, ctypes.c_uint8) for k in ("slot", "tape")] + [("ratio", ctypes.c_int8)] + [(k, ctypes.c_uint8) for k in ("format", "end", "reserved")])
+
+
+class EbenPcmChunk(ctypes.Structure):
+    _fields_ = [("bytes", c_void_p), ("n", c_int32), ("format", c_int32), ("dst_row", c_int32)]
+
+
 class EbenPackEntry(ctypes.Structure):
     _fields_ = [("tensor", c_void_p), ("image_offset", c_int64), ("nbytes", c_int64), ("kind", c_int32), ("reserved", c_int32)]
 
@@ -282,6 +294,10 @@ SIGNATURES = {
     "eben_pcm_resample_ragged": (c_int, [_P, c_int64, _P, _P, _P, _P, _P, _P, _P, c_int, c_int64, c_int, c_int, c_int, _P]),
     "eben_pcm_encode_plan": (c_int, [POINTER(c_int), c_int]),
     "eben_pcm_encode_ragged": (c_int, [_P, c_int64, _P, _P, _P, c_int64, _P, c_int, _P]),
+    "eben_stream_pcm_plan": (c_int, [c_int, c_int, c_int, POINTER(c_int), c_int]),
+    "eben_stream_pcm_out": (c_int, [_P, _P, c_int, c_int, _P, c_int, c_int, POINTER(EbenRateRatio), c_int, _P, c_int64, _P, POINTER(EbenStreamPcmPiece),
+                                    c_int, _P]),
+    "eben_pcm_chunks_in": (c_int, [POINTER(EbenPcmChunk), c_int, _P, c_int, c_int, _P]),
     "eben_pack_tensors": (c_int, [POINTER(EbenPackEntry), c_int, _P, c_int64, _P, _P]),
     "eben_unpack_tensors": (c_int, [POINTER(EbenPackEntry), c_int, _P, c_int64, _P]),
     "eben_pack_plan": (c_int, [POINTER(EbenPackEntry), c_int, POINTER(c_int64), POINTER(c_int)]),

@@ -53,14 +53,33 @@ def _rated(input_rate, model_rate) -> bool:
 
 
 @torch.no_grad()
-def enhance_stream(generator, clip: torch.Tensor, chunk_samples: int = STREAM_CHUNK, input_rate: Optional[int] = None, model_rate: int = 16000):
+def enhance_stream(generator, clip: torch.Tensor, chunk_samples: int = STREAM_CHUNK, input_rate: Optional[int] = None, model_rate: int = 16000,
+                   output_rate: Optional[int] = None, format: Optional[str] = None):
     """One long ``clip`` (rows, 1, T) through a ``streaming.StreamingEnhancer`` in pushes of ``chunk_samples``: the activations alive at
     any time are those of one chunk plus the stream state, not those of the whole recording.  Returns what
     ``generator(generator.cut_to_valid_length(clip))`` returns, (enhanced (rows, 1, T'), bands (rows, m, L)).  Nothing here waits for
     the device.  With ``input_rate`` the clip is at that rate and enters in pushes of ``chunk_samples`` model-rate samples' worth
     (``StreamingEnhancer.input_chunk_samples``); the result is that of ``augment.resample(clip, input_rate, model_rate)``, at the
-    model's rate."""
+    model's rate.
+
+    ``output_rate`` / ``format`` (one of ``corpus.FORMATS``): the enhanced samples leave every push through the enhancer's way out
+    (``StreamingEnhancer(output_rate=, output_format=)``) and the call returns their concatenation alone: uint8 (rows, bytes) with
+    ``format``, else float32 (rows, 1, T'') at ``output_rate``."""
     from . import streaming
+
+    if format is not None or (output_rate is not None and int(output_rate) != int(model_rate)):
+        if clip.dim() != 3 or clip.shape[1] != 1 or clip.dtype is not torch.float32:
+            raise ValueError(f"enhance_stream: expected a float32 (rows, 1, T) tensor, got {clip.dtype} {tuple(clip.shape)}")
+        rated = _rated(input_rate, model_rate)
+        total = clip.shape[2]
+        ragged.plan(generator, [resampled_length(total, input_rate, model_rate) if rated else total])
+        enhancer = streaming.StreamingEnhancer(generator, chunk_samples, streams=clip.shape[0], input_rate=input_rate if rated else None,
+                                               model_rate=model_rate, output_rate=output_rate, output_format=format)
+        chunk, parts = enhancer.input_chunk_samples, []
+        for pos in range(0, total - chunk + 1, chunk):
+            parts.append(enhancer.push(clip[:, :, pos : pos + chunk]))
+        parts.append(enhancer.finish(clip[:, :, len(parts) * chunk :]))
+        return torch.cat(parts, dim=-1)
 
     if clip.dim() != 3 or clip.shape[1] != 1 or clip.dtype is not torch.float32:
         raise ValueError(f"enhance_stream: expected a float32 (rows, 1, T) tensor, got {clip.dtype} {tuple(clip.shape)}")

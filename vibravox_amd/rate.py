@@ -26,7 +26,10 @@ into the tape's ping-pong twin -- the carry is never updated by the launch that 
 ``tests/rate_oracle.py`` executes it in float64.  ``ChunkFront`` is the resampler in front of a consumer of whole chunks
 (``streaming.StreamingEnhancer(input_rate=...)``).  ``SlotFront`` is the same front for independent sessions in the slots of one state
 (``streaming.StreamPool(input_rates=...)``): a ``Schedule`` and a parity per slot on the host, and two launches for all slots of a tick
-(``eben_rate_splice_slots``, ``eben_resample_slots``: per-slot descriptors by value), executed by ``SlotTapes``.
+(``eben_rate_splice_slots``, ``eben_resample_slots``: per-slot descriptors by value), executed by ``SlotTapes``.  ``SlotBack`` is its
+mirror behind the model (``streaming.StreamPool(output_rates=...)``): a ``Schedule(model_rate, output_rate)`` and a parity per slot, and
+ONE launch for all sessions of a run that splices, resamples and encodes to PCM bytes (``eben_stream_pcm_out``, ``csrc/stream_pcm.hip``),
+executed by ``BackTapes``; ``pcm_chunks_in`` is the PCM front of a tick (``eben_pcm_chunks_in``).
 """
 from __future__ import annotations
 
@@ -571,3 +574,202 @@ class SlotTapes:
                                                                                            p.ratio, p.tape, p.fifo) for p in part]))
             check(lib.eben_resample_slots(ptr(self.tapes[0]), ptr(self.tapes[1]), f.tape_samples, ptr(self.fifo[0]), ptr(self.fifo[1]), f.chunk_samples,
                                           f.slots, self.ratios, len(self.tables), table, len(part), stream()), "resample_slots")
+
+
+# ---- the way out: sessions that leave as PCM at the caller's rate (streaming.StreamPool with output_rates) ----------------------------
+class BackPiece(NamedTuple):
+    """One session of one run, for ``eben_stream_pcm_out``: slot ``slot`` emitted row ``src_row`` of the run's compact output, ``n_new``
+    samples at the model's rate.  ``ratio`` -1: they leave as they are (``n_out == n_new``).  Else tape ``tape`` of the slot :=
+    ``[the other tape[prev_off : prev_off + n_carry] | those samples]`` and ``n_out`` outputs of it at ratio ``ratio`` with ``p0``,
+    ``base0``, ``end`` as in ``RatePush``.  The outputs go to the image as ``format`` (an index of ``corpus.FORMATS``) from
+    ``byte_offset`` on, a multiple of 16."""
+    slot: int
+    src_row: int
+    ratio: int
+    tape: int
+    prev_off: int
+    n_carry: int
+    n_new: int
+    p0: int
+    base0: int
+    n_out: int
+    end: bool
+    format: int
+    byte_offset: int
+
+    @property
+    def nbytes(self) -> int:
+        return self.n_out * PCM_BYTES[self.format]
+
+
+PCM_FORMATS = ("PCM16", "PCM24", "PCM32", "FLOAT32")   # corpus.FORMATS: index = EBEN_PCM_*
+PCM_BYTES = (2, 3, 4, 4)                               # bytes per sample
+
+
+def pcm_format(format, who: str = "rate") -> int:
+    """The index of a format name; ``ValueError`` naming the four that exist."""
+    if format not in PCM_FORMATS:
+        raise ValueError(f"{who}: format must be one of {', '.join(PCM_FORMATS)}, got {format!r}")
+    return PCM_FORMATS.index(format)
+
+
+@dataclasses.dataclass
+class _BackSlot:
+    ratio: int                      # -1: leaves at the model's rate
+    schedule: Optional[Schedule]
+    format: int
+    tape: int = 0                   # the current tape of the slot's two
+
+
+class SlotBack:
+    """``SlotFront``'s mirror behind the model (host only, no GPU needed): every slot has a ``Schedule(model_rate, output_rate)`` and a
+    parity of tapes of its own.  ``emit`` turns "slot s emitted k samples (final or not)" into the pieces of one ``eben_stream_pcm_out``
+    call and the byte range of every session in one image: each session's bytes contiguous, each starting at a 16-byte boundary.
+    ``BackTapes`` executes the pieces on the device.  Any ratio the kernels' tile admits may be declared: there is no whole-chunk
+    condition on this side, the number of samples a push returns simply varies (``final_outputs``).  ``max_emit``: the most samples a
+    slot emits in one run (a finish hands over the model's latency and a tail at once); the tapes are sized for it."""
+
+    def __init__(self, chunk_samples: int, slots: int, output_rates, model_rate: int = 16000, max_emit: Optional[int] = None):
+        from ._lib import RATE_MAX_RATIOS
+
+        self.chunk_samples, self.slots, self.model_rate = int(chunk_samples), int(slots), int(model_rate)
+        self.max_emit = max(self.chunk_samples, int(max_emit or 0))
+        self.declared = tuple(int(r) for r in output_rates)
+        self.rates: List[int] = []                 # the declared rates that need resampling; a slot's ``ratio`` indexes these lists
+        self.ratios: List[Tuple[int, int, int]] = []
+        for r in self.declared:
+            if r == self.model_rate or r in self.rates:
+                continue
+            orig, new, width = ratio(self.model_rate, r)
+            tile_of_back(orig, new, width)         # refuses a ratio that fits no tile, in the library's words
+            self.rates.append(r)
+            self.ratios.append((orig, new, width))
+        if len(self.rates) > RATE_MAX_RATIOS:
+            raise ValueError(f"{len(self.rates)} output rates to resample, at most {RATE_MAX_RATIOS}")
+        self.tape_samples = max((2 * w + o - 1 + self.max_emit for o, _, w in self.ratios), default=0)
+        self.slot: List[Optional[_BackSlot]] = [None] * self.slots
+
+    def check(self, output_rate: Optional[int], format: Optional[str], who: str = "rate") -> Tuple[Optional[int], int]:
+        """(the rate to resample to or None, the format's index) of a session that asks for ``output_rate`` and ``format``; ``ValueError``
+        for a rate that was not declared or a format that does not exist.  Only a rate: FLOAT32."""
+        fmt = pcm_format("FLOAT32" if format is None else format, who)
+        if output_rate is None or int(output_rate) == self.model_rate:
+            return None, fmt
+        if int(output_rate) not in self.rates:
+            raise ValueError(f"{who}: a session that leaves at {int(output_rate)} Hz in a pool that declared output_rates = {self.declared} "
+                             f"(the model's {self.model_rate} Hz needs no declaration)")
+        return int(output_rate), fmt
+
+    def open(self, slot: int, output_rate: Optional[int], format: Optional[str]) -> None:
+        """Slot ``slot`` starts a stream that leaves at ``output_rate`` as ``format``: nothing is carried over, the tapes need no clearing."""
+        r, fmt = self.check(output_rate, format)
+        self.slot[slot] = _BackSlot(-1, None, fmt) if r is None else _BackSlot(self.rates.index(r), Schedule(self.model_rate, r), fmt)
+
+    def release(self, slot: int) -> None:
+        self.slot[slot] = None
+
+    def lookahead(self, slot: int) -> int:
+        """Model-rate samples past an output's own position that its value depends on, at most."""
+        st = self.slot[slot]
+        return 0 if st.schedule is None else st.schedule.lookahead
+
+    def emit(self, emits):
+        """``emits``: (slot, row of the run's compact output, samples emitted, final) per session of one run, each slot once.
+        Returns ``(pieces, ranges, image_bytes)``: the pieces of the call, per slot the ``(byte_offset, samples)`` of its outputs in the
+        image, and the image's size.  A session that emitted nothing and goes on has no piece and an empty range."""
+        pieces: List[BackPiece] = []
+        ranges: dict = {}
+        at = 0
+        for slot, row, k, final in emits:
+            st, k = self.slot[slot], int(k)
+            if slot in ranges or st is None:
+                raise RuntimeError(f"rate back: slot {slot} is {'named twice' if slot in ranges else 'not open'}")
+            if not 0 <= k <= self.max_emit:
+                raise RuntimeError(f"rate back: slot {slot} emitted {k} samples in one run, the tapes were sized for {self.max_emit}")
+            at = -(-at // 16) * 16
+            if st.schedule is None:
+                piece = BackPiece(slot, row, -1, 0, 0, 0, k, 0, 0, k, bool(final), st.format, at) if k else None
+            elif k == 0 and not final:
+                piece = None
+            else:
+                op = st.schedule.push(k, final)
+                if op.length:
+                    st.tape ^= 1
+                    piece = BackPiece(slot, row, st.ratio, st.tape, op.prev_off, op.n_carry, op.n_new, op.p0, op.base0, op.n_out, op.end, st.format, at)
+                else:
+                    piece = None
+            if piece is None:
+                ranges[slot] = (at, 0)
+                continue
+            pieces.append(piece)
+            ranges[slot] = (at, piece.n_out)
+            at += piece.nbytes
+        return pieces, ranges, at
+
+
+def tile_of_back(orig: int, new: int, width: int) -> dict:
+    """``eben_stream_pcm_out``'s tile for a ratio (``eben_stream_pcm_plan``; no GPU needed): ``outputs_per_block``, ``window_floats`` of
+    input staged in LDS and ``table_route`` (0 through L2, 1 in LDS, 2 in LDS with one value per tap).  (1, 1, 0): no resampling."""
+    from ._lib import check, load
+
+    out = (ctypes.c_int * 3)()
+    check(load().eben_stream_pcm_plan(orig, new, width, out, 3), "stream_pcm_plan")
+    return dict(outputs_per_block=out[0], window_floats=out[1], table_route=out[2])
+
+
+_BACK_POD = struct.Struct("=7iH2Bb3B")   # EbenStreamPcmPiece as bytes
+
+
+def pack_back_pieces(pieces):
+    """The ``EbenStreamPcmPiece`` table of a list of ``BackPiece``."""
+    from ._lib import EbenStreamPcmPiece
+
+    return (EbenStreamPcmPiece * len(pieces)).from_buffer_copy(b"".join([_BACK_POD.pack(
+        p.prev_off, p.n_carry, p.n_new, p.p0, p.base0, p.n_out, p.byte_offset, p.src_row, p.slot, p.tape, p.ratio, p.format, 1 if p.end else 0, 0) for p in pieces]))
+
+
+class BackTapes:
+    """The device state of a ``SlotBack`` and the executor of its pieces: two tapes ``(slots, tape_samples)``, the ``clipped`` table (int32,
+    one counter per slot, accumulated by the kernel and zeroed when a slot is opened) and the declared ratios' tables
+    (``augment.resample``'s own), allocated here once.  The image of a call is allocated by that call."""
+
+    def __init__(self, back: SlotBack, device):
+        from ._lib import EbenRateRatio
+
+        self.back, self.device = back, torch.empty(0, device=device).device
+        self.tapes = [torch.empty((back.slots, max(back.tape_samples, 1)), dtype=torch.float32, device=self.device) for _ in range(2)]
+        self.clipped = torch.zeros(back.slots, dtype=torch.int32, device=self.device)
+        self.tables = [_table(back.model_rate, r, self.device)[0] for r in back.rates]
+        self.ratios = (EbenRateRatio * max(len(self.tables), 1))(*[EbenRateRatio(t.data_ptr(), o, n, w, 0) for t, (o, n, w) in zip(self.tables, back.ratios)])
+        self._counts = self.clipped.unbind(0)   # a 0-dim view per slot, built once
+
+    def count(self, slot: int) -> torch.Tensor:
+        return self._counts[slot]
+
+    def run(self, pieces, image_bytes: int, src: Optional[torch.Tensor], image: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``src``: the run's compact output (rows, 1, k) or (rows, k), or None when nothing was emitted.  Returns the image (uint8, 1-D,
+        allocated here unless given); one launch per ``STREAM_PCM_MAX_PIECES`` pieces, nothing waits."""
+        from ._lib import STREAM_PCM_MAX_PIECES, check, load, ptr, stream
+
+        b = self.back
+        if image is None:
+            image = torch.empty(max(int(image_bytes), 16), dtype=torch.uint8, device=self.device)
+        rows, pitch = (0, 0) if src is None else (src.shape[0], src.shape[-1])
+        for i in range(0, len(pieces), STREAM_PCM_MAX_PIECES):
+            part = pieces[i : i + STREAM_PCM_MAX_PIECES]
+            check(load().eben_stream_pcm_out(ptr(self.tapes[0]), ptr(self.tapes[1]), self.tapes[0].shape[1], b.slots, ptr(src), pitch, rows, self.ratios,
+                                             len(self.tables), image.data_ptr(), image.numel(), self.clipped.data_ptr(), pack_back_pieces(part), len(part),
+                                             stream()), "stream_pcm_out")
+        return image
+
+
+def pcm_chunks_in(chunks, dst: torch.Tensor) -> None:
+    """``eben_pcm_chunks_in``: ``chunks`` is a list of ``(bytes, samples, format index, dst_row)`` with ``bytes`` a uint8 device tensor (any
+    alignment); row ``dst_row`` of the float32 ``(rows, pitch)`` buffer ``dst`` receives the converted samples.  One launch per
+    ``PCM_MAX_CHUNKS`` chunks, nothing waits."""
+    from ._lib import PCM_MAX_CHUNKS, EbenPcmChunk, check, load, ptr, stream
+
+    for i in range(0, len(chunks), PCM_MAX_CHUNKS):
+        part = chunks[i : i + PCM_MAX_CHUNKS]
+        table = (EbenPcmChunk * len(part))(*[EbenPcmChunk(t.data_ptr(), n, f, r) for t, n, f, r in part])
+        check(load().eben_pcm_chunks_in(table, len(part), ptr(dst), dst.shape[0], dst.shape[1], stream()), "pcm_chunks_in")

@@ -28,6 +28,9 @@ Everything here is arithmetic on positions (host only, no GPU needed):
     In a ``StreamPool(input_rates=...)`` every session has a rate of its own: ``rate.SlotFront`` keeps a resampler schedule and a FIFO per
     slot, one splice launch and one resampling launch serve all slots that push in a tick (``FrontRun``), and the chunk a session's
     FIFO completes is its push of that tick (``Hand``).
+  * The way out mirrors that front: ``StreamPool(output_rates=...)`` / ``StreamingEnhancer(output_rate=, output_format=)`` hand every
+    run's emitted samples to ``rate.SlotBack``, whose one launch resamples them per slot with carried state and stores them as PCM
+    bytes; ``input_format=`` lets the pushes arrive as PCM bytes, decoded by one launch per tick.
 
 Audio hold-back: ``cut_to_valid_length`` drops up to ``multiple - 1`` samples from the end of a clip, so a sample pushed now may turn
 out to lie behind the stream's valid length.  The analysis bank therefore treats only ``ragged.cut_length(pushed)`` samples as
@@ -482,17 +485,44 @@ class StreamingEnhancer(_Driver):
     the final model-rate samples in a device FIFO and hands the enhancer whole chunks; at the end it makes as many pushes as the FIFO
     holds, then ``finish`` with the rest.  Known cost: the resampler's look-ahead is ``width + orig - 1`` input samples (7 model-rate
     samples at 3:1), so a push completes one chunk less that lag and the enhancer gets chunk k - 1 at push k: one ``chunk_samples`` of
-    extra latency (16 ms at 256), which ``input_latency`` states in input samples."""
+    extra latency (16 ms at 256), which ``input_latency`` states in input samples.
+
+    ``output_format`` (one of ``corpus.FORMATS``), ``output_rate``: the enhanced samples leave as PCM bytes, at a rate of their own -- per
+    call a uint8 ``(streams, k * bytes per sample)`` view into ``image`` (every row starts at a 16-byte boundary), k by
+    ``rate.final_outputs`` at ``output_rate``; ``finish`` hands over what the resampler held back (``output_lookahead`` model-rate
+    samples).  Only ``output_rate``: float32 ``(streams, 1, k)`` at that rate.  ``clipped``: int32 ``(streams,)`` on the device, the samples
+    the encoder clamped so far.  ``input_format``: ``push`` takes uint8 ``(streams, input_chunk_samples * bytes per sample)`` of that
+    format, ``finish`` a shorter tail.  Both are the pool's kernels (``eben_stream_pcm_out``, ``eben_pcm_chunks_in``) with slot = row:
+    one launch each per 64 rows and run."""
 
     _who, _last = "StreamingEnhancer", "finish"
 
     def __init__(self, generator, chunk_samples: int, streams: int = 1, return_bands: bool = False, input_rate: Optional[int] = None,
-                 model_rate: int = 16000):
+                 model_rate: int = 16000, output_rate: Optional[int] = None, output_format: Optional[str] = None, input_format: Optional[str] = None):
         if int(streams) < 1:
             raise ValueError(f"streams must be positive, got {streams}")
         self.streams = int(streams)
         super().__init__(generator, chunk_samples, return_bands)
         self._schedule = Schedule(generator, chunk_samples)
+        self.output_rate = int(model_rate) if output_rate is None else int(output_rate)
+        self.output_format, self.input_format = output_format, input_format
+        self._back = self._back_tapes = self._staging = None   # rate.SlotBack and rate.BackTapes with slot = row; the decoded PCM chunk
+        self.clipped = self.image = None
+        self.output_lookahead = 0
+        if output_format is not None or self.output_rate != int(model_rate):
+            from . import rate
+
+            if self.streams > 256:
+                raise ValueError(f"StreamingEnhancer: at most 256 streams leave as PCM or at a rate of their own, got {streams}")
+            most = max(self.plan.latency, self.plan.warmup_pushes * self.chunk_samples) + self.chunk_samples
+            self._back = rate.SlotBack(self.chunk_samples, self.streams, (self.output_rate,), model_rate, most)
+            self._back.check(self.output_rate, output_format, "StreamingEnhancer")
+            self._open_back()
+            self.output_lookahead = self._back.lookahead(0)
+        if input_format is not None:
+            from . import rate
+
+            rate.pcm_format(input_format, "StreamingEnhancer")
         self._front = None   # rate.ChunkFront: the resampler and its FIFO, when the stream arrives at another rate
         if input_rate is not None and int(input_rate) != int(model_rate):
             from . import rate
@@ -514,11 +544,24 @@ class StreamingEnhancer(_Driver):
         orig, new = self._ratio
         return self._front.input_chunk_samples + _ceil(self.plan.latency * orig, new)
 
+    def _open_back(self) -> None:
+        for r in range(self.streams):
+            self._back.open(r, self.output_rate, self.output_format)
+
     def prepare(self, device) -> "StreamingEnhancer":
         """Allocates the state on ``device`` now instead of at the first push (it is allocated once either way)."""
         self._allocate(device, self.streams)
         if self._front is not None:
             self._front.prepare(device)
+        if self._back is not None and (self._back_tapes is None or self._back_tapes.device != self.state.device):
+            from . import rate
+
+            self._back_tapes = rate.BackTapes(self._back, self.state.device)
+            self.clipped = self._back_tapes.clipped
+        if self.input_format is not None and (self._staging is None or self._staging.device != self.state.device):
+            import torch
+
+            self._staging = torch.zeros((self.streams, 1, self.input_chunk_samples), dtype=torch.float32, device=self.state.device)
         return self
 
     def reset(self) -> None:
@@ -528,6 +571,38 @@ class StreamingEnhancer(_Driver):
             self.state.reset()
         if self._front is not None:
             self._front.reset()
+        if self._back is not None:
+            self._open_back()
+            if self.clipped is not None:
+                self.clipped.zero_()
+
+    def _leave(self, src, final: bool):
+        """The way out of one run: ``src`` its ``enhanced`` (streams, 1, k) or None.  Returns the rows' bytes (or float32 samples) in a
+        fresh image, every row at a 16-byte boundary."""
+        import torch
+
+        from . import rate
+
+        k = 0 if src is None else src.shape[2]
+        pieces, ranges, _ = self._back.emit([(r, r, k, final) for r in range(self.streams)])
+        n, b = ranges[0][1], 4 if self.output_format is None else rate.PCM_BYTES[rate.PCM_FORMATS.index(self.output_format)]
+        pitch = -(-(n * b) // 16) * 16
+        self.image = torch.empty(max(16, self.streams * pitch), dtype=torch.uint8, device=self.state.device)
+        if pieces:
+            self._back_tapes.run(pieces, self.image.numel(), src, self.image)
+        rows = self.image[: self.streams * pitch].view(self.streams, pitch)[:, : n * b]
+        if self.output_format is not None:
+            return rows
+        return rows.view(torch.float32).unsqueeze(1) if n else torch.empty((self.streams, 1, 0), dtype=torch.float32, device=self.state.device)
+
+    def _nothing(self, device):
+        """What a call returns that ran nothing."""
+        import torch
+
+        got = self._emitted({}, self.streams, device)
+        if self.output_format is not None:
+            got[0] = torch.empty((self.streams, 0), dtype=torch.uint8, device=device)
+        return tuple(got) if self.return_bands else got[0]
 
     def _run(self, chunk, n_in: int, final: bool):
         from . import gen_engine
@@ -537,6 +612,8 @@ class StreamingEnhancer(_Driver):
         self.prepare(device)
         out = engine.stream_run(self.state, self._schedule.push(n_in, final), chunk)
         got = self._emitted(out, self.streams, device)
+        if self._back is not None:
+            got[0] = self._leave(out.get("enhanced"), final)
         return tuple(got) if self.return_bands else got[0]
 
     def _joined(self, results: list, device):
@@ -544,13 +621,35 @@ class StreamingEnhancer(_Driver):
         import torch
 
         if not results:
-            got = self._emitted({}, self.streams, device)
-            return tuple(got) if self.return_bands else got[0]
+            return self._nothing(device)
         if len(results) == 1:
             return results[0]
         if self.return_bands:
-            return tuple(torch.cat(parts, dim=2) for parts in zip(*results))
-        return torch.cat(results, dim=2)
+            return tuple(torch.cat(parts, dim=-1) for parts in zip(*results))
+        return torch.cat(results, dim=-1)
+
+    def _decoded(self, chunk, what: str):
+        """A pushed chunk of PCM bytes, uint8 (streams, n * bytes per sample), as float32 (streams, 1, n): one launch per 64 rows."""
+        import torch
+
+        from . import rate
+
+        fmt = rate.PCM_FORMATS.index(self.input_format)
+        b, last = rate.PCM_BYTES[fmt], what == self._last
+        want = self.input_chunk_samples * b
+        if (not isinstance(chunk, torch.Tensor) or chunk.dtype is not torch.uint8 or chunk.dim() != 2 or chunk.shape[0] != self.streams or chunk.shape[1] % b
+                or not (chunk.shape[1] < want if last else chunk.shape[1] == want)):
+            got = f"{chunk.dtype} {tuple(chunk.shape)}" if isinstance(chunk, torch.Tensor) else type(chunk).__name__
+            raise ValueError(f"StreamingEnhancer: {what} expects a uint8 ({self.streams}, {want}) tensor of {self.input_format} bytes"
+                             f"{' or a shorter last one of whole samples' if last else ''}, got {got}")
+        if not chunk.is_cuda:
+            from ._lib import EbenError
+
+            raise EbenError(f"StreamingEnhancer runs only on an MI355X HIP device (got a tensor on '{chunk.device}'); there is no CPU path")
+        self.prepare(chunk.device)
+        chunk, n = chunk.contiguous(), chunk.shape[1] // b
+        rate.pcm_chunks_in([(chunk[r], n, fmt, r) for r in range(self.streams)], self._staging.view(self.streams, self._staging.shape[2]))
+        return self._staging[:, :, :n].contiguous()
 
     def _run_rated(self, chunk, final: bool):
         """A chunk at the recording's rate: through the resampler into the FIFO, every chunk the FIFO fills through the enhancer."""
@@ -567,6 +666,8 @@ class StreamingEnhancer(_Driver):
 
     def push(self, chunk):
         self._no_grad("push")
+        if self.input_format is not None:
+            chunk = self._decoded(chunk, "push")
         if self._front is not None:
             self._check(chunk, self.streams, "push", self._front.input_chunk_samples)
             return self._run_rated(chunk.contiguous(), False)
@@ -579,6 +680,8 @@ class StreamingEnhancer(_Driver):
         self._no_grad("finish")
         if tail is not None and tail.shape[-1] == 0:
             tail = None
+        if tail is not None and self.input_format is not None:
+            tail = self._decoded(tail, "finish")
         if tail is not None:
             self._check(tail, self.streams, "finish", self.input_chunk_samples)
             tail = tail.contiguous()
@@ -636,8 +739,17 @@ class Session:
     at; ``input_chunk_samples``: samples per push at that rate; ``input_latency``: input samples pushed minus those the emitted ones
     correspond to in the steady state (``StreamingEnhancer``'s properties of the same names)."""
 
-    def __init__(self, book: "PoolBook", slot: int, private: int, schedule: Schedule, input_rate: Optional[int] = None):
+    def __init__(self, book: "PoolBook", slot: int, private: int, schedule: Schedule, input_rate: Optional[int] = None,
+                 output_rate: Optional[int] = None, output_format: Optional[str] = None, input_format: Optional[str] = None):
         self.book, self.slot, self.schedule = book, slot, schedule
+        # the way out: ``output_rate`` the rate its results leave at, ``output_format`` one of ``corpus.FORMATS`` (None: float32),
+        # ``output_lookahead`` the model-rate samples the resampler behind the model holds back, ``clipped`` a 0-dim int32 device view of
+        # the samples the encoder clamped so far (set by the pool).  ``input_format``: its pushes are PCM bytes of that format.
+        self.egress = output_format is not None or (output_rate is not None and output_rate != book.model_rate)
+        self.output_rate = book.model_rate if output_rate is None else output_rate
+        self.output_format, self.input_format = output_format, input_format
+        self.output_lookahead = book.back.lookahead(slot) if self.egress else 0
+        self.clipped = None
         self.rated = input_rate is not None   # its chunks pass through the book's rate front first
         self.input_rate = book.model_rate if input_rate is None else input_rate
         self.input_chunk_samples, self.input_latency = book.chunk, book.plan.latency
@@ -661,7 +773,8 @@ class PoolBook:
     A session warms up and finishes on a private batch-1 state with its own ``Schedule`` and lives in a slot in between; a pooled push
     costs a counter increment here."""
 
-    def __init__(self, gen, chunk_samples: int, slots: int = 64, stream_plan: Optional[StreamPlan] = None, input_rates=(), model_rate: int = 16000):
+    def __init__(self, gen, chunk_samples: int, slots: int = 64, stream_plan: Optional[StreamPlan] = None, input_rates=(), model_rate: int = 16000,
+                 output_rates=()):
         slots = int(slots)
         if not 1 <= slots <= 256:
             raise ValueError(f"slots must lie in 1 ... 256, got {slots}")
@@ -675,6 +788,11 @@ class PoolBook:
             from . import rate
 
             self.front = rate.SlotFront(self.chunk, slots, self.input_rates, self.model_rate, gen.multiple)
+        self.output_rates = tuple(int(r) for r in output_rates)   # the rates sessions may leave at, beside the model's own
+        self.back = None    # rate.SlotBack: a resampler schedule per slot behind the model, once declared or first asked for
+        if self.output_rates:
+            self._back()
+        self.pcm_in = False   # a session pushed PCM bytes: the pool keeps a staging buffer
         self.words = (slots + 63) // 64
         self.free_slots = list(range(slots))
         self.free_private: List[int] = []
@@ -692,7 +810,17 @@ class PoolBook:
         self.free_private.append(i)
         self.free_private.sort()
 
-    def open(self, input_rate: Optional[int] = None) -> Session:
+    def _back(self):
+        if self.back is None:
+            from . import rate
+
+            # the most a session emits in one run: at the end, the model's latency (or a whole warm-up) and a tail at once
+            most = max(self.plan.latency, self.plan.warmup_pushes * self.chunk) + self.chunk
+            self.back = rate.SlotBack(self.chunk, self.slots, self.output_rates, self.model_rate, most)
+        return self.back
+
+    def open(self, input_rate: Optional[int] = None, output_rate: Optional[int] = None, output_format: Optional[str] = None,
+             input_format: Optional[str] = None) -> Session:
         if not self.free_slots:
             raise RuntimeError(f"StreamPool: all {self.slots} slots hold an open session")
         if input_rate is not None and int(input_rate) == self.model_rate:
@@ -702,15 +830,28 @@ class PoolBook:
             if self.front is None or input_rate not in self.front.rates:
                 raise ValueError(f"StreamPool: a session at {input_rate} Hz in a pool that declared input_rates = {self.input_rates} "
                                  f"(the model's {self.model_rate} Hz needs no declaration)")
+        if output_rate is not None and int(output_rate) == self.model_rate:
+            output_rate = None
+        if output_rate is not None or output_format is not None or input_format is not None:
+            from . import rate
+
+            if input_format is not None:
+                rate.pcm_format(input_format, "StreamPool")
+            if output_rate is not None or output_format is not None:
+                output_rate = self._back().check(output_rate, output_format, "StreamPool")[0]
         if self.spare:
             schedule = self.spare.pop()
             schedule.reset()
         else:
             schedule = Schedule(self.gen, self.chunk)
             schedule._steady = self.plan.steady
-        session = Session(self, self.free_slots.pop(0), -1, schedule, input_rate)   # a private state is taken at the first push, the slot now
+        slot = self.free_slots.pop(0)
+        if output_rate is not None or output_format is not None:
+            self.back.open(slot, output_rate, output_format)
+        session = Session(self, slot, -1, schedule, input_rate, output_rate, output_format, input_format)   # a private state is taken at the first push, the slot now
         if session.rated:
             self.front.open(session.slot, input_rate)
+        self.pcm_in = self.pcm_in or input_format is not None
         return session
 
     def check(self, sessions) -> None:
@@ -819,16 +960,26 @@ class StreamPool(_Driver):
     takes a shorter tail; per session the returns are those of ``StreamingEnhancer(..., input_rate=r)``: nothing at the first push, one
     ``chunk_samples`` of extra latency (``session.input_latency``).  All rated sessions of a tick share one splice launch per pushed
     length and one resampling launch (``eben_rate_splice_slots``, ``eben_resample_slots``).  Without ``input_rates`` the pool is what it
-    was."""
+    was.
+
+    ``output_rates``: the rates sessions may leave at beside ``model_rate``, declared up front for the same reason (any ratio the
+    resampling tile admits).  ``open(..., output_rate=, output_format=, input_format=)`` opens a session that leaves as PCM bytes at a
+    rate of its own and/or arrives as PCM bytes (see ``open``): ``rate.SlotBack`` keeps a resampler schedule per slot behind the model,
+    one ``eben_stream_pcm_out`` behind every run that emitted serves all its sessions, one ``eben_pcm_chunks_in`` in front of a tick
+    decodes every PCM session's frame.  A pool that declares ``output_rates`` and uses none makes today's entries and library calls."""
 
     _who, _per, _last = "StreamPool", " per session", "close"
 
-    def __init__(self, generator, chunk_samples: int, slots: int = 64, return_bands: bool = False, input_rates=(), model_rate: int = 16000):
+    def __init__(self, generator, chunk_samples: int, slots: int = 64, return_bands: bool = False, input_rates=(), model_rate: int = 16000,
+                 output_rates=()):
         super().__init__(generator, chunk_samples, return_bands)   # ``state``: the shared one
-        self.book = PoolBook(generator, chunk_samples, slots, self.plan, input_rates, model_rate)
+        self.book = PoolBook(generator, chunk_samples, slots, self.plan, input_rates, model_rate, output_rates)
         self.slots = self.book.slots
         self.private = {}      # id -> batch-1 StreamState, allocated when the book first hands the id out and kept
         self.tapes = None      # rate.SlotTapes: the front's tapes, FIFO buffers and tables, when the pool admits recording rates
+        self.back = None       # rate.BackTapes: the tapes, tables and clipped counts of the way out, when a session leaves as PCM or at a rate
+        self.image = None      # the byte image of the latest run that left this way (allocated by that run)
+        self.staging = None    # (slots, 1, longest input chunk) float32: where the PCM bytes of a tick are decoded to
 
     def prepare(self, device, private: int = 0) -> "StreamPool":
         """Allocates the shared state on ``device`` now instead of at the first step, and ``private`` batch-1 states for sessions that
@@ -847,14 +998,64 @@ class StreamPool(_Driver):
             from . import rate
 
             self.tapes = rate.SlotTapes(self.book.front, self.state.device)
+        if self.book.back is not None and (self.back is None or self.back.device != self.state.device):
+            from . import rate
+
+            if self.back is not None and any(s is not None for s in self.book.back.slot):
+                raise RuntimeError(f"StreamPool: sessions that leave at a rate of their own are open on {self.back.device}; their tapes do not "
+                                   f"move to '{device}': close them first")
+            self.back = rate.BackTapes(self.book.back, self.state.device)
+        if self.book.pcm_in and (self.staging is None or self.staging.device != self.state.device):
+            import torch
+
+            front = self.book.front
+            pitch = max([self.chunk_samples] + (list(front.input_chunk) if front is not None else []))
+            self.staging = torch.zeros((self.slots, 1, pitch), dtype=torch.float32, device=self.state.device)
+            self._staged = self.staging.split(1, dim=0)
         for i in range(min(int(private), self.slots)):
             self._private_state(i)
         return self
 
-    def open(self, input_rate: Optional[int] = None) -> Session:
+    def open(self, input_rate: Optional[int] = None, *, output_rate: Optional[int] = None, output_format: Optional[str] = None,
+             input_format: Optional[str] = None) -> Session:
         """A session for a stream that begins now.  ``input_rate``: the rate its audio arrives at, one of the declared ``input_rates``
-        (None or ``model_rate``: the model's own); ``ValueError`` for a rate that was not declared."""
-        return self.book.open(input_rate)
+        (None or ``model_rate``: the model's own); ``ValueError`` for a rate that was not declared.
+
+        ``output_format`` (one of ``corpus.FORMATS``): ``step`` and ``close`` return this session's samples as a uint8 device tensor of
+        ``k * bytes per sample`` bytes, a view into ``pool.image`` -- the image of that run, freshly allocated, in which every session's
+        bytes are contiguous and start at a 16-byte boundary, so one ``copy_(non_blocking=True)`` to pinned memory moves a whole tick.
+        ``output_rate`` (one of the declared ``output_rates``; the model's needs no declaration): the samples leave at that rate, k by
+        ``rate.final_outputs`` (``session.output_lookahead`` model-rate samples are held back until ``close``); alone it gives float32
+        ``(1, 1, k)``.  ``session.clipped``: a 0-dim int32 device view of the samples the encoder has clamped (or found NaN) so far.
+        ``input_format``: ``step`` takes a uint8 device tensor of ``session.input_chunk_samples * bytes per sample`` bytes of that
+        format (any alignment), ``close`` a shorter one; one launch decodes all such sessions of a tick."""
+        session = self.book.open(input_rate, output_rate, output_format, input_format)
+        if session.egress:   # the counter lives on the device: one that has not been chosen yet is the generator's
+            self.prepare(self.state.device if self.state is not None else next(self.generator.parameters()).device)
+            session.clipped = self.back.count(session.slot)
+            session.clipped.zero_()
+        return session
+
+    def _leave(self, src, sessions, final, enhanced: list) -> None:
+        """The way out of one run: ``src`` its compact ``enhanced`` (rows, 1, k) or None, row a that of ``sessions[a]``.  One
+        ``eben_stream_pcm_out`` for all sessions that leave as PCM or at a rate; ``enhanced[a]`` becomes that session's view of the image."""
+        import torch
+
+        from . import rate
+
+        k = 0 if src is None else src.shape[2]
+        mine = [(a, s) for a, s in enumerate(sessions) if s.egress]
+        pieces, ranges, nbytes = self.book.back.emit([(s.slot, a, k, s is final) for a, s in mine])
+        if pieces:
+            self.image = self.back.run(pieces, nbytes, src)
+        else:
+            self.image = torch.empty(16, dtype=torch.uint8, device=self.state.device)
+        for a, s in mine:
+            off, n = ranges[s.slot]
+            if s.output_format is None:
+                enhanced[a] = self.image[off : off + 4 * n].view(torch.float32).view(1, 1, n)
+            else:
+                enhanced[a] = self.image[off : off + n * rate.PCM_BYTES[rate.PCM_FORMATS.index(s.output_format)]]
 
     def _private_state(self, i: int):
         from . import gen_engine
@@ -863,19 +1064,56 @@ class StreamPool(_Driver):
             self.private[i] = gen_engine.engine_of(self.generator).stream_state(self.plan, 1, self.state.device)
         return self.private[i]
 
-    def _results(self, out, sessions, results: dict) -> None:
+    def _results(self, out, sessions, results: dict, final=None) -> None:
         """The emitted tensors, a row per session, as what each session's call returns (rows are split in one call: a view per session
         built one by one costs more host time at 64 sessions than the mask does)."""
         import torch
 
         per_name = [t.split(1, dim=0) if len(sessions) > 1 else (t,) for t in self._emitted(out, len(sessions), self.state.device)]
+        if self.back is not None and any(s.egress for s in sessions):
+            per_name[0] = list(per_name[0])
+            self._leave(out.get("enhanced"), sessions, final, per_name[0])
         for a, s in enumerate(sessions):
             got = (per_name[0][a], per_name[1][a]) if self.return_bands else per_name[0][a]
             if s in results:   # a close at a recording rate whose FIFO completed one more chunk: that push, then the final one
-                got = tuple(torch.cat(pair, dim=2) for pair in zip(results[s], got)) if self.return_bands else torch.cat((results[s], got), dim=2)
+                got = tuple(torch.cat(pair, dim=-1) for pair in zip(results[s], got)) if self.return_bands else torch.cat((results[s], got), dim=-1)
             results[s] = got
 
-    def _execute(self, entries, chunks) -> dict:
+    def _decode(self, chunks: dict) -> dict:
+        """The sessions that push PCM bytes: one ``eben_pcm_chunks_in`` for all of them, their chunks replaced by views of the staging buffer."""
+        from . import rate
+
+        pcm = [(s, c) for s, c in chunks.items() if s.input_format is not None]
+        if not pcm:
+            return chunks
+        table = []
+        for s, c in pcm:
+            fmt = rate.PCM_FORMATS.index(s.input_format)
+            n = c.numel() // rate.PCM_BYTES[fmt]
+            table.append((c, n, fmt, s.slot))
+            chunks[s] = self._staged[s.slot][:, :, :n]
+        rate.pcm_chunks_in(table, self.staging.view(self.slots, self.staging.shape[2]))
+        return chunks
+
+    def _check_bytes(self, chunk, session: Session, what: str) -> None:
+        """``chunk``: a session's PCM bytes, one chunk of them, or fewer whole samples in the call that ends the stream."""
+        import torch
+
+        from . import rate
+
+        b = rate.PCM_BYTES[rate.PCM_FORMATS.index(session.input_format)]
+        want, last = session.input_chunk_samples * b, what == self._last
+        if (not isinstance(chunk, torch.Tensor) or chunk.dtype is not torch.uint8 or chunk.dim() != 1 or chunk.stride(0) != 1 or chunk.numel() % b
+                or not (chunk.numel() < want if last else chunk.numel() == want)):
+            got = f"{chunk.dtype} {tuple(chunk.shape)}" if isinstance(chunk, torch.Tensor) else type(chunk).__name__
+            raise ValueError(f"{self._who}: {what} expects a uint8 ({want},) tensor of {session.input_format} bytes{self._per}"
+                             f"{' or a shorter last one of whole samples' if last else ''}, got {got}")
+        if not chunk.is_cuda:
+            from ._lib import EbenError
+
+            raise EbenError(f"{self._who} runs only on an MI355X HIP device (got a tensor on '{chunk.device}'); there is no CPU path")
+
+    def _execute(self, entries, chunks, final_entry=None) -> dict:
         import torch
 
         from . import gen_engine
@@ -896,7 +1134,7 @@ class StreamPool(_Driver):
                 state = self._private_state(e.private)
                 if e.fresh:
                     state.reset()
-                self._results(engine.stream_run(state, e.ops, chunks.get(e.session)), (e.session,), results)
+                self._results(engine.stream_run(state, e.ops, chunks.get(e.session)), (e.session,), results, e.session if e is final_entry else None)
             else:
                 engine.stream_move(self.state, e.slot, self._private_state(e.private), self.book.moved, e.into_pool)
         return results
@@ -908,17 +1146,29 @@ class StreamPool(_Driver):
             raise ValueError(f"StreamPool: step expects a dict of session -> chunk, got {type(chunks).__name__}")
         self.book.check(chunks)
         for s, chunk in chunks.items():
-            self._check(chunk, 1, "step", s.input_chunk_samples)
+            if s.input_format is not None:
+                self._check_bytes(chunk, s, "step")
+            else:
+                self._check(chunk, 1, "step", s.input_chunk_samples)
         if not chunks:
             return {}
         chunks = {s: c.contiguous() for s, c in chunks.items()}
         self.prepare(next(iter(chunks.values())).device)
-        results = self._execute(self.book.tick(chunks), dict(chunks))
+        results = self._execute(self.book.tick(chunks), self._decode(dict(chunks)))
         if len(results) < len(chunks):   # a stream at a recording rate completes no chunk at its first push
             got = self._emitted({}, 1, self.state.device)
             nothing = tuple(got) if self.return_bands else got[0]
-            return {s: results.get(s, nothing) for s in chunks}
+            return {s: results[s] if s in results else self._nothing(s, nothing) for s in chunks}
         return {s: results[s] for s in chunks}
+
+    def _nothing(self, session: Session, nothing):
+        """What a session gets in a tick that ran nothing for it."""
+        import torch
+
+        if session.output_format is None:
+            return nothing
+        empty = torch.empty(0, dtype=torch.uint8, device=self.state.device)
+        return (empty, nothing[1]) if self.return_bands else empty
 
     def close(self, session: Session, tail=None):
         """The rest of ``session``'s stream, as ``StreamingEnhancer.finish``; its slot is free for the next ``open()``."""
@@ -929,9 +1179,16 @@ class StreamPool(_Driver):
         if tail is not None and isinstance(tail, torch.Tensor) and tail.shape[-1] == 0:
             tail = None
         if tail is not None:
-            self._check(tail, 1, "close", session.input_chunk_samples)
+            if session.input_format is not None:
+                self._check_bytes(tail, session, "close")
+            else:
+                self._check(tail, 1, "close", session.input_chunk_samples)
             tail = tail.contiguous()
         self.prepare(tail.device if tail is not None else self.state.device if self.state is not None
                      else next(self.generator.parameters()).device)
-        entries = self.book.close(session, 0 if tail is None else tail.shape[2])
-        return self._execute(entries, {} if tail is None else {session: tail})[session]
+        chunks = {} if tail is None else self._decode({session: tail})
+        entries = self.book.close(session, 0 if tail is None else chunks[session].shape[2])
+        got = self._execute(entries, chunks, entries[-1])[session]
+        if session.egress:
+            self.book.back.release(session.slot)
+        return got
