@@ -316,7 +316,8 @@ EBEN_API int eben_bl_head_dw(const EbenBlHeadJob* job, int rows, float* slabs, s
  * (batch, 1, l_out); input gradient of `rows` stacked seeds (rows, 1, l_out) with the epilogue of eben_bl_conv1d_bwd_dx (act = the
  * layer's input embedding); weight gradient of `nbranch` hinge branches in one launch -- branch br pairs seed rows and input rows
  * [br rows, (br + 1) rows) of the given pointers -- into slabs [nbranch][nslab][channels ksize + 1] (last column = bias).  The built
- * head shapes are the two of DiscriminatorEBENMultiScales (4 -> 24 k 3, 1 -> 16 k 15): EBEN_EUNSUPPORTED otherwise. */
+ * head shapes are the two of DiscriminatorEBENMultiScales (4 -> 24 k 3, 1 -> 16 k 15): EBEN_EUNSUPPORTED otherwise.  All three tail entry
+ * points require pad >= 0 and l_out = length + 2 pad - (ksize - 1) > 0 (EBEN_EINVAL). */
 EBEN_API int eben_bl_tail_fwd(const void* x_hi, const void* x_lo, int batch, int channels, int length, int ksize, int pad, const float* v,
                      const float* scale, const float* bias, float out_slope, float* y, void* stream);
 EBEN_API int eben_bl_tail_dx(const float* seeds, int rows, int channels, int length, int ksize, int pad, const float* v, const float* scale,
@@ -326,7 +327,8 @@ EBEN_API size_t eben_bl_tail_dw_workspace(int rows, int channels, int l_out, int
 EBEN_API int eben_bl_tail_dw(const float* seeds, const void* x_hi, const void* x_lo, int rows, int nbranch, int channels, int length, int ksize, int pad,
                     float* slabs, size_t ws_bytes, void* stream);
 /* feature-matching sums (eben_fm_sums) over embeddings in bundle planes: planes = HOST array (hi_0, lo_0, hi_1, lo_1, ...), the
- * enhanced rows are the first units[i] units of pair i's planes and the reference rows the next units[i] (a = hi + lo). */
+ * enhanced rows are the first units[i] units of pair i's planes and the reference rows the next units[i] (a = hi + lo).  Both planes of
+ * every pair are required: a NULL hi or lo plane is EBEN_EINVAL before any launch. */
 EBEN_API size_t eben_bl_fm_sums_workspace(int npairs);
 EBEN_API int eben_bl_fm_sums(const void* const* planes, const int64_t* units, int npairs, float* partial_ws, size_t ws_bytes, float* sums,
                     void* stream);

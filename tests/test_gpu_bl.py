@@ -201,7 +201,7 @@ def test_chain_tail_forward_backward(hip, channels, length, k):
     assert rel_err(g.to_f32(), want) < 2e-5
     # weight gradient of the two hinge branches in one launch: seed rows [fake | real] against embedding rows [enhanced | reference]
     nslab, rs = ctypes.c_int(0), ctypes.c_int(0)
-    nbytes = hip.eben_bl_tail_dw_workspace(half, channels, length, k, 2, ctypes.byref(nslab), ctypes.byref(rs))
+    nbytes = hip.eben_bl_tail_dw_workspace(half, channels, length + 2 * pad - (k - 1), k, 2, ctypes.byref(nslab), ctypes.byref(rs))
     slabs = torch.empty(nbytes // 4, dtype=torch.float32, device=DEV)
     sd = seeds[2 * half:].contiguous()
     check(hip.eben_bl_tail_dw(sd.data_ptr(), act.hi.data_ptr(), act.lo.data_ptr(), half, 2, channels, length, k, pad, slabs.data_ptr(), nbytes, st), "tail_dw")

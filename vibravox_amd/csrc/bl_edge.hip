@@ -847,6 +847,7 @@ extern "C" int eben_bl_tail_dx(const float* seeds, int rows, int channels, int l
   EBEN_REQUIRE(seeds && v && act_hi && g_hi && rows > 0 && channels % 8 == 0 && channels > 0 && length > 0 && ksize >= 1 && ksize <= 8, "bad tail input-gradient arguments");
   EBEN_REQUIRE(seg >= 0 && (seg == 0 || (seg_map && rows <= 4 * seg)), "bad batch segment map");
   EBEN_REQUIRE(fm_rows == 0 || (fm_sums && act_lo && fm_rows > 0), "feature-matching rows need the sums and both planes of the embedding");
+  EBEN_REQUIRE(pad >= 0 && length + 2 * pad - (ksize - 1) > 0, "tail input gradient: negative padding or empty seeds");
   BlTailDxArgs P;
   P.seeds = seeds; P.v = v; P.scale = scale; P.ah = static_cast<const u32x4*>(act_hi); P.al = static_cast<const u32x4*>(act_lo);
   P.gh = static_cast<u32x4*>(g_hi); P.gl = static_cast<u32x4*>(g_lo);
@@ -951,6 +952,7 @@ extern "C" int eben_bl_tail_dw(const float* seeds, const void* x_hi, const void*
   EBEN_REQUIRE(seeds && x_hi && slabs && rows > 0 && nbranch > 0 && channels % 8 == 0 && channels > 0 && length > 0 && ksize >= 1 && ksize <= 8,
                "bad tail weight-gradient arguments");
   const int l_out = length + 2 * pad - (ksize - 1);
+  EBEN_REQUIRE(pad >= 0 && l_out > 0, "tail weight gradient: negative padding or empty seeds");
   int ns = 0;
   if (ws_bytes < eben_bl_tail_dw_workspace(rows, channels, l_out, ksize, nbranch, &ns, nullptr)) return fail(EBEN_EWORKSPACE, "bl_tail_dw workspace too small");
   static const int un = getenv("EBEN_TAIL_DW_UN") ? atoi(getenv("EBEN_TAIL_DW_UN")) : 4;
@@ -976,6 +978,9 @@ extern "C" int eben_bl_fm_sums_codes(const void* const* planes, const int64_t* u
                                      float* sums, void* stream) {
   EBEN_REQUIRE(planes && units && npairs > 0 && partial_ws && sums, "bad bl_fm_sums arguments");
   if (ws_bytes < eben_bl_fm_sums_workspace(npairs)) return fail(EBEN_EWORKSPACE, "bl_fm_sums workspace too small");
+  // both planes of every pair, before the first launch: the two-unit loop of bl_fm_partial_kernel reads lo without a test
+  for (int p = 0; p < npairs; ++p)
+    if (!planes[2 * p] || !planes[2 * p + 1] || units[p] <= 0) return fail(EBEN_EINVAL, "feature-matching pair %d is null (hi or lo plane) or empty", p);
   for (int p0 = 0; p0 < npairs; p0 += BLFM_MAX_PAIRS) {
     const int cnt = npairs - p0 < BLFM_MAX_PAIRS ? npairs - p0 : BLFM_MAX_PAIRS;
     BlFmTable T;
@@ -984,7 +989,6 @@ extern "C" int eben_bl_fm_sums_codes(const void* const* planes, const int64_t* u
       T.lo[i] = static_cast<const u32x4*>(planes[2 * (p0 + i) + 1]);
       T.units[i] = units[p0 + i];
       T.code[i] = codes ? static_cast<uint2*>(codes[p0 + i]) : nullptr;
-      if (!T.hi[i] || T.units[i] <= 0) return fail(EBEN_EINVAL, "feature-matching pair %d is null or empty", p0 + i);
     }
     float* part = partial_ws + (size_t)p0 * BLFM_BLOCKS * 2;
     hipLaunchKernelGGL(bl_fm_partial_kernel, dim3(BLFM_BLOCKS, cnt), dim3(256), 0, as_stream(stream), T, part);
