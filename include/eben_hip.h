@@ -662,6 +662,60 @@ EBEN_API int eben_phase_vocoder(const float* spec, float* out, int rows, int bin
 EBEN_API int eben_resample(const float* x, const float* kernels, float* out, int rows, int t_in, int t_out, int orig, int nw,
                   int width, void* stream);
 
+/* ---- per-clip waveform augmentation at a constant batch length (csrc/augment_clips.hip; vibravox_amd/augment.py, per_clip=True) ----
+ * The kernels above with parameters PER ROW.  Every `rows` / `clips` / `bands` argument is a HOST array (device pointers inside),
+ * checked whole before the first launch and passed to the kernels by value, 48 rows a launch.  A row's arithmetic is the
+ * batch-level kernel's on that row alone, operation for operation (finite samples: a skipped zero tap does not propagate an
+ * inf / NaN the dense sum would).
+ * eben_resample_clips: eben_resample's sum over the taps that can be non-zero, the ratio chosen per row:
+ *     out[dst_row, n] = sum_{j < W} band[p, j] * x[src_offset + q*orig - width + first[p] + j],  n = q*nw + p < min(ceil(nw*t_in/orig), t)
+ *   (one accumulator, fmaf, j ascending, zero outside [0, t_in)), and 0 for the remaining n < t: crop / right padding to t fused.
+ *   band (nw, W) fp32 and first (nw) int32 on the device: kernels[p, first[p] + j] of eben_resample's table, every value outside
+ *   being exactly 0; W <= 2*width + orig; orig, nw <= 2^20; 1 <= nbands <= EBEN_CLIP_MAX_BANDS; x holds x_floats floats, out is
+ *   (out_rows, t), not overlapping x; no two rows share a dst_row.
+ * eben_phase_vocoder_clips: eben_phase_vocoder with spec (2*bins, nrows*frames) dense and row i walking rows[i].frames_out frames
+ *   at rows[i].rate into columns [col_out, col_out + frames_out) of out (2*bins, out_cols); columns ascending and disjoint.
+ * eben_overlap_add_clips: row i = overlap-add of columns [col, col + frames_out) of frames_buf (win, cols) (eben_overlap_add_ex
+ *   without reflection, sample u at u + pad) times float32(1 / sum_f w2[u + pad - f*hop]), the sum over the covering frames in
+ *   float64 and ascending f (w2: win doubles on the device, the squared window); len_stretch samples at out + dst_offset, zero from
+ *   `valid` on; valid <= min(len_stretch, win + hop*(frames_out-1) - pad); rows ascending and disjoint in both buffers.
+ * eben_time_mask_clips: x[row, first : first + count] = 0 per clip, x (rows, t); count = 0 allowed. */
+#define EBEN_CLIP_MAX_BANDS 16
+typedef struct EbenClipBand {
+  const float* band;
+  const int32_t* first;
+  int32_t orig, nw, width, W;
+} EbenClipBand;
+typedef struct EbenResampleClip {
+  int64_t src_offset;   /* floats from x to the row's first sample */
+  int32_t t_in;
+  int32_t band;         /* index into bands */
+  int32_t dst_row;
+  int32_t reserved;
+} EbenResampleClip;
+typedef struct EbenVocoderClip {
+  double rate;
+  int32_t frames_out;
+  int32_t col_out;
+} EbenVocoderClip;
+typedef struct EbenOlaClip {
+  int64_t dst_offset;   /* floats from out to the row's first sample */
+  int32_t col;
+  int32_t frames_out;
+  int32_t len_stretch;
+  int32_t valid;
+} EbenOlaClip;
+typedef struct EbenMaskClip {
+  int32_t row, first, count;
+} EbenMaskClip;
+EBEN_API int eben_resample_clips(const float* x, int64_t x_floats, float* out, int out_rows, int t, const EbenClipBand* bands, int nbands,
+                                 const EbenResampleClip* rows, int nrows, void* stream);
+EBEN_API int eben_phase_vocoder_clips(const float* spec, float* out, int bins, int frames, int64_t out_cols, const EbenVocoderClip* rows, int nrows,
+                                      float hop, void* stream);
+EBEN_API int eben_overlap_add_clips(const float* frames_buf, int64_t cols, const double* w2, float* out, int64_t out_floats, int win, int hop, int pad,
+                                    const EbenOlaClip* rows, int nrows, void* stream);
+EBEN_API int eben_time_mask_clips(float* x, int rows, int t, const EbenMaskClip* clips, int nclips, void* stream);
+
 /* ---- multi-rate downsampling (MelganMultiScalesDiscriminator: torchaudio Resample, "sinc_interp_kaiser") -----------------
  * Same arithmetic as eben_resample: y[r, q*nw + p] = sum_{j < taps} kernels[p, j] * x[r, q*orig + j - width] (zero outside the row).
  * eben_multirate_down: every scale s = 1 .. scales-1 reduces to orig = 2^s, new = 1; tables holds their (1, taps_s =

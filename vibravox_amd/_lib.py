@@ -132,6 +132,29 @@ class EbenClip(ctypes.Structure):
     _fields_ = [("data", c_void_p), ("length", c_int64)]
 
 
+CLIP_MAX_BANDS = 16   # EBEN_CLIP_MAX_BANDS ratios a call of eben_resample_clips
+
+
+class EbenClipBand(ctypes.Structure):
+    _fields_ = [("band", c_void_p), ("first", c_void_p), ("orig", c_int32), ("nw", c_int32), ("width", c_int32), ("W", c_int32)]
+
+
+class EbenResampleClip(ctypes.Structure):
+    _fields_ = [("src_offset", c_int64), ("t_in", c_int32), ("band", c_int32), ("dst_row", c_int32), ("reserved", c_int32)]
+
+
+class EbenVocoderClip(ctypes.Structure):
+    _fields_ = [("rate", ctypes.c_double), ("frames_out", c_int32), ("col_out", c_int32)]
+
+
+class EbenOlaClip(ctypes.Structure):
+    _fields_ = [("dst_offset", c_int64), ("col", c_int32), ("frames_out", c_int32), ("len_stretch", c_int32), ("valid", c_int32)]
+
+
+class EbenMaskClip(ctypes.Structure):
+    _fields_ = [("row", c_int32), ("first", c_int32), ("count", c_int32)]
+
+
 _P = c_void_p
 _D = POINTER(EbenConv1dDesc)
 
@@ -237,6 +260,10 @@ SIGNATURES = {
     "eben_time_mask": (c_int, [_P, c_int64, c_int, c_int, c_int, _P]),
     "eben_phase_vocoder": (c_int, [_P, _P, c_int, c_int, c_int, c_int, ctypes.c_double, c_float, _P]),
     "eben_resample": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "eben_resample_clips": (c_int, [_P, c_int64, _P, c_int, c_int, POINTER(EbenClipBand), c_int, POINTER(EbenResampleClip), c_int, _P]),
+    "eben_phase_vocoder_clips": (c_int, [_P, _P, c_int, c_int, c_int64, POINTER(EbenVocoderClip), c_int, c_float, _P]),
+    "eben_overlap_add_clips": (c_int, [_P, c_int64, _P, _P, c_int64, c_int, c_int, c_int, POINTER(EbenOlaClip), c_int, _P]),
+    "eben_time_mask_clips": (c_int, [_P, c_int, c_int, POINTER(EbenMaskClip), c_int, _P]),
     "eben_stft_frames": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "eben_stft_frames_folded": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "eben_split3": (c_int, [_P, _P, c_int, c_int, c_int64, _P]),
