@@ -1097,6 +1097,23 @@ EBEN_API size_t eben_lsd_workspace(int rows, int t_max, int n_fft, int hop, int 
 EBEN_API int eben_lsd(const float* preds, const float* target, int rows, int t_max, const int32_t* lengths, int n_fft, int hop,
                       const int* band_lo, const int* band_hi, int nbands, void* workspace, size_t ws_bytes, float* out, void* stream);
 
+/* ---- BSS-eval signal-to-distortion ratio (torchmetrics signal_distortion_ratio, direct-solve branch; csrc/sdr.hip) -------------------
+ * The conventions of the evaluation metrics above: rows t_max floats apart, a NULLABLE device lengths, one float per row, fp64 sums in
+ * an order that depends on the row's own length and on filter_length only, so out[r] has the bits of the call on row r alone; nothing
+ * behind a row's end is read; no host synchronisation.  Per row of N samples, in float64: t, p = target, preds (zero_mean = 1: minus
+ * their means over the N samples), each divided by max(its norm, 1e-6); r[k] = sum_n t[n] t[n + k] and b[k] = sum_n t[n] p[n + k] for
+ * k < filter_length (linear correlations, 0 for k >= N); r[0] += load_diag (0.0 for torchmetrics' None); Toeplitz(r) h = b by Levinson's
+ * recursion; coh = b . h; out[r] = 10 log10(coh / (1 - coh)).  There is no eps: a silent target gives NaN, preds proportional to
+ * target whatever 1 - coh leaves (a very large value, +inf or NaN); a lengths[r] outside [1, t_max] gives NaN.  With filter_length = 1
+ * this is SI-SDR without its eps.  workspace: eben_sdr_workspace(rows, t_max, filter_length) bytes on the device (two means and two
+ * inverse norms per row, then 2 filter_length doubles per row and segment of 8192 samples of t_max); the entry trusts its size.
+ * EBEN_EINVAL before any launch for a null pointer (other than lengths), rows outside [1, 65535], t_max outside [1, INT_MAX - 16384],
+ * filter_length outside [1, 512], zero_mean neither 0 nor 1 or a NaN load_diag; eben_sdr_workspace returns 0 for such arguments.
+ * Added without a version bump: functions only. */
+EBEN_API size_t eben_sdr_workspace(int rows, int t_max, int filter_length);
+EBEN_API int eben_sdr(const float* preds, const float* target, int rows, int t_max, const int32_t* lengths, int filter_length,
+                      int zero_mean, double load_diag, void* workspace, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,8 @@ EVAL_RATE = 16000
 #: bandwidth-extension model -- "lsd" over the whole band, "lsd_hf" over [lsd_hf_cutoff_hz, EVAL_RATE / 2] (the band being reconstructed)
 EVAL_METRICS = ("si_sdr", "stoi", "estoi", "si_snr", "snr", "lsd", "lsd_hf")
 DEFAULT_EVAL_METRICS = ("si_sdr", "stoi")
+#: scored after a short distortion filter: "sdr" is the BSS-eval SDR (``metrics.sdr``) with ``sdr_filter_length`` taps
+EVAL_METRICS_FILTERED = ("sdr",)
 LSD_N_FFT, LSD_HOP = 2048, 512
 
 #: buffer samples (rows x padded length) per batch: 262 s at 16 kHz.  The widest activations (32 channels at 1/4 of the audio rate,
@@ -381,12 +383,15 @@ def _batch_losses(terms: LossTerms, generator, plan, enh: torch.Tensor, bnd: tor
 def evaluate_clips(generator, corrupted: Sequence[torch.Tensor], reference: Sequence[torch.Tensor], *, sample_rate: int = EVAL_RATE,
                    max_batch_samples: int = MAX_BATCH_SAMPLES, return_enhanced: bool = False,
                    metrics: Sequence[str] = DEFAULT_EVAL_METRICS, lsd_hf_cutoff_hz: Optional[float] = None,
-                   loss_terms: Optional[LossTerms] = None, input_rate: Optional[int] = None) -> Dict[str, object]:
+                   loss_terms: Optional[LossTerms] = None, input_rate: Optional[int] = None,
+                   sdr_filter_length: int = 512) -> Dict[str, object]:
     """Per-clip SI-SDR and STOI of the enhanced ``corrupted[i]`` against ``reference[i]``, at 16 kHz as ``base_se.py`` logs them:
     ``{"si_sdr": (N,) float32, "stoi": (N,) float32}`` on the device, in input order; with ``return_enhanced`` also ``"enhanced"``, the
     list ``enhance_clips`` returns.  ``metrics`` selects among ``EVAL_METRICS``, one key each, all on the same 16 kHz buffers and lengths;
     ``"lsd_hf"`` is the LSD over ``[lsd_hf_cutoff_hz, 8000]`` Hz (Nyquist bin excluded) and needs that cutoff -- it depends on the sensor.
-    ``"stoi"`` and ``"estoi"`` together share one resampling / silence-removal / band-envelope run.
+    ``"stoi"`` and ``"estoi"`` together share one resampling / silence-removal / band-envelope run.  ``"sdr"`` (``EVAL_METRICS_FILTERED``)
+    is the BSS-eval SDR, which allows the enhanced clip a distortion filter of ``sdr_filter_length`` taps (1 to 512): one ``metrics.sdr``
+    call per batch on the same buffers and lengths.
     Clips as for ``enhance_clips``; a pair has one length, and both are scored on their first
     ``cut_to_valid_length`` samples (a reference may carry anything behind them).  Batches as in ``enhance_clips``: per batch one
     ``forward_ragged`` and the metric kernels with ``lengths = plan.cut`` on the padded buffers -- nothing is unpacked unless
@@ -405,8 +410,8 @@ def evaluate_clips(generator, corrupted: Sequence[torch.Tensor], reference: Sequ
 
     names = list(metrics)
     for name in names:
-        if name not in EVAL_METRICS:
-            raise ValueError(f"evaluate_clips: unknown metric {name!r}; known: {', '.join(EVAL_METRICS)}")
+        if name not in EVAL_METRICS and name not in EVAL_METRICS_FILTERED:
+            raise ValueError(f"evaluate_clips: unknown metric {name!r}; known: {', '.join(EVAL_METRICS + EVAL_METRICS_FILTERED)}")
     if len(set(names)) != len(names):
         raise ValueError(f"evaluate_clips: a metric is named twice in {names}")
     if not names:
@@ -414,6 +419,7 @@ def evaluate_clips(generator, corrupted: Sequence[torch.Tensor], reference: Sequ
     if "lsd_hf" in names and lsd_hf_cutoff_hz is None:
         raise ValueError("evaluate_clips: 'lsd_hf' needs lsd_hf_cutoff_hz, the lower edge of the band being reconstructed (there is no default: "
                          "it depends on the sensor)")
+    sdr_taps = M.sdr_filter_length(sdr_filter_length, "evaluate_clips: sdr_filter_length") if "sdr" in names else None
     lsd_bands = [None] * ("lsd" in names) + [(lsd_hf_cutoff_hz, EVAL_RATE // 2)] * ("lsd_hf" in names)
     for band in lsd_bands:
         M.lsd_band_bins(band, EVAL_RATE, LSD_N_FFT)   # a cutoff that leaves no bin is refused before anything runs
@@ -507,6 +513,8 @@ def evaluate_clips(generator, corrupted: Sequence[torch.Tensor], reference: Sequ
             both = M.lsd(enh, ref, EVAL_RATE, lens, LSD_N_FFT, LSD_HOP, lsd_bands)
             for name, row in zip([n for n in ("lsd", "lsd_hf") if n in values], both):
                 values[name].append(row)
+        if "sdr" in values:
+            values["sdr"].append(M.sdr(enh, ref, lens, filter_length=sdr_taps))
     order = torch.tensor(back, dtype=torch.int64).to(values[names[0]][0].device, non_blocking=True)
     out: Dict[str, object] = {name: torch.cat(values[name]).index_select(0, order) for name in names}
     for key, rows_of in losses.items():

@@ -10,7 +10,9 @@
 Beyond those two, for scoring a bandwidth-extension model: ``si_sdr(..., zero_mean=True)`` / ``si_snr`` and ``snr`` (torchmetrics'
 ``scale_invariant_signal_noise_ratio`` and ``signal_noise_ratio``; ``eben_signal_ratio``), ``stoi(..., extended=True)`` (ESTOI: pystoi's
 row- and column-normalised tail on the same envelopes, without its ``EPS * randn`` dither; ``eben_estoi``) and ``lsd`` (log-spectral
-distance over the whole band or over ``band_hz`` ranges; ``eben_lsd``).
+distance over the whole band or over ``band_hz`` ranges; ``eben_lsd``).  ``sdr`` is the BSS-eval signal-to-distortion ratio (torchmetrics'
+``signal_distortion_ratio``, direct solve: up to 512 lags of both correlations and a Toeplitz solve per row, float64; ``eben_sdr``), restated
+from torchmetrics 1.x without the package at hand (parity unpinned).
 
 All take ``(..., T)`` float tensors on a HIP device and return ``(...)`` float32 on that device, with torchmetrics' argument
 order (preds first).  There is no CPU path: a CPU tensor raises ``EbenError`` (the float64 restatement used to check these
@@ -134,6 +136,41 @@ def si_snr(preds: torch.Tensor, target: torch.Tensor, lengths: Lengths = None) -
 def snr(preds: torch.Tensor, target: torch.Tensor, lengths: Lengths = None, zero_mean: bool = False) -> torch.Tensor:
     """torchmetrics ``signal_noise_ratio`` in dB per signal: 10 log10((sum t^2 + eps) / (sum (t - p)^2 + eps))."""
     return _signal_ratio(preds, target, lengths, RATIO_SNR, zero_mean, "snr")
+
+
+SDR_SEGMENT = 8192      # samples of a row per workgroup of the correlation kernel (csrc/sdr.hip kSegment)
+SDR_MAX_FILTER = 512    # taps of the distortion filter, at most
+
+
+def sdr_filter_length(value, what: str) -> int:
+    """``value`` as the taps of the distortion filter; ``ValueError`` unless it is an integer in [1, SDR_MAX_FILTER]."""
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)) or int(value) != value \
+            or not 1 <= int(value) <= SDR_MAX_FILTER:
+        raise ValueError(f"{what} must be an integer in [1, {SDR_MAX_FILTER}], got {value!r}")
+    return int(value)
+
+
+def sdr(preds: torch.Tensor, target: torch.Tensor, lengths: Lengths = None, filter_length: int = 512, zero_mean: bool = False,
+        load_diag: Optional[float] = None, use_cg_iter: Optional[int] = None) -> torch.Tensor:
+    """BSS-eval signal-to-distortion ratio in dB per signal, torchmetrics ``signal_distortion_ratio`` (direct solve): the estimate is
+    allowed a ``filter_length``-tap distortion filter before what is left counts as distortion.  (..., T) -> (...); with ``lengths``, of
+    ``[..., :lengths[r]]`` per row, each value the bits of the call on that row alone.  float64 throughout (``eben_sdr``: ragged
+    correlations and a Levinson solve per row); there is no eps, so a silent target gives NaN.  The conjugate-gradient branch
+    (``use_cg_iter``) is not built."""
+    if use_cg_iter is not None:
+        raise NotImplementedError("sdr: the conjugate-gradient solver (use_cg_iter) is not built; pass None for the direct solve")
+    taps = sdr_filter_length(filter_length, "sdr: filter_length")
+    diag = 0.0 if load_diag is None else float(load_diag)   # the ABI's 0.0 adds nothing
+    if diag != diag:
+        raise ValueError("sdr: load_diag is NaN")
+    p2, g2, lead, lens = _rows(preds, target, "sdr", lengths)
+    rows, t = p2.shape
+    lib = load()
+    ws = torch.empty(lib.eben_sdr_workspace(rows, t, taps), dtype=torch.uint8, device=p2.device)
+    out = torch.empty(rows, dtype=torch.float32, device=p2.device)
+    check(lib.eben_sdr(ptr(p2), ptr(g2), rows, t, _lens_ptr(lens), taps, int(bool(zero_mean)), diag, ws.data_ptr(), ptr(out),
+                       stream()), "sdr")
+    return out.reshape(lead)
 
 
 def stoi_resample_table(fs: int) -> Tuple[np.ndarray, int, int]:
@@ -329,6 +366,18 @@ class SignalNoiseRatio(_MeanMetric):
 
     def _values(self, preds, target, lengths=None):
         return snr(preds, target, lengths, zero_mean=self.zero_mean)
+
+
+class SignalDistortionRatio(_MeanMetric):
+    """Mean BSS-eval SDR (``sdr``), torchmetrics' class of the same name without its conjugate-gradient option."""
+
+    def __init__(self, filter_length: int = 512, zero_mean: bool = False, load_diag: Optional[float] = None):
+        super().__init__()
+        self.filter_length = sdr_filter_length(filter_length, "SignalDistortionRatio: filter_length")
+        self.zero_mean, self.load_diag = bool(zero_mean), load_diag
+
+    def _values(self, preds, target, lengths=None):
+        return sdr(preds, target, lengths, self.filter_length, self.zero_mean, self.load_diag)
 
 
 class ShortTimeObjectiveIntelligibility(_MeanMetric):
