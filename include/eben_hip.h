@@ -1114,6 +1114,43 @@ EBEN_API size_t eben_sdr_workspace(int rows, int t_max, int filter_length);
 EBEN_API int eben_sdr(const float* preds, const float* target, int rows, int t_max, const int32_t* lengths, int filter_length,
                       int zero_mean, double load_diag, void* workspace, float* out, void* stream);
 
+/* ---- frame-based objective speech measures (Hu & Loizou 2008: segmental SNR, frequency-weighted segmental SNR, LPC log-likelihood
+ * ratio, LPC cepstral distance; csrc/speech_measures.hip) -----------------------------------------------------------------------------
+ * The conventions of the evaluation metrics above: rows t_max floats apart, a NULLABLE device lengths, one float per row and measure,
+ * every reduction in an order that depends on the row's own length only, so a value has the bits of the call on its row alone; nothing
+ * at or behind a row's end is read; no host synchronisation.  preds = processed, target = clean.  The definitions restate the published
+ * code (parity unpinned):
+ *   fs 16000 or 8000; W = floor(0.030 fs + 0.5) (480 / 240), S = W / 4, F = (N - W) / S frames for a row of N >= W samples (one fewer
+ *   than would fit), frame f = samples [f S, f S + W).  window: W DOUBLES on the device, w[n] = 0.5 (1 - cos(2 pi (n + 1) / (W + 1))),
+ *   computed by the caller.  c = w * target frame, p = w * preds frame, in float64.  eps = 2^-52.  A frame is EMPTY when sum c^2 == 0 or
+ *   sum p^2 == 0.
+ *   EBEN_MEASURE_SEG_SNR     mean over all F frames of clip(10 log10(sum c^2 / (sum (c - p)^2 + eps) + eps), -10, 35)
+ *   EBEN_MEASURE_FW_SEG_SNR  n_fft = 1024 / 512, n2 = n_fft / 2; C[j] = |FFT(c)|[j] for j < n2 divided by its sum over j, P likewise
+ *                            (one float32 complex transform of c / |c| + i p / |p|); 25 critical bands with Gaussian-shaped filters
+ *                            g_i[j] = exp(-11 ((j - floor(cent_i / (fs / 2) n2)) / (bw_i / (fs / 2) n2))^2 + ln 70 - ln bw_i), set to 0
+ *                            where <= exp(-30 / 4.606) (centres 50 ... 3597.63 Hz and bandwidths 70 ... 346.136 Hz: the table in
+ *                            speech_measures.hip); Ec_i = sum_j C[j] g_i[j], Ep_i likewise; snr_i = clip(10 log10(Ec_i^2 /
+ *                            max((Ec_i - Ep_i)^2, eps)), -10, 35); frame value sum_i Ec_i^0.2 snr_i / sum_i Ec_i^0.2; the mean over
+ *                            the non-empty frames
+ *   LPC of order 16 / 10: R[k] = sum_n x[n] x[n + k], Levinson-Durbin, A = [1, -a_1 ... -a_P], float64.
+ *   EBEN_MEASURE_LLR         per non-empty frame min(2, ln((A_p T A_p') / (A_c T A_c'))), T the Toeplitz matrix of the clean frame's R
+ *   EBEN_MEASURE_CD          cep_1 = a_1, cep_m = a_m + (1 / m) sum_{k < m} k cep_k a_{m - k}; per non-empty frame
+ *                            min(10, (10 / ln 10) sqrt(2 sum_m (cep_c[m] - cep_p[m])^2))
+ *   LLR and CD of a row: the mean of the (95 F' + 50) / 100 smallest of its F' non-empty frames' values.
+ * measures: a non-empty mask of EBEN_MEASURE_*; out: one plane of `rows` floats per set bit, in bit order.  A row with F < 1 (N < W + S,
+ * or a lengths[r] outside [1, t_max]) is NaN in every plane; a row without a non-empty frame is NaN in all but the SEG_SNR plane.
+ * workspace: eben_speech_measures_workspace(rows, t_max, fs, measures) bytes on the device (the transform's twiddles and the band
+ * filters, then one double per row, possible frame and measure); the entry trusts its size.  EBEN_EINVAL before any launch for a null
+ * pointer (other than lengths), rows outside [1, 65535], t_max outside [1, INT_MAX - 4096], an fs other than the two or a mask that is
+ * empty or has other bits; eben_speech_measures_workspace returns 0 for such arguments.  Added without a version bump: functions only. */
+#define EBEN_MEASURE_SEG_SNR 1
+#define EBEN_MEASURE_FW_SEG_SNR 2
+#define EBEN_MEASURE_LLR 4
+#define EBEN_MEASURE_CD 8
+EBEN_API size_t eben_speech_measures_workspace(int rows, int t_max, int fs, int measures);
+EBEN_API int eben_speech_measures(const float* preds, const float* target, int rows, int t_max, const int32_t* lengths, int fs,
+                                  int measures, const double* window, void* workspace, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -299,6 +299,8 @@ SIGNATURES = {
     "eben_lsd": (c_int, [_P, _P, c_int, c_int, _P, c_int, c_int, POINTER(c_int), POINTER(c_int), c_int, _P, c_size_t, _P, _P]),
     "eben_sdr_workspace": (c_size_t, [c_int, c_int, c_int]),
     "eben_sdr": (c_int, [_P, _P, c_int, c_int, _P, c_int, c_int, ctypes.c_double, _P, _P, _P]),
+    "eben_speech_measures_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "eben_speech_measures": (c_int, [_P, _P, c_int, c_int, _P, c_int, c_int, _P, _P, _P, _P]),
     "eben_multirate_down": (c_int, [_P, _P, POINTER(c_int), POINTER(c_void_p), c_int, c_int, c_int, _P]),
     "eben_multirate_down_adjoint": (c_int, [_P, POINTER(c_void_p), _P, POINTER(c_int), _P, c_int, c_int, c_int, _P]),
     "eben_resample_adjoint": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),

@@ -34,6 +34,9 @@ EVAL_METRICS = ("si_sdr", "stoi", "estoi", "si_snr", "snr", "lsd", "lsd_hf")
 DEFAULT_EVAL_METRICS = ("si_sdr", "stoi")
 #: scored after a short distortion filter: "sdr" is the BSS-eval SDR (``metrics.sdr``) with ``sdr_filter_length`` taps
 EVAL_METRICS_FILTERED = ("sdr",)
+#: the frame-based measures of ``metrics.speech_measures`` (segmental SNR, frequency-weighted segmental SNR, LPC log-likelihood ratio,
+#: LPC cepstral distance): one call per batch for those that are named
+EVAL_METRICS_FRAMED = ("seg_snr", "fw_seg_snr", "llr", "cd")
 LSD_N_FFT, LSD_HOP = 2048, 512
 
 #: buffer samples (rows x padded length) per batch: 262 s at 16 kHz.  The widest activations (32 channels at 1/4 of the audio rate,
@@ -391,7 +394,8 @@ def evaluate_clips(generator, corrupted: Sequence[torch.Tensor], reference: Sequ
     ``"lsd_hf"`` is the LSD over ``[lsd_hf_cutoff_hz, 8000]`` Hz (Nyquist bin excluded) and needs that cutoff -- it depends on the sensor.
     ``"stoi"`` and ``"estoi"`` together share one resampling / silence-removal / band-envelope run.  ``"sdr"`` (``EVAL_METRICS_FILTERED``)
     is the BSS-eval SDR, which allows the enhanced clip a distortion filter of ``sdr_filter_length`` taps (1 to 512): one ``metrics.sdr``
-    call per batch on the same buffers and lengths.
+    call per batch on the same buffers and lengths.  ``EVAL_METRICS_FRAMED`` (``"seg_snr"``, ``"fw_seg_snr"``, ``"llr"``, ``"cd"``) are the
+    frame-based measures of ``metrics.speech_measures``: one call per batch for those named; a clip needs 600 samples at 16 kHz after the cut.
     Clips as for ``enhance_clips``; a pair has one length, and both are scored on their first
     ``cut_to_valid_length`` samples (a reference may carry anything behind them).  Batches as in ``enhance_clips``: per batch one
     ``forward_ragged`` and the metric kernels with ``lengths = plan.cut`` on the padded buffers -- nothing is unpacked unless
@@ -410,8 +414,8 @@ def evaluate_clips(generator, corrupted: Sequence[torch.Tensor], reference: Sequ
 
     names = list(metrics)
     for name in names:
-        if name not in EVAL_METRICS and name not in EVAL_METRICS_FILTERED:
-            raise ValueError(f"evaluate_clips: unknown metric {name!r}; known: {', '.join(EVAL_METRICS + EVAL_METRICS_FILTERED)}")
+        if name not in EVAL_METRICS + EVAL_METRICS_FILTERED + EVAL_METRICS_FRAMED:
+            raise ValueError(f"evaluate_clips: unknown metric {name!r}; known: {', '.join(EVAL_METRICS + EVAL_METRICS_FILTERED + EVAL_METRICS_FRAMED)}")
     if len(set(names)) != len(names):
         raise ValueError(f"evaluate_clips: a metric is named twice in {names}")
     if not names:
@@ -459,6 +463,13 @@ def evaluate_clips(generator, corrupted: Sequence[torch.Tensor], reference: Sequ
             t16 = resampled_length(ragged.cut_length(generator, t), sample_rate, EVAL_RATE)   # the cut length itself at 16 kHz
             if t16 <= LSD_N_FFT // 2:
                 raise ValueError(f"clip {i}: {t16} samples at {EVAL_RATE} Hz cannot be reflect-padded for the LSD ({LSD_N_FFT // 2 + 1} at least)")
+    framed = [name for name in names if name in EVAL_METRICS_FRAMED]
+    if framed:
+        w, hop = M.measures_geometry(EVAL_RATE)[:2]
+        for i, t in enumerate(lengths):
+            t16 = resampled_length(ragged.cut_length(generator, t), sample_rate, EVAL_RATE)
+            if t16 < w + hop:
+                raise ValueError(f"clip {i}: {t16} samples at {EVAL_RATE} Hz hold no frame of the frame-based measures ({w + hop} at least)")
     values: Dict[str, List[torch.Tensor]] = {name: [] for name in names}
     enhanced: List[torch.Tensor] = []
     losses: Dict[str, List[torch.Tensor]] = {key: [] for key in (loss_terms.keys() if loss_terms is not None else ())}
@@ -515,6 +526,9 @@ def evaluate_clips(generator, corrupted: Sequence[torch.Tensor], reference: Sequ
                 values[name].append(row)
         if "sdr" in values:
             values["sdr"].append(M.sdr(enh, ref, lens, filter_length=sdr_taps))
+        if framed:
+            for name, row in M.speech_measures(enh, ref, EVAL_RATE, lens, framed).items():
+                values[name].append(row)
     order = torch.tensor(back, dtype=torch.int64).to(values[names[0]][0].device, non_blocking=True)
     out: Dict[str, object] = {name: torch.cat(values[name]).index_select(0, order) for name in names}
     for key, rows_of in losses.items():

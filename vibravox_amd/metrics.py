@@ -14,6 +14,11 @@ distance over the whole band or over ``band_hz`` ranges; ``eben_lsd``).  ``sdr``
 ``signal_distortion_ratio``, direct solve: up to 512 lags of both correlations and a Toeplitz solve per row, float64; ``eben_sdr``), restated
 from torchmetrics 1.x without the package at hand (parity unpinned).
 
+``speech_measures`` (and ``seg_snr``, ``fw_seg_snr``, ``llr``, ``cepstral_distance`` on top of it) are the classic frame-based objective
+measures of Hu & Loizou (2008), the ``pysepm`` set without WSS and the PESQ composites: segmental SNR, frequency-weighted segmental SNR,
+the LPC log-likelihood ratio and the LPC cepstral distance over 30 ms frames (``eben_speech_measures``; LPC and sums float64, the
+transform float32).  pysepm is not installed here either: the definitions are restated from the published code (parity unpinned).
+
 All take ``(..., T)`` float tensors on a HIP device and return ``(...)`` float32 on that device, with torchmetrics' argument
 order (preds first).  There is no CPU path: a CPU tensor raises ``EbenError`` (the float64 restatement used to check these
 kernels is test code under ``tests/``).
@@ -309,6 +314,97 @@ def lsd(preds: torch.Tensor, target: torch.Tensor, fs: int, lengths: Lengths = N
     return out.reshape((len(bins),) + lead) if many else out[0].reshape(lead)
 
 
+#: the frame-based measures of ``speech_measures`` and their bits in ``eben_speech_measures`` (include/eben_hip.h EBEN_MEASURE_*)
+SPEECH_MEASURES = {"seg_snr": 1, "fw_seg_snr": 2, "llr": 4, "cd": 8}
+MEASURES_TILE_FRAMES = 16   # frames of a row per workgroup of the frame kernels (csrc/speech_measures.hip kTileFrames)
+
+
+def measures_geometry(fs) -> Tuple[int, int, int, int]:
+    """``(W, S, P, n_fft)`` of the frame-based measures at ``fs``: 30 ms frames, a quarter of that between them, the LPC order and the
+    transform of ``fw_seg_snr``.  ``ValueError`` unless ``fs`` is 16000 or 8000."""
+    if isinstance(fs, bool) or not isinstance(fs, (int, np.integer)) or int(fs) not in (16000, 8000):
+        raise ValueError(f"speech measures: fs must be 16000 or 8000, got {fs!r}")
+    w = int(math.floor(0.030 * int(fs) + 0.5))
+    return w, w // 4, 16 if int(fs) == 16000 else 10, 1 << math.ceil(math.log2(2 * w))
+
+
+def measures_window(fs: int) -> np.ndarray:
+    """The analysis window in float64: w[n] = 0.5 (1 - cos(2 pi (n + 1) / (W + 1))), n = 0 .. W - 1."""
+    w = measures_geometry(fs)[0]
+    return 0.5 * (1.0 - np.cos(2.0 * np.pi * np.arange(1, w + 1) / (w + 1)))
+
+
+_windows: Dict[Tuple[int, torch.device], torch.Tensor] = {}
+
+
+def _measures_window(fs: int, dev: torch.device) -> torch.Tensor:
+    """The window on ``dev``, uploaded once per (fs, device) and kept for the life of the module, like ``_stoi_table``'s tables.  The
+    upload is a blocking copy from pageable host memory (the one host wait of a (fs, device)'s first call): it has finished when
+    ``.to`` returns, so launches on any stream may read the tensor without an event."""
+    key = (fs, dev)
+    if key not in _windows:
+        _windows[key] = torch.from_numpy(measures_window(fs)).to(dev)
+    return _windows[key]
+
+
+def speech_measures(preds: torch.Tensor, target: torch.Tensor, fs: int, lengths: Lengths = None,
+                    which: Sequence[str] = ("seg_snr", "fw_seg_snr", "llr", "cd")) -> Dict[str, torch.Tensor]:
+    """The frame-based objective measures of Hu & Loizou (2008), the non-WSS, non-PESQ part of the ``pysepm`` set, per signal (preds =
+    processed, target = clean): ``{"seg_snr": segmental SNR in dB, "fw_seg_snr": frequency-weighted segmental SNR in dB, "llr": LPC
+    log-likelihood ratio, "cd": LPC cepstral distance}``, the keys of ``which`` in its order.  (..., T) -> (...) each; with ``lengths``, of
+    ``[..., :lengths[r]]`` per row, each value the bits of the call on that row alone.
+
+    Frames of W = 30 ms every S = W / 4 under ``measures_window``, (N - W) // S of them (one fewer than fit, as in the published code);
+    ``fs`` is 16000 or 8000; a row needs W + S samples (a shorter one in a device ``lengths`` is NaN).  ``llr`` and ``cd`` are the means of
+    the smallest 95 % of the frame values, ``fw_seg_snr``, ``llr`` and ``cd`` leave out frames in which either signal is all zero (NaN
+    when none is left).  The definitions are written out at ``eben_speech_measures`` in ``include/eben_hip.h``; pysepm is not installed
+    here, so they are restated from the published code (parity unpinned).  One launch sequence for whatever is asked
+    (``eben_speech_measures``): the spectral kernel runs only for ``fw_seg_snr``, the LPC work only for ``llr`` or ``cd``; LPC, segmental
+    sums and all means in float64, the transform in float32."""
+    names = list(which)
+    if not names:
+        raise ValueError("speech_measures: no measure requested")
+    for name in names:
+        if name not in SPEECH_MEASURES:
+            raise ValueError(f"speech_measures: unknown measure {name!r}; known: {', '.join(SPEECH_MEASURES)}")
+    if len(set(names)) != len(names):
+        raise ValueError(f"speech_measures: a measure is named twice in {names}")
+    w, s, _, _ = measures_geometry(fs)
+    fs = int(fs)
+    if preds.dim() >= 1 and preds.shape == target.shape and preds.shape[-1] < w + s:
+        raise ValueError(f"speech_measures: signals of {preds.shape[-1]} samples hold no frame at {fs} Hz ({w + s} at least)")
+    p2, g2, lead, lens = _rows(preds, target, "speech_measures", lengths, least=w + s)
+    rows, t = p2.shape
+    mask = sum(SPEECH_MEASURES[name] for name in names)
+    lib = load()
+    ws = torch.empty(lib.eben_speech_measures_workspace(rows, t, fs, mask), dtype=torch.uint8, device=p2.device)
+    out = torch.empty((len(names), rows), dtype=torch.float32, device=p2.device)
+    check(lib.eben_speech_measures(ptr(p2), ptr(g2), rows, t, _lens_ptr(lens), fs, mask, _measures_window(fs, p2.device).data_ptr(),
+                                   ws.data_ptr(), ptr(out), stream()), "speech_measures")
+    planes = sorted(names, key=SPEECH_MEASURES.get)   # the planes come in bit order
+    return {name: out[planes.index(name)].reshape(lead) for name in names}
+
+
+def seg_snr(preds: torch.Tensor, target: torch.Tensor, fs: int, lengths: Lengths = None) -> torch.Tensor:
+    """Segmental SNR in dB per signal (``speech_measures``): the mean of the frames' SNR, each clipped to [-10, 35] dB."""
+    return speech_measures(preds, target, fs, lengths, ("seg_snr",))["seg_snr"]
+
+
+def fw_seg_snr(preds: torch.Tensor, target: torch.Tensor, fs: int, lengths: Lengths = None) -> torch.Tensor:
+    """Frequency-weighted segmental SNR in dB per signal (``speech_measures``): 25 critical bands, weights (clean band magnitude)^0.2."""
+    return speech_measures(preds, target, fs, lengths, ("fw_seg_snr",))["fw_seg_snr"]
+
+
+def llr(preds: torch.Tensor, target: torch.Tensor, fs: int, lengths: Lengths = None) -> torch.Tensor:
+    """LPC log-likelihood ratio per signal (``speech_measures``): frame values capped at 2, the mean of the smallest 95 %."""
+    return speech_measures(preds, target, fs, lengths, ("llr",))["llr"]
+
+
+def cepstral_distance(preds: torch.Tensor, target: torch.Tensor, fs: int, lengths: Lengths = None) -> torch.Tensor:
+    """LPC cepstral distance per signal (``speech_measures``): frame values capped at 10, the mean of the smallest 95 %."""
+    return speech_measures(preds, target, fs, lengths, ("cd",))["cd"]
+
+
 class _MeanMetric(torch.nn.Module):
     """torchmetrics-style mean of a per-signal metric: state is a device-side sum and count (not buffers)."""
 
@@ -378,6 +474,36 @@ class SignalDistortionRatio(_MeanMetric):
 
     def _values(self, preds, target, lengths=None):
         return sdr(preds, target, lengths, self.filter_length, self.zero_mean, self.load_diag)
+
+
+class _SpeechMeasure(_MeanMetric):
+    """Mean of one of ``speech_measures``' values at ``fs`` (16000 or 8000)."""
+
+    measure = ""
+
+    def __init__(self, fs: int):
+        super().__init__()
+        measures_geometry(fs)   # another rate is refused here
+        self.fs = int(fs)
+
+    def _values(self, preds, target, lengths=None):
+        return speech_measures(preds, target, self.fs, lengths, (self.measure,))[self.measure]
+
+
+class SegmentalSignalNoiseRatio(_SpeechMeasure):
+    measure = "seg_snr"
+
+
+class FrequencyWeightedSegmentalSNR(_SpeechMeasure):
+    measure = "fw_seg_snr"
+
+
+class LogLikelihoodRatio(_SpeechMeasure):
+    measure = "llr"
+
+
+class CepstralDistance(_SpeechMeasure):
+    measure = "cd"
 
 
 class ShortTimeObjectiveIntelligibility(_MeanMetric):
