@@ -943,6 +943,14 @@ typedef struct EbenPcmEncRow {
 EBEN_API int eben_pcm_encode_plan(int* out, int n);
 EBEN_API int eben_pcm_encode_ragged(const float* src, long long src_floats, const EbenPcmEncRow* rows_host, const EbenPcmEncRow* rows_dev, void* image,
                                     long long image_bytes, int32_t* clipped, int rows, void* stream);
+/* eben_pcm_encode_ragged with a factor per row: gains is a DEVICE float32 table of `rows` entries (required, 4-byte aligned), and sample
+ * n of row r is converted from v = x[n] * gains[r], rounded to float32 first -- the same kernel body, tile, rounding, clamp, NaN rule and
+ * clipped count (a NaN gain makes every sample of its row a NaN); EBEN_PCM_F32 stores the bits of v.  With every gain exactly 1.0 the
+ * image is that of eben_pcm_encode_ragged (a signalling NaN in an EBEN_PCM_F32 row aside: the product quiets it).  The table is read by
+ * the kernel alone, so it may come from a launch queued in front of this one (eben_loudness) without a host wait.  Refusals as above,
+ * plus a null or misaligned gains.  Added without a version bump: a function only. */
+EBEN_API int eben_pcm_encode_ragged_gain(const float* src, long long src_floats, const EbenPcmEncRow* rows_host, const EbenPcmEncRow* rows_dev,
+                                         void* image, long long image_bytes, int32_t* clipped, const float* gains, int rows, void* stream);
 
 /* ---- live sessions in and out as PCM at the caller's rate (csrc/stream_pcm.hip): the pool's front and back end, one launch each ----------
  * eben_stream_pcm_out: the back end of all sessions of one run -- what eben_rate_splice_slots, eben_resample_slots and
@@ -1150,6 +1158,37 @@ EBEN_API int eben_sdr(const float* preds, const float* target, int rows, int t_m
 EBEN_API size_t eben_speech_measures_workspace(int rows, int t_max, int fs, int measures);
 EBEN_API int eben_speech_measures(const float* preds, const float* target, int rows, int t_max, const int32_t* lengths, int fs,
                                   int measures, const double* window, void* workspace, float* out, void* stream);
+
+/* ---- integrated loudness of ITU-R BS.1770-4, one channel, per row (csrc/loudness.hip) ------------------------------------------------------
+ * Restated from the recommendation (parity with pyloudnorm / libebur128 unpinned).  x: (rows, t_max) float32 on the device; row r is its
+ * first lengths[r] samples (lengths: DEVICE int32, or NULL: every row has t_max), nothing behind them is read.
+ *   K-weighting  two second-order sections in cascade from a zero state at the row's first sample, coefficients for `fs` in float64 on the
+ *                host (eben_k_weighting: coef = shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2).  Shelf: f0 = 1681.974450955533,
+ *                G = 3.999843853973347 dB, Q = 0.7071752369554196, K = tan(pi f0 / fs), Vh = 10^(G/20), Vb = Vh^0.4996667741545416,
+ *                a0 = 1 + K/Q + K^2, b = [(Vh + Vb K/Q + K^2)/a0, 2(K^2 - Vh)/a0, (Vh - Vb K/Q + K^2)/a0], a = [1, 2(K^2 - 1)/a0,
+ *                (1 - K/Q + K^2)/a0].  High-pass: f0 = 38.13547087602444, Q = 0.5003270373238773, b = [1, -2, 1], a as above with its own
+ *                K and a0.  At 48 kHz these are the recommendation's printed coefficients.
+ *   blocks       n = 0.4 fs samples every h = 0.1 fs, only those wholly inside the row; z_j = the mean square of block j's weighted samples,
+ *                l_j = -0.691 + 10 log10 z_j.
+ *   gates        absolute: l_j > -70; relative: Gr = -0.691 + 10 log10(mean of the z_j kept by the absolute gate) - 10;
+ *                loudness[r] = -0.691 + 10 log10(mean of the z_j with l_j > -70 and l_j > Gr), -inf when no block is left (or there is none).
+ *   peak[r]      max |x| over the row's own samples (sample peak), 0 for an empty row.
+ *   gain[r]      (gain may be NULL) g = 10^((target_lufs - L) / 20), L before its rounding to float32; if g * peak > 10^(peak_dbfs / 20)
+ *                then g = 10^(peak_dbfs / 20) / peak; g = 1 when L is not finite or the peak is 0.  Formed in float64, stored as float32.
+ * Filter state, squares and every sum are float64 on the float32 input; each sum has one fixed order that depends only on a sample's
+ * place in its own row (no floating-point atomics), so a row's three values are the bits of the call on that row alone, in any batch,
+ * at any position and buffer width.  A lengths[r] outside [0, t_max] makes loudness[r] and peak[r] NaN and gain[r] 1; NaN samples make
+ * them NaN as well.  The weighted signal is never stored: the workspace (eben_loudness_workspace bytes on the device, 8-byte aligned)
+ * holds a state per 4096-sample chunk, a sum per (chunk, hop) piece and per hop, and a peak per chunk.  Launches: two passes over the
+ * input with a carry between them (one pass when t_max <= 4096) and one workgroup per row for the gates.
+ * EBEN_EINVAL before any launch for: a null pointer (other than lengths and gain) or a misaligned one (workspace to 8 bytes, the others to
+ * 4); rows outside [1, 65535]; t_max outside [1, INT_MAX - 4096]; an fs that is no positive multiple of 10; a non-finite target_lufs or
+ * peak_dbfs; ws_bytes below eben_loudness_workspace(rows, t_max, fs), which returns 0 for arguments that would be refused.
+ * Added without a version bump: functions only. */
+EBEN_API int eben_k_weighting(int fs, double* coef /* 10 values, HOST */);
+EBEN_API size_t eben_loudness_workspace(int rows, int t_max, int fs);
+EBEN_API int eben_loudness(const float* x, int rows, int t_max, const int32_t* lengths, int fs, double target_lufs, double peak_dbfs, float* loudness,
+                           float* peak, float* gain, void* workspace, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -325,6 +325,10 @@ SIGNATURES = {
     "eben_pcm_resample_ragged": (c_int, [_P, c_int64, _P, _P, _P, _P, _P, _P, _P, c_int, c_int64, c_int, c_int, c_int, _P]),
     "eben_pcm_encode_plan": (c_int, [POINTER(c_int), c_int]),
     "eben_pcm_encode_ragged": (c_int, [_P, c_int64, _P, _P, _P, c_int64, _P, c_int, _P]),
+    "eben_pcm_encode_ragged_gain": (c_int, [_P, c_int64, _P, _P, _P, c_int64, _P, _P, c_int, _P]),
+    "eben_k_weighting": (c_int, [c_int, POINTER(ctypes.c_double)]),
+    "eben_loudness_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "eben_loudness": (c_int, [_P, c_int, c_int, _P, c_int, ctypes.c_double, ctypes.c_double, _P, _P, _P, _P, c_size_t, _P]),
     "eben_stream_pcm_plan": (c_int, [c_int, c_int, c_int, POINTER(c_int), c_int]),
     "eben_stream_pcm_out": (c_int, [_P, _P, c_int, c_int, _P, c_int, c_int, POINTER(EbenRateRatio), c_int, _P, c_int64, _P, POINTER(EbenStreamPcmPiece),
                                     c_int, _P]),

@@ -327,12 +327,17 @@ def pcm_to_rows(data: torch.Tensor, rows: np.ndarray, *, rates: Optional[Tuple[i
     return out, out_lens
 
 
-def rows_to_pcm(src: torch.Tensor, rows: np.ndarray, image: torch.Tensor, clipped: Optional[torch.Tensor] = None) -> torch.Tensor:
+def rows_to_pcm(src: torch.Tensor, rows: np.ndarray, image: torch.Tensor, clipped: Optional[torch.Tensor] = None,
+                gains: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``csrc/pcm_encode.hip`` on buffers that are on the device: the way back of ``pcm_to_rows``.  ``src``: a contiguous float32 device
     tensor of any shape, addressed flat; ``rows``: an ``ENC_ROW_DTYPE`` array, one descriptor per row (``src_offset`` in floats,
     ``byte_offset`` a multiple of 16, ``samples``, ``format`` an index of ``FORMATS``), uploaded here; ``image``: a contiguous uint8
     device tensor (its storage 16-byte aligned) that receives the rows' bytes and nothing else.  Returns ``clipped``, an int32 device
-    tensor with the clipped-sample count of every row (allocated here unless given).  One launch, nothing waits."""
+    tensor with the clipped-sample count of every row (allocated here unless given).  One launch, nothing waits.
+
+    ``gains``: a contiguous float32 device tensor with one factor per row; every sample is then converted from ``x * gains[r]``, rounded
+    to float32 first (``eben_pcm_encode_ragged_gain``, the same kernel body).  The table may come straight from
+    ``metrics.loudness_gain``: only the kernel reads it."""
     from ._lib import check, load, ptr, stream
 
     rows = np.ascontiguousarray(rows, dtype=ENC_ROW_DTYPE)
@@ -344,6 +349,12 @@ def rows_to_pcm(src: torch.Tensor, rows: np.ndarray, image: torch.Tensor, clippe
     elif clipped.dtype is not torch.int32 or tuple(clipped.shape) != (n,) or clipped.device != image.device or not clipped.is_contiguous():
         raise ValueError(f"rows_to_pcm: clipped must be a contiguous int32 ({n},) tensor on {image.device}, got {clipped.dtype} {tuple(clipped.shape)}")
     rows_dev = torch.from_numpy(rows.view(np.uint8).reshape(-1)).to(image.device, non_blocking=True)
+    if gains is not None:
+        if gains.dtype is not torch.float32 or tuple(gains.shape) != (n,) or gains.device != image.device or not gains.is_contiguous():
+            raise ValueError(f"rows_to_pcm: gains must be a contiguous float32 ({n},) tensor on {image.device}, got {gains.dtype} {tuple(gains.shape)}")
+        check(load().eben_pcm_encode_ragged_gain(ptr(src), src.numel(), rows.ctypes.data, rows_dev.data_ptr(), image.data_ptr(), image.numel(),
+                                                 clipped.data_ptr(), gains.data_ptr(), n, stream()), "pcm_encode_ragged_gain")
+        return clipped
     check(load().eben_pcm_encode_ragged(ptr(src), src.numel(), rows.ctypes.data, rows_dev.data_ptr(), image.data_ptr(), image.numel(), clipped.data_ptr(), n,
                                         stream()), "pcm_encode_ragged")
     return clipped

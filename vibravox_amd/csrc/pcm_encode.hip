@@ -11,6 +11,8 @@
 //                       one per lane (coalesced wherever the row starts on the 4-byte grid), converts into LDS and stores 16 bytes (8
 //                       samples) per lane from there: the image offset is a multiple of 16, so every full vector is aligned; the last
 //                       partial vector of a row goes out sample by sample.  The other formats store sample by sample.
+//                       pcm_encode_kernel<true> (eben_pcm_encode_ragged_gain) is the same body with every sample read as x * gains[row],
+//                       rounded to float32, in front of the conversion: a loudness-normalised export without a scaled copy of the rows.
 //
 // Only the rows' own bytes are written.  The host validates its own copy of the table before anything is launched; the kernel reads the
 // uploaded copy and treats a row whose numbers would reach outside the source or the image as empty.
@@ -34,6 +36,7 @@ struct EncArgs {
   unsigned char* image;
   long long image_bytes;
   int* clipped;
+  const float* gains;   // pcm_encode_kernel<true> only: one factor per row
 };
 
 __host__ __device__ inline int enc_bytes(int format) { return format == EBEN_PCM_S16 ? 2 : format == EBEN_PCM_S24 ? 3 : 4; }
@@ -69,6 +72,7 @@ __device__ __forceinline__ int enc_int(float x, int* clip) {
   return (int)v;
 }
 
+template <bool GAIN>
 __global__ __launch_bounds__(ENC_THREADS) void pcm_encode_kernel(EncArgs p) {
   __shared__ __attribute__((aligned(16))) short buf[ENC_TILE];
   __shared__ int block_clip;
@@ -83,11 +87,13 @@ __global__ __launch_bounds__(ENC_THREADS) void pcm_encode_kernel(EncArgs p) {
   const float* x = p.src + d.src_offset;
   unsigned char* o = p.image + d.byte_offset;
   int clip = 0;
+  const float g = GAIN ? p.gains[r] : 1.f;
+  auto sample = [&](long long n) { return GAIN ? x[n] * g : x[n]; };   // the product rounds to float32 before anything else sees it
   if (d.format == EBEN_PCM_S16) {
 #pragma unroll
     for (int k = 0; k < ENC_PER_THREAD; ++k) {
       const int s = t + ENC_THREADS * k;
-      if (n0 + s < samples) buf[s] = (short)enc_int<16>(x[n0 + s], &clip);
+      if (n0 + s < samples) buf[s] = (short)enc_int<16>(sample(n0 + s), &clip);
     }
     if (clip) atomicAdd(&block_clip, clip);
     __syncthreads();
@@ -103,13 +109,15 @@ __global__ __launch_bounds__(ENC_THREADS) void pcm_encode_kernel(EncArgs p) {
       const long long n = n0l + t + ENC_THREADS * k;
       if (n >= samples) continue;
       if (d.format == EBEN_PCM_S24) {
-        const int v = enc_int<24>(x[n], &clip);
+        const int v = enc_int<24>(sample(n), &clip);
         unsigned char* b = o + 3 * n;
         b[0] = (unsigned char)v;
         b[1] = (unsigned char)(v >> 8);
         b[2] = (unsigned char)(v >> 16);
       } else if (d.format == EBEN_PCM_S32) {
-        *reinterpret_cast<int*>(o + 4 * n) = enc_int<32>(x[n], &clip);
+        *reinterpret_cast<int*>(o + 4 * n) = enc_int<32>(sample(n), &clip);
+      } else if (GAIN) {
+        *reinterpret_cast<float*>(o + 4 * n) = sample(n);
       } else {
         *reinterpret_cast<unsigned*>(o + 4 * n) = reinterpret_cast<const unsigned*>(x)[n];
       }
@@ -127,20 +135,9 @@ struct EncSpan {
   int row;
 };
 
-}  // namespace
-}  // namespace eben
-
-using namespace eben;
-
-extern "C" int eben_pcm_encode_plan(int* out, int n) {
-  EBEN_REQUIRE(out && n >= 1, "pcm_encode_plan: needs room for 1 value, got %d at %p", n, (void*)out);
-  out[0] = ENC_TILE;
-  return EBEN_OK;
-}
-
-extern "C" int eben_pcm_encode_ragged(const float* src, long long src_floats, const EbenPcmEncRow* rows_host, const EbenPcmEncRow* rows_dev, void* image,
-                                      long long image_bytes, int32_t* clipped, int rows, void* stream) {
-  const char* what = "pcm_encode_ragged";
+// what the two entry points share: `gains` null is eben_pcm_encode_ragged
+int enc_launch(const char* what, const float* src, long long src_floats, const EbenPcmEncRow* rows_host, const EbenPcmEncRow* rows_dev, void* image,
+               long long image_bytes, int32_t* clipped, const float* gains, int rows, void* stream) {
   EBEN_REQUIRE(src && rows_host && rows_dev && image && clipped, "%s: null pointer", what);
   EBEN_REQUIRE(enc_aligned(image, 16) && enc_aligned(rows_host, 8) && enc_aligned(rows_dev, 8) && enc_aligned(src, 4) && enc_aligned(clipped, 4),
                "%s: misaligned pointer (image to 16 bytes, tables to 8, src and clipped to 4)", what);
@@ -171,8 +168,35 @@ extern "C" int eben_pcm_encode_ragged(const float* src, long long src_floats, co
   if (e != hipSuccess) return hip_fail(e, "pcm_encode_ragged: zeroing the clipped counts");
   if (longest == 0) return EBEN_OK;   // every row empty
   const int tiles = (longest + ENC_TILE - 1) / ENC_TILE;
-  const EncArgs p{src, src_floats, rows_dev, static_cast<unsigned char*>(image), image_bytes, clipped};
-  hipLaunchKernelGGL(pcm_encode_kernel, dim3((unsigned)tiles, (unsigned)rows), dim3(ENC_THREADS), 0, as_stream(stream), p);
+  const EncArgs p{src, src_floats, rows_dev, static_cast<unsigned char*>(image), image_bytes, clipped, gains};
+  const dim3 grid((unsigned)tiles, (unsigned)rows);
+  if (gains) {
+    hipLaunchKernelGGL(pcm_encode_kernel<true>, grid, dim3(ENC_THREADS), 0, as_stream(stream), p);
+  } else {
+    hipLaunchKernelGGL(pcm_encode_kernel<false>, grid, dim3(ENC_THREADS), 0, as_stream(stream), p);
+  }
   EBEN_CHECK_LAUNCH("pcm_encode_kernel");
   return EBEN_OK;
+}
+
+}  // namespace
+}  // namespace eben
+
+using namespace eben;
+
+extern "C" int eben_pcm_encode_plan(int* out, int n) {
+  EBEN_REQUIRE(out && n >= 1, "pcm_encode_plan: needs room for 1 value, got %d at %p", n, (void*)out);
+  out[0] = ENC_TILE;
+  return EBEN_OK;
+}
+
+extern "C" int eben_pcm_encode_ragged(const float* src, long long src_floats, const EbenPcmEncRow* rows_host, const EbenPcmEncRow* rows_dev, void* image,
+                                      long long image_bytes, int32_t* clipped, int rows, void* stream) {
+  return enc_launch("pcm_encode_ragged", src, src_floats, rows_host, rows_dev, image, image_bytes, clipped, nullptr, rows, stream);
+}
+
+extern "C" int eben_pcm_encode_ragged_gain(const float* src, long long src_floats, const EbenPcmEncRow* rows_host, const EbenPcmEncRow* rows_dev,
+                                           void* image, long long image_bytes, int32_t* clipped, const float* gains, int rows, void* stream) {
+  EBEN_REQUIRE(gains && enc_aligned(gains, 4), "pcm_encode_ragged_gain: a null or misaligned table of gains");
+  return enc_launch("pcm_encode_ragged_gain", src, src_floats, rows_host, rows_dev, image, image_bytes, clipped, gains, rows, stream);
 }

@@ -37,6 +37,9 @@ EVAL_METRICS_FILTERED = ("sdr",)
 #: the frame-based measures of ``metrics.speech_measures`` (segmental SNR, frequency-weighted segmental SNR, LPC log-likelihood ratio,
 #: LPC cepstral distance): one call per batch for those that are named
 EVAL_METRICS_FRAMED = ("seg_snr", "fw_seg_snr", "llr", "cd")
+#: level: "lufs_diff" is the integrated loudness (ITU-R BS.1770-4, ``metrics.integrated_loudness``) of the enhanced clip minus its
+#: reference's, in LU -- one measuring call per signal per batch; NaN when neither has a finite loudness, +-inf when one has none
+EVAL_METRICS_LEVEL = ("lufs_diff",)
 LSD_N_FFT, LSD_HOP = 2048, 512
 
 #: buffer samples (rows x padded length) per batch: 262 s at 16 kHz.  The widest activations (32 channels at 1/4 of the audio rate,
@@ -181,23 +184,31 @@ def _batch_forwards(generator, clips, lengths, batches, rated: bool, input_rate,
 
 
 def _encode_group(generator, clips, lengths, counts, group, fmt: int, rated: bool, input_rate, model_rate: int, out_rate: int, max_batch_samples: int,
-                  dev_image: torch.Tensor, host_half: torch.Tensor):
+                  dev_image: torch.Tensor, host_half: torch.Tensor, loudness: Optional[float] = None, peak: float = -1.0):
     """Queues one group of ``enhance_to_pcm``: its clips' batches through the generator, per batch one encode launch from the output
     buffer's rows into the device image (behind one ``rate.resample_ragged`` launch when the files are at another rate), then one
     asynchronous copy of image and clipped counts into ``host_half``.  Returns ``(order, event)``: the group's clips in the order of
-    their counts, and the event behind the copy.  Nothing waits."""
+    their counts, and the event behind the copy.  Nothing waits.
+
+    With ``loudness`` every batch's rows are measured where they lie, at ``out_rate``, by one ``metrics.loudness_gain`` call in front of
+    the encode launch, which reads the gains from the device; the rows' loudness and gain follow the counts in the image's tail
+    (float32, ``n`` each) and travel in the same copy."""
     import numpy as np
 
     from . import corpus as C
+    from . import metrics as M
     from . import rate
 
     lo, hi = group.lo, group.hi
     n = hi - lo
     sub_clips, sub_lengths = clips[lo:hi], lengths[lo:hi]
     counts_at = group.nbytes
-    total = counts_at + 4 * n
+    total = counts_at + (4 if loudness is None else 12) * n
     image = dev_image[:counts_at]
-    clipped = dev_image[counts_at:total].view(torch.int32)
+    clipped = dev_image[counts_at:counts_at + 4 * n].view(torch.int32)
+    if loudness is not None:
+        measured = dev_image[counts_at + 4 * n:counts_at + 8 * n].view(torch.float32)
+        applied = dev_image[counts_at + 8 * n:total].view(torch.float32)
     order: List[int] = []
     with torch.no_grad(), torch.cuda.device(dev_image.device):
         batches, _ = ragged.compose_batches(generator, sub_lengths, max_batch_samples)
@@ -208,7 +219,13 @@ def _encode_group(generator, clips, lengths, counts, group, fmt: int, rated: boo
             table = np.zeros(len(idx), dtype=C.ENC_ROW_DTYPE)
             for r, i in enumerate(idx):   # the batches are not in clip order: every row carries its own place in the image
                 table[r] = (r * pitch, group.starts[i] + C.HEADER_BYTES, counts[lo + i], fmt)
-            C.rows_to_pcm(src, table, image, clipped[len(order):len(order) + len(idx)])
+            at = slice(len(order), len(order) + len(idx))
+            gains = None
+            if loudness is not None:
+                level, _, gains = M.loudness_gain(src.reshape(len(idx), pitch), out_rate, [counts[lo + i] for i in idx], loudness, peak)
+                measured[at].copy_(level)
+                applied[at].copy_(gains)
+            C.rows_to_pcm(src, table, image, clipped[at], gains)
             order.extend(idx)
         host_half[:total].copy_(dev_image[:total], non_blocking=True)
         event = torch.cuda.Event()
@@ -218,7 +235,7 @@ def _encode_group(generator, clips, lengths, counts, group, fmt: int, rated: boo
 
 def enhance_to_pcm(generator, clips: Sequence[torch.Tensor], *, format: str = "PCM16", input_rate: Optional[int] = None,
                    output_rate: Optional[int] = None, model_rate: int = 16000, max_batch_samples: int = MAX_BATCH_SAMPLES,
-                   max_stage_bytes: int = 1 << 30):
+                   max_stage_bytes: int = 1 << 30, loudness: Optional[float] = None, peak: float = -1.0):
     """``enhance_clips`` whose results leave the device as the bytes of WAVE files: a generator that yields, group by group,
     ``(indices, image, spans, clipped)``.  ``indices``: the clips of the group, a run of consecutive input positions; ``image``: a pinned
     uint8 host tensor; ``spans[k]``: the ``(start, stop)`` of clip ``indices[k]``'s complete mono file in it (``corpus.wav_header`` and
@@ -232,7 +249,14 @@ def enhance_to_pcm(generator, clips: Sequence[torch.Tensor], *, format: str = "P
     the output buffer where they lie (one ``rate.resample_ragged`` launch in front of it when the rate changes) and writes at the clips'
     places of the group's image (``corpus.plan_image``: groups of at most ``max_stage_bytes``, halved when there are several, plus 4
     bytes a file for the counts); one asynchronous copy per group brings image and counts to the host, and the next group's launches are
-    queued before the previous copy's event is waited for -- the only wait.  The host writes the headers once the copy has arrived."""
+    queued before the previous copy's event is waited for -- the only wait.  The host writes the headers once the copy has arrived.
+
+    ``loudness`` (LUFS, e.g. -23.0): every file is brought to that integrated loudness (ITU-R BS.1770-4, ``metrics.loudness_gain``) with its
+    sample peak held at or below ``peak`` dBFS.  Per batch one measuring call on the rows that are about to be encoded -- behind
+    ``rate.resample_ragged`` when there is an ``output_rate``, and at that rate -- whose gains the encode launch reads on the device
+    (``eben_pcm_encode_ragged_gain``): no scaled copy, no host wait.  The generator then yields a fifth element, ``levels``:
+    ``levels[k] = (measured LUFS, gain as a factor)`` of clip ``indices[k]``, brought over in the counts' copy; a clip without a finite
+    loudness (silence, or shorter than 0.4 s) keeps its level, gain 1.  Without ``loudness`` nothing changes: four elements, the same bytes."""
     import numpy as np
 
     from . import corpus as C
@@ -244,6 +268,12 @@ def enhance_to_pcm(generator, clips: Sequence[torch.Tensor], *, format: str = "P
     out_rate = model_rate if output_rate is None else int(output_rate)
     if out_rate <= 0 or model_rate <= 0:
         raise ValueError(f"enhance_to_pcm: output_rate and model_rate must be positive, got {output_rate} and {model_rate}")
+    if loudness is not None:
+        loudness, peak = float(loudness), float(peak)
+        if not (math.isfinite(loudness) and math.isfinite(peak)):
+            raise ValueError(f"enhance_to_pcm: loudness and peak must be finite, got {loudness} LUFS and {peak} dBFS")
+        if out_rate % 10:
+            raise ValueError(f"enhance_to_pcm: loudness is measured over 100 ms hops, which {out_rate} Hz does not divide into whole samples")
     if not clips:
         return
     ragged.plan(generator, lengths)   # refuses a clip that is too short, by index, before anything runs
@@ -256,7 +286,7 @@ def enhance_to_pcm(generator, clips: Sequence[torch.Tensor], *, format: str = "P
     if len(groups) > 1:
         groups = C.plan_image(counts, format, max_stage_bytes // 2)
     n_halves = 2 if len(groups) > 1 else 1
-    half = max(g.nbytes + C._up(4 * (g.hi - g.lo)) for g in groups)
+    half = max(g.nbytes + C._up((4 if loudness is None else 12) * (g.hi - g.lo)) for g in groups)
     device = clips[0].device
     with torch.cuda.device(device):
         dev_image = torch.empty(half, dtype=torch.uint8, device=device)   # one: a group's launches follow the previous copy in stream order
@@ -277,13 +307,19 @@ def enhance_to_pcm(generator, clips: Sequence[torch.Tensor], *, format: str = "P
         clipped = [0] * n
         for pos, i in enumerate(order):
             clipped[i] = int(got[pos])
-        return list(range(group.lo, group.hi)), image, spans, clipped
+        if loudness is None:
+            return list(range(group.lo, group.hi)), image, spans, clipped
+        tail = host[h * half + group.nbytes + 4 * n:h * half + group.nbytes + 12 * n].numpy().view("<f4")
+        levels = [(0.0, 1.0)] * n
+        for pos, i in enumerate(order):
+            levels[i] = (float(tail[pos]), float(tail[n + pos]))
+        return list(range(group.lo, group.hi)), image, spans, clipped, levels
 
     pending = None
     for g, group in enumerate(groups):
         h = g % n_halves
         order, event = _encode_group(generator, clips, lengths, counts, group, fmt, rated, input_rate, model_rate, out_rate, max_batch_samples,
-                                     dev_image, host[h * half:(h + 1) * half])
+                                     dev_image, host[h * half:(h + 1) * half], loudness, peak)
         if pending is not None:
             yield arrived(*pending)
         pending = (group, h, order, event)
@@ -396,6 +432,7 @@ def evaluate_clips(generator, corrupted: Sequence[torch.Tensor], reference: Sequ
     is the BSS-eval SDR, which allows the enhanced clip a distortion filter of ``sdr_filter_length`` taps (1 to 512): one ``metrics.sdr``
     call per batch on the same buffers and lengths.  ``EVAL_METRICS_FRAMED`` (``"seg_snr"``, ``"fw_seg_snr"``, ``"llr"``, ``"cd"``) are the
     frame-based measures of ``metrics.speech_measures``: one call per batch for those named; a clip needs 600 samples at 16 kHz after the cut.
+    ``"lufs_diff"`` (``EVAL_METRICS_LEVEL``) is the enhanced clip's integrated loudness minus its reference's, in LU.
     Clips as for ``enhance_clips``; a pair has one length, and both are scored on their first
     ``cut_to_valid_length`` samples (a reference may carry anything behind them).  Batches as in ``enhance_clips``: per batch one
     ``forward_ragged`` and the metric kernels with ``lengths = plan.cut`` on the padded buffers -- nothing is unpacked unless
@@ -414,8 +451,9 @@ def evaluate_clips(generator, corrupted: Sequence[torch.Tensor], reference: Sequ
 
     names = list(metrics)
     for name in names:
-        if name not in EVAL_METRICS + EVAL_METRICS_FILTERED + EVAL_METRICS_FRAMED:
-            raise ValueError(f"evaluate_clips: unknown metric {name!r}; known: {', '.join(EVAL_METRICS + EVAL_METRICS_FILTERED + EVAL_METRICS_FRAMED)}")
+        if name not in EVAL_METRICS + EVAL_METRICS_FILTERED + EVAL_METRICS_FRAMED + EVAL_METRICS_LEVEL:
+            known = EVAL_METRICS + EVAL_METRICS_FILTERED + EVAL_METRICS_FRAMED + EVAL_METRICS_LEVEL
+            raise ValueError(f"evaluate_clips: unknown metric {name!r}; known: {', '.join(known)}")
     if len(set(names)) != len(names):
         raise ValueError(f"evaluate_clips: a metric is named twice in {names}")
     if not names:
@@ -529,6 +567,8 @@ def evaluate_clips(generator, corrupted: Sequence[torch.Tensor], reference: Sequ
         if framed:
             for name, row in M.speech_measures(enh, ref, EVAL_RATE, lens, framed).items():
                 values[name].append(row)
+        if "lufs_diff" in values:
+            values["lufs_diff"].append(M.integrated_loudness(enh, EVAL_RATE, lens) - M.integrated_loudness(ref, EVAL_RATE, lens))
     order = torch.tensor(back, dtype=torch.int64).to(values[names[0]][0].device, non_blocking=True)
     out: Dict[str, object] = {name: torch.cat(values[name]).index_select(0, order) for name in names}
     for key, rows_of in losses.items():

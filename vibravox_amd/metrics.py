@@ -19,6 +19,10 @@ measures of Hu & Loizou (2008), the ``pysepm`` set without WSS and the PESQ comp
 the LPC log-likelihood ratio and the LPC cepstral distance over 30 ms frames (``eben_speech_measures``; LPC and sums float64, the
 transform float32).  pysepm is not installed here either: the definitions are restated from the published code (parity unpinned).
 
+``integrated_loudness`` / ``loudness_gain`` measure one signal's level as a listener perceives it: the integrated loudness of ITU-R
+BS.1770-4 (K-weighting, gated 400 ms blocks; ``eben_loudness``), its sample peak and the gain to a target level under a peak ceiling --
+what ``inference.enhance_to_pcm(loudness=)`` normalises its files with.  Restated from the recommendation (parity unpinned).
+
 All take ``(..., T)`` float tensors on a HIP device and return ``(...)`` float32 on that device, with torchmetrics' argument
 order (preds first).  There is no CPU path: a CPU tensor raises ``EbenError`` (the float64 restatement used to check these
 kernels is test code under ``tests/``).
@@ -405,6 +409,72 @@ def cepstral_distance(preds: torch.Tensor, target: torch.Tensor, fs: int, length
     return speech_measures(preds, target, fs, lengths, ("cd",))["cd"]
 
 
+def _loudness_fs(fs, what: str) -> int:
+    if isinstance(fs, bool) or not isinstance(fs, (int, np.integer)) or int(fs) <= 0 or int(fs) % 10:
+        raise ValueError(f"{what}: fs must be a positive multiple of 10 (the 100 ms hop is a whole number of samples), got {fs!r}")
+    return int(fs)
+
+
+def k_weighting_coefficients(fs) -> Tuple[np.ndarray, np.ndarray]:
+    """The two second-order sections of the K-weighting of ITU-R BS.1770-4 at ``fs``, in float64 on the host: ``(shelf, highpass)``, each
+    ``[b0, b1, b2, a1, a2]`` with ``a0 = 1`` (the formulas stand at ``eben_loudness`` in ``include/eben_hip.h``; at 48 kHz they give the
+    recommendation's printed table).  ``ValueError`` unless ``fs`` is a positive multiple of 10."""
+    fs = _loudness_fs(fs, "k_weighting_coefficients")
+    f0, gain_db, q = 1681.974450955533, 3.999843853973347, 0.7071752369554196
+    k = math.tan(math.pi * f0 / fs)
+    vh = 10.0 ** (gain_db / 20.0)
+    vb = vh ** 0.4996667741545416
+    a0 = 1.0 + k / q + k * k
+    shelf = np.array([(vh + vb * k / q + k * k) / a0, 2.0 * (k * k - vh) / a0, (vh - vb * k / q + k * k) / a0,
+                      2.0 * (k * k - 1.0) / a0, (1.0 - k / q + k * k) / a0], dtype=np.float64)
+    f0, q = 38.13547087602444, 0.5003270373238773
+    k = math.tan(math.pi * f0 / fs)
+    a0 = 1.0 + k / q + k * k
+    highpass = np.array([1.0, -2.0, 1.0, 2.0 * (k * k - 1.0) / a0, (1.0 - k / q + k * k) / a0], dtype=np.float64)
+    return shelf, highpass
+
+
+def loudness_gain(x: torch.Tensor, fs: int, lengths: Lengths = None, target: float = -23.0,
+                  peak: float = -1.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``(loudness, peak, gain)`` per signal, (..., T) -> (...) float32 each: the integrated loudness of ITU-R BS.1770-4 in LUFS (one
+    channel: K-weighting, 400 ms blocks every 100 ms, the -70 LUFS and the -10 LU gate; ``-inf`` when no block is left), the sample peak
+    ``max |x|``, and the factor that brings the signal to ``target`` LUFS without its peak passing ``peak`` dBFS: ``10^((target - L) / 20)``,
+    lowered to ``10^(peak / 20) / max|x|`` where that binds, 1 for a signal whose loudness is not finite.  With ``lengths``, of
+    ``[..., :lengths[r]]`` per row (0 is a legal length), each value the bits of the call on that row alone.  One launch sequence
+    (``eben_loudness``, ``csrc/loudness.hip``): filter state and sums float64, the weighted signal never stored.  Restated from the
+    recommendation (parity with pyloudnorm / libebur128 unpinned)."""
+    what = "loudness_gain"
+    fs = _loudness_fs(fs, what)
+    target, peak = float(target), float(peak)
+    if not (math.isfinite(target) and math.isfinite(peak)):
+        raise ValueError(f"{what}: target and peak must be finite, got {target} LUFS and {peak} dBFS")
+    if x.dim() < 1 or x.shape[-1] < 1:
+        raise ValueError(f"{what}: expected a (..., time) signal, got shape {tuple(x.shape)}")
+    lead, t = tuple(x.shape[:-1]), x.shape[-1]
+    rows = math.prod(lead)
+    if not 1 <= rows <= 65535:
+        raise ValueError(f"{what}: {rows} signals in one call (1 ... 65535)")
+    host = _host_lengths(lengths, rows, t, what, least=0) if lengths is not None else None   # refused before anything touches a device
+    if not x.is_cuda:
+        raise EbenError(f"{what} runs only on an MI355X HIP device (got a tensor on '{x.device}'); there is no CPU path")
+    x2 = x.detach().to(torch.float32).contiguous().reshape(rows, t)
+    lens = None
+    if lengths is not None:
+        lens = host.to(x2.device, non_blocking=True) if host is not None else _device_lengths(lengths, rows, lead, x2.device, what)
+    lib = load()
+    nbytes = lib.eben_loudness_workspace(rows, t, fs)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x2.device)
+    out = torch.empty((3, rows), dtype=torch.float32, device=x2.device)
+    check(lib.eben_loudness(ptr(x2), rows, t, _lens_ptr(lens), fs, target, peak, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+                            ws.data_ptr(), nbytes, stream()), what)
+    return out[0].reshape(lead), out[1].reshape(lead), out[2].reshape(lead)
+
+
+def integrated_loudness(x: torch.Tensor, fs: int, lengths: Lengths = None) -> torch.Tensor:
+    """Integrated loudness in LUFS per signal (``loudness_gain``'s first value): (..., T) -> (...)."""
+    return loudness_gain(x, fs, lengths)[0]
+
+
 class _MeanMetric(torch.nn.Module):
     """torchmetrics-style mean of a per-signal metric: state is a device-side sum and count (not buffers)."""
 
@@ -504,6 +574,37 @@ class LogLikelihoodRatio(_SpeechMeasure):
 
 class CepstralDistance(_SpeechMeasure):
     measure = "cd"
+
+
+class IntegratedLoudness(_MeanMetric):
+    """Mean integrated loudness in LUFS (``integrated_loudness``) of the signals seen; a level has no reference, so ``update`` and
+    ``forward`` take one signal.  Signals without a finite loudness (silence, nothing over the gates) are left out of sum and count,
+    without a host wait."""
+
+    def __init__(self, fs: int):
+        super().__init__()
+        self.fs = _loudness_fs(fs, "IntegratedLoudness")
+
+    def _values(self, x, lengths=None):   # noqa: D102 -- one signal, not a pair
+        return integrated_loudness(x, self.fs, lengths)
+
+    def _accumulate(self, values: torch.Tensor) -> None:
+        if self._sum is None or self._sum.device != values.device:
+            self._sum = torch.zeros((), dtype=torch.float64, device=values.device)
+            self._count = torch.zeros((), dtype=torch.int64, device=values.device)
+        finite = torch.isfinite(values)
+        self._sum += torch.where(finite, values, torch.zeros_like(values)).sum(dtype=torch.float64)
+        self._count += finite.sum()
+
+    def update(self, x: torch.Tensor, lengths: Lengths = None) -> None:
+        self._accumulate(self._values(x, lengths))
+
+    def forward(self, x: torch.Tensor, lengths: Lengths = None) -> torch.Tensor:
+        """Mean over this call's signals with a finite loudness (NaN when there is none); also accumulated into the running state."""
+        values = self._values(x, lengths)
+        self._accumulate(values)
+        finite = torch.isfinite(values)
+        return (torch.where(finite, values, torch.zeros_like(values)).sum(dtype=torch.float64) / finite.sum()).to(torch.float32)
 
 
 class ShortTimeObjectiveIntelligibility(_MeanMetric):
